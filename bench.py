@@ -18,7 +18,10 @@ A "step" is one complete render of the frame (all 256 spp of every pixel, GMoN, 
 and — for N > 1 — the reduce of the per-rank framebuffers to rank 0). Scene upload and
 BVH build are outside the timed region; the framebuffer stays in HBM (a torch tensor).
 
-Rank 0 prints ONE JSON line (DESIGN.md §5 explains every field). The line also carries (at N > 1 for rank 0's share of the frame,
+A plain run sets up, warms up, times `--steps` steps and prints the line; `--dump-outputs DIR` then also writes the frame of the
+last timed step (DIR/frame.npy, float32), so that two builds can be compared output for output on the same inputs.
+
+Rank 0 prints ONE JSON line (DESIGN.md §5 explains every field). With `--full` the line also carries (at N > 1 for rank 0's share of the frame,
 with `per_rank` = every rank's device time and stage times and `reduce_ms` = the RCCL reduce per step)
   parity        the same scene / camera / depth at `--cpu-spp` samples rendered on the GPU and compared with the
                 frame the CPU baseline leg just rendered (RMSE in linear HDR, identical-pixel fraction); the bench
@@ -98,7 +101,34 @@ def parse():
     ap.add_argument("--dry-launch", action="store_true",
                     help="no GPU: start the --gpus N ranks with gloo and reduce synthetic frames (launch-path rehearsal)")
     ap.add_argument("--keep-pmc", default="", help="directory to keep the raw counter csv files in (e.g. profiles/...)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: counter passes, CPU baseline and parity gate, rooflines, one_batch, "
+                         "secondary workloads (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the frame of the last timed step as DIR/frame.npy (float32, H x W x 4; rows and columns strided "
+                         "when it exceeds 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if not args.full:
+        # a plain run measures the headline only
+        args.no_cpu_baseline = args.no_roofline = args.no_pmc = args.no_secondary = True
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_frame(d, img):
+    """The frame a caller of the timed path receives, as d/frame.npy (float32). A frame above DUMP_MAX_BYTES is cut to every
+    s-th row and column (the same pixels on every run with the same arguments)."""
+    import numpy as np
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    s = 1
+    while img[::s, ::s].nbytes > DUMP_MAX_BYTES:
+        s += 1
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "frame.npy"), np.ascontiguousarray(img[::s, ::s]))
 
 
 def workload(args):
@@ -425,6 +455,8 @@ def inproc_run(args):
     for _ in range(args.steps):
         img, st = ms.render(p, flags=args.flags)
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_frame(args.dump_outputs, img)
     W, H = p["size"]
     out = {"metric": "Msamples/sec (W*H*spp/s), Sponza-class 1080p 8-bounce", "value": round(W * H * p["spp"] * args.steps / dt * 1e-6, 3),
            "unit": "Msamples/s", "n_gpus": n, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -601,6 +633,8 @@ def main():
             stage_sum[k] += last[k]
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_frame(args.dump_outputs, fb.cpu().numpy())       # (at N > 1: the frame merged by the last step's reduce)
     per_rank = None
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")

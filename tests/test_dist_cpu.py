@@ -116,6 +116,30 @@ def test_bench_cpu_baseline_leg_runs_on_a_small_case():
         assert ref_order["box_tests"] > ref_order["shadow_box_tests"] > 0 and ref_order["tri_tests"] > 0
 
 
+def test_bench_plain_run_and_dump(monkeypatch, tmp_path):
+    """A plain run measures the headline only (every extra leg is switched off unless --full); --dump-outputs writes the frame
+    as float32, whole up to 64 MB, strided above it; --steps < 1 is refused."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3"])
+    a = bench.parse()
+    assert a.steps == 3 and not a.full and a.no_pmc and a.no_cpu_baseline and a.no_roofline and a.no_secondary
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-pmc"])
+    a = bench.parse()
+    assert a.full and a.no_pmc and not (a.no_cpu_baseline or a.no_roofline or a.no_secondary)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    small = np.arange(36 * 64 * 4, dtype=np.float32).reshape(36, 64, 4)
+    bench.dump_frame(str(tmp_path / "s"), small)
+    got = np.load(tmp_path / "s" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    big = np.zeros((2160, 3840, 4), np.float32)
+    big[::2, ::2] = 1.0
+    bench.dump_frame(str(tmp_path / "b"), big)
+    got = np.load(tmp_path / "b" / "frame.npy")
+    assert got.nbytes <= bench.DUMP_MAX_BYTES and got.shape == (1080, 1920, 4) and np.all(got == 1.0)
+
+
 def test_bench_kernel_name_parsing():
     import bench
     assert bench.kernel_base("void (anonymous namespace)::k_wf_shade<false>((anonymous namespace)::WfArgs)") == "k_wf_shade"
