@@ -66,8 +66,10 @@ typedef struct YartMeshDesc {
   const int32_t* face_light;/* 1 per face: light index or -1 */
 } YartMeshDesc;
 
-/* Scene-graph node (src/core/scene.hpp:11-64), pre-order, node 0 = root.
- * fwd / inv: row-major 4x4 Transform matrices (src/math/transform.hpp). */
+/* Scene-graph node (src/core/scene.hpp:11-64), pre-order (a node's parent comes before it), node 0 = root.
+ * fwd / inv: row-major 4x4 Transform matrices (src/math/transform.hpp).
+ * There is no nesting limit (the reference's testNode recurses to any depth); a scene holds fewer than 2^20 nodes.
+ * The glTF import instances a node shared by several parents once per path and refuses a cycle (YART_E_IO). */
 typedef struct YartNodeDesc {
   int32_t parent, mesh;
   float fwd[16], inv[16];
@@ -209,7 +211,8 @@ typedef struct YartStats {
 
 typedef struct YartScene YartScene;
 
-/* Build the device scene (BVH build per mesh — on the device, see yart_hip_scene_create_flags —, flattening, upload). device < 0: current. */
+/* Build the device scene (BVH build per mesh — on the device, see yart_hip_scene_create_flags —, flattening, upload). device < 0: current.
+ * desc->nodes: pre-order, any nesting depth, fewer than 2^20 nodes (YartNodeDesc). */
 int yart_hip_scene_create(const YartSceneDesc* desc, int device, YartScene** out);
 /* ... with options. The BVH of every mesh is built on the device (yart_hip_bvh_build_device: the same node array and index
  * permutation as the host build, so the same frames; a mesh the device build refuses is built on the host) unless

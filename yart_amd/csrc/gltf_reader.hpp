@@ -223,7 +223,7 @@ class Importer {
     if (scenes.size() == 0) fail("asset has no scenes");
     const size_t sceneIdx = size_t(doc_.get("scene").integer(0));
     const json::Value& sceneNodes = scenes.at(sceneIdx).get("nodes");
-    for (size_t i = 0; i < sceneNodes.size(); i++) node(size_t(sceneNodes.at(i).integer(-1)), 0, identityX(), 0);
+    for (size_t i = 0; i < sceneNodes.size(); i++) node(size_t(sceneNodes.at(i).integer(-1)));
     finish();
     return std::move(out_);
   }
@@ -465,45 +465,69 @@ class Importer {
   static bool emissive(const YartMaterialDesc& m) {                       // bsdf/parametric.cpp:66
     return m.emission[0] * m.emission[0] + m.emission[1] * m.emission[1] + m.emission[2] * m.emission[2] > 0.0f;
   }
-  void node(size_t nodeIdx, int32_t parent, const Xform& global, int depth) {   // gltf.cpp:272-317
+  // gltf.cpp:272-317 (processNode) without recursion: an explicit stack of the open nodes, so that a hierarchy of any depth
+  // imports without exhausting the host stack. The reference's observable order is kept: node records in pre-order,
+  // localTransform = node.transform * globalTransform (:293), and a node's area lights after those of all its children
+  // (:295-314: the recursion into the children comes first). A node reachable from two parents is instanced once per path,
+  // as the recursion does; a node that is its own ancestor is refused (the reference would recurse until its stack runs out).
+  void node(size_t rootIdx) {
     const json::Value& nodes = doc_.get("nodes");
-    if (nodeIdx >= nodes.size()) fail("node index out of range");
-    if (depth > 512) fail("node hierarchy too deep (cycle?)");
-    const json::Value& n = nodes.at(nodeIdx);
-    float t[3] = {0, 0, 0}, q[4] = {0, 0, 0, 1}, s[3] = {1, 1, 1};
-    if (n.has("matrix")) {
-      double cm[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-      const json::Value& mv = n.get("matrix");
-      for (size_t i = 0; i < 16 && i < mv.size(); i++) cm[i] = mv.at(i).number(cm[i]);
-      decomposeMatrix(cm, t, q, s);
-    } else { vec(n.get("translation"), t, 3); vec(n.get("rotation"), q, 4); vec(n.get("scale"), s, 3); }
-    const Xform local = fromTRS(t, q, s);
-    YartNodeDesc d{};
-    d.parent = parent;
-    d.mesh = -1;
-    if (n.has("mesh")) {
-      const int64_t mi = n.get("mesh").integer(-1);
-      if (mi < 0 || size_t(mi) >= meshData_.size()) fail("mesh index out of range");
-      d.mesh = int32_t(mi);
-    }
-    put(d.fwd, local.fwd); put(d.inv, local.inv);
-    const int32_t self = int32_t(out_->nodes.size());
-    out_->nodes.push_back(d);
-    const Xform localGlobal = compose(local, global);                      // :293 — node.transform * globalTransform
-    const json::Value& ch = n.get("children");
-    for (size_t i = 0; i < ch.size(); i++) node(size_t(ch.at(i).integer(-1)), self, localGlobal, depth + 1);
-    if (d.mesh >= 0) {
-      MeshData& md = meshData_[size_t(d.mesh)];
-      int32_t li = 0;
-      for (size_t f = 0; f < md.faceLight.size(); f++) {
-        const YartMaterialDesc& mat = out_->materials[md.faces[f * 4 + 3]];
-        if (!emissive(mat)) continue;
-        YartLightDesc l{};
-        l.type = 0; l.mesh = d.mesh; l.tri = uint32_t(f); l.two_sided = 0; l.texture = -1; l.radius = 100.0f;
-        std::memcpy(l.emission, mat.emission, sizeof(l.emission));
-        put(l.fwd, localGlobal.fwd); put(l.inv, localGlobal.inv);
-        out_->lights.push_back(l);
-        md.faceLight[f] = li++;
+    struct Open { size_t idx; int32_t self; int32_t mesh; Xform global; size_t next; };
+    std::vector<Open> stack;
+    std::vector<uint8_t> onPath(nodes.size(), 0);
+    auto enter = [&](size_t nodeIdx, int32_t parent, const Xform& global) {
+      if (nodeIdx >= nodes.size()) fail("node index out of range");
+      if (onPath[nodeIdx]) fail("node hierarchy has a cycle: node " + std::to_string(nodeIdx) + " is its own ancestor");
+      if (out_->nodes.size() >= (1u << 20) - 1u) fail("more than 2^20 scene nodes (a node shared by many parents is instanced once per path)");
+      const json::Value& n = nodes.at(nodeIdx);
+      float t[3] = {0, 0, 0}, q[4] = {0, 0, 0, 1}, s[3] = {1, 1, 1};
+      if (n.has("matrix")) {
+        double cm[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        const json::Value& mv = n.get("matrix");
+        for (size_t i = 0; i < 16 && i < mv.size(); i++) cm[i] = mv.at(i).number(cm[i]);
+        decomposeMatrix(cm, t, q, s);
+      } else { vec(n.get("translation"), t, 3); vec(n.get("rotation"), q, 4); vec(n.get("scale"), s, 3); }
+      const Xform local = fromTRS(t, q, s);
+      YartNodeDesc d{};
+      d.parent = parent;
+      d.mesh = -1;
+      if (n.has("mesh")) {
+        const int64_t mi = n.get("mesh").integer(-1);
+        if (mi < 0 || size_t(mi) >= meshData_.size()) fail("mesh index out of range");
+        d.mesh = int32_t(mi);
+      }
+      put(d.fwd, local.fwd); put(d.inv, local.inv);
+      const int32_t self = int32_t(out_->nodes.size());
+      out_->nodes.push_back(d);
+      onPath[nodeIdx] = 1;
+      stack.push_back(Open{nodeIdx, self, d.mesh, compose(local, global), 0});     // :293 — node.transform * globalTransform
+    };
+    enter(rootIdx, 0, identityX());
+    while (!stack.empty()) {
+      Open& top = stack.back();
+      const json::Value& ch = nodes.at(top.idx).get("children");
+      if (top.next < ch.size()) {
+        const size_t c = size_t(ch.at(top.next++).integer(-1));
+        const Xform g = top.global;                 // (enter() may reallocate the stack)
+        enter(c, top.self, g);
+        continue;
+      }
+      const Open done = top;
+      stack.pop_back();
+      onPath[done.idx] = 0;
+      if (done.mesh >= 0) {
+        MeshData& md = meshData_[size_t(done.mesh)];
+        int32_t li = 0;
+        for (size_t f = 0; f < md.faceLight.size(); f++) {
+          const YartMaterialDesc& mat = out_->materials[md.faces[f * 4 + 3]];
+          if (!emissive(mat)) continue;
+          YartLightDesc l{};
+          l.type = 0; l.mesh = done.mesh; l.tri = uint32_t(f); l.two_sided = 0; l.texture = -1; l.radius = 100.0f;
+          std::memcpy(l.emission, mat.emission, sizeof(l.emission));
+          put(l.fwd, done.global.fwd); put(l.inv, done.global.inv);
+          out_->lights.push_back(l);
+          md.faceLight[f] = li++;
+        }
       }
     }
   }

@@ -396,7 +396,6 @@ inline HostImage buildHostImage(const YartSceneDesc& d, MeshBvhFn bvhFn = nullpt
       nd.pad[0] = (ident ? 1u : 0u) | (parentIdent ? 2u : 0u);
       if (!ident) im.allIdentity = false;
     }
-    require(nd.depth < kMaxNodeDepth, "scene graph deeper than 8 levels");
     require(nn < (1u << 20), "more than 2^20 scene nodes are not supported");   // wavefront.hpp::wfHitWord
     if (nd.depth > im.maxNodeDepth) im.maxNodeDepth = nd.depth;
     if (n.mesh >= 0) {                                          // Node(Mesh*), scene.hpp:17-22
@@ -418,25 +417,42 @@ inline HostImage buildHostImage(const YartSceneDesc& d, MeshBvhFn bvhFn = nullpt
     nb[c.parent].join(boundsFromPoints(ptr, 8));
   }
   // NB: children are joined in reverse order here; min/max folding is order independent.
+  // Skip link: the first later node that is not in the subtree (depth <= the node's), found with a stack of the open
+  // subtrees in one pass (linear for any shape; a forward scan per node is quadratic on a chain).
+  std::vector<uint32_t> open;
   for (uint32_t i = 0; i < nn; i++) {
     NodeDev& nd = im.nodes[i];
     for (int c = 0; c < 3; c++) { nd.bmin[c] = nb[i].mn[c]; nd.bmax[c] = nb[i].mx[c]; }
-    uint32_t j = i + 1;
-    while (j < nn && im.nodes[j].depth > nd.depth) j++;
-    nd.skip = j;
+    while (!open.empty() && im.nodes[open.back()].depth >= nd.depth) { im.nodes[open.back()].skip = i; open.pop_back(); }
+    open.push_back(i);
   }
+  for (uint32_t k : open) im.nodes[k].skip = nn;
 
   // Conservative world-space box per node: the node's local box pushed through its forward chain in
   // double precision, then padded far beyond the rounding of the reference's object-space test
   // (2e-3 + 1e-4 * |coordinate|; the boxes themselves already carry the reference's +-0.001).
   // The device tests it first (world ray, no transform) and runs the reference's exact test only on
   // the survivors, so it can only skip work the exact test would also have skipped.
+  //
+  // Nodes at depth kMaxNodeDepth and more get an unbounded box (no pre-cull; the exact test alone decides). Why: the pad
+  // has to cover the distance, mapped back to world space, between the object-space ray the reference computes and the
+  // exact one. Level k adds a rounding error of at most gamma_4 * (|inv_k| |o_{k-1}| + |t_k|) per component
+  // (gamma_4 = 4u / (1 - 4u), u = 2^-24: a 4-term dot product), and the forward chain F_k = fwd_0 ... fwd_k carries it
+  // to world space, so the world-space error is bounded by
+  //     sum_k ||F_k|| * gamma_4 * (||inv_k|| * ||o_{k-1}|| + ||t_k||),
+  // and ||o_{k-1}|| <= ||F_{k-1}^-1|| * ||o_world|| + (the chain's translations). The sum grows with the depth and with
+  // the product of the per-level condition numbers ||fwd_k|| ||inv_k||, which can be large even when the composite is
+  // benign (diag(4, 1/4, 1), a 45-degree rotation, diag(1/4, 4, 1), repeated), and it scales with ||o_world||: the
+  // distance of the ray origin, which the scene build cannot bound (the camera and the surfaces a ray leaves from can be
+  // anywhere). A pad that is valid for every ray therefore is not small relative to the box at depth, and the box falls
+  // back to the whole space. Shallower nodes keep the fixed pad (at most 8 levels of products: the argument above) and
+  // exactly the boxes they have always had; a deep node's shallow ancestors keep theirs, and they cull its subtree.
   im.nodeWorld.resize(size_t(nn) * 2);
   for (uint32_t i = 0; i < nn; i++) {
     double mn[3] = {1e300, 1e300, 1e300}, mx[3] = {-1e300, -1e300, -1e300};
     const NodeDev& nd = im.nodes[i];
-    bool finite = true;
-    for (int corner = 0; corner < 8; corner++) {
+    bool finite = nd.depth < kMaxNodeDepth;
+    for (int corner = 0; corner < 8 && finite; corner++) {
       double p[3] = {(corner & 4) ? nd.bmax[0] : nd.bmin[0], (corner & 2) ? nd.bmax[1] : nd.bmin[1],
                      (corner & 1) ? nd.bmax[2] : nd.bmin[2]};
       for (int32_t a = int32_t(i); a >= 0; a = im.nodes[a].parent) {

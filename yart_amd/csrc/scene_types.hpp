@@ -19,7 +19,10 @@
 
 namespace yart_hip {
 
-constexpr uint32_t kMaxNodeDepth = 8;   // scene-graph nesting the node walk supports
+// Scene graphs have no nesting limit. traverse.hpp::objectRay applies a node's chain in windows of this many levels (a node
+// shallower than this is one window: the walk it always was); nodes this deep and deeper have no world-space pre-cull box
+// (host_scene.hpp explains why).
+constexpr uint32_t kMaxNodeDepth = 8;
 
 enum : uint32_t { TEX_LINEAR = 0, TEX_SRGB = 1, TEX_NONCOLOR = 2 };
 enum : uint32_t { LIGHT_AREA = 0, LIGHT_UNIFORM_INF = 1, LIGHT_IMAGE_INF = 2 };

@@ -301,6 +301,12 @@ YART_HD bool traverseMesh(const SceneDev& sc, const MeshDev& mesh, uint32_t node
 
 // World ray -> object space of scene node `idx`: the reference re-derives the ray at
 // every level from its parent's object-space ray (ray-integrator.cpp:26-29).
+// Scene graphs have no depth limit, and no per-lane array may grow with the depth: the chain is applied root first, one
+// window of up to kMaxNodeDepth levels at a time. For each window the walk goes up from `idx` to the window's deepest
+// node, collects the window and applies it in order — the same per-level products as the reference, with no data beyond
+// the parent links. A node at depth < kMaxNodeDepth is one window and no walk-up: the same work as a single chain walk.
+// Deeper nodes: O(depth^2 / 16) parent reads, O(depth) products (NodeRayCache keeps the general walk at one product per
+// level down a chain).
 YART_HD void objectRay(const SceneDev& sc, uint32_t idx, f3 o, f3 d, f3& oo, f3& od) {
   if (sc.nodes[idx].pad[0] & 1u) {
     // every transform on the chain is the identity: each 4x4 product reduces to x + 0.0f
@@ -309,13 +315,20 @@ YART_HD void objectRay(const SceneDev& sc, uint32_t idx, f3 o, f3 d, f3& oo, f3&
     oo = o + 0.0f; od = d + 0.0f;
     return;
   }
-  uint32_t chain[kMaxNodeDepth];
-  uint32_t n = 0;
-  for (int32_t i = int32_t(idx); i >= 0 && n < kMaxNodeDepth; i = sc.nodes[i].parent) chain[n++] = uint32_t(i);
-  for (uint32_t k = n; k-- > 0;) {
-    const NodeDev& nd = sc.nodes[chain[k]];
-    o = mulPoint(nd.xf.inv, o);
-    d = mulVector(nd.xf.inv, d);
+  const uint32_t depth = sc.nodes[idx].depth;
+  uint32_t w = (depth + 1u) % kMaxNodeDepth;                   // levels of the first window (the rest are full)
+  if (w == 0u) w = kMaxNodeDepth;
+  for (uint32_t hi = w - 1u; hi <= depth; hi += kMaxNodeDepth, w = kMaxNodeDepth) {    // window [hi + 1 - w, hi]
+    int32_t i = int32_t(idx);
+    for (uint32_t k = depth; k > hi; k--) i = sc.nodes[i].parent;
+    uint32_t chain[kMaxNodeDepth];
+    uint32_t n = 0;
+    for (; n < w; i = sc.nodes[i].parent) chain[n++] = uint32_t(i);
+    for (uint32_t k = n; k-- > 0;) {
+      const NodeDev& nd = sc.nodes[chain[k]];
+      o = mulPoint(nd.xf.inv, o);
+      d = mulVector(nd.xf.inv, d);
+    }
   }
   oo = o; od = d;
 }
@@ -323,7 +336,11 @@ YART_HD void objectRay(const SceneDev& sc, uint32_t idx, f3 o, f3 d, f3& oo, f3&
 // Object-space ray of consecutive scene nodes without re-walking the ancestor chain: the
 // reference hands each child the parent's object-space ray (ray-integrator.cpp:26-29), so
 // siblings share it. One cached (parent node, ray) pair covers a pre-order walk of groups
-// of siblings; identity chains need no cache (world ray + 0.0f).
+// of siblings; identity chains need no cache (world ray + 0.0f). For a node deeper than
+// kMaxNodeDepth, a miss whose grandparent is cached takes one level from the cache (a chain
+// walked downwards costs one product per level, not the whole chain per level); the result
+// is the same sequence of per-level products. Shallower misses re-walk their (at most
+// 8-level) chain, as before.
 struct NodeRayCache {
   int32_t node = -2;
   f3 o, d;
@@ -335,7 +352,10 @@ YART_HD void nodeObjectRay(const SceneDev& sc, uint32_t idx, const NodeDev& nd, 
   if (nd.pad[0] & 2u) { po = wo + 0.0f; pd = wd + 0.0f; }
   else if (nd.parent == cache.node) { po = cache.o; pd = cache.d; }
   else {
-    objectRay(sc, uint32_t(nd.parent), wo, wd, po, pd);
+    // (the parent's chain is not the identity here: nd has no bit 1)
+    const NodeDev* pn = nd.depth > kMaxNodeDepth ? &sc.nodes[nd.parent] : nullptr;
+    if (pn && pn->parent == cache.node) { po = mulPoint(pn->xf.inv, cache.o); pd = mulVector(pn->xf.inv, cache.d); }
+    else objectRay(sc, uint32_t(nd.parent), wo, wd, po, pd);
     cache.node = nd.parent; cache.o = po; cache.d = pd;
   }
   (void)idx;

@@ -12,6 +12,7 @@ the vocabulary of ``oracle/params.hpp``.
   probe scene of BASELINE.md §2.
 * :func:`sponza_class`  — C3/C4: env-lit atrium, ≈262k triangles, textured.
 * :func:`mclaren_class` — C5: clearcoat / thin-glass / chrome body with DoF.
+* :func:`deep_instances` — scene graphs nested to any depth (:func:`fuzz_deep_case`: seeded ones).
 """
 from __future__ import annotations
 
@@ -634,6 +635,83 @@ def instances(width=96, height=96, spp=4, depth=4, n_instances=70, groups=4, see
                           rng.uniform(-child_extent, child_extent)), rng.uniform(0, 6.28), tuple(rng.uniform(scale[0], scale[1], 3)))
             s.add_node(cube, gi, f2, i2)
     s.create_area_lights()
+    return s, p
+
+
+def deep_instances(depth=12, branching=1, width=48, height=48, spp=4, bounces=4, ill_conditioned=True, pad_nodes=0,
+                   mesh_every=3, light_every=5, seed=5):
+    """Cornell room + a scene graph `depth` levels deep (the root is level 0: the deepest node sits at depth - 1): a spine
+    chain from the root down, every level a transform with rotation, non-uniform scale and translation, and `branching` - 1
+    side branches per spine level (a mesh node with a mesh child of its own). ill_conditioned: the spine cycles through
+    diag(4, 1/4, 1), a rotation, diag(1/4, 4, 1) — the per-level condition numbers multiply up while the composite stays
+    within a factor 16 of a rotation; otherwise each level is T * R * S with S the inverse of the previous level's scale on
+    odd levels. Boxes every `mesh_every` spine levels and on the deepest one, emissive boxes every `light_every` and on the
+    deepest one (area lights under deep chains).
+    pad_nodes: that many small boxes under the root after the graph (more than 64 nodes in all: the chunked candidate
+    masks, the per-lane walk and the top-level hierarchy of the lean kernels)."""
+    s, p = cornell(width, height, spp, bounces)
+    rng = np.random.RandomState(seed)
+    mats = [s.add_material(Material(base=tuple(rng.uniform(0.2, 0.9, 3)), roughness=float(rng.uniform(0.2, 1.0)),
+                                    metallic=float(rng.rand() > 0.7))) for _ in range(3)]
+    glow = s.add_material(Material(base=(0.8, 0.8, 0.8), roughness=1.0, emission=(6.0, 5.0, 3.5)))
+
+    def box_mesh(h, mat):
+        b = MeshBuilder()
+        b.box((-h, -h, -h), (h, h, h), mat)
+        return s.add_mesh(b.build())
+    boxes = [box_mesh(0.15, m) for m in mats]
+    lamp = box_mesh(0.08, glow)
+    side = box_mesh(0.1, mats[0])
+
+    def rot():
+        a = rng.normal(size=3)
+        return a / np.linalg.norm(a), float(rng.uniform(0.3, 1.2))
+
+    def jitter(r=0.02):
+        return tuple(rng.uniform(-r, r, 3))
+    prev_scale = np.ones(3)
+    parent = s.add_node(-1, 0, *trs(translation=(0.0, 4.5, 0.0), axis=(0, 1, 0), angle=0.4, scale=(1.0, 1.0, 1.0)))
+    for level in range(2, depth):
+        # side branches of the spine node `parent` (pre-order: a branch's subtree is complete before the next node)
+        for _ in range(branching - 1):
+            ax, an = rot()
+            b = s.add_node(side, parent, *trs(translation=jitter(0.4), axis=ax, angle=an, scale=tuple(rng.uniform(0.7, 1.4, 3))))
+            ax, an = rot()
+            if level < depth - 1:
+                s.add_node(boxes[level % 3], b, *trs(translation=jitter(0.3), axis=ax, angle=an,
+                                                     scale=tuple(rng.uniform(0.5, 1.0, 3))))
+        ax, an = rot()
+        if ill_conditioned:
+            k = level % 3
+            sc = (4.0, 0.25, 1.0) if k == 0 else (0.25, 4.0, 1.0) if k == 2 else (1.0, 1.0, 1.0)
+            f, i = trs(translation=jitter(0.01), axis=(0, 0, 1) if k else ax, angle=(math.pi / 4 + an * 0.1) if k == 1 else 0.0,
+                       scale=sc)
+        else:
+            sc = 1.0 / prev_scale if level % 2 else rng.uniform(0.6, 1.6, 3)
+            prev_scale = np.asarray(sc)
+            f, i = trs(translation=jitter(0.05), axis=ax, angle=an, scale=tuple(sc))
+        lit = light_every and (level % light_every == 0 or level == depth - 1)        # (the deepest node always has a mesh)
+        mesh = lamp if lit else boxes[level % 3] if level == depth - 1 or (mesh_every and level % mesh_every == 0) else -1
+        parent = s.add_node(mesh, parent, f, i)
+    for k in range(pad_nodes):
+        x, z = rng.uniform(-4.2, 4.2), rng.uniform(-4.2, 4.2)
+        ax, an = rot()
+        s.add_node(boxes[k % 3], 0, *trs(translation=(x, rng.uniform(0.3, 9.0), z), axis=ax, angle=an,
+                                         scale=tuple(rng.uniform(0.8, 2.0, 3))))
+    s.create_area_lights()
+    return s, p
+
+
+def fuzz_deep_case(seed, width=32, height=24):
+    """Seeded deep scene graphs for the parity fuzz: 9 to 40 levels, chains and trees, both transform patterns, some
+    graphs padded past 64 nodes, 1-16 spp, 2-8 bounces."""
+    rng = np.random.RandomState(seed ^ 0xDEE9)
+    depth = int(rng.randint(9, 41))
+    branching = int(rng.choice([1, 1, 2, 3]))
+    pad = int(rng.choice([0, 0, 70]))
+    s, p = deep_instances(depth, branching, width, height, int(rng.choice([1, 2, 4, 16])), int(rng.randint(2, 9)),
+                          ill_conditioned=bool(rng.rand() < 0.5), pad_nodes=pad, mesh_every=int(rng.randint(1, 5)),
+                          light_every=int(rng.choice([0, 3, 7])), seed=seed)
     return s, p
 
 

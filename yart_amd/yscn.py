@@ -199,10 +199,15 @@ class Scene:
         for i, n in enumerate(self.nodes):
             if n.parent >= 0: children[n.parent].append(i)
 
-        def visit(i):
-            for c in children[i]: visit(c)
+        # post-order (children first, in order) with an explicit stack: no recursion limit on the nesting depth
+        stack = [(0, 0)]
+        while stack:
+            i, k = stack.pop()
+            if k < len(children[i]):
+                stack.append((i, k + 1)); stack.append((children[i][k], 0))
+                continue
             n = self.nodes[i]
-            if n.mesh < 0: return
+            if n.mesh < 0: continue
             mesh = self.meshes[n.mesh]
             fwd, inv = self._global(i)
             li = 0
@@ -212,7 +217,6 @@ class Scene:
                     area.append(Light(LIGHT_AREA, mesh=n.mesh, tri=t, emission=tuple(mat.emission),
                                       fwd=fwd, inv=inv))
                     mesh.face_light[t] = li; li += 1
-        visit(0)
         # area lights precede infinite lights (main.cpp adds env lights after load)
         self.lights = area + self.lights
 
