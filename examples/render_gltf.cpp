@@ -4,9 +4,12 @@
 //   (frontend main.cpp:263-275 -> output/ppm.cpp:7-21). No window: the frontend is out of scope.
 //
 //   g++ -std=c++17 -Iinclude examples/render_gltf.cpp -Lyart_amd -lyart_hip -Wl,-rpath,$PWD/yart_amd -lpthread -o render_gltf
-//   ./render_gltf asset.glb sky_oct.hdr out.ppm [width height spp depth  eye(3) target(3)  focal fnumber exposure look]
+//   ./render_gltf asset.glb sky_oct.hdr out.ppm [width height spp depth  eye(3) target(3)  focal fnumber exposure look  aov_prefix]
+// aov_prefix: also render the first-hit feature buffers (yart_hip_render_aovs) and write <prefix>_albedo.ppm, <prefix>_normal.ppm
+// (n * 0.5 + 0.5) and <prefix>_depth.ppm (t / the frame's largest t) through the same 8-bit encoding.
 #include <cstdio>
 #include <cstdlib>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -14,7 +17,7 @@
 
 int main(int argc, char** argv) {
   if (argc < 4) {
-    std::fprintf(stderr, "usage: %s asset.glb env_oct.hdr|- out.ppm [w h spp depth ex ey ez tx ty tz focal fnumber exposure look]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s asset.glb env_oct.hdr|- out.ppm [w h spp depth ex ey ez tx ty tz focal fnumber exposure look aov_prefix]\n", argv[0]);
     return 1;
   }
   auto num = [&](int i, double dflt) { return argc > i ? std::atof(argv[i]) : dflt; };
@@ -49,6 +52,28 @@ int main(int argc, char** argv) {
     std::fprintf(f, "P6\n%u %u\n255\n", w, h);
     std::fwrite(rgb8.data(), 1, rgb8.size(), f);
     std::fclose(f);
+    if (argc > 18) {
+      YartRenderParams rp{};
+      rp.samples = rp.first_wave_samples = rp.max_wave_samples = renderer.samples;
+      rp.tile_size = 64; rp.max_depth = renderer.maxDepth; rp.world_size = 1;
+      const yart::hip::AovFrame a = scene.renderAovs(cam, rp, YART_AOV_ALBEDO | YART_AOV_NORMAL | YART_AOV_DEPTH);
+      float tMax = 0.0f;
+      for (float t : a.depth) tMax = t > tMax ? t : tMax;
+      auto write = [&](const char* name, auto value) {          // value(pixel, channel) -> linear [0, 1]
+        std::vector<float> rgba(size_t(w) * h * 4, 1.0f);
+        for (size_t i = 0; i < size_t(w) * h; i++) for (int c = 0; c < 3; c++) rgba[4 * i + c] = value(i, c);
+        yart::hip::check(yart_hip_tonemap_host(rgba.data(), w, h, -1, nullptr, rgb8.data()));
+        const std::string path = std::string(argv[18]) + "_" + name + ".ppm";
+        FILE* g = std::fopen(path.c_str(), "wb");
+        if (!g) throw std::runtime_error("cannot create " + path);
+        std::fprintf(g, "P6\n%u %u\n255\n", w, h);
+        std::fwrite(rgb8.data(), 1, rgb8.size(), g);
+        std::fclose(g);
+      };
+      write("albedo", [&](size_t i, int c) { return a.albedo[3 * i + c]; });
+      write("normal", [&](size_t i, int c) { return a.normal[3 * i + c] * 0.5f + 0.5f; });
+      write("depth", [&](size_t i, int) { return tMax > 0.0f ? a.depth[i] / tMax : 0.0f; });
+    }
     const auto& st = renderer.stats();
     std::printf("{\"samples\": %zu, \"rays\": %llu, \"ms\": %lld, \"ms_device\": %.1f, \"msamples_per_s\": %.1f}\n", done.totalSamples,
                 (unsigned long long) done.totalRays, (long long) done.totalTime.count(), st.ms_device,

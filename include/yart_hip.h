@@ -134,7 +134,8 @@ typedef struct YartRenderParams {
   /* Upper bound on the (pixel, sample) paths per batch; 0 = 2^28 (a fixed number: the memory a render holds does not depend on
    * what happens to be free on the device; only a device that cannot hold the batch renders smaller ones). A wave is rendered
    * batch by batch over this rank's pixels in tile order, every batch through all bounces and the estimator: 251 bytes per path
-   * of the batch (path state, queues, per-sample radiance, the compacted state of the late bounces). A smaller batch means
+   * of the batch (path state, queues, per-sample radiance, the compacted state of the late bounces; feature buffers, YartAovBuffers
+   * below, add nothing to it in this pipeline and 48 bytes per path under YART_FLAG_MEGAKERNEL / YART_FLAG_PATH_POOL). A smaller batch means
    * finished tiles arrive earlier (yart_hip_render_tiles) and less memory is held, at ~10 ms per batch on an MI355X (the C3 frame
    * of 531 M paths: +1.4 % in 2 batches, +4.5 % in 4, +19 % in 16). The frame does not depend on it. */
   uint32_t max_batch_paths;
@@ -283,6 +284,52 @@ int yart_hip_render_tiles(YartScene* scene, const YartCameraDesc* cam, const Yar
 int yart_hip_render_device(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params,
                            float* d_out_rgba, void* stream, YartStats* stats);
 
+/* First-hit feature buffers ("AOVs"): what bounce 0 of every path of the frame knows about the surface it sees, from the SAME
+ * camera samples as the frame — guides for a denoiser (albedo, normal), compositing (coverage, depth), picking (ids), and the
+ * per-pixel ray count (where the time goes). The definition is the reference's Hit (cpu/hit.hpp) as testNode / testMesh leave it
+ * (cpu/ray-integrator.cpp:20-82) for the camera ray of (pixel, sample): the candidate the stochastic alpha test accepted (the
+ * path and the buffers see the same surface), n after BSDF::normal (normal-mapped, world space). For a pixel and its samples
+ * s = 0 .. samples-1, misses contributing nothing:
+ *   albedo, normal, position, depth   float32 sum over the hitting samples in ASCENDING s, then one division by float(samples);
+ *                                     albedo = the base colour ParametricBSDF::fImpl starts from (parametric.cpp:75-78, 90-91)
+ *                                     at Hit.uv, depth = Hit.t, position = Hit.p. The order is part of the contract: the result
+ *                                     is a pure function of the per-sample values.
+ *   coverage                          hitting samples / samples
+ *   ids                               of sample 0's hit: node (index into YartSceneDesc.nodes), mesh, material, triangle (Hit.idx);
+ *                                     all -1 when sample 0 misses
+ *   rays                              the pixel's rays over the whole render (mis-integrator.cpp:22, 126); sums to YartStats.rays
+ * Pixels of other ranks are left 0 (ids -1), as in out_rgba: the ranks' buffers add up to the unsharded ones (ids: by max).
+ * The buffers do not depend on flags (megakernel and path pool included), max_batch_paths, the wave schedule or the estimator.
+ * Memory: the default pipeline holds nothing more per path (the 48-byte feature record of a path lives in the shadow-ray arrays,
+ * which are unused until bounce 0 is shaded: still 251 bytes per path); YART_FLAG_MEGAKERNEL and YART_FLAG_PATH_POOL hold 48 bytes
+ * more per path of the batch (the batch clamp of max_batch_paths accounts for it); every pipeline 68 bytes per pixel of the rank.
+ * start_sample / stop_sample other than the full range are refused (YART_E_INVALID). Several GPUs: yart_hip_multi_* has no feature
+ * buffers; shard with rank / world_size, one call per device, and add the buffers. */
+#define YART_AOV_ALBEDO   1u   /* 3 floats / pixel */
+#define YART_AOV_NORMAL   2u   /* 3 floats */
+#define YART_AOV_POSITION 4u   /* 3 floats */
+#define YART_AOV_DEPTH    8u   /* 1 float  */
+#define YART_AOV_COVERAGE 16u  /* 1 float  */
+#define YART_AOV_IDS      32u  /* 4 x int32: node, mesh, material, triangle */
+#define YART_AOV_RAYS     64u  /* 1 x uint32 */
+#define YART_AOV_ALL      127u
+typedef struct YartAovBuffers {
+  uint32_t struct_size;        /* sizeof(YartAovBuffers): lets the struct grow without an ABI bump */
+  uint32_t mask;               /* YART_AOV_* requested; a requested buffer must be non-NULL, the others are not touched */
+  float *albedo, *normal, *position, *depth, *coverage;
+  int32_t* ids;
+  uint32_t* rays;
+} YartAovBuffers;
+/* yart_hip_render + feature buffers: host pointers, width * height * channels each, row-major like out_rgba. out_rgba and
+ * YartStats.samples / rays are those of yart_hip_render with the same arguments, bit for bit; mask == 0 (or aovs == NULL) is
+ * yart_hip_render. A NULL requested buffer, a struct_size that ends before a requested field, unknown mask bits and a partial
+ * sample range return YART_E_INVALID before anything is launched. */
+int yart_hip_render_aovs(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, float* out_rgba,
+                         const YartAovBuffers* aovs, YartStats* stats);
+/* yart_hip_render_device + feature buffers: DEVICE pointers (e.g. torch tensors' data_ptr) */
+int yart_hip_render_aovs_device(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, float* d_out_rgba,
+                                const YartAovBuffers* d_aovs, void* stream, YartStats* stats);
+
 /* Several GPUs of one node behind one handle — what the reference's worker pool is to CPU threads
  * (TileRenderer::renderImpl starts threadCount workers that pull tiles, tile-renderer.hpp:150-197; finishTile merges
  * each finished tile into the one m_hdrBuffer, :225-241). The scene is replicated on every listed device; device i of
@@ -333,6 +380,10 @@ int yart_hip_probe_sampler(YartScene* scene, uint32_t spp, uint32_t tile, uint32
 /* closest hit of n world rays (ox,oy,oz,dx,dy,dz) -> 16 floats each:
  * hit, t, u, v, px,py,pz, nx,ny,nz, tx,ty,tz, triIdx, lightIdx, backSide */
 int yart_hip_probe_hits(YartScene* scene, uint32_t n, const float* rays, float* out);
+/* Diagnostic: the camera ray of n (x, y, sample) triples -> 6 floats each (origin, direction), drawn exactly as bounce 0 of that
+ * sample draws it: startPixelSample, the film and the lens draw (core/sampler.hpp), Camera::getRay (core/camera.hpp:138-164) */
+int yart_hip_probe_camera_rays(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, uint32_t n,
+                               const uint32_t* xys, float* out_rays);
 /* the BVH the kernels traverse: nodes (8 x u32 each: bounds, left|first, span) and
  * the index permutation of mesh `mesh` */
 /* the 32 device counter words of the last render on this scene ([0] rays, [1..4] exact

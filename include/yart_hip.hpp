@@ -37,6 +37,14 @@ inline void requireAbi() {
 }
 
 // Owns a device-resident scene (flattened geometry, BVHs, materials, lights).
+// The frame and the first-hit feature buffers of one render (YartAovBuffers): only the requested ones are sized.
+struct AovFrame {
+  uint32_t width = 0, height = 0, mask = 0;
+  std::vector<float> rgba, albedo, normal, position, depth, coverage;   // 4 / 3 / 3 / 3 / 1 / 1 floats per pixel
+  std::vector<int32_t> ids;                                             // node, mesh, material, triangle of sample 0 (-1: miss)
+  std::vector<uint32_t> rays;                                           // rays of the pixel over the whole render
+};
+
 class DeviceScene {
  public:
   explicit DeviceScene(const YartSceneDesc& desc, int device = -1) { requireAbi(); check(yart_hip_scene_create(&desc, device, &h_)); }
@@ -56,6 +64,25 @@ class DeviceScene {
   DeviceScene& operator=(const DeviceScene&) = delete;
   ~DeviceScene() { yart_hip_scene_destroy(h_); }
   YartScene* handle() const { return h_; }
+  // yart_hip_render_aovs: the frame plus the feature buffers of `mask` (YART_AOV_*), from the same camera samples. Several GPUs:
+  // one call per device with params.rank / world_size, then add the buffers (ids: by max).
+  AovFrame renderAovs(const YartCameraDesc& cam, const YartRenderParams& params, uint32_t mask = YART_AOV_ALL, YartStats* stats = nullptr) {
+    AovFrame f;
+    f.width = cam.width; f.height = cam.height; f.mask = mask;
+    const size_t n = size_t(cam.width) * cam.height;
+    f.rgba.resize(n * 4);
+    YartAovBuffers b{};
+    b.struct_size = uint32_t(sizeof(b)); b.mask = mask;
+    if (mask & YART_AOV_ALBEDO) { f.albedo.resize(n * 3); b.albedo = f.albedo.data(); }
+    if (mask & YART_AOV_NORMAL) { f.normal.resize(n * 3); b.normal = f.normal.data(); }
+    if (mask & YART_AOV_POSITION) { f.position.resize(n * 3); b.position = f.position.data(); }
+    if (mask & YART_AOV_DEPTH) { f.depth.resize(n); b.depth = f.depth.data(); }
+    if (mask & YART_AOV_COVERAGE) { f.coverage.resize(n); b.coverage = f.coverage.data(); }
+    if (mask & YART_AOV_IDS) { f.ids.resize(n * 4); b.ids = f.ids.data(); }
+    if (mask & YART_AOV_RAYS) { f.rays.resize(n); b.rays = f.rays.data(); }
+    check(yart_hip_render_aovs(h_, &cam, &params, f.rgba.data(), &b, stats));
+    return f;
+  }
 
  private:
   explicit DeviceScene(YartScene* h) : h_(h) {}

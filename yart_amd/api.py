@@ -159,6 +159,39 @@ class TileInfo(C.Structure):
 TILE_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(TileInfo))
 
 
+class AovBuffers(C.Structure):
+    """YartAovBuffers (include/yart_hip.h): the first-hit feature buffers a render fills next to the frame."""
+    _fields_ = [("struct_size", C.c_uint32), ("mask", C.c_uint32),
+                ("albedo", C.c_void_p), ("normal", C.c_void_p), ("position", C.c_void_p), ("depth", C.c_void_p),
+                ("coverage", C.c_void_p), ("ids", C.c_void_p), ("rays", C.c_void_p)]
+
+
+# name -> (YART_AOV_* bit, values per pixel, dtype)
+AOVS = {"albedo": (1, 3, np.float32), "normal": (2, 3, np.float32), "position": (4, 3, np.float32), "depth": (8, 1, np.float32),
+        "coverage": (16, 1, np.float32), "ids": (32, 4, np.int32), "rays": (64, 1, np.uint32)}
+AOV_ALL = tuple(AOVS)
+
+
+def reduce_aov_samples(values, hit, samples=None):
+    """The definition of an averaged feature buffer, in numpy: ``values`` [..., S, C] per-sample values, ``hit`` [..., S]
+    bool. The float32 sum over the hitting samples in ascending sample order (misses contribute nothing), then one
+    division by float32(samples). Returns [..., C] float32."""
+    values = np.asarray(values, np.float32)
+    hit = np.asarray(hit, bool)
+    n = values.shape[-2] if samples is None else samples
+    acc = np.zeros(values.shape[:-2] + values.shape[-1:], np.float32)
+    for s in range(values.shape[-2]):
+        acc = np.where(hit[..., s, None], acc + values[..., s, :], acc).astype(np.float32)
+    return (acc / np.float32(n)).astype(np.float32)
+
+
+def reduce_aov_coverage(hit, samples=None):
+    """coverage: hitting samples (an integer count) / samples, one float32 division."""
+    hit = np.asarray(hit, bool)
+    n = hit.shape[-1] if samples is None else samples
+    return (hit.sum(axis=-1).astype(np.float32) / np.float32(n)).astype(np.float32)
+
+
 class ImportOptions(C.Structure):
     """YartImportOptions (include/yart_hip.h): the environment the frontend adds after gltf::load."""
     _fields_ = [("env_hdr_path", C.c_char_p), ("env_radius", C.c_float), ("uniform_env", C.c_uint32),
@@ -194,7 +227,8 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_probe_hits", "yart_hip_probe_sampler", "yart_hip_bvh_info", "yart_hip_bvh_copy", "yart_hip_scene_create_flags", "yart_hip_bvh_build_device", "yart_hip_bvh_build_host", "yart_hip_debug_counters", "yart_hip_debug_shade_regions",
            "yart_hip_tonemap_agx", "yart_hip_encode_rgb8", "yart_hip_tonemap_host",
            "yart_hip_multi_create", "yart_hip_multi_load", "yart_hip_multi_destroy", "yart_hip_multi_device_count", "yart_hip_multi_failed_devices",
-           "yart_hip_multi_render", "yart_hip_multi_render_tiles", "yart_hip_multi_rccl_selftest"]
+           "yart_hip_multi_render", "yart_hip_multi_render_tiles", "yart_hip_multi_rccl_selftest",
+           "yart_hip_render_aovs", "yart_hip_render_aovs_device", "yart_hip_probe_camera_rays"]
 
 LIB_COUNT_PATH = os.path.join(_HERE, "libyart_hip_count.so")   # instrumented twin (exact test counters)
 _libs = {}
@@ -243,6 +277,12 @@ def lib(instrumented: bool = False):
         L.yart_hip_multi_render.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p, C.POINTER(Stats)]
         L.yart_hip_multi_render_tiles.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p,
                                                   C.POINTER(Stats), WAVE_CALLBACK, TILE_CALLBACK, C.c_void_p]
+        L.yart_hip_render_aovs.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p,
+                                           C.POINTER(AovBuffers), C.POINTER(Stats)]
+        L.yart_hip_render_aovs_device.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p,
+                                                  C.POINTER(AovBuffers), C.c_void_p, C.POINTER(Stats)]
+        L.yart_hip_probe_camera_rays.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint32,
+                                                 C.c_void_p, C.c_void_p]
         L.yart_hip_bvh_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.yart_hip_bvh_copy.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         _libs[path] = L
@@ -461,7 +501,49 @@ class DeviceScene:
                                             C.c_void_p(tensor.data_ptr()), sp, C.byref(st)))
         return st.asdict()
 
+    def render_aovs(self, p: dict, aovs: Sequence[str] = AOV_ALL, rank=0, world_size=1, flags=0):
+        """``render`` + first-hit feature buffers (include/yart_hip.h: YartAovBuffers) from the same camera samples.
+        Returns (frame HxWx4 float32, {name: ndarray HxWxC (HxW for one channel)}, stats dict); names from ``AOVS``."""
+        cam, rp, st = make_camera(p), make_params(p, rank, world_size, flags), Stats()
+        out = np.empty((cam.height, cam.width, 4), np.float32)
+        ab, bufs = AovBuffers(), {}
+        ab.struct_size = C.sizeof(AovBuffers)
+        for name in aovs:
+            bit, ch, dt = AOVS[name]
+            bufs[name] = np.empty((cam.height, cam.width, ch) if ch > 1 else (cam.height, cam.width), dt)
+            ab.mask |= bit
+            setattr(ab, name, bufs[name].ctypes.data_as(C.c_void_p))
+        _check(self._L.yart_hip_render_aovs(self._h, C.byref(cam), C.byref(rp), out.ctypes.data_as(C.c_void_p),
+                                            C.byref(ab), C.byref(st)), self._L)
+        return out, bufs, st.asdict()
+
+    def render_aovs_into(self, tensor, aov_tensors: dict, p: dict, rank=0, world_size=1, flags=0, stream=None):
+        """``render_into`` + feature buffers written into CUDA/HIP torch tensors: ``aov_tensors`` maps names of ``AOVS`` to
+        contiguous device tensors of H*W*channels elements (float32; ids int32; rays int32 holding the uint32 counts)."""
+        cam, rp, st = make_camera(p), make_params(p, rank, world_size, flags), Stats()
+        assert tensor.is_cuda and tensor.is_contiguous() and tensor.numel() == cam.width * cam.height * 4
+        ab = AovBuffers()
+        ab.struct_size = C.sizeof(AovBuffers)
+        for name, t in aov_tensors.items():
+            bit, ch, _ = AOVS[name]
+            assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() == cam.width * cam.height * ch, name
+            ab.mask |= bit
+            setattr(ab, name, C.c_void_p(t.data_ptr()))
+        sp = C.c_void_p(stream) if stream else None
+        _check(self._L.yart_hip_render_aovs_device(self._h, C.byref(cam), C.byref(rp), C.c_void_p(tensor.data_ptr()),
+                                                   C.byref(ab), sp, C.byref(st)), self._L)
+        return st.asdict()
+
     # -- diagnostics ----------------------------------------------------------------
+    def probe_camera_rays(self, p: dict, xys: Sequence[Sequence[int]]):
+        """The camera ray (origin, direction: 6 floats) of each (x, y, sample), drawn as bounce 0 of that sample draws it."""
+        cam, rp = make_camera(p), make_params(p)
+        a = np.ascontiguousarray(xys, np.uint32).reshape(-1, 3)
+        out = np.empty((len(a), 6), np.float32)
+        _check(self._L.yart_hip_probe_camera_rays(self._h, C.byref(cam), C.byref(rp), len(a), a.ctypes.data_as(C.c_void_p),
+                                                  out.ctypes.data_as(C.c_void_p)), self._L)
+        return out
+
     def probe_samples(self, p: dict, xys: Sequence[Sequence[int]]):
         cam, rp = make_camera(p), make_params(p)
         a = np.ascontiguousarray(xys, np.uint32).reshape(-1, 3)

@@ -10,6 +10,7 @@
 #pragma once
 #include "lights.hpp"
 #include "traverse.hpp"
+#include "aov.hpp"
 
 namespace yart_hip {
 
@@ -124,7 +125,9 @@ YART_HD f3 directLight(const PathCtx& cx, Sampler& smp, f3 wo, const Hit& hit, u
 }
 
 // MISIntegrator::Li (mis-integrator.cpp:13-106)
-YART_HD f3 pathRadiance(const PathCtx& cx, Sampler& smp, f3 ro, f3 rd, uint32_t& rays) {
+// CAPTURE: the feature record of bounce 0's closest hit goes to *rec / *ids (aov.hpp); without it the code is unchanged
+template <bool CAPTURE = false>
+YART_HD f3 pathRadiance(const PathCtx& cx, Sampler& smp, f3 ro, f3 rd, uint32_t& rays, AovRecord* rec = nullptr, AovIds* ids = nullptr) {
   const SceneDev& sc = *cx.sc;
   f3 lastP = mk3(0);
   f3 L = mk3(0.0f), attenuation = mk3(1.0f);
@@ -160,6 +163,7 @@ YART_HD f3 pathRadiance(const PathCtx& cx, Sampler& smp, f3 ro, f3 rd, uint32_t&
     didHit = traverseScene<false>(sc, ro, rd, 0.001f, hr, dummy, cx.stk, ac);
 #endif
     YART_FOLD_COUNTS(cx, ac);
+    if (CAPTURE && depth == 0) *rec = aovCapture(sc, hr, didHit, ro, rd, *ids);
     if (!didHit) {
       for (uint32_t k = 0; k < sc.nInfinite; k++) {
         const LightDev& l = sc.lights[sc.infiniteLights[k]];
@@ -222,15 +226,16 @@ YART_HD f3 pathRadiance(const PathCtx& cx, Sampler& smp, f3 ro, f3 rd, uint32_t&
 }
 
 // RayIntegrator::sample (ray-integrator.cpp:11-18): one radiance sample of pixel (px,py)
+template <bool CAPTURE = false>
 YART_HD f3 samplePixel(const PathCtx& cx, const CameraDev& cam, uint32_t px, uint32_t py, uint32_t s,
-                       uint32_t& rays) {
+                       uint32_t& rays, AovRecord* rec = nullptr, AovIds* ids = nullptr) {
   Sampler smp;
   startPixelSample(smp, cx.rc.sampler, px, py, s);
   f2 uvFilm = get2D(smp, cx.rc.sampler, cx.sobol);      // getPixel2D(); evaluated first (Appendix A.1)
   f2 uvLens = get2D(smp, cx.rc.sampler, cx.sobol);
   f3 o, d;
   cameraRay(cam, px, py, uvFilm, uvLens, o, d);
-  return pathRadiance(cx, smp, o, d, rays);
+  return pathRadiance<CAPTURE>(cx, smp, o, d, rays, rec, ids);
 }
 
 }  // namespace yart_hip

@@ -109,8 +109,14 @@ struct MegaArgs {
   uint32_t* cursor;
   unsigned long long* rays;
   uint64_t* spill;             // kSpillDepth entries per launched thread, lane-interleaved
+  // feature buffers (k_render_mega<true> only): the three record arrays (per path of the batch) and the ids of sample 0 (per pixel of the rank)
+  f4 *aov0, *aov1, *aov2;
+  int32_t* aovIds;
+  uint32_t pixBase, padA;
 };
 
+// AOV: also writes the feature record of every path's first hit (aov.hpp); <false> is the kernel as it was before feature buffers existed
+template <bool AOV>
 __global__ void __launch_bounds__(kBlock) k_render_mega(MegaArgs a) {
   __shared__ uint64_t ldsStack[kLdsStack * kBlock];
   const uint32_t lane = threadIdx.x & 63u;
@@ -134,8 +140,16 @@ __global__ void __launch_bounds__(kBlock) k_render_mega(MegaArgs a) {
       const uint32_t pi = w / a.spp, s = w - pi * a.spp;
       const uint32_t pk = a.pixels[pi];
       const uint32_t before = rays;
-      f3 L = samplePixel(cx, a.cam, pk & 0xffffu, pk >> 16, s + a.sampleOffset, rays);
+      AovRecord rec; AovIds ids;
+      f3 L = samplePixel<AOV>(cx, a.cam, pk & 0xffffu, pk >> 16, s + a.sampleOffset, rays, &rec, &ids);
       a.L[w] = mk4(L.x, L.y, L.z, asF(rays - before));
+      if (AOV) {
+        wfSt(a.aov0 + w, rec.r0); wfSt(a.aov1 + w, rec.r1); wfSt(a.aov2 + w, rec.r2);
+        if (s + a.sampleOffset == 0u) {
+          int32_t* o = a.aovIds + size_t(a.pixBase + pi) * 4;
+          o[0] = ids.node; o[1] = ids.mesh; o[2] = ids.material; o[3] = ids.tri;
+        }
+      }
     }
   }
   // one atomic per wave
@@ -348,6 +362,7 @@ __global__ void __launch_bounds__(kBlock) k_tex_quads(TexQuadArgs a) {
 
 #include "wavefront_kernels.inc"
 #if YART_TU == 0
+#include "aov_kernels.inc"
 #include "bvh_build_device.inc"
 #endif
 
@@ -465,6 +480,9 @@ struct YartScene {
   DevBuf<uint32_t> wfTailMap[2];
   DevBuf<WfDyn> wfDyn;
   DevBuf<unsigned long long> pathsLog;     // paths entering bounce b, summed over the batches of a render (YartStats::paths_at_bounce)
+  // feature buffers (aov_kernels.inc): running sums / ray counts / ids per pixel of the rank; the records of the megakernel and path-pool
+  // pipelines (3 x 16 B per path of the batch); the device side of the host-pointer entry point's buffers
+  DevBuf<f4> aovAcc[3], aovRec; DevBuf<uint32_t> aovRays; DevBuf<int32_t> aovIds; DevBuf<uint32_t> aovOut;
   DevBuf<uint32_t> poolMap;                // path pool: the path (index of L) each slot carries, kWfFreeSlot = free
   uint32_t* poolHost = nullptr;            // pinned: the queue counters of the last rounds (the host's view of "is the batch done")
   ~YartScene() { if (poolHost) (void)hipHostFree(poolHost); }
@@ -666,8 +684,9 @@ struct StageTimer {
 struct BatchInfo { uint32_t c0, n, wave, waveSamples, samplesTaken, totalSamples; };
 typedef std::function<bool(const BatchInfo&)> BatchHook;
 
+// aov: feature buffers to fill as well (device pointers, checked by checkAovs; nullptr: none — nothing below differs from a plain render then)
 bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRenderParams& p, float* dOut,
-                    hipStream_t stream, YartStats* stats, const BatchHook* hook = nullptr) {
+                    hipStream_t stream, YartStats* stats, const BatchHook* hook = nullptr, const YartAovBuffers* aov = nullptr) {
   bool aborted = false;
   auto wall0 = std::chrono::high_resolution_clock::now();
   TraceRange rgRender("yart:render");
@@ -718,7 +737,8 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
   auto kRetryS = wfKernel(tu::shadowRetry(nodesForm));
   auto kExtendGen = wfKernel(tu::extendGeneral(false)), kExtendGenRetry = wfKernel(tu::extendGeneral(true));
   auto kShadowGen = wfKernel(tu::shadowGeneral(false)), kShadowGenRetry = wfKernel(tu::shadowGeneral(true));
-  const int gridMega = persistentGrid(s, reinterpret_cast<const void*>(k_render_mega), 3);
+  const auto kMega = aov ? k_render_mega<true> : k_render_mega<false>;
+  const int gridMega = persistentGrid(s, reinterpret_cast<const void*>(kMega), 3);
   const int gridExtendFast = persistentGrid(s, reinterpret_cast<const void*>(kExtendFast), 8);
   const int gridShadowFast = persistentGrid(s, reinterpret_cast<const void*>(kShadowFast), 8);
   const int gridExtend = persistentGrid(s, reinterpret_cast<const void*>(kExtendGen), 8);
@@ -769,6 +789,7 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
     for (auto& t : s.wfTail) for (auto& b : t) held += uint64_t(b.n) * 16;
     held += (uint64_t(s.wfTailMap[0].n) + s.wfTailMap[1].n) * 4;
     held += uint64_t(s.smpEntries.n) * 8;      // the sampler tables of the previous render stay allocated
+    held += uint64_t(s.aovRec.n) * 16;
     if (std::getenv("YART_FAKE_FREE_MB")) held = 0;
     // what grows with the batch: 9 x 16 B of path state + 4 queue words + 16 B of radiance = 176 B per path; with compaction two
     // a tail state of 1/2 of the batch (9 x 16 B + a slot map word) and a slot map of 1/4 = 75 B more; the resume records of an eighth of
@@ -785,9 +806,11 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
     } else {
       // pool: 16 B of radiance per path of the batch + 168 B (+ resume records) per slot of the pool: the batch gets at most half
       // of the budget, the pool what is left
-      const uint64_t fits = std::max<uint64_t>(avail / 2 / 16, 1u << 16);
+      // (feature buffers: + 48 B of feature record per path of the batch; the default pipeline keeps its records in the shadow-ray arrays)
+      const uint64_t perBatchPath = aov ? 16 + 48 : 16;
+      const uint64_t fits = std::max<uint64_t>(avail / 2 / perBatchPath, 1u << 16);
       maxPaths = std::min<uint64_t>(maxPaths, fits);
-      const uint64_t left = avail > std::min<uint64_t>(maxPaths, uint64_t(nPix ? nPix : 1) * waveCap) * 16 ? avail - std::min<uint64_t>(maxPaths, uint64_t(nPix ? nPix : 1) * waveCap) * 16 : 0;
+      const uint64_t left = avail > std::min<uint64_t>(maxPaths, uint64_t(nPix ? nPix : 1) * waveCap) * perBatchPath ? avail - std::min<uint64_t>(maxPaths, uint64_t(nPix ? nPix : 1) * waveCap) * perBatchPath : 0;
       poolFit = std::max<uint64_t>(left / (176 + (kResumeWords * 16 + 7) / 8), 64);
     }
   }
@@ -798,6 +821,24 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
     chunk = (nPix + nb - 1) / nb;
   }
   s.L.ensure(size_t(chunk) * waveCap);
+  // feature buffers: per-pixel accumulators (zero; ids -1), the caller's buffers cleared as the frame is, and — megakernel / path pool —
+  // the record arrays of the batch
+  const size_t aovStride = size_t(chunk) * waveCap;
+  if (aov) {
+    const size_t np1 = std::max<uint32_t>(nPix, 1u), wh = size_t(W) * H;
+    for (auto& b : s.aovAcc) { b.ensure(np1); HIP_CHECK(hipMemsetAsync(b.p, 0, np1 * sizeof(f4), stream)); }
+    s.aovRays.ensure(np1); HIP_CHECK(hipMemsetAsync(s.aovRays.p, 0, np1 * sizeof(uint32_t), stream));
+    s.aovIds.ensure(np1 * 4); HIP_CHECK(hipMemsetAsync(s.aovIds.p, 0xff, np1 * 4 * sizeof(int32_t), stream));
+    s.pixRays.ensure(np1);
+    if (mega || pool) s.aovRec.ensure(3 * aovStride);
+    if (aov->mask & YART_AOV_ALBEDO) HIP_CHECK(hipMemsetAsync(aov->albedo, 0, wh * 3 * sizeof(float), stream));
+    if (aov->mask & YART_AOV_NORMAL) HIP_CHECK(hipMemsetAsync(aov->normal, 0, wh * 3 * sizeof(float), stream));
+    if (aov->mask & YART_AOV_POSITION) HIP_CHECK(hipMemsetAsync(aov->position, 0, wh * 3 * sizeof(float), stream));
+    if (aov->mask & YART_AOV_DEPTH) HIP_CHECK(hipMemsetAsync(aov->depth, 0, wh * sizeof(float), stream));
+    if (aov->mask & YART_AOV_COVERAGE) HIP_CHECK(hipMemsetAsync(aov->coverage, 0, wh * sizeof(float), stream));
+    if (aov->mask & YART_AOV_IDS) HIP_CHECK(hipMemsetAsync(aov->ids, 0xff, wh * 4 * sizeof(int32_t), stream));
+    if (aov->mask & YART_AOV_RAYS) HIP_CHECK(hipMemsetAsync(aov->rays, 0, wh * sizeof(uint32_t), stream));
+  }
   uint32_t poolSlots = 0;
   if (!mega) {
     const size_t npBatch = size_t(chunk) * waveCap;
@@ -874,17 +915,30 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
     size_t tileDone = 0;                     // blocks of this wave whose ray counts have been summed (tile callbacks only)
     for (uint32_t c0 = 0; inRange && !aborted && c0 < nPix; c0 += chunk) {
       const uint32_t n = std::min(chunk, nPix - c0);
+      AovArgs av{};
+      if (aov) {
+        av.acc0 = s.aovAcc[0].p; av.acc1 = s.aovAcc[1].p; av.acc2 = s.aovAcc[2].p; av.accRays = s.aovRays.p; av.ids = s.aovIds.p;
+        av.nPixels = n; av.spp = uint32_t(waveSamples); av.pixBase = c0; av.sampleOffset = uint32_t(takenBefore);
+        if (mega || pool) { av.r0 = s.aovRec.p; av.r1 = s.aovRec.p + aovStride; av.r2 = s.aovRec.p + 2 * aovStride; }
+      }
+      auto aovReduce = [&]() {
+        TraceRange rgA("yart:aov_reduce", stream);
+        hipLaunchKernelGGL(k_aov_reduce, dim3((n * 4u + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, av);
+        HIP_CHECK(hipGetLastError());
+      };
       if (mega) {
         HIP_CHECK(hipMemsetAsync(s.cursor.p, 0, sizeof(uint32_t), stream));
         MegaArgs a{};
         a.sc = s.dev; a.cam = cam; a.rc = rc; a.pixels = s.pixels.p + c0; a.nPixels = n;
         a.spp = uint32_t(waveSamples); a.sampleOffset = uint32_t(takenBefore); a.L = s.L.p;
         a.cursor = s.cursor.p; a.rays = s.counters.p; a.spill = s.spill.p;
+        a.aov0 = av.r0; a.aov1 = av.r1; a.aov2 = av.r2; a.aovIds = av.ids; a.pixBase = c0;
         TraceRange rgMega("yart:megakernel", stream);
         tMega.begin(stream);
-        hipLaunchKernelGGL(k_render_mega, dim3(gridMega), dim3(kBlock), 0, stream, a);
+        hipLaunchKernelGGL(kMega, dim3(gridMega), dim3(kBlock), 0, stream, a);
         HIP_CHECK(hipGetLastError());
         tMega.end(stream);
+        if (aov) aovReduce();
       } else if (pool) {
         WfArgs a{};
         a.sc = s.dev; a.cam = cam; a.rc = rcw; a.pixBase = c0;
@@ -938,6 +992,10 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
           }
           HIP_CHECK(hipGetLastError());
           tExtend.end(stream);
+          if (aov) {                             // the paths this round's refill started stand at bounce 0 with their hit records final
+            hipLaunchKernelGGL(k_aov_capture, dim3(s.numCUs * YART_STREAM_BLOCKS), dim3(kBlock), 0, stream, a, av);
+            HIP_CHECK(hipGetLastError());
+          }
           tShade.begin(stream);
           tShadeK.begin(stream);
           hipLaunchKernelGGL(kShade, dim3(gridShade), dim3(kShadeBlock), 0, stream, a);
@@ -970,6 +1028,7 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
             if (c[WC_NEXT] == 0u) done = true;                  // no live slot after its refill: nothing left to start either
           }
         }
+        if (aov) aovReduce();
       } else {
         WfArgs a{};
         a.sc = s.dev; a.cam = cam; a.rc = rcw; a.pixBase = c0;
@@ -1020,6 +1079,16 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
           HIP_CHECK(hipGetLastError());
           tExtend.end(stream);
           rgExtend.end();
+          if (aov && bounce == 0) {
+            // feature records of every path of the batch, written into the shadow-ray arrays (unused until the shade stage below
+            // writes bounce 0's shadow rays) and summed per pixel at once, before that happens
+            TraceRange rgA("yart:aov_capture", stream);
+            av.r0 = a.st.sh0; av.r1 = a.st.sh1; av.r2 = a.st.sh2;
+            hipLaunchKernelGGL(k_aov_capture, dim3(s.numCUs * YART_STREAM_BLOCKS), dim3(kBlock), 0, stream, a, av);
+            HIP_CHECK(hipGetLastError());
+            rgA.end();
+            aovReduce();
+          }
           TraceRange rgShade("yart:shade", stream);
           tShade.begin(stream);
           tShadeK.begin(stream);
@@ -1066,6 +1135,7 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
       }
       GmonArgs g{};
       if (hook && *hook) { s.pixRays.ensure(std::max<uint32_t>(nPix, 1u)); g.pixRays = s.pixRays.p + c0; }
+      if (aov) g.pixRays = s.pixRays.p + c0;
       g.L = s.L.p; g.pixels = s.pixels.p + c0; g.nPixels = n; g.spp = uint32_t(waveSamples); g.width = W;
       g.exposureScale = cam.exposureScale; g.wCurrent = wCurrent; g.wWave = wWave; g.hdr = dOut;
       g.kind = int(p.estimator);
@@ -1074,6 +1144,10 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
       hipLaunchKernelGGL(k_gmon_blend, dim3((n + kGmonPixPerBlock - 1) / kGmonPixPerBlock), dim3(kBlock), 0, stream, g);
       HIP_CHECK(hipGetLastError());
       tGmon.end(stream);
+      if (aov) {
+        hipLaunchKernelGGL(k_aov_add_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, s.aovRays.p + c0, s.pixRays.p + c0, n);
+        HIP_CHECK(hipGetLastError());
+      }
       HIP_CHECK(hipStreamSynchronize(stream));
       rgBlend.end();
       tMega.resolve(); tExtend.resolve(); tShade.resolve(); tConnect.resolve(); tGmon.resolve(); tLean.resolve(); tShadeK.resolve(); tShadowLean.resolve();
@@ -1100,6 +1174,16 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
     uint64_t next = (currentWave > 0 || waveSamples > 1) ? std::min<uint64_t>(waveSamples * 2, p.max_wave_samples) : 1;
     waveSamples = std::min(next, remaining);
     currentWave++;
+  }
+  if (aov && nPix > 0 && !aborted) {
+    AovFinishArgs f{};
+    f.acc0 = s.aovAcc[0].p; f.acc1 = s.aovAcc[1].p; f.acc2 = s.aovAcc[2].p; f.accRays = s.aovRays.p; f.ids = s.aovIds.p;
+    f.pixels = s.pixels.p; f.nPixels = nPix; f.width = W; f.samples = p.samples; f.mask = aov->mask;
+    f.albedo = aov->albedo; f.normal = aov->normal; f.position = aov->position; f.depth = aov->depth; f.coverage = aov->coverage;
+    f.outIds = aov->ids; f.outRays = aov->rays;
+    TraceRange rgA("yart:aov_finish", stream);
+    hipLaunchKernelGGL(k_aov_finish, dim3((nPix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, f);
+    HIP_CHECK(hipGetLastError());
   }
   HIP_CHECK(hipEventRecord(tAll.b, stream));
   HIP_CHECK(hipEventSynchronize(tAll.b));
@@ -1260,6 +1344,88 @@ int yart_hip_render(YartScene* scene, const YartCameraDesc* cam, const YartRende
     if (params->start_sample > 0) HIP_CHECK(hipMemcpy(scene->hdr.p, out_rgba, n * sizeof(float), hipMemcpyHostToDevice));
     renderToDevice(*scene, *cam, *params, scene->hdr.p, nullptr, stats);
     HIP_CHECK(hipMemcpy(out_rgba, scene->hdr.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (stats)
+      stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+  });
+}
+
+// Feature buffers: the caller's YartAovBuffers checked (before anything touches a device) and copied into a struct of this
+// build's size; false: nothing is requested (a plain render)
+static bool checkAovs(const YartAovBuffers* in, const YartCameraDesc* cam, const YartRenderParams* params, YartAovBuffers& out) {
+  out = YartAovBuffers{};
+  if (in) {
+    require(in->struct_size >= 2 * sizeof(uint32_t), "YartAovBuffers.struct_size is too small for the struct's head");
+    require((in->mask & ~YART_AOV_ALL) == 0u, "YartAovBuffers.mask has bits that are no YART_AOV_* value");
+    const struct { uint32_t bit; size_t off; const char* null; } fields[] = {
+        {YART_AOV_ALBEDO, offsetof(YartAovBuffers, albedo), "YART_AOV_ALBEDO is requested and YartAovBuffers.albedo is null"},
+        {YART_AOV_NORMAL, offsetof(YartAovBuffers, normal), "YART_AOV_NORMAL is requested and YartAovBuffers.normal is null"},
+        {YART_AOV_POSITION, offsetof(YartAovBuffers, position), "YART_AOV_POSITION is requested and YartAovBuffers.position is null"},
+        {YART_AOV_DEPTH, offsetof(YartAovBuffers, depth), "YART_AOV_DEPTH is requested and YartAovBuffers.depth is null"},
+        {YART_AOV_COVERAGE, offsetof(YartAovBuffers, coverage), "YART_AOV_COVERAGE is requested and YartAovBuffers.coverage is null"},
+        {YART_AOV_IDS, offsetof(YartAovBuffers, ids), "YART_AOV_IDS is requested and YartAovBuffers.ids is null"},
+        {YART_AOV_RAYS, offsetof(YartAovBuffers, rays), "YART_AOV_RAYS is requested and YartAovBuffers.rays is null"}};
+    for (const auto& f : fields) {
+      if (!(in->mask & f.bit)) continue;
+      require(in->struct_size >= f.off + sizeof(void*), "YartAovBuffers.struct_size ends before a buffer the mask requests");
+      void* ptr = *reinterpret_cast<void* const*>(reinterpret_cast<const char*>(in) + f.off);
+      require(ptr != nullptr, f.null);
+      *reinterpret_cast<void**>(reinterpret_cast<char*>(&out) + f.off) = ptr;
+    }
+    out.struct_size = uint32_t(sizeof(YartAovBuffers)); out.mask = in->mask;
+  }
+  validate(cam, params);
+  if (out.mask != 0u)
+    require(params->start_sample == 0 && (params->stop_sample == 0 || params->stop_sample == params->samples),
+            "feature buffers need the full sample range (start_sample = 0, stop_sample = 0 or samples)");
+  return out.mask != 0u;
+}
+
+int yart_hip_render_aovs_device(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, float* d_out_rgba,
+                                const YartAovBuffers* d_aovs, void* stream, YartStats* stats) {
+  return guarded([&] {
+    YartAovBuffers av;
+    const bool any = checkAovs(d_aovs, cam, params, av);
+    require(scene && d_out_rgba, "scene / output pointer is null");
+    std::lock_guard<std::mutex> lock(scene->mu);
+    renderToDevice(*scene, *cam, *params, d_out_rgba, static_cast<hipStream_t>(stream), stats, nullptr, any ? &av : nullptr);
+  });
+}
+
+int yart_hip_render_aovs(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, float* out_rgba,
+                         const YartAovBuffers* aovs, YartStats* stats) {
+  return guarded([&] {
+    YartAovBuffers host;
+    const bool any = checkAovs(aovs, cam, params, host);
+    require(scene && out_rgba, "scene / output pointer is null");
+    std::lock_guard<std::mutex> lock(scene->mu);
+    auto t0 = std::chrono::high_resolution_clock::now();
+    HIP_CHECK(hipSetDevice(scene->device));
+    const size_t wh = size_t(cam->width) * cam->height, n = wh * 4;
+    scene->hdr.ensure(n);
+    if (params->start_sample > 0) HIP_CHECK(hipMemcpy(scene->hdr.p, out_rgba, n * sizeof(float), hipMemcpyHostToDevice));
+    // the requested buffers side by side in one device allocation (4-byte words: 3, 3, 3, 1, 1, 4, 1 per pixel)
+    const struct { uint32_t bit; size_t words; size_t off; } fields[] = {
+        {YART_AOV_ALBEDO, 3, offsetof(YartAovBuffers, albedo)}, {YART_AOV_NORMAL, 3, offsetof(YartAovBuffers, normal)},
+        {YART_AOV_POSITION, 3, offsetof(YartAovBuffers, position)}, {YART_AOV_DEPTH, 1, offsetof(YartAovBuffers, depth)},
+        {YART_AOV_COVERAGE, 1, offsetof(YartAovBuffers, coverage)}, {YART_AOV_IDS, 4, offsetof(YartAovBuffers, ids)},
+        {YART_AOV_RAYS, 1, offsetof(YartAovBuffers, rays)}};
+    YartAovBuffers dev = host;
+    if (any) {
+      size_t words = 0;
+      for (const auto& f : fields) if (host.mask & f.bit) words += f.words * wh;
+      scene->aovOut.ensure(words);
+      size_t at = 0;
+      for (const auto& f : fields) if (host.mask & f.bit) {
+        *reinterpret_cast<void**>(reinterpret_cast<char*>(&dev) + f.off) = scene->aovOut.p + at;
+        at += f.words * wh;
+      }
+    }
+    renderToDevice(*scene, *cam, *params, scene->hdr.p, nullptr, stats, nullptr, any ? &dev : nullptr);
+    HIP_CHECK(hipMemcpy(out_rgba, scene->hdr.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (any)
+      for (const auto& f : fields) if (host.mask & f.bit)
+        HIP_CHECK(hipMemcpy(*reinterpret_cast<void**>(reinterpret_cast<char*>(&host) + f.off),
+                            *reinterpret_cast<void**>(reinterpret_cast<char*>(&dev) + f.off), f.words * wh * 4, hipMemcpyDeviceToHost));
     if (stats)
       stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
   });
@@ -1481,6 +1647,30 @@ int yart_hip_probe_hits(YartScene* scene, uint32_t n, const float* rays, float* 
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(out, res.p, size_t(n) * 16 * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int yart_hip_probe_camera_rays(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, uint32_t n,
+                               const uint32_t* xys, float* out_rays) {
+  return guarded([&] {
+    require(scene && xys && out_rays && n > 0, "probe_camera_rays: null pointer or n == 0");
+    validate(cam, params);
+    for (uint32_t i = 0; i < n; i++)
+      require(xys[3 * i] < cam->width && xys[3 * i + 1] < cam->height && xys[3 * i + 2] < params->samples, "probe_camera_rays: pixel / sample out of range");
+    YartScene& s = *scene;
+    std::lock_guard<std::mutex> lk(s.mu);
+    HIP_CHECK(hipSetDevice(s.device));
+    DevBuf<uint32_t> dIn; DevBuf<float> dOut;
+    dIn.upload(std::vector<uint32_t>(xys, xys + size_t(n) * 3));
+    dOut.ensure(size_t(n) * 6);
+    ProbeCameraArgs a{};
+    a.cam = makeCamera(*cam); a.rc = makeRenderConst(*params);
+    a.sobol = reinterpret_cast<const uint32_t*>(s.dev.lut + LutDev::sobol);
+    a.xys = dIn.p; a.n = n; a.out = dOut.p;
+    hipLaunchKernelGGL(k_probe_camera_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, a);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out_rays, dOut.p, size_t(n) * 6 * sizeof(float), hipMemcpyDeviceToHost));
   });
 }
 
