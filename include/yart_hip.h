@@ -213,7 +213,11 @@ typedef struct YartStats {
 typedef struct YartScene YartScene;
 
 /* Build the device scene (BVH build per mesh — on the device, see yart_hip_scene_create_flags —, flattening, upload). device < 0: current.
- * desc->nodes: pre-order, any nesting depth, fewer than 2^20 nodes (YartNodeDesc). */
+ * desc->nodes: pre-order, any nesting depth, fewer than 2^20 nodes (YartNodeDesc).
+ * Traversal stack: every mesh's BVH is measured here (inner levels on its deepest path = the stack entries a ray can hold at
+ * once); the scene's maximum sizes the kernels' stack spill area — 64 entries, the reference's own stack, or more if a tree
+ * needs more. A mesh whose tree is deeper than 192 levels is refused: YART_E_INVALID, and yart_hip_last_error() names the
+ * mesh and its depth. Nothing is launched for such a scene. (The same holds for every other scene-creating entry point.) */
 int yart_hip_scene_create(const YartSceneDesc* desc, int device, YartScene** out);
 /* ... with options. The BVH of every mesh is built on the device (yart_hip_bvh_build_device: the same node array and index
  * permutation as the host build, so the same frames; a mesh the device build refuses is built on the host) unless

@@ -12,7 +12,26 @@
 #include <atomic>
 #include <chrono>
 #include <cstdio>
+#include <cstdint>
+#include <memory>
+#include <mutex>
 #include <thread>
+
+// stackcheck: what the traversal stack of every ray reaches. The device headers call YART_STACK_PROBE at a ray's start (0), at
+// every push (1, entries after the push) and where the fast walk hands a ray over (2, entries held); only this host build
+// defines it — in the kernels the macro is empty.
+struct StackProbe {
+  uint32_t rayMax = 0; bool open = false;
+  uint64_t rays = 0, rayHist[65] = {0}, handHist[65] = {0}; uint32_t maxIndex = 0;
+  void flush() { if (open) { rayHist[rayMax < 64u ? rayMax : 64u]++; rays++; if (rayMax > maxIndex) maxIndex = rayMax; } open = false; rayMax = 0; }
+  void event(int what, uint32_t k) {
+    if (what == 0) { flush(); open = true; }
+    else if (what == 1) { if (k > rayMax) rayMax = k; }
+    else handHist[k < 64u ? k : 64u]++;
+  }
+};
+static thread_local StackProbe* t_stackProbe = nullptr;
+#define YART_STACK_PROBE(what, k) do { if (t_stackProbe) t_stackProbe->event((what), (k)); } while (0)
 
 #include "../../oracle/kat_common.hpp"
 #include "../../oracle/params.hpp"
@@ -40,12 +59,32 @@ struct Ctx {
   RenderConst rc;
 };
 
-static PathCtx pathCtx(const Ctx& c, uint64_t* stack) {
+// The traversal stacks of `lanes` threads, laid out as the kernels lay them out: the first `split` entries of a lane in one
+// block ("LDS"), the rest in another ("spill"), both lane-interleaved (entry k of lane t at block[k * stride + t], stride > 1).
+// The blocks are heap allocations of exactly split * stride and (bound - split) * stride words, so that under
+// AddressSanitizer an index past either one is a report. bound = the scene's stack bound (host_scene.hpp), at least the
+// reference's 64. YART_HOSTSIM_LDS_STACK (read here only) sets the split; without it every entry is in the first block, as before.
+// YART_HOSTSIM_STACK_BOUND overrides the bound (tests: the area sized one entry short must be reported).
+struct StackMem {
+  uint32_t split, bound, stride;
+  std::unique_ptr<uint64_t[]> lds, spill;
+  StackMem(const Ctx& c, unsigned lanes) {
+    bound = std::max(kRefStackDepth, c.im.stackBound);
+    if (const char* e = std::getenv("YART_HOSTSIM_STACK_BOUND")) bound = uint32_t(std::atoi(e));
+    split = bound;
+    if (const char* e = std::getenv("YART_HOSTSIM_LDS_STACK")) split = std::min(bound, uint32_t(std::max(1, std::atoi(e))));
+    stride = std::max(2u, lanes);
+    lds.reset(new uint64_t[size_t(split) * stride]);
+    spill.reset(new uint64_t[size_t(bound - split) * stride]);
+  }
+};
+
+static PathCtx pathCtx(const Ctx& c, const StackMem& m, unsigned lane) {
   PathCtx px;
   px.sc = &c.sc;
   px.sobol = reinterpret_cast<const uint32_t*>(c.sc.lut + LutDev::sobol);
-  px.stk.lds = stack; px.stk.ldsStride = 1; px.stk.ldsDepth = kRefStackDepth;
-  px.stk.spill = nullptr; px.stk.spillStride = 0;
+  px.stk.lds = m.lds.get() + lane; px.stk.ldsStride = m.stride; px.stk.ldsDepth = m.split;
+  px.stk.spill = m.spill.get() + lane; px.stk.spillStride = m.stride;
   px.rc = c.rc;
   return px;
 }
@@ -116,8 +155,8 @@ static int doKat(Ctx& c, const params::Params& p, const std::string& outPath) {
     }
     w.u64("bvh", out);
   }
-  uint64_t stack[kRefStackDepth];
-  PathCtx px = pathCtx(c, stack);
+  StackMem stackMem(c, 1);
+  PathCtx px = pathCtx(c, stackMem, 0);
   {
     std::vector<float> fo, ro6;
     std::vector<int64_t> io;
@@ -246,18 +285,32 @@ static int doKat(Ctx& c, const params::Params& p, const std::string& outPath) {
   return 0;
 }
 
-static int doRender(Ctx& c, const params::Params& p, const std::string& outPath) {
+// need(leaf) = 0, need(inner) = 1 + max(need(left), need(right)) of every mesh, through the function scene creation uses
+static std::string meshNeedsJson(const Ctx& c) {
+  std::string s = "[";
+  for (size_t m = 0; m < c.im.meshes.size(); m++) {
+    const MeshDev& md = c.im.meshes[m];
+    s += (m ? ", " : "") + std::to_string(bvhStackNeed(c.im.bvhNodes.data() + md.nodeOffset, md.nNodes));
+  }
+  return s + "]";
+}
+
+static int doRender(Ctx& c, const params::Params& p, const std::string& outPath, bool stackcheck = false) {
   const uint32_t W = p.width, H = p.height;
   std::vector<float> img(size_t(W) * H * 4, 0.0f);
   std::atomic<uint32_t> nextRow{0};
   std::atomic<uint64_t> totalRays{0};
   unsigned nt = p.threads ? p.threads : std::thread::hardware_concurrency();
   auto t0 = std::chrono::high_resolution_clock::now();
+  StackMem stackMem(c, nt);
+  StackProbe total;
+  std::mutex totalLock;
   std::vector<std::thread> th;
   for (unsigned t = 0; t < nt; t++)
-    th.emplace_back([&] {
-      uint64_t stack[kRefStackDepth];
-      PathCtx px = pathCtx(c, stack);
+    th.emplace_back([&, t] {
+      PathCtx px = pathCtx(c, stackMem, t);
+      StackProbe probe;
+      if (stackcheck) t_stackProbe = &probe;
       uint32_t rays = 0;
       int m = gmonBuckets(int32_t(p.spp));
       for (;;) {
@@ -279,6 +332,13 @@ static int doRender(Ctx& c, const params::Params& p, const std::string& outPath)
         }
       }
       totalRays += rays;
+      if (stackcheck) {
+        t_stackProbe = nullptr;
+        probe.flush();
+        std::lock_guard<std::mutex> g(totalLock);
+        total.rays += probe.rays; total.maxIndex = std::max(total.maxIndex, probe.maxIndex);
+        for (int k = 0; k < 65; k++) { total.rayHist[k] += probe.rayHist[k]; total.handHist[k] += probe.handHist[k]; }
+      }
     });
   for (auto& t : th) t.join();
   double sec = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
@@ -286,8 +346,75 @@ static int doRender(Ctx& c, const params::Params& p, const std::string& outPath)
   if (!f) return 2;
   std::fwrite(img.data(), 4, img.size(), f);
   std::fclose(f);
+  if (stackcheck) {
+    auto hist = [](const uint64_t* h) {
+      std::string s = "[";
+      for (int k = 0; k < 65; k++) s += (k ? ", " : "") + std::to_string(h[k]);
+      return s + "]";
+    };
+    std::printf("{\"stackcheck\": \"ok\", \"mesh_need\": %s, \"tlas_height\": %u, \"stack_bound\": %u, \"lds_entries\": %u, \"spill_entries\": %u, "
+                "\"traversals\": %llu, \"max_stack_index\": %u, \"ray_max_hist\": %s, \"handover_hist\": %s, \"rays\": %llu}\n",
+                meshNeedsJson(c).c_str(), c.im.tlasHeight, c.im.stackBound, stackMem.split, stackMem.bound - stackMem.split,
+                (unsigned long long) total.rays, total.maxIndex, hist(total.rayHist).c_str(), hist(total.handHist).c_str(),
+                (unsigned long long) totalRays.load());
+    return 0;
+  }
   std::printf("{\"rays\": %llu, \"seconds\": %.6f, \"msamples_per_s\": %.6f, \"threads\": %u}\n",
               (unsigned long long) totalRays.load(), sec, double(W) * H * p.spp / sec * 1e-6, nt);
+  return 0;
+}
+
+// stackbound: the stack bound of scene creation (host_scene.hpp: bvhStackNeed + checkStackBound) on a synthetic node array — a
+// chain of `levels` inner nodes, each with a leaf and the next inner node as children. Finite f32 geometry does not drive the
+// reference's builder far past the limit, a node array does.
+static int doStackBound(unsigned levels) {
+  std::vector<BvhNode> nodes(size_t(levels) * 2 + 1, BvhNode{});
+  for (unsigned k = 0; k < levels; k++) {
+    nodes[2 * k].leftFirst = 2 * k + 1; nodes[2 * k].span = 0;       // children at 2k + 1 (leaf), 2k + 2 (the chain goes on)
+    nodes[2 * k + 1].leftFirst = k; nodes[2 * k + 1].span = 1;
+  }
+  nodes[2 * size_t(levels)].leftFirst = levels; nodes[2 * size_t(levels)].span = 1;
+  const uint32_t need = bvhStackNeed(nodes.data(), nodes.size());
+  std::string msg;
+  try { checkStackBound(need, 0); } catch (const std::invalid_argument& e) { msg = e.what(); }
+  std::printf("{\"stackbound\": \"ok\", \"levels\": %u, \"need\": %u, \"cap\": %u, \"refused\": %s, \"message\": \"%s\"}\n",
+              levels, need, kMaxStackBound, msg.empty() ? "false" : "true", msg.c_str());
+  return 0;
+}
+
+// stackops: stackPush / Pop / Peek / Poke of csrc/traverse.hpp on three interleaved lanes with `split` entries in one heap block
+// and bound - split in another (exact sizes: an index past either is an AddressSanitizer report), against a plain array.
+static int doStackOps(unsigned split, unsigned bound) {
+  const unsigned lanes = 3;
+  std::unique_ptr<uint64_t[]> lds(new uint64_t[size_t(split) * lanes]), spill(new uint64_t[size_t(bound - split) * lanes]);
+  for (size_t k = 0; k < size_t(split) * lanes; k++) lds[k] = ~0ull;
+  for (size_t k = 0; k < size_t(bound - split) * lanes; k++) spill[k] = ~0ull;
+  TravStack st[lanes];
+  for (unsigned l = 0; l < lanes; l++) {
+    st[l].lds = lds.get() + l; st[l].ldsStride = lanes; st[l].ldsDepth = split;
+    st[l].spill = spill.get() + l; st[l].spillStride = lanes;
+  }
+  auto node = [](unsigned l, unsigned k, unsigned gen) { return (l + 1u) * 100000u + k * 7u + gen; };
+  auto dist = [](unsigned l, unsigned k, unsigned gen) { return float(l) * 1000.0f + float(k) + 0.25f * float(gen); };
+  auto word = [&](unsigned l, unsigned k, unsigned gen) {
+    return uint64_t(node(l, k, gen)) | (uint64_t(__builtin_bit_cast(uint32_t, dist(l, k, gen))) << 32);
+  };
+  auto fail = [&](const char* what, unsigned l, unsigned k) { std::fprintf(stderr, "stackops: %s, lane %u entry %u (split %u)\n", what, l, k, split); return 3; };
+  for (unsigned k = 0; k < bound; k++)
+    for (unsigned l = 0; l < lanes; l++) stackPush(st[l], k, node(l, k, 0), dist(l, k, 0));
+  for (unsigned l = 0; l < lanes; l++)
+    for (unsigned k = 0; k < bound; k++) if (stackPeek(st[l], k) != word(l, k, 0)) return fail("peek after push", l, k);
+  for (unsigned k = 0; k < bound; k++)
+    for (unsigned l = 0; l < lanes; l++) if ((k + l) % 2u) stackPoke(st[l], k, word(l, k, 1));
+  for (unsigned l = 0; l < lanes; l++)
+    for (unsigned k = bound; k-- > 0;) {
+      uint32_t n; float d;
+      stackPop(st[l], k, n, d);
+      const unsigned gen = (k + l) % 2u;
+      if (n != node(l, k, gen) || d != dist(l, k, gen)) return fail("pop after poke", l, k);
+      if (stackPeek(st[l], k) != word(l, k, gen)) return fail("peek after poke", l, k);
+    }
+  std::printf("{\"stackops\": \"ok\", \"split\": %u, \"bound\": %u}\n", split, bound);
   return 0;
 }
 
@@ -546,6 +673,12 @@ static int doLoadStress(const char* scenePath, unsigned callers) {
 
 int main(int argc, char** argv) {
   if (argc == 2 && std::string(argv[1]) == "selftest") return doSelfTest();
+  if (argc == 3 && std::string(argv[1]) == "stackbound") return doStackBound(unsigned(std::atoi(argv[2])));
+  if (argc == 4 && std::string(argv[1]) == "stackops") {     // split 0: every split from 1 to the bound
+    const unsigned split = unsigned(std::atoi(argv[2])), bound = unsigned(std::atoi(argv[3]));
+    for (unsigned k = split ? split : 1u; k <= (split ? split : bound); k++) if (int rc = doStackOps(k, bound)) return rc;
+    return 0;
+  }
   if (argc == 4 && std::string(argv[1]) == "loadstress") return doLoadStress(argv[2], unsigned(std::atoi(argv[3])));
   if (argc == 4 && std::string(argv[1]) == "bvhcheck") return doBvhCheck(argv[2], unsigned(std::atoi(argv[3])));
   if (argc == 6 && std::string(argv[1]) == "estimator")
@@ -553,7 +686,7 @@ int main(int argc, char** argv) {
   if (argc == 8 && std::string(argv[1]) == "tonemap")
     return doTonemap(argv[2], unsigned(std::atoi(argv[3])), unsigned(std::atoi(argv[4])), argv[5], argv[6], argv[7]);
   if (argc != 5) {
-    std::fprintf(stderr, "usage: hostsim kat|render <scene.yscn> <params.txt> <out>\n");
+    std::fprintf(stderr, "usage: hostsim kat|render|stackcheck <scene.yscn> <params.txt> <out>\n");
     return 1;
   }
   try {
@@ -569,6 +702,7 @@ int main(int argc, char** argv) {
     std::string mode = argv[1];
     if (mode == "kat") return doKat(c, p, argv[4]);
     if (mode == "render") return doRender(c, p, argv[4]);
+    if (mode == "stackcheck") return doRender(c, p, argv[4], true);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "hostsim: %s\n", e.what());
     return 2;

@@ -53,5 +53,5 @@ def test_big_leaves_on_device(built, tmp_path):
             want = np.fromfile(ref, np.float32).reshape(img.shape)
         same = float(np.mean(np.all(img.view(np.uint32) == want.view(np.uint32), axis=-1)))
         print(f"stacked leaves / {name}: identical_pixels={same:.4f}")
-        assert same > 0.999, name
+        assert np.array_equal(img.view(np.uint32), want.view(np.uint32)), name      # (measured on an MI355X: every pixel, every pipeline)
     scene.close()

@@ -52,6 +52,10 @@ struct HostImage {
   std::vector<float> envData;
   std::vector<uint32_t> envGuide;                  // CDF search guide tables (EnvDev::guideOffset)
   std::vector<f4> nodeWorld;                       // conservative world-space node boxes (traverse.hpp)
+  // Traversal stack entries a walk of this scene can hold at once: the largest bvhStackNeed over the meshes (and the height of
+  // the top-level hierarchy, which is walked on the same stack), 0 for a scene of single-leaf meshes. The spill area of the
+  // kernels' stacks is sized from it.
+  uint32_t stackBound = 0, tlasHeight = 0;
   std::vector<TlasNode> tlas;                      // spatial hierarchy over the mesh nodes' boxes (scenes of 64 nodes and more)
   std::vector<uint32_t> infiniteLights, areaLights;
   std::vector<float> areaPowerCdf;
@@ -157,6 +161,29 @@ inline void appendLutFootprints(std::vector<float>& lut) {
         o[2] = at(LutDev::baseEavg, (i + 1) * 16 + j); o[3] = at(LutDev::baseEavg, (i + 1) * 16 + j1);
       }
   }
+}
+
+// The traversal stack a tree can need: need(leaf) = 0, need(inner) = 1 + max(need(left), need(right)) — a walk pushes at most
+// one entry per inner node on the way down. Children are allocated after their parent (bvh_build.hpp, bvh_build_device.inc),
+// so one sweep from the last node to the first does it without recursion (hostile meshes make trees thousands deep).
+// `nodes` as the builders return them (plain leftFirst) or as the device image holds them (flag bits above kLinkIndexMask).
+inline uint32_t bvhStackNeed(const BvhNode* nodes, size_t n) {
+  std::vector<uint32_t> need(n, 0u);
+  for (size_t k = n; k-- > 0;) {
+    if (nodes[k].span > 0) continue;
+    const size_t l = nodes[k].leftFirst & kLinkIndexMask;
+    if (l <= k || l + 1 >= n) throw std::invalid_argument("bvh: child link does not point behind its node");
+    need[k] = 1u + std::max(need[l], need[l + 1]);
+  }
+  return n ? need[0] : 0u;
+}
+// The deepest tree a scene may hold: the level limit of the device builder (bvh_build_device.inc; the host builder has none).
+// Up to here the spill area grows with the scene; past it scene creation fails before anything is launched.
+constexpr uint32_t kMaxStackBound = 192;
+inline void checkStackBound(uint32_t need, uint32_t mesh) {
+  if (need > kMaxStackBound)
+    throw std::invalid_argument("mesh " + std::to_string(mesh) + ": its BVH is " + std::to_string(need) +
+                                " levels deep, the traversal stack holds at most " + std::to_string(kMaxStackBound));
 }
 
 inline HostImage buildHostImage(const YartSceneDesc& d, MeshBvhFn bvhFn = nullptr, void* bvhCtx = nullptr) {
@@ -312,6 +339,11 @@ inline HostImage buildHostImage(const YartSceneDesc& d, MeshBvhFn bvhFn = nullpt
       b.nodes = std::move(hb.nodes); b.indices = std::move(hb.indices);
     }
     md.nNodes = uint32_t(b.nodes.size());
+    {
+      const uint32_t need = bvhStackNeed(b.nodes.data(), b.nodes.size());
+      checkStackBound(need, uint32_t(im.meshes.size()));
+      im.stackBound = std::max(im.stackBound, need);
+    }
     im.bvhNodes.insert(im.bvhNodes.end(), b.nodes.begin(), b.nodes.end());
     for (uint32_t k = 0; k < m.n_faces; k++) {
       uint32_t t = b.indices[k];
@@ -500,7 +532,10 @@ inline HostImage buildHostImage(const YartSceneDesc& d, MeshBvhFn bvhFn = nullpt
       };
       im.tlas.resize(2 * ids.size() - 1);
       uint32_t used = 1;
-      std::function<void(uint32_t, uint32_t, uint32_t)> build = [&](uint32_t at, uint32_t lo, uint32_t hi) {
+      // (median splits: a range of n ids is ceil(log2 n) levels high, 32 at the very most — far below the 64 entries every
+      // scene's stack has; checked below all the same, since the query pushes on the lane's traversal stack unguarded)
+      std::function<void(uint32_t, uint32_t, uint32_t, uint32_t)> build = [&](uint32_t at, uint32_t lo, uint32_t hi, uint32_t level) {
+        im.tlasHeight = std::max(im.tlasHeight, level);
         TlasNode t{};
         for (int c = 0; c < 3; c++) { t.lo[c] = kInf; t.hi[c] = -kInf; }
         float cmin[3] = {kInf, kInf, kInf}, cmax[3] = {-kInf, -kInf, -kInf};
@@ -517,9 +552,11 @@ inline HostImage buildHostImage(const YartSceneDesc& d, MeshBvhFn bvhFn = nullpt
                          [&](uint32_t x, uint32_t y) { const float cx = centre(x, axis), cy = centre(y, axis); return cx < cy || (cx == cy && x < y); });
         t.a = used; t.b = 0; used += 2;
         im.tlas[at] = t;
-        build(t.a, lo, mid); build(t.a + 1, mid, hi);
+        build(t.a, lo, mid, level + 1); build(t.a + 1, mid, hi, level + 1);
       };
-      build(0, 0, uint32_t(ids.size()));
+      build(0, 0, uint32_t(ids.size()), 0);
+      require(im.tlasHeight <= 32u, "top-level hierarchy: higher than a median split can make it");
+      im.stackBound = std::max(im.stackBound, im.tlasHeight);
     }
   }
   if (im.tlas.empty()) im.tlas.resize(1);

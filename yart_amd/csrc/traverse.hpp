@@ -14,8 +14,10 @@
 //    and siblings adjacent), a leaf visit streams 48-byte LeafTri records;
 //  * the 64-entry traversal stack lives in LDS, lane-interleaved (8-byte
 //    entries: node index + entry distance), with a global-memory spill area for
-//    the entries beyond LDS_STACK — no overflow is possible up to the
-//    reference's own fixed depth of 64;
+//    the entries beyond LDS_STACK, sized at scene creation from the scene's stack
+//    bound (host_scene.hpp: the deepest mesh tree, at least the reference's own
+//    fixed depth of 64; a mesh past kMaxStackBound is refused there) — the walk
+//    itself checks nothing;
 //  * only (t, u, v, slot, node) is tracked during the walk; normals, uvs,
 //    tangents and the object->world chain are evaluated once for the final hit.
 #pragma once
@@ -87,7 +89,12 @@ struct TravStack {
   // resume records of this launch (null: every hand-over is a restart): written by the lean kernels, read by the general ones
   f4* rec = nullptr; uint32_t* recCursor = nullptr; uint32_t recCap = 0;
 };
+// Host test builds (tests/hostsim) define YART_STACK_PROBE to record stack indices; in every other build it is empty.
+#if !defined(YART_STACK_PROBE)
+#define YART_STACK_PROBE(what, k) ((void)0)
+#endif
 YART_HD void stackPush(const TravStack& s, uint32_t k, uint32_t node, float d) {
+  YART_STACK_PROBE(1, k + 1u);
   uint32_t db = __builtin_bit_cast(uint32_t, d);
   uint64_t e = uint64_t(node) | (uint64_t(db) << 32);
   if (k < s.ldsDepth) s.lds[k * s.ldsStride] = e;
@@ -258,6 +265,7 @@ YART_HD bool traverseMesh(const SceneDev& sc, const MeshDev& mesh, uint32_t node
         if ((MODE & TRAV_FAST) &&
             (tr.matFlags & ((NEE && !(occludedBefore || didHit)) ? (MAT_HAS_ALPHA | MAT_TRANSPARENT) : MAT_HAS_ALPHA))) {
           actx.deferred = true;
+          YART_STACK_PROBE(2, stackIdx);
           return false;
         }
         // (lean shadow walk, already occluded: the interval stays what it was at the first hit — see the leaf loop's end)
@@ -370,6 +378,7 @@ YART_HD bool traverseScene(const SceneDev& sc, f3 o, f3 d, float tMin, HitRec& h
   bool didHit = false;
   uint32_t i = 0;
   YART_COUNT(nTrav, 1);
+  YART_STACK_PROBE(0, 0u);
   NodeRayCache cache;
   RayO ray;
   bool rayIsWorld = false;       // `ray` holds makeRay(o + 0, d + 0): shared by every identity-chain node

@@ -364,6 +364,18 @@ __global__ void __launch_bounds__(kBlock) k_tex_quads(TexQuadArgs a) {
 #if YART_TU == 0
 #include "aov_kernels.inc"
 #include "bvh_build_device.inc"
+
+namespace {
+static_assert(devbvh::kMaxLevels == int(kMaxStackBound), "the stack bound's cap is the device builder's level limit");
+// Spill entries per lane for a scene: what they always were (the reference's 64-entry stack) unless one of the scene's trees
+// needs more (host_scene.hpp: HostImage::stackBound, at most kMaxStackBound — deeper meshes do not get past scene creation).
+// wholeStack: the area is sized for the whole stack (the render kernels: their LDS parts differ, the shallowest has 8 entries);
+// otherwise for what lies beyond the kLdsStack entries of the probe kernels.
+static size_t spillDepthFor(const HostImage& im, bool wholeStack) {
+  if (wholeStack) return size_t(std::max<uint32_t>(uint32_t(kSpillDepthMax), im.stackBound));
+  return size_t(std::max<int>(kSpillDepth, int(im.stackBound) - kLdsStack));
+}
+}  // namespace
 #endif
 
 #if YART_TU != 0
@@ -755,7 +767,7 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
   int gridMax = std::max(gridMega, std::max(gridExtend, gridShadow));
   gridMax = std::max(gridMax, std::max(gridExtendFast, gridShadowFast));
   gridMax = std::max(gridMax, std::max(gridRetryE, gridRetryS));
-  s.spill.ensure(size_t(gridMax) * kBlock * kSpillDepthMax);
+  s.spill.ensure(size_t(gridMax) * kBlock * spillDepthFor(s.host, true));
   // the lanes' node bitsets of the top-level-hierarchy form (trace_lean_tlas.hpp): all zero between launches
   const uint32_t nodeBitWords = nodesForm == 3 ? uint32_t((s.host.nodes.size() + 63u) / 64u) : 0u;
   if (nodeBitWords) {
@@ -797,7 +809,7 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
     // the resume records' per-wave ranges and the traversal spill area — taken off the budget first.
     const uint64_t perPath = (compact ? 251 : 176) + ((p.flags & YART_FLAG_NO_RESUME) ? 0 : (kResumeWords * 16 + 7) / 8);
     const uint64_t dimsEst = std::min<uint32_t>(256u, (4u + 8u * p.max_depth + 16u + 7u) & ~7u);
-    const uint64_t fixedB = uint64_t(nPix) * dimsEst * 8 + uint64_t(gridMax) * kBlock * (kResumeWords * 16 + uint64_t(kSpillDepthMax) * 8);
+    const uint64_t fixedB = uint64_t(nPix) * dimsEst * 8 + uint64_t(gridMax) * kBlock * (kResumeWords * 16 + uint64_t(spillDepthFor(s.host, true)) * 8);
     const uint64_t budget = (uint64_t(freeB) + held) * 8 / 10;
     const uint64_t avail = budget > fixedB ? budget - fixedB : 0;
     if (!pool) {
@@ -1610,7 +1622,7 @@ int yart_hip_probe_samples(YartScene* scene, const YartCameraDesc* cam, const Ya
     YartScene& s = *scene;
     HIP_CHECK(hipSetDevice(s.device));
     const int grid = int((n + kBlock - 1) / kBlock);
-    s.spill.ensure(size_t(grid) * kBlock * kSpillDepth);
+    s.spill.ensure(size_t(grid) * kBlock * spillDepthFor(s.host, false));
     s.probeIn.ensure(size_t(n) * 3); s.probeOut.ensure(size_t(n) * 3); s.counters.ensure(8);
     HIP_CHECK(hipMemcpy(s.probeIn.p, xys, size_t(n) * 3 * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemset(s.counters.p, 0, 8 * sizeof(unsigned long long)));
@@ -1637,7 +1649,7 @@ int yart_hip_probe_hits(YartScene* scene, uint32_t n, const float* rays, float* 
     YartScene& s = *scene;
     HIP_CHECK(hipSetDevice(s.device));
     const int grid = int((n + kBlock - 1) / kBlock);
-    s.spill.ensure(size_t(grid) * kBlock * kSpillDepth);
+    s.spill.ensure(size_t(grid) * kBlock * spillDepthFor(s.host, false));
     DevBuf<float> in, res;
     in.ensure(size_t(n) * 6); res.ensure(size_t(n) * 16);
     HIP_CHECK(hipMemcpy(in.p, rays, size_t(n) * 6 * 4, hipMemcpyHostToDevice));

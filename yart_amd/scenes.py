@@ -13,6 +13,7 @@ the vocabulary of ``oracle/params.hpp``.
 * :func:`sponza_class`  — C3/C4: env-lit atrium, ≈262k triangles, textured.
 * :func:`mclaren_class` — C5: clearcoat / thin-glass / chrome body with DoF.
 * :func:`deep_instances` — scene graphs nested to any depth (:func:`fuzz_deep_case`: seeded ones).
+* :func:`deep_tree`      — one mesh whose BVH is a chain of a chosen depth (the traversal stack's seams).
 """
 from __future__ import annotations
 
@@ -777,6 +778,82 @@ def many_records(width=96, height=96, spp=4, depth=5, n_materials=80, n_lights=1
         b.quad((x0, 9.9, 1.0), (x0 + 0.4, 9.9, 1.0), (x0 + 0.4, 9.9, 1.5), (x0, 9.9, 1.5), e)
     s.add_node(s.add_mesh(b.build()))
     s.create_area_lights()
+    return s, p
+
+
+def chain_mesh(levels, materials, alpha_levels=(), alpha_material=None, ratio=24.0):
+    """One mesh whose BVH, as the reference's 20-bin SAH builder makes it, is a chain of `levels` inner nodes: every split
+    separates ONE triangle from the rest, and a ray through the middle of the mesh is inside both children's boxes at every
+    level, the rest's box first — it holds `levels` traversal-stack entries when it reaches the bottom leaf.
+
+    levels + 2 long triangles (the last two share the bottom leaf) through the cube [-1, 1]^3, triangle i along axis i % 3. Its vertices are (-B, +B, s) on that axis
+    and sum to exactly 0 on the other two, so the builder's centroid ((v0 + v1) + v2) / 3 is s / 3 on the triangle's own axis
+    and 0 elsewhere — independent of its size. s grows by `ratio` (> 20: the builder's bins per axis) from one triangle of an axis to
+    the next: of the triangles of a node, the one with the largest s stands alone in the last bin of its axis and all others
+    share the first, on all three axes — cutting off one triangle is the only kind of split the builder can see, and the
+    cheapest of the three is the shortest triangle (B shrinks with i), the last. The positions keep the range of f32: s runs
+    from 0.75 down by ratio ** (levels // 3), the box areas stay near 100. About 80 levels fit above the smallest normal f32.
+
+    alpha_levels: the triangle a walk tests while it holds that many entries (the one cut off at inner level k + 1, popped
+    with k entries left) gets `alpha_material` — a fast walk that hits it hands its ray over with k entries."""
+    n = levels + 2
+    jmax = (n - 1) // 3
+    smin = 0.75 / float(ratio) ** jmax
+    if not smin > 1e-37:
+        raise ValueError(f"chain_mesh: {levels} levels do not fit the range of f32 (ratio {ratio})")
+    b = MeshBuilder()
+    for i in range(n):
+        a, j = i % 3, i // 3
+        B = 3.0 + 0.05 * (n - 1 - i)
+        sgn = 1.0 if j % 2 == 0 else -1.0
+        sv = np.float32(smin * float(ratio) ** j)
+        v = np.array([[-B, -sgn, -1.0], [B, sgn, -1.0], [sv, 0.0, 2.0]], np.float32)
+        v = np.roll(v, a, axis=1)                       # the long axis becomes a
+        e1, e2 = v[1].astype(np.float64) - v[0], v[2].astype(np.float64) - v[0]
+        nrm = np.cross(e1, e2); nrm /= np.linalg.norm(nrm)
+        tg = e1 / np.linalg.norm(e1)
+        held = n - 1 - i                                # entries left on the stack when this triangle's leaf is popped
+        mat = alpha_material if (held in alpha_levels and alpha_material is not None) else materials[i % len(materials)]
+        b.add(v, nrm, [*tg, 1.0], np.array([[0, 0], [1, 0], [0.5, 1]], np.float32), [[0, 1, 2]], mat)
+    return b.build()
+
+
+def deep_tree(levels, alpha_levels=(), width=48, height=48, spp=4, bounces=4, instances=0, seed=3, tex=32):
+    """A floor, a back wall and a quad light (one mesh) and :func:`chain_mesh` in front of them: camera rays, shadow rays and
+    bounce rays walk a tree whose stack need is exactly `levels` (the tests measure it: tests/hostsim stackcheck).
+    instances = 0: the chain mesh under an identity node at the origin (the identity walk). instances = n: n instances of it
+    under rotated, non-uniformly scaled nodes of a translated group — the general walk through the same depths, and with
+    enough of them the many-node forms of the lean kernels."""
+    s = Scene()
+    rng = np.random.RandomState(seed)
+    white = s.add_material(_white())
+    light = s.add_material(Material(base=(0.78, 0.78, 0.78), roughness=1.0, emission=(12.0, 11.0, 9.0)))
+    mats = [s.add_material(Material(base=c, roughness=r, metallic=m)) for c, r, m in
+            (((0.8, 0.25, 0.2), 1.0, 0.0), ((0.2, 0.7, 0.3), 0.5, 0.0), ((0.25, 0.35, 0.9), 0.3, 1.0), ((0.85, 0.8, 0.3), 0.8, 0.0))]
+    # alpha strictly between 0 and 1 everywhere: every candidate draws, none is decided without a draw
+    alpha = (64 + 128 * _noise(tex, 21)).astype(np.uint8)
+    cut = s.add_material(Material(base=(1, 1, 1), roughness=0.7,
+                                  tex_base=s.add_texture(tex_base_color(tex, 20, (0.5, 0.2, 0.6), (0.9, 0.7, 0.9), alpha=alpha))))
+    room = MeshBuilder()
+    room.quad((-14, -4, 14), (14, -4, 14), (14, -4, -14), (-14, -4, -14), white)
+    room.quad((-14, -4, -9), (14, -4, -9), (14, 14, -9), (-14, 14, -9), white)
+    room.quad((-2.5, 11, -2.5), (2.5, 11, -2.5), (2.5, 11, 2.5), (-2.5, 11, 2.5), light)
+    s.add_node(s.add_mesh(room.build()))
+    chain = s.add_mesh(chain_mesh(levels, mats, tuple(alpha_levels), cut))
+    if instances == 0:
+        s.add_node(chain)
+    else:
+        group = s.add_node(-1, 0, *trs(translation=(0.0, 0.3, 0.0), axis=(0, 1, 0), angle=0.2))
+        for k in range(instances):
+            ax = rng.normal(size=3); ax /= np.linalg.norm(ax)
+            far = 0.0 if k == 0 else 1.0
+            t = (far * rng.uniform(-9, 9), far * rng.uniform(-2, 7), far * rng.uniform(-7, 3))
+            sc = tuple(rng.uniform(0.45, 0.9, 3) * (1.0 if k == 0 else 0.35))
+            s.add_node(chain, group, *trs(translation=t, axis=ax, angle=float(rng.uniform(0.3, 2.5)), scale=sc))
+    s.create_area_lights()
+    p = dict(size=(width, height), spp=spp, depth=bounces, focal=35.0, fnumber=0.0,
+             eye=(2.5, 2.0, 11.0), target=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), exposure=0.0,
+             background=(0.05, 0.06, 0.08))
     return s, p
 
 
