@@ -381,6 +381,18 @@ int yart_hip_probe_samples(YartScene* scene, const YartCameraDesc* cam, const Ya
  * out receives sum(pattern) floats per case. use_tables != 0: through the per-render sampler tables the wavefront kernels read. */
 int yart_hip_probe_sampler(YartScene* scene, uint32_t spp, uint32_t tile, uint32_t n, const uint32_t* cases, uint32_t n_draws,
                            const uint8_t* pattern, int use_tables, float* out);
+/* Diagnostic: one math function of the device code at a time, on device 0, without a scene: the inline functions the render
+ * kernels call (csrc/ymath.hpp ysinf / ycosf / ysinf2pi / ycosf2pi / ylogf / yexpf, csrc/tonemap.hpp ylog2f / ypowf), the fp32
+ * divide and square root as the kernels are compiled, and reverseBits32 (operand and result are raw 32-bit words in float slots).
+ * Range form: fn at bit_cast<float>(first_bits + i), i < count (count <= 2^28, the range may not wrap); y is the exponent of
+ * YART_MATH_POWF and ignored otherwise; YART_MATH_DIV has no range form. Pairs form: explicit operands a[i], b[i] (b may be
+ * NULL for the one-operand functions; for YART_MATH_POWF b holds the exponents). out_host receives one float per input. */
+enum YartMathFn {
+  YART_MATH_SINF = 0, YART_MATH_COSF = 1, YART_MATH_SINF_2PI = 2, YART_MATH_COSF_2PI = 3, YART_MATH_LOGF = 4, YART_MATH_EXPF = 5,
+  YART_MATH_LOG2F = 6, YART_MATH_POWF = 7, YART_MATH_DIV = 8, YART_MATH_SQRT = 9, YART_MATH_BREV = 10, YART_MATH_COUNT = 11
+};
+int yart_hip_probe_math(int fn, uint32_t first_bits, uint64_t count, float y, float* out_host);
+int yart_hip_probe_math_pairs(int fn, uint64_t n, const float* a, const float* b, float* out_host);
 /* closest hit of n world rays (ox,oy,oz,dx,dy,dz) -> 16 floats each:
  * hit, t, u, v, px,py,pz, nx,ny,nz, tx,ty,tz, triIdx, lightIdx, backSide */
 int yart_hip_probe_hits(YartScene* scene, uint32_t n, const float* rays, float* out);

@@ -560,6 +560,83 @@ static int doSelfTest() {
   return 0;
 }
 
+// libm: the device's libm emulation (csrc/ymath.hpp libm_emul, compiled for the host: __builtin_fma is libm's correctly rounded
+// fma here) against this machine's libm, bit for bit (NaN == NaN), over the domains tests/test_device_math.py sweeps on the GPU at
+// full density — here at a stride, with the windows of +-4096 bit patterns around every branch constant and the special values
+// always at full density. log2f / powf (libm_pow.hpp) have their sweep in `selftest`.
+namespace libmcheck {
+typedef float (*Fn)(float);
+struct Sweep { const char* name; Fn emul; Fn volatile libm; uint64_t checked = 0, bad = 0; };
+static uint32_t fbits(float f) { return __builtin_bit_cast(uint32_t, f); }
+static void one(Sweep& s, uint32_t bits) {
+  const float x = __builtin_bit_cast(float, bits);
+  const float a = s.emul(x), b = s.libm(x);
+  s.checked++;
+  if (fbits(a) == fbits(b) || (a != a && b != b)) return;
+  if (s.bad++ < 8) std::fprintf(stderr, "libm: %s(%a = 0x%08x): emulation 0x%08x, this machine's libm 0x%08x\n", s.name, x, bits, fbits(a), fbits(b));
+}
+// [lo, hi] at `stride`, both ends included; with `bothSigns` the mirrored negative range too
+static void range(Sweep& s, uint32_t lo, uint32_t hi, uint32_t stride, bool bothSigns) {
+  for (uint64_t b = lo; b <= hi; b += stride) { one(s, uint32_t(b)); if (bothSigns) one(s, uint32_t(b) | 0x80000000u); }
+  one(s, hi); if (bothSigns) one(s, hi | 0x80000000u);
+}
+static void window(Sweep& s, float c) {
+  const uint32_t b = fbits(c);
+  range(s, b - 4096u, b + 4096u, 1, true);
+}
+static void specials(Sweep& s) {
+  const uint32_t sp[] = {0u, 0x80000000u, 1u, 0x80000001u, 0x007fffffu, 0x807fffffu, 0x00800000u, 0x80800000u, 0x7f7fffffu, 0xff7fffffu,
+                         0x7f800000u, 0xff800000u, 0x7fc00000u, 0xffc00000u, 0x7f800001u, 0x7fffffffu};
+  for (uint32_t b : sp) one(s, b);
+}
+}  // namespace libmcheck
+
+static int doLibmCheck() {
+  using namespace libmcheck;
+  const uint32_t twoPi = fbits(0x1.921fb6p+2f), fltMax = 0x7f7fffffu;
+  Sweep sw[6] = {{"sinf", libm_emul::sinf_, sinf}, {"cosf", libm_emul::cosf_, cosf}, {"sinf (2 pi form)", libm_emul::sinf2pi_, sinf},
+                 {"cosf (2 pi form)", libm_emul::cosf2pi_, cosf}, {"logf", libm_emul::logf_, logf}, {"expf", libm_emul::expf_, expf}};
+  for (int k = 0; k < 4; k++) {
+    Sweep& s = sw[k];
+    range(s, 0u, twoPi, 167, false);                              // the reachable domain [0, 2 pi]
+    window(s, 0x1p-12f); window(s, 0x1.921FB6p-1f);
+    range(s, twoPi - 4096u, twoPi, 1, false);
+    if (k >= 2) continue;                                         // the 2 pi forms are defined on [0, 120) only
+    range(s, twoPi, fbits(120.0f) - 1u, 64 * 7, true);
+    window(s, 120.0f);
+    range(s, fbits(120.0f), fltMax, 4096 * 3, true);              // the |x| >= 120 tail
+    specials(s);
+  }
+  {
+    Sweep& s = sw[4];
+    range(s, 0u, 0x3f800000u, 89, false);                        // [+0, 1]: the sampler's values
+    range(s, 0u, 4096u, 1, false); window(s, 0x1p-126f); window(s, 1.0f); window(s, 0x1.66p-1f);
+    range(s, 0x3f800000u, fltMax, 64 * 61, false);
+    range(s, 0x80000000u, 0xff800000u, 65536 * 3 + 1, false);     // negative: NaN
+    specials(s);
+  }
+  {
+    Sweep& s = sw[5];
+    range(s, fbits(0x1p-40f), fbits(104.0f), 37, true);
+    window(s, 80.0f); window(s, 88.0f); window(s, 0x1.62e42ep6f); window(s, 0x1.9fe368p6f); window(s, 0x1.9d1d9ep6f); window(s, 104.0f);
+    range(s, 0u, fbits(0x1p-40f), 4096, true);                    // +-0, denormals, tiny
+    range(s, fbits(104.0f), fltMax, 4096, true);
+    specials(s);
+    one(s, 0x4202422fu); one(s, 0xc27c65d9u);                     // the two inputs a product rounded before "z - kd" gets wrong (ymath.hpp expf_)
+  }
+  uint64_t checked = 0, bad = 0;
+  for (const Sweep& s : sw) { checked += s.checked; bad += s.bad; }
+  if (bad) {
+    std::fprintf(stderr, "libm: %llu of %llu results of the device's libm emulation differ from this machine's libm. Either csrc/ymath.hpp was "
+                 "edited, or this machine's glibc selects other sinf / cosf / logf / expf variants than the FMA forms of glibc 2.35 the emulation "
+                 "states (the YART_ALLOW_LIBM_DRIFT scenario): then the frame tests' bit identity cannot hold here either.\n",
+                 (unsigned long long) bad, (unsigned long long) checked);
+    return 3;
+  }
+  std::printf("{\"libm\": \"ok\", \"checked\": %llu}\n", (unsigned long long) checked);
+  return 0;
+}
+
 // tonemap: csrc/tonemap.hpp (the device functions, compiled for the host) over an RGBA32F file
 static int doTonemap(const char* in, unsigned w, unsigned h, const std::string& look, const char* outF32, const char* outPpm) {
   std::vector<float> px(size_t(w) * h * 4);
@@ -673,6 +750,7 @@ static int doLoadStress(const char* scenePath, unsigned callers) {
 
 int main(int argc, char** argv) {
   if (argc == 2 && std::string(argv[1]) == "selftest") return doSelfTest();
+  if (argc == 2 && std::string(argv[1]) == "libm") return doLibmCheck();
   if (argc == 3 && std::string(argv[1]) == "stackbound") return doStackBound(unsigned(std::atoi(argv[2])));
   if (argc == 4 && std::string(argv[1]) == "stackops") {     // split 0: every split from 1 to the bound
     const unsigned split = unsigned(std::atoi(argv[2])), bound = unsigned(std::atoi(argv[3]));

@@ -47,6 +47,11 @@ def test_null_arguments_are_rejected(built):
     assert L.yart_hip_scene_create(None, 0, None) == api.YART_E_INVALID
     assert L.yart_hip_render(None, None, None, None, None) == api.YART_E_INVALID
     assert b"null" in L.yart_hip_last_error()
+    # the math probe validates before it touches a device
+    assert L.yart_hip_probe_math(0, 0, 16, 0.0, None) == api.YART_E_INVALID
+    assert L.yart_hip_probe_math(api.MATH_FNS["brev"] + 1, 0, 16, 0.0, None) == api.YART_E_INVALID
+    assert L.yart_hip_probe_math_pairs(api.MATH_FNS["div"], 16, None, None, None) == api.YART_E_INVALID
+    assert b"probe_math" in L.yart_hip_last_error()
 
 
 def test_product_does_not_reference_oracle():

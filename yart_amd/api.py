@@ -228,7 +228,8 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_tonemap_agx", "yart_hip_encode_rgb8", "yart_hip_tonemap_host",
            "yart_hip_multi_create", "yart_hip_multi_load", "yart_hip_multi_destroy", "yart_hip_multi_device_count", "yart_hip_multi_failed_devices",
            "yart_hip_multi_render", "yart_hip_multi_render_tiles", "yart_hip_multi_rccl_selftest",
-           "yart_hip_render_aovs", "yart_hip_render_aovs_device", "yart_hip_probe_camera_rays"]
+           "yart_hip_render_aovs", "yart_hip_render_aovs_device", "yart_hip_probe_camera_rays",
+           "yart_hip_probe_math", "yart_hip_probe_math_pairs"]
 
 LIB_COUNT_PATH = os.path.join(_HERE, "libyart_hip_count.so")   # instrumented twin (exact test counters)
 _libs = {}
@@ -283,6 +284,8 @@ def lib(instrumented: bool = False):
                                                   C.POINTER(AovBuffers), C.c_void_p, C.POINTER(Stats)]
         L.yart_hip_probe_camera_rays.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint32,
                                                  C.c_void_p, C.c_void_p]
+        L.yart_hip_probe_math.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_float, C.c_void_p]
+        L.yart_hip_probe_math_pairs.argtypes = [C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.yart_hip_bvh_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.yart_hip_bvh_copy.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         _libs[path] = L
@@ -292,6 +295,40 @@ def lib(instrumented: bool = False):
 def _check(code, L=None):
     if code != YART_OK:
         raise YartError(code, (L or lib()).yart_hip_last_error().decode())
+
+
+# enum YartMathFn (include/yart_hip.h): what yart_hip_probe_math[_pairs] evaluates
+MATH_FNS = {"sinf": 0, "cosf": 1, "sinf2pi": 2, "cosf2pi": 3, "logf": 4, "expf": 5, "log2f": 6, "powf": 7, "div": 8, "sqrt": 9,
+            "brev": 10}
+
+
+def probe_math(fn, first_bits=None, count=None, y=0.0, a=None, b=None, out=None):
+    """One math function of the device code (csrc/ymath.hpp, csrc/tonemap.hpp; ``fn`` a key of MATH_FNS) on device 0.
+    Range form: ``first_bits`` and ``count`` — fn at every float whose bits are first_bits + i; ``y`` is powf's exponent.
+    Pairs form: ``a`` (and ``b``) — arrays of float32 values or uint32 bit patterns. Returns the results as a uint32 array
+    of bit patterns (``out``, if given: a C-contiguous uint32 / float32 array of that many elements, is filled and returned)."""
+    L = lib()
+    code = MATH_FNS[fn]
+
+    def words(v):
+        v = np.asarray(v)
+        if v.dtype != np.uint32:
+            v = v.astype(np.float32)
+        return np.ascontiguousarray(v).reshape(-1)
+    if a is None:
+        n = int(count)
+        res = np.empty(n, np.uint32) if out is None else out
+        assert res.size == n and res.itemsize == 4 and res.flags.c_contiguous
+        _check(L.yart_hip_probe_math(code, int(first_bits), n, float(y), res.ctypes.data_as(C.c_void_p)), L)
+    else:
+        wa = words(a)
+        wb = None if b is None else words(b)
+        assert wb is None or wb.size == wa.size
+        res = np.empty(wa.size, np.uint32) if out is None else out
+        assert res.size == wa.size and res.itemsize == 4 and res.flags.c_contiguous
+        _check(L.yart_hip_probe_math_pairs(code, wa.size, wa.ctypes.data_as(C.c_void_p),
+                                           None if wb is None else wb.ctypes.data_as(C.c_void_p), res.ctypes.data_as(C.c_void_p)), L)
+    return res
 
 
 def bvh_build(positions, faces, device=None, threads=0):

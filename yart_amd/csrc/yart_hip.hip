@@ -326,6 +326,33 @@ __global__ void __launch_bounds__(kBlock) k_probe_hits(ProbeHitArgs a) {
   }
 }
 
+// the math the frames rest on, one function at a time (diagnostic, yart_hip_probe_math[_pairs]): the very inline functions the
+// render kernels call (ymath.hpp, libm_pow.hpp via tonemap.hpp) and the fp32 divide / sqrt / bit reversal as this build compiles them
+struct ProbeMathArgs { int fn; uint32_t firstBits; uint64_t n; float y; const float* a; const float* b; float* out; };
+YART_HD float probeMathEval(int fn, float a, float b) {   // (host + device only so that the host pass resolves the names)
+  switch (fn) {
+    case YART_MATH_SINF: return ysinf(a);
+    case YART_MATH_COSF: return ycosf(a);
+    case YART_MATH_SINF_2PI: return ysinf2pi(a);
+    case YART_MATH_COSF_2PI: return ycosf2pi(a);
+    case YART_MATH_LOGF: return ylogf(a);
+    case YART_MATH_EXPF: return yexpf(a);
+    case YART_MATH_LOG2F: return ylog2f(a);
+    case YART_MATH_POWF: return ypowf(a, b);
+    case YART_MATH_DIV: return a / b;
+    case YART_MATH_SQRT: return sqrtf(a);
+    default: return __builtin_bit_cast(float, reverseBits32(__builtin_bit_cast(uint32_t, a)));   // YART_MATH_BREV
+  }
+}
+__global__ void __launch_bounds__(kBlock) k_probe_math(ProbeMathArgs q) {
+  const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
+  for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < q.n; i += stride) {
+    const float a = q.a ? q.a[i] : __builtin_bit_cast(float, q.firstBits + uint32_t(i));
+    const float b = q.b ? q.b[i] : q.y;
+    q.out[i] = probeMathEval(q.fn, a, b);
+  }
+}
+
 // 2x2 footprint records of one texture (scene_types.hpp TexDev::quadOffset), expanded on the device at upload from the plain
 // texel arrays: record (x, y) = the four taps texture.cpp:21-35 reads for a lookup whose base texel is (x, y)
 struct TexQuadArgs { const uint8_t* u8; const float* f32; TexDev t; uint8_t* out; };
@@ -1723,6 +1750,43 @@ int yart_hip_probe_sampler(YartScene* scene, uint32_t spp, uint32_t tile, uint32
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(out, dOut.p, size_t(n) * nOut * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+namespace {
+constexpr uint64_t kProbeMathMax = 1ull << 28;   // results per call: 1 GiB of device memory
+void probeMath(int fn, uint32_t firstBits, uint64_t n, float y, const float* a, const float* b, float* out) {
+  HIP_CHECK(hipSetDevice(0));
+  DevBuf<float> dA, dB, dOut;
+  dOut.ensure(size_t(n));
+  if (a) { dA.ensure(size_t(n)); HIP_CHECK(hipMemcpy(dA.p, a, size_t(n) * 4, hipMemcpyHostToDevice)); }
+  if (b) { dB.ensure(size_t(n)); HIP_CHECK(hipMemcpy(dB.p, b, size_t(n) * 4, hipMemcpyHostToDevice)); }
+  ProbeMathArgs q{};
+  q.fn = fn; q.firstBits = firstBits; q.n = n; q.y = y; q.a = dA.p; q.b = dB.p; q.out = dOut.p;
+  const uint64_t blocks = std::min<uint64_t>((n + kBlock - 1) / kBlock, 1u << 16);
+  hipLaunchKernelGGL(k_probe_math, dim3(uint32_t(blocks)), dim3(kBlock), 0, nullptr, q);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipDeviceSynchronize());
+  HIP_CHECK(hipMemcpy(out, dOut.p, size_t(n) * 4, hipMemcpyDeviceToHost));
+}
+}  // namespace
+
+int yart_hip_probe_math(int fn, uint32_t first_bits, uint64_t count, float y, float* out_host) {
+  return guarded([&] {
+    require(fn >= 0 && fn < YART_MATH_COUNT, "probe_math: unknown function");
+    require(fn != YART_MATH_DIV, "probe_math: the divide takes explicit operands (yart_hip_probe_math_pairs)");
+    require(out_host && count > 0 && count <= kProbeMathMax, "probe_math: null output, count == 0 or count > 2^28");
+    require(uint64_t(first_bits) + count <= (1ull << 32), "probe_math: the range runs past the last bit pattern");
+    probeMath(fn, first_bits, count, y, nullptr, nullptr, out_host);
+  });
+}
+
+int yart_hip_probe_math_pairs(int fn, uint64_t n, const float* a, const float* b, float* out_host) {
+  return guarded([&] {
+    require(fn >= 0 && fn < YART_MATH_COUNT, "probe_math_pairs: unknown function");
+    require(a && out_host && n > 0 && n <= kProbeMathMax, "probe_math_pairs: null pointer, n == 0 or n > 2^28");
+    require(b || (fn != YART_MATH_DIV && fn != YART_MATH_POWF), "probe_math_pairs: this function takes a second operand");
+    probeMath(fn, 0, n, 0.0f, a, b, out_host);
   });
 }
 

@@ -238,21 +238,31 @@ YART_HD f3 invOctahedralUV(f2 uv) {                            // math.hpp:168-1
 // ---------------------------------------------------------------------------
 // Transcendentals. The reference calls libm's sinf / cosf / logf / expf (pixel
 // jitter, disk / hemisphere / VNDF sampling, volume attenuation). On the host
-// the library calls the same libm. On the device the same results are produced
-// by evaluating glibc 2.35's algorithms (the ARM "optimized routines" float
-// functions: a double-precision polynomial after a table / quadrant reduction,
-// in the FMA-contracted form x86-64 glibc selects on FMA-capable CPUs), which
-// were checked here against libm.so.6 over every float in [0,100] (sin, cos:
-// 1.12e9 inputs, 0 mismatches), [1e-30,1e30] (log: 1.67e9, 0 mismatches) and
-// |x| in [1e-10,80] (exp: 6.6e8, 2 mismatches). ocml's own sinf/cosf differ
-// from glibc's in the last bit for roughly a quarter of the inputs, which is
-// what made rare paths diverge; these do not.
+// the library calls the same libm (ysinf ... yexpf below). On the device the same
+// results are produced by evaluating glibc 2.35's algorithms (the ARM "optimized
+// routines" float functions: a double-precision polynomial after a table /
+// quadrant reduction, in the FMA-contracted form x86-64 glibc selects on
+// FMA-capable CPUs). ocml's own sinf / cosf differ from glibc's in the last bit
+// for roughly a quarter of the inputs, which is what made rare paths diverge.
+//
+// libm_emul compiles for the host as well (there __builtin_fma is libm's fma),
+// under names that are not the libm-backed ones: tests/hostsim `libm` runs it
+// against the machine's libm without a GPU. What is ASSERTED, on the device, bit
+// for bit against the libm of the machine the test runs on, zero mismatches
+// (tests/test_device_math.py through yart_hip_probe_math):
+//   sinf_, cosf_, sinf2pi_, cosf2pi_  every float of [+0, 2 pi] (every caller's range), the 2pi forms also
+//                                     against sinf_ / cosf_ themselves
+//   sinf_, cosf_                      [2 pi, 120) and (-120, -0] at every 64th float, the windows around the
+//                                     branch constants, |x| >= 120 (reduceLarge) at every 4096th, inf, NaN
+//   logf_                             every float of [+0, 1]; (1, FLT_MAX] at every 64th, negative, inf, NaN
+//   expf_                             every float with 2^-40 <= |x| <= 104; 0, denormals, the rest strided, inf, NaN
+// The two expf inputs an earlier sweep found one ulp low (0x1.04845ep+5, -0x1.f8cbb2p+5) came from rounding
+// InvLn2N * x before subtracting kd; libm's FMA build contracts the two (expf_ below). They are fixed, not pinned.
 // ---------------------------------------------------------------------------
-#if defined(__HIP_DEVICE_COMPILE__)
 namespace libm_emul {
 struct SinCosTab { double c0, c1, c2, c3, c4, s1, s2, s3; };
-__device__ __forceinline__ uint32_t top12(float x) { return (__builtin_bit_cast(uint32_t, x) >> 20) & 0x7ffu; }
-__device__ __forceinline__ float poly(double x, double x2, bool neg, int n) {
+YART_HD uint32_t top12(float x) { return (__builtin_bit_cast(uint32_t, x) >> 20) & 0x7ffu; }
+YART_HD float poly(double x, double x2, bool neg, int n) {
   // __sincosf_table[neg]: the second table negates the cosine coefficients
   const double sg = neg ? -1.0 : 1.0;
   if ((n & 1) == 0) {
@@ -273,13 +283,33 @@ __device__ __forceinline__ float poly(double x, double x2, bool neg, int n) {
     return float(__builtin_fma(x6, cc2, c));
   }
 }
-__device__ __forceinline__ double reduceFast(double x, int& n) {
+YART_HD double reduceFast(double x, int& n) {
   double r = x * 0x1.45F306DC9C883p+23;
   n = (int32_t(r) + 0x800000) >> 24;
   return __builtin_fma(-double(n), 0x1.921FB54442D18p0, x);
 }
-__device__ __forceinline__ double quadSign(int n) { return ((n & 3) == 1 || (n & 3) == 2) ? -1.0 : 1.0; }
-__device__ __forceinline__ float sinf_(float y) {
+YART_HD double quadSign(int n) { return ((n & 3) == 1 || (n & 3) == 2) ? -1.0 : 1.0; }
+// |x| >= 120 (sincosf.h reduce_large): the product of the 24-bit mantissa with a 96-bit window of 4/pi (__inv_pio4: the bits of
+// 4/pi, one entry per byte offset), in integers; the top two bits of the fraction are the quadrant, the rest times pi/2^63 the angle
+YART_HD double reduceLarge(uint32_t xi, int& n) {
+  const uint32_t P[24] = {
+    0x000000a2u, 0x0000a2f9u, 0x00a2f983u, 0xa2f9836eu, 0xf9836e4eu, 0x836e4e44u, 0x6e4e4415u, 0x4e441529u,
+    0x441529fcu, 0x1529fc27u, 0x29fc2757u, 0xfc2757d1u, 0x2757d1f5u, 0x57d1f534u, 0xd1f534ddu, 0xf534ddc0u,
+    0x34ddc0dbu, 0xddc0db62u, 0xc0db6295u, 0xdb629599u, 0x6295993cu, 0x95993c43u, 0x993c4390u, 0x3c439041u};
+  const uint32_t* arr = &P[(xi >> 26) & 15u];
+  const uint32_t shift = (xi >> 23) & 7u;
+  xi = ((xi & 0xffffffu) | 0x800000u) << shift;
+  uint64_t res0 = uint64_t(uint32_t(xi * arr[0]));       // the low word only: the bits above it are whole turns
+  const uint64_t res1 = uint64_t(xi) * arr[4];
+  const uint64_t res2 = uint64_t(xi) * arr[8];
+  res0 = (res2 >> 32) | (res0 << 32);
+  res0 += res1;
+  const uint64_t q = (res0 + (1ull << 61)) >> 62;
+  res0 -= q << 62;
+  n = int(q);
+  return double(int64_t(res0)) * 0x1.921FB54442D18p-62;
+}
+YART_HD float sinf_(float y) {
   double x = y;
   if (top12(y) < top12(0x1.921FB6p-1f)) {
     if (top12(y) < top12(0x1p-12f)) return y;
@@ -288,10 +318,16 @@ __device__ __forceinline__ float sinf_(float y) {
     int n;
     x = reduceFast(x, n);
     return poly(x * quadSign(n), x * x, (n & 2) != 0, n);
+  } else if (top12(y) < top12(kInf)) {
+    const uint32_t xi = __builtin_bit_cast(uint32_t, y);
+    int n;
+    x = reduceLarge(xi, n);
+    const int m = n + int(xi >> 31);                            // the sign of y turns the quadrant's sign
+    return poly(x * quadSign(m), x * x, (m & 2) != 0, n);
   }
-  return float(sin(double(y)));
+  return __builtin_nanf("");                                    // __math_invalidf: inf, NaN
 }
-__device__ __forceinline__ float cosf_(float y) {
+YART_HD float cosf_(float y) {
   double x = y;
   if (top12(y) < top12(0x1.921FB6p-1f)) {
     if (top12(y) < top12(0x1p-12f)) return 1.0f;
@@ -300,10 +336,16 @@ __device__ __forceinline__ float cosf_(float y) {
     int n;
     x = reduceFast(x, n);
     return poly(x * quadSign(n + 1), x * x, ((n + 1) & 2) != 0, n ^ 1);
+  } else if (top12(y) < top12(kInf)) {
+    const uint32_t xi = __builtin_bit_cast(uint32_t, y);
+    int n;
+    x = reduceLarge(xi, n);
+    const int m = n + int(xi >> 31);
+    return poly(x * quadSign(m), x * x, (m & 2) != 0, n ^ 1);
   }
-  return float(cos(double(y)));
+  return __builtin_nanf("");
 }
-__device__ __forceinline__ float logf_(float x) {
+YART_HD float logf_(float x) {
   const double T[16][2] = {
     {0x1.661ec79f8f3bep+0, -0x1.57bf7808caadep-2}, {0x1.571ed4aaf883dp+0, -0x1.2bef0a7c06ddbp-2},
     {0x1.49539f0f010bp+0, -0x1.01eae7f513a67p-2},  {0x1.3c995b0b80385p+0, -0x1.b31d8a68224e9p-3},
@@ -335,7 +377,7 @@ __device__ __forceinline__ float logf_(float x) {
   y = __builtin_fma(y, r2, y0 + r);
   return float(y);
 }
-__device__ __forceinline__ float expf_(float x) {
+YART_HD float expf_(float x) {
   const uint64_t T[32] = {
     0x3ff0000000000000ull, 0x3fefd9b0d3158574ull, 0x3fefb5586cf9890full, 0x3fef9301d0125b51ull,
     0x3fef72b83c7d517bull, 0x3fef54873168b9aaull, 0x3fef387a6e756238ull, 0x3fef1e9df51fdee1ull,
@@ -345,7 +387,14 @@ __device__ __forceinline__ float expf_(float x) {
     0x3feeace5422aa0dbull, 0x3feeb737b0cdc5e5ull, 0x3feec49182a3f090ull, 0x3feed503b23e255dull,
     0x3feee89f995ad3adull, 0x3feeff76f2fb5e47ull, 0x3fef199bdd85529cull, 0x3fef3720dcef9069ull,
     0x3fef5818dcfba487ull, 0x3fef7c97337b9b5full, 0x3fefa4afa2a490daull, 0x3fefd0765b6e4540ull};
-  if (!(fabsf(x) < 80.0f)) return float(exp(double(x)));        // overflow / underflow / NaN tails
+  const uint32_t abstop = top12(x);
+  if (abstop >= top12(88.0f)) {                                  // e_expf.c: |x| >= 88 or NaN
+    if (__builtin_bit_cast(uint32_t, x) == 0xff800000u) return 0.0f;
+    if (abstop >= top12(kInf)) return x + x;
+    if (x > 0x1.62e42ep6f) return kInf;                          // x > log(2^128): __math_oflowf
+    if (x < -0x1.9fe368p6f) return 0.0f;                         // x < log(2^-150): __math_uflowf
+    if (x < -0x1.9d1d9ep6f) return 0x1p-149f;                    // x < log(2^-149): __math_may_uflowf, 0x1.4p-75f squared
+  }                                                              // in between the polynomial, rounded once from double (subnormals too)
   const double InvLn2N = 0x1.71547652b82fep+0 * 32, SHIFT = 0x1.8p+52;
   const double C0 = 0x1.c6af84b912394p-5 / 32 / 32 / 32, C1 = 0x1.ebfce50fac4f3p-3 / 32 / 32,
                C2 = 0x1.62e42ff0c52d6p-1 / 32;
@@ -353,7 +402,10 @@ __device__ __forceinline__ float expf_(float x) {
   double kd = z + SHIFT;
   uint64_t ki = __builtin_bit_cast(uint64_t, kd);
   kd -= SHIFT;
-  double r = z - kd;
+  // "r = z - kd" of the source is contracted with z's product in the FMA build of libm: r = InvLn2N * x - kd, rounded once.
+  // With the product rounded first, 2 of the 7.8e8 floats with 2^-40 <= |x| <= 104 come out one ulp low (0x1.04845ep+5,
+  // -0x1.f8cbb2p+5: tests/test_device_math.py names them)
+  double r = __builtin_fma(InvLn2N, double(x), -kd);
   uint64_t t = T[ki % 32] + (ki << 47);
   double s = __builtin_bit_cast(double, t);
   z = __builtin_fma(C0, r, C1);
@@ -362,12 +414,9 @@ __device__ __forceinline__ float expf_(float x) {
   y = __builtin_fma(z, r2, y);
   return float(y * s);
 }
-}  // namespace libm_emul
 // Arguments known to lie in [0, 2 pi] (2 pi u with a sampler value u in [0, 1)): the same two branches without the
-// |x| >= 120 tail, whose double-precision sin / cos (Payne-Hanek reduction, ~700 fp64 instructions inlined per call site)
-// can never run for them. NOT valid outside [0, 120).
-__device__ __forceinline__ float ysinf2pi(float y) {
-  using namespace libm_emul;
+// |x| >= 120 tail, which can never run for them. NOT valid outside (-120, 120); asserted equal to sinf_ / cosf_ on [0, 2 pi].
+YART_HD float sinf2pi_(float y) {
   double x = y;
   if (top12(y) < top12(0x1.921FB6p-1f)) {
     if (top12(y) < top12(0x1p-12f)) return y;
@@ -377,8 +426,7 @@ __device__ __forceinline__ float ysinf2pi(float y) {
   x = reduceFast(x, n);
   return poly(x * quadSign(n), x * x, (n & 2) != 0, n);
 }
-__device__ __forceinline__ float ycosf2pi(float y) {
-  using namespace libm_emul;
+YART_HD float cosf2pi_(float y) {
   double x = y;
   if (top12(y) < top12(0x1.921FB6p-1f)) {
     if (top12(y) < top12(0x1p-12f)) return 1.0f;
@@ -388,6 +436,10 @@ __device__ __forceinline__ float ycosf2pi(float y) {
   x = reduceFast(x, n);
   return poly(x * quadSign(n + 1), x * x, ((n + 1) & 2) != 0, n ^ 1);
 }
+}  // namespace libm_emul
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ float ysinf2pi(float x) { return libm_emul::sinf2pi_(x); }
+__device__ __forceinline__ float ycosf2pi(float x) { return libm_emul::cosf2pi_(x); }
 __device__ __forceinline__ float ysinf(float x) { return libm_emul::sinf_(x); }
 __device__ __forceinline__ float ycosf(float x) { return libm_emul::cosf_(x); }
 __device__ __forceinline__ float ylogf(float x) { return libm_emul::logf_(x); }
