@@ -4,9 +4,11 @@
 //   (frontend main.cpp:263-275 -> output/ppm.cpp:7-21). No window: the frontend is out of scope.
 //
 //   g++ -std=c++17 -Iinclude examples/render_gltf.cpp -Lyart_amd -lyart_hip -Wl,-rpath,$PWD/yart_amd -lpthread -o render_gltf
-//   ./render_gltf asset.glb sky_oct.hdr out.ppm [width height spp depth  eye(3) target(3)  focal fnumber exposure look  aov_prefix]
+//   ./render_gltf asset.glb sky_oct.hdr out.ppm [width height spp depth  eye(3) target(3)  focal fnumber exposure look  aov_prefix  denoised.ppm]
 // aov_prefix: also render the first-hit feature buffers (yart_hip_render_aovs) and write <prefix>_albedo.ppm, <prefix>_normal.ppm
 // (n * 0.5 + 0.5) and <prefix>_depth.ppm (t / the frame's largest t) through the same 8-bit encoding.
+// denoised.ppm: also filter that render's linear frame with the à-trous filter (yart::hip::denoise: default parameters, the three
+// guides, demodulated), tonemap it with `look` and write it there.
 #include <cstdio>
 #include <cstdlib>
 #include <stdexcept>
@@ -17,7 +19,7 @@
 
 int main(int argc, char** argv) {
   if (argc < 4) {
-    std::fprintf(stderr, "usage: %s asset.glb env_oct.hdr|- out.ppm [w h spp depth ex ey ez tx ty tz focal fnumber exposure look aov_prefix]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s asset.glb env_oct.hdr|- out.ppm [w h spp depth ex ey ez tx ty tz focal fnumber exposure look aov_prefix denoised.ppm]\n", argv[0]);
     return 1;
   }
   auto num = [&](int i, double dflt) { return argc > i ? std::atof(argv[i]) : dflt; };
@@ -73,6 +75,18 @@ int main(int argc, char** argv) {
       write("albedo", [&](size_t i, int c) { return a.albedo[3 * i + c]; });
       write("normal", [&](size_t i, int c) { return a.normal[3 * i + c] * 0.5f + 0.5f; });
       write("depth", [&](size_t i, int) { return tMax > 0.0f ? a.depth[i] / tMax : 0.0f; });
+      if (argc > 19) {
+        std::vector<float> clean = yart::hip::denoise(a.rgba, w, h, yart::hip::DenoiseGuides{a.albedo, a.normal, a.depth},
+                                                      yart::hip::denoiseDefaults(true));
+        if (renderer.tonemapLook >= 0)
+          yart::hip::check(yart_hip_tonemap_host(clean.data(), w, h, renderer.tonemapLook, clean.data(), nullptr));
+        yart::hip::check(yart_hip_tonemap_host(clean.data(), w, h, -1, nullptr, rgb8.data()));
+        FILE* g = std::fopen(argv[19], "wb");
+        if (!g) throw std::runtime_error(std::string("cannot create ") + argv[19]);
+        std::fprintf(g, "P6\n%u %u\n255\n", w, h);
+        std::fwrite(rgb8.data(), 1, rgb8.size(), g);
+        std::fclose(g);
+      }
     }
     const auto& st = renderer.stats();
     std::printf("{\"samples\": %zu, \"rays\": %llu, \"ms\": %lld, \"ms_device\": %.1f, \"msamples_per_s\": %.1f}\n", done.totalSamples,

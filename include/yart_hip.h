@@ -433,6 +433,62 @@ int yart_hip_encode_rgb8(const float* d_rgba, uint32_t width, uint32_t height, u
 int yart_hip_tonemap_host(const float* hdr_rgba, uint32_t width, uint32_t height, int look, float* ldr_rgba,
                           uint8_t* rgb8);
 
+/* The stage between yart_hip_render_aovs and yart_hip_tonemap_agx: an edge-avoiding à-trous wavelet filter (Dammertz, Sewtz,
+ * Hanika, Lensch 2010) of the linear-HDR RGBA32F frame, guided by any subset of the albedo, normal and depth feature buffers
+ * (3 / 3 / 1 floats per pixel, as YartAovBuffers holds them; NULL: that guide is not used), entirely on the device.
+ * DEFINITION. Every operation is an individually rounded binary32 operation in the order written (no FMA contraction); expf and
+ * logf have glibc's values (csrc/ymath.hpp yexpf / ylogf). csrc/denoise.hpp states it; yart_amd/denoise.py atrous_reference is
+ * the NumPy statement the tests compare with, on bits.
+ *   Prepare, once per pixel p:
+ *     alb      = albedo(p) with YART_DENOISE_DEMODULATE, else (1, 1, 1) (the albedo buffer is not read at all then)
+ *     d        = alb > 1e-3f ? alb : 1.0f                      per channel
+ *     c_0(p)   = rgb(p) / d                                    per channel
+ *     n(p)     = normal(p);  lz(p) = logf(depth(p) > 1e-30f ? depth(p) : 1e-30f)          (each only if that buffer is given)
+ *     valid(p) = every component of c_0(p) is finite, and of albedo(p) when demodulating, and of normal(p) and depth(p) where given
+ *   Iteration i = 0 .. iterations-1, step s = 1 << i, from image c_i to c_(i+1):
+ *     acc = (0, 0, 0); wsum = 0
+ *     for dy = -2 .. 2 (outer), dx = -2 .. 2 (inner):  q = p + s * (dx, dy)
+ *       q outside the image: skipped (no clamping, no mirroring);  !valid(q): skipped
+ *       h  = k[|dy|] * k[|dx|],  k = {0.375f, 0.25f, 0.0625f}
+ *       dc = (dr * dr + dg * dg) + db * db   over c_i(q) - c_i(p);   dn the same over n(q) - n(p);   dl = lz(q) - lz(p)
+ *       e  = (dc * icol_i + dn * inrm) + (dl * dl) * idep
+ *              icol_i = icol * float(1u << (2 * i)) (the colour sigma halves with every iteration); icol = 1.0f / (sigma_color *
+ *              sigma_color), inrm and idep likewise from their sigmas, each formed once on the host in fp32.
+ *              A term whose sigma is <= 0 or whose buffer is not given does not exist: e is the sum of the others, in this order
+ *              and association (colour and depth only: dc * icol_i + (dl * dl) * idep); no term at all: e = 0.0f.
+ *              !valid(p): e = 0.0f for every tap (the pixel is filled from its valid neighbours; it is no tap of anyone's, its
+ *              own included, in any iteration).
+ *       w  = h * expf(-e)
+ *       acc.r = acc.r + w * c_i(q).r   (a multiply, then an add; g and b likewise);   wsum = wsum + w
+ *     c_(i+1)(p) = acc / wsum per channel; (0, 0, 0) if wsum == 0
+ *   Finish: out.rgb(p) = c_iterations(p) * d per channel, out.a(p) = in.a(p).
+ * iterations == 0 copies the frame (no demodulation round trip). out may be the input frame; it may not overlap a guide buffer.
+ * Memory: 48 bytes per pixel while the call runs — two working-colour images and the guide records {n, lz}, 16 bytes each, allocated
+ * and freed by the library; d is not stored (the finish pass forms it again from the albedo buffer, which the call never writes).
+ * The defaults are the sigmas with the smallest worst-case error over host renders of the two golden scenes, 16 spp filtered against
+ * 1024 spp, all guides, demodulated (profiles/denoise_sigma_sweep.txt: RMSE 0.60 / 0.85 of the unfiltered frame's). */
+#define YART_DENOISE_DEMODULATE 1u          /* divide the frame by the albedo before filtering, multiply after (needs albedo) */
+#define YART_DENOISE_DEFAULT_ITERATIONS 5u
+#define YART_DENOISE_DEFAULT_SIGMA_COLOR 0.5f
+#define YART_DENOISE_DEFAULT_SIGMA_NORMAL 0.5f
+#define YART_DENOISE_DEFAULT_SIGMA_DEPTH 0.3f
+typedef struct YartDenoiseParams {
+  uint32_t struct_size;        /* sizeof(YartDenoiseParams): lets the struct grow without an ABI bump */
+  uint32_t iterations;         /* 0 .. 8 */
+  float sigma_color, sigma_normal, sigma_depth;   /* finite; <= 0: that term is left out */
+  uint32_t flags;              /* YART_DENOISE_* */
+} YartDenoiseParams;
+/* DEVICE pointers (e.g. torch tensors' data_ptr) on `stream` (hipStream_t, may be NULL); returns after completion on that stream.
+ * YART_E_INVALID, with a message and before any device is touched: a NULL d_rgba, d_out_rgba or params; a struct_size smaller than
+ * YartDenoiseParams; iterations > 8; a width or height of 0 (or more than 2^28 pixels); a sigma that is not finite; unknown flags
+ * bits; YART_DENOISE_DEMODULATE without d_albedo. YART_E_NO_DEVICE without a HIP device. */
+int yart_hip_denoise_atrous_device(const float* d_rgba, const float* d_albedo, const float* d_normal, const float* d_depth,
+                                   uint32_t width, uint32_t height, const YartDenoiseParams* params, float* d_out_rgba,
+                                   void* stream);
+/* Same, HOST pointers: the buffers are copied to the current device, filtered there and the frame copied back. */
+int yart_hip_denoise_atrous_host(const float* rgba, const float* albedo, const float* normal, const float* depth, uint32_t width,
+                                 uint32_t height, const YartDenoiseParams* params, float* out_rgba);
+
 const char* yart_hip_last_error(void);
 int yart_hip_abi_version(void);
 int yart_hip_device_count(void);

@@ -104,6 +104,29 @@ class Buffer {
   std::vector<float> data_;
 };
 
+// The à-trous filter between renderAovs and the tonemap (yart_hip_denoise_atrous_host): host vectors in, the filtered frame out.
+// An empty guide vector means that guide is not used.
+struct DenoiseGuides { std::vector<float> albedo, normal, depth; };       // 3 / 3 / 1 floats per pixel
+inline YartDenoiseParams denoiseDefaults(bool demodulate = false) {
+  YartDenoiseParams p{};
+  p.struct_size = uint32_t(sizeof(p)); p.iterations = YART_DENOISE_DEFAULT_ITERATIONS;
+  p.sigma_color = YART_DENOISE_DEFAULT_SIGMA_COLOR; p.sigma_normal = YART_DENOISE_DEFAULT_SIGMA_NORMAL;
+  p.sigma_depth = YART_DENOISE_DEFAULT_SIGMA_DEPTH; p.flags = demodulate ? YART_DENOISE_DEMODULATE : 0u;
+  return p;
+}
+inline std::vector<float> denoise(const std::vector<float>& rgba, uint32_t width, uint32_t height, const DenoiseGuides& guides,
+                                  const YartDenoiseParams& params) {
+  const size_t n = size_t(width) * height;
+  if (rgba.size() != n * 4 || (!guides.albedo.empty() && guides.albedo.size() != n * 3) ||
+      (!guides.normal.empty() && guides.normal.size() != n * 3) || (!guides.depth.empty() && guides.depth.size() != n))
+    throw Error(YART_E_INVALID, "denoise: a buffer does not have width * height * channels floats");
+  std::vector<float> out(rgba.size());
+  check(yart_hip_denoise_atrous_host(rgba.data(), guides.albedo.empty() ? nullptr : guides.albedo.data(),
+                                     guides.normal.empty() ? nullptr : guides.normal.data(),
+                                     guides.depth.empty() ? nullptr : guides.depth.data(), width, height, &params, out.data()));
+  return out;
+}
+
 // The scene replicated on several GPUs of this node (yart_hip_multi_*): TileRenderer's worker pool with a GPU per worker.
 class MultiDeviceScene {
  public:

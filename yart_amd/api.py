@@ -24,6 +24,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import yscn
+from .denoise import (DEFAULT_ITERATIONS, DEFAULT_SIGMA_COLOR, DEFAULT_SIGMA_DEPTH, DEFAULT_SIGMA_NORMAL, FLAG_DEMODULATE,
+                      atrous_reference)  # noqa: F401 (atrous_reference: the NumPy statement of denoise / denoise_into)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libyart_hip.so")
@@ -192,6 +194,18 @@ def reduce_aov_coverage(hit, samples=None):
     return (hit.sum(axis=-1).astype(np.float32) / np.float32(n)).astype(np.float32)
 
 
+class DenoiseParams(C.Structure):
+    """YartDenoiseParams (include/yart_hip.h): the knobs of the à-trous filter."""
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("sigma_color", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
+
+
+def make_denoise_params(iterations=DEFAULT_ITERATIONS, sigma_color=DEFAULT_SIGMA_COLOR, sigma_normal=DEFAULT_SIGMA_NORMAL,
+                        sigma_depth=DEFAULT_SIGMA_DEPTH, demodulate=False) -> DenoiseParams:
+    return DenoiseParams(C.sizeof(DenoiseParams), int(iterations), float(sigma_color), float(sigma_normal), float(sigma_depth),
+                         FLAG_DEMODULATE if demodulate else 0)
+
+
 class ImportOptions(C.Structure):
     """YartImportOptions (include/yart_hip.h): the environment the frontend adds after gltf::load."""
     _fields_ = [("env_hdr_path", C.c_char_p), ("env_radius", C.c_float), ("uniform_env", C.c_uint32),
@@ -229,7 +243,8 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_multi_create", "yart_hip_multi_load", "yart_hip_multi_destroy", "yart_hip_multi_device_count", "yart_hip_multi_failed_devices",
            "yart_hip_multi_render", "yart_hip_multi_render_tiles", "yart_hip_multi_rccl_selftest",
            "yart_hip_render_aovs", "yart_hip_render_aovs_device", "yart_hip_probe_camera_rays",
-           "yart_hip_probe_math", "yart_hip_probe_math_pairs"]
+           "yart_hip_probe_math", "yart_hip_probe_math_pairs",
+           "yart_hip_denoise_atrous_device", "yart_hip_denoise_atrous_host"]
 
 LIB_COUNT_PATH = os.path.join(_HERE, "libyart_hip_count.so")   # instrumented twin (exact test counters)
 _libs = {}
@@ -286,6 +301,10 @@ def lib(instrumented: bool = False):
                                                  C.c_void_p, C.c_void_p]
         L.yart_hip_probe_math.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_float, C.c_void_p]
         L.yart_hip_probe_math_pairs.argtypes = [C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.yart_hip_denoise_atrous_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                     C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p]
+        L.yart_hip_denoise_atrous_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                   C.POINTER(DenoiseParams), C.c_void_p]
         L.yart_hip_bvh_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.yart_hip_bvh_copy.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         _libs[path] = L
@@ -571,6 +590,24 @@ class DeviceScene:
                                                    C.byref(ab), sp, C.byref(st)), self._L)
         return st.asdict()
 
+    def render_denoised(self, p: dict, iterations=DEFAULT_ITERATIONS, sigma_color=DEFAULT_SIGMA_COLOR,
+                        sigma_normal=DEFAULT_SIGMA_NORMAL, sigma_depth=DEFAULT_SIGMA_DEPTH, demodulate=True, rank=0, world_size=1,
+                        flags=0, device="cuda"):
+        """``render_aovs_into`` for albedo, normal and depth, then the à-trous filter (``denoise_into``) on the same device
+        buffers, on torch's current stream: no host round trip. Returns (noisy frame, denoised frame, {name: guide}) as torch
+        tensors of ``device`` ((H, W, 4); guides (H, W, 3) / (H, W))."""
+        import torch
+        w, h = int(p["size"][0]), int(p["size"][1])
+        noisy = torch.empty((h, w, 4), dtype=torch.float32, device=device)
+        guides = {"albedo": torch.empty((h, w, 3), dtype=torch.float32, device=device),
+                  "normal": torch.empty((h, w, 3), dtype=torch.float32, device=device),
+                  "depth": torch.empty((h, w), dtype=torch.float32, device=device)}
+        stream = torch.cuda.current_stream(noisy.device).cuda_stream
+        self.render_aovs_into(noisy, guides, p, rank, world_size, flags, stream=stream)
+        clean = torch.empty_like(noisy)
+        denoise_into(clean, noisy, guides, iterations, sigma_color, sigma_normal, sigma_depth, demodulate)
+        return noisy, clean, guides
+
     # -- diagnostics ----------------------------------------------------------------
     def probe_camera_rays(self, p: dict, xys: Sequence[Sequence[int]]):
         """The camera ray (origin, direction: 6 floats) of each (x, y, sample), drawn as bounce 0 of that sample draws it."""
@@ -818,6 +855,66 @@ def tonemap(hdr: np.ndarray, look: Optional[str] = "none"):
     _check(lib().yart_hip_tonemap_host(hdr.ctypes.data_as(C.c_void_p), w, h, -1 if look is None else AGX_LOOKS[look],
                                        ldr.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p)))
     return ldr, rgb
+
+
+def denoise(frame, albedo=None, normal=None, depth=None, iterations=DEFAULT_ITERATIONS, sigma_color=DEFAULT_SIGMA_COLOR,
+            sigma_normal=DEFAULT_SIGMA_NORMAL, sigma_depth=DEFAULT_SIGMA_DEPTH, demodulate=None, out=None):
+    """The edge-avoiding à-trous filter (include/yart_hip.h: yart_hip_denoise_atrous_host) of an (H, W, 4) float32 linear-HDR
+    frame on the device, guided by whichever of ``albedo`` (H, W, 3), ``normal`` (H, W, 3) and ``depth`` (H, W) are given;
+    ``demodulate`` divides by the albedo before and multiplies after (None: whenever ``albedo`` is given). ``out``: a C-contiguous float32 array to fill (may be
+    ``frame``). yart_amd.denoise.atrous_reference states the same arithmetic in NumPy."""
+    frame = np.ascontiguousarray(frame, np.float32)
+    h, w = frame.shape[:2]
+    assert frame.shape == (h, w, 4)
+    if demodulate is None:
+        demodulate = albedo is not None
+
+    def guide(a, ch):
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(a, np.float32)
+        assert a.size == h * w * ch
+        return a, a.ctypes.data_as(C.c_void_p)
+    (ka, pa), (kn, pn), (kd, pd) = guide(albedo, 3), guide(normal, 3), guide(depth, 1)
+    if out is None:
+        out = np.empty_like(frame)
+    assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == frame.shape
+    dp = make_denoise_params(iterations, sigma_color, sigma_normal, sigma_depth, demodulate)
+    L = lib()
+    _check(L.yart_hip_denoise_atrous_host(frame.ctypes.data_as(C.c_void_p), pa, pn, pd, w, h, C.byref(dp),
+                                          out.ctypes.data_as(C.c_void_p)), L)
+    return out
+
+
+def denoise_into(out_tensor, frame_tensor, guides=None, iterations=DEFAULT_ITERATIONS, sigma_color=DEFAULT_SIGMA_COLOR,
+                 sigma_normal=DEFAULT_SIGMA_NORMAL, sigma_depth=DEFAULT_SIGMA_DEPTH, demodulate=None, stream=None):
+    """``denoise`` on CUDA/HIP torch tensors through ``data_ptr()`` (yart_hip_denoise_atrous_device): ``frame_tensor`` and
+    ``out_tensor`` (H, W, 4) float32 (they may be the same tensor), ``guides`` a dict with any of "albedo", "normal" (H*W*3
+    elements) and "depth" (H*W). Runs on ``stream`` (a raw hipStream_t), by default torch's current stream of the frame's
+    device, and returns after completion there."""
+    import torch
+    h, w = int(frame_tensor.shape[0]), int(frame_tensor.shape[1])
+    if demodulate is None:
+        demodulate = (guides or {}).get("albedo") is not None
+    ptrs = {}
+    for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1)):
+        t = (guides or {}).get(name)
+        if t is not None:
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == h * w * ch, name
+        ptrs[name] = None if t is None else C.c_void_p(t.data_ptr())
+    unknown = set(guides or {}) - set(ptrs)
+    assert not unknown, f"denoise_into: unknown guides {sorted(unknown)}"
+    for t in (frame_tensor, out_tensor):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4)
+    if stream is None:
+        stream = torch.cuda.current_stream(frame_tensor.device).cuda_stream
+    dp = make_denoise_params(iterations, sigma_color, sigma_normal, sigma_depth, demodulate)
+    L = lib()
+    with torch.cuda.device(frame_tensor.device):
+        _check(L.yart_hip_denoise_atrous_device(C.c_void_p(frame_tensor.data_ptr()), ptrs["albedo"], ptrs["normal"], ptrs["depth"],
+                                                w, h, C.byref(dp), C.c_void_p(out_tensor.data_ptr()),
+                                                C.c_void_p(stream) if stream else None), L)
+    return out_tensor
 
 
 def write_ppm(path, rgb8: np.ndarray):

@@ -46,6 +46,7 @@
 #include "trace_lean_walk.hpp"
 #include "trace_lean_tlas.hpp"
 #include "tonemap.hpp"
+#include "denoise.hpp"
 #include "trace_ranges.hpp"
 
 using namespace yart_hip;
@@ -390,6 +391,7 @@ __global__ void __launch_bounds__(kBlock) k_tex_quads(TexQuadArgs a) {
 #include "wavefront_kernels.inc"
 #if YART_TU == 0
 #include "aov_kernels.inc"
+#include "denoise_kernels.inc"
 #include "bvh_build_device.inc"
 
 namespace {
@@ -1838,6 +1840,95 @@ int yart_hip_tonemap_host(const float* hdr_rgba, uint32_t width, uint32_t height
     HIP_CHECK(hipDeviceSynchronize());
     if (ldr_rgba) HIP_CHECK(hipMemcpy(ldr_rgba, src, n * 16, hipMemcpyDeviceToHost));
     if (rgb8) HIP_CHECK(hipMemcpy(rgb8, bytes.p, n * 3, hipMemcpyDeviceToHost));
+  });
+}
+
+// Edge-avoiding à-trous filter (denoise_kernels.inc). The arguments are judged here, before any device is touched.
+namespace {
+struct DnCall { DnConst k; uint32_t iterations; bool demodulate; };
+DnCall denoiseCheck(const void* rgba, const void* albedo, const void* normal, const void* depth, uint32_t width, uint32_t height,
+                    const YartDenoiseParams* params, const void* out) {
+  require(rgba && out, "denoise: rgba / out pointer is null");
+  require(params != nullptr, "denoise: params pointer is null");
+  require(params->struct_size >= sizeof(YartDenoiseParams), "denoise: struct_size is smaller than YartDenoiseParams");
+  require(params->iterations <= 8u, "denoise: iterations > 8");
+  require(width > 0 && height > 0, "denoise: width or height is 0");
+  require(uint64_t(width) * height <= (1ull << 28), "denoise: more than 2^28 pixels");
+  require(std::isfinite(params->sigma_color) && std::isfinite(params->sigma_normal) && std::isfinite(params->sigma_depth),
+          "denoise: a sigma is not finite");
+  require((params->flags & ~uint32_t(YART_DENOISE_DEMODULATE)) == 0u, "denoise: unknown flags bits");
+  DnCall c;
+  c.iterations = params->iterations;
+  c.demodulate = (params->flags & YART_DENOISE_DEMODULATE) != 0u;
+  require(!c.demodulate || albedo, "denoise: YART_DENOISE_DEMODULATE without an albedo buffer");
+  c.k.icol = dnInvSigma2(params->sigma_color);
+  c.k.inrm = normal ? dnInvSigma2(params->sigma_normal) : 0.0f;
+  c.k.idep = depth ? dnInvSigma2(params->sigma_depth) : 0.0f;
+  c.k.terms = (params->sigma_color > 0.0f ? kDnColor : 0u) | (normal && params->sigma_normal > 0.0f ? kDnNormal : 0u) |
+              (depth && params->sigma_depth > 0.0f ? kDnDepth : 0u);
+  return c;
+}
+
+// device pointers; enqueues on `st` and returns after completion
+void denoiseRun(const DnCall& c, const float* rgba, const float* albedo, const float* normal, const float* depth, uint32_t width,
+                uint32_t height, float* out, hipStream_t st) {
+  const uint32_t n = width * height;
+  if (c.iterations == 0u) {                         // a plain copy: no demodulation round trip
+    if (out != rgba) HIP_CHECK(hipMemcpyAsync(out, rgba, size_t(n) * 16, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return;
+  }
+  DevBuf<f4> scratch;                               // colour image 0 | colour image 1 | guide records: 48 bytes per pixel
+  scratch.ensure(size_t(n) * 3);
+  f4 *img[2] = {scratch.p, scratch.p + n}, *guide = scratch.p + size_t(n) * 2;
+  const dim3 flat((n + kBlock - 1) / kBlock), block(kBlock);
+  DnPrepareArgs pa{rgba, c.demodulate ? albedo : nullptr, normal, depth, img[0], guide, n, 0u};
+  hipLaunchKernelGGL(k_dn_prepare, flat, block, 0, st, pa);
+  HIP_CHECK(hipGetLastError());
+  for (uint32_t i = 0; i < c.iterations; i++) {
+    DnAtrousArgs aa{img[i & 1u], guide, img[(i + 1u) & 1u], width, height, i, 0u, c.k};
+    if (i < 2u) {
+      aa.tilesX = (width + 15u) / 16u;
+      hipLaunchKernelGGL(k_dn_atrous<0>, dim3(aa.tilesX * ((height + 15u) / 16u)), block, 0, st, aa);
+    } else {
+      aa.tilesX = (width + 63u) / 64u;
+      hipLaunchKernelGGL(k_dn_atrous<1>, dim3(aa.tilesX * ((height + 3u) / 4u)), block, 0, st, aa);
+    }
+    HIP_CHECK(hipGetLastError());
+  }
+  DnFinishArgs fa{img[c.iterations & 1u], rgba, c.demodulate ? albedo : nullptr, out, n, 0u};
+  hipLaunchKernelGGL(k_dn_finish, flat, block, 0, st, fa);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(st));
+}
+}  // namespace
+
+int yart_hip_denoise_atrous_device(const float* d_rgba, const float* d_albedo, const float* d_normal, const float* d_depth,
+                                   uint32_t width, uint32_t height, const YartDenoiseParams* params, float* d_out_rgba,
+                                   void* stream) {
+  return guarded([&] {
+    const DnCall c = denoiseCheck(d_rgba, d_albedo, d_normal, d_depth, width, height, params, d_out_rgba);
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw HipError("no HIP device");
+    denoiseRun(c, d_rgba, d_albedo, d_normal, d_depth, width, height, d_out_rgba, static_cast<hipStream_t>(stream));
+  });
+}
+
+int yart_hip_denoise_atrous_host(const float* rgba, const float* albedo, const float* normal, const float* depth, uint32_t width,
+                                 uint32_t height, const YartDenoiseParams* params, float* out_rgba) {
+  return guarded([&] {
+    const DnCall c = denoiseCheck(rgba, albedo, normal, depth, width, height, params, out_rgba);
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw HipError("no HIP device");
+    const size_t n = size_t(width) * height;
+    DevBuf<float> frame, alb, nrm, dep;               // the frame is filtered in place on the device
+    frame.ensure(n * 4);
+    HIP_CHECK(hipMemcpy(frame.p, rgba, n * 16, hipMemcpyHostToDevice));
+    if (albedo && c.demodulate) { alb.ensure(n * 3); HIP_CHECK(hipMemcpy(alb.p, albedo, n * 12, hipMemcpyHostToDevice)); }
+    if (normal) { nrm.ensure(n * 3); HIP_CHECK(hipMemcpy(nrm.p, normal, n * 12, hipMemcpyHostToDevice)); }
+    if (depth) { dep.ensure(n); HIP_CHECK(hipMemcpy(dep.p, depth, n * 4, hipMemcpyHostToDevice)); }
+    denoiseRun(c, frame.p, alb.p, nrm.p, dep.p, width, height, frame.p, nullptr);
+    HIP_CHECK(hipMemcpy(out_rgba, frame.p, n * 16, hipMemcpyDeviceToHost));
   });
 }
 
