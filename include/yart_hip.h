@@ -334,6 +334,54 @@ int yart_hip_render_aovs(YartScene* scene, const YartCameraDesc* cam, const Yart
 int yart_hip_render_aovs_device(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, float* d_out_rgba,
                                 const YartAovBuffers* d_aovs, void* stream, YartStats* stats);
 
+/* Per-pixel sample moments: how noisy a pixel of the frame is, from the frame's OWN samples — the per-(pixel, sample) radiance every
+ * pipeline holds at the end of a batch, before the estimator collapses it. For a pixel and its samples s = 0 .. samples-1 over the
+ * whole render, in ASCENDING s:
+ *   w_s = L_s.xyz * exposureScale      per channel, binary32: the value the estimator is fed
+ *   y_s = luma(w_s)                    (w.r * 0.2126f + w.g * 0.7152f) + w.b * 0.0722f, binary32 (csrc/estimator.hpp)
+ *   accepted                           iff no component of w_s is NaN, none is negative, and y_s is finite. The rule is fixed: it does
+ *                                      not follow params->estimator.
+ *   state                              N (uint32) and five BINARY64 sums Sr, Sg, Sb, S1, S2: an accepted sample adds double(w.r),
+ *                                      double(w.g), double(w.b), double(y) and double(y) * double(y) (exact); no FMA contraction
+ *   finish, once after the last wave   mean.c   = float(S_c / double(N)); 0 when N == 0
+ *                                      variance = 0 when N < 2, else v = ((S2 - (S1 * S1) / N) / (N - 1)) / N, every binary64
+ *                                                 operation rounded in the order written, a negative v replaced by 0, then rounded
+ *                                                 once to binary32: the variance of the pixel's MEAN luminance estimate
+ *                                      count    = N
+ * The order is part of the contract: the result is a pure function of the per-sample values. It does not depend on flags (megakernel
+ * and path pool included), max_batch_paths, pool_paths, the wave schedule or the estimator. csrc/moments.hpp states the arithmetic,
+ * yart_amd/moments.py moments_reference is the NumPy statement the tests compare with, on bits. (The sums are binary64 because a
+ * pixel's samples arrive wave by wave — no second pass — and a binary32 S2 - S1 * S1 / N cancels on low-noise pixels.)
+ * Pixels of other ranks are left 0: the ranks' buffers add up to the unsharded ones. Memory: nothing more per path in any pipeline
+ * (only the per-sample radiance is read); 48 bytes per pixel of the rank (the 44 bytes of state, padded), which the batch clamp of
+ * max_batch_paths takes off its budget. start_sample / stop_sample other than the full range are refused (YART_E_INVALID). Several
+ * GPUs: yart_hip_multi_* does not carry the moments; shard with rank / world_size, one call per device, and add the buffers. */
+#define YART_MOMENT_MEAN 1u      /* 3 floats / pixel */
+#define YART_MOMENT_VARIANCE 2u  /* 1 float  */
+#define YART_MOMENT_COUNT 4u     /* 1 uint32 */
+#define YART_MOMENT_ALL 7u
+typedef struct YartMomentBuffers {
+  uint32_t struct_size;        /* sizeof(YartMomentBuffers): lets the struct grow without an ABI bump */
+  uint32_t mask;               /* YART_MOMENT_* requested; a requested buffer must be non-NULL, the others are not touched */
+  float *mean, *variance;
+  uint32_t* count;
+} YartMomentBuffers;
+/* yart_hip_render_aovs + moments: host pointers, width * height * channels each, row-major like out_rgba. out_rgba, YartStats.samples /
+ * rays and the feature buffers are those of yart_hip_render_aovs with the same arguments, bit for bit; an empty moment mask (or
+ * moments == NULL) is yart_hip_render_aovs. aovs may be NULL. A NULL requested buffer, a struct_size that ends before a requested
+ * field, unknown mask bits and a partial sample range return YART_E_INVALID before anything is launched. */
+int yart_hip_render_moments(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, float* out_rgba,
+                            const YartAovBuffers* aovs, const YartMomentBuffers* moments, YartStats* stats);
+/* yart_hip_render_aovs_device + moments: DEVICE pointers (e.g. torch tensors' data_ptr) */
+int yart_hip_render_moments_device(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, float* d_out_rgba,
+                                   const YartAovBuffers* d_aovs, const YartMomentBuffers* d_moments, void* stream, YartStats* stats);
+/* Diagnostic, no scene: the accumulate and finish kernels of the moments on caller-supplied per-sample records, on the current device.
+ * L_rgba: n_pixels * spp records of 4 floats (host; pixel-major, samples ascending; the fourth float is not read). chunks: n_chunks
+ * sample counts (each > 0) that sum to spp: one accumulate launch per chunk, as a render launches one per wave. mean (3 per pixel),
+ * variance, count (1 per pixel): host, all required. */
+int yart_hip_probe_moments(const float* L_rgba, uint32_t n_pixels, uint32_t spp, const uint32_t* chunks, uint32_t n_chunks,
+                           float exposure_scale, float* mean, float* variance, uint32_t* count);
+
 /* Several GPUs of one node behind one handle — what the reference's worker pool is to CPU threads
  * (TileRenderer::renderImpl starts threadCount workers that pull tiles, tile-renderer.hpp:150-197; finishTile merges
  * each finished tile into the one m_hdrBuffer, :225-241). The scene is replicated on every listed device; device i of
@@ -488,6 +536,45 @@ int yart_hip_denoise_atrous_device(const float* d_rgba, const float* d_albedo, c
 /* Same, HOST pointers: the buffers are copied to the current device, filtered there and the frame copied back. */
 int yart_hip_denoise_atrous_host(const float* rgba, const float* albedo, const float* normal, const float* depth, uint32_t width,
                                  uint32_t height, const YartDenoiseParams* params, float* out_rgba);
+
+/* The variance-guided form of the filter above — the spatial filter of SVGF (Schied, Kaplanyan, Wyman, Patney, Chaitanya, Burgess,
+ * Liu, Dachsbacher, Lefohn, Salvi 2017) — with the per-pixel variance of yart_hip_render_moments (YART_MOMENT_VARIANCE) as a fourth
+ * input: a colour difference is measured against the local standard deviation of the luminance instead of one global sigma_color, and
+ * the variance is filtered along. It is the DEFINITION above with these changes and nothing else (csrc/denoise.hpp dnPrepareVar /
+ * dnFilterPixelVar state it; yart_amd/denoise.py atrous_var_reference is the NumPy statement the tests compare with, on bits):
+ *   Prepare:   v_0(p) = variance(p) / (ld * ld), ld = luma(d) = (d.r * 0.2126f + d.g * 0.7152f) + d.b * 0.0722f of the demodulation
+ *              divisor d ((1, 1, 1) when not demodulating). valid(p) additionally requires variance(p) to be finite and >= 0.
+ *   Iteration, once per centre pixel p:  g(p) = the 3 x 3 Gaussian of v_i around p, ALWAYS at distance 1: weights k3[|dy|] * k3[|dx|],
+ *              k3 = {0.5f, 0.25f} (0.25f centre, 0.125f edge, 0.0625f corner), over the valid pixels inside the image, dy outer, dx
+ *              inner: gv = gv + k * v_i(q), gk = gk + k; g = gv / gk, 0.0f if no tap counts.
+ *   Colour term of e:  fabsf(ly(q) - ly(p)) / (sigma_luma * sqrtf(g(p)) + 1e-6f), ly = luma(c_i), in place of dc * icol_i: no 4^i
+ *              scaling (the filtered variance shrinks instead). The normal and depth terms, their order, the association of e, the
+ *              rule that a term whose sigma is <= 0 does not exist, and the handling of invalid pixels are unchanged.
+ *   Variance:  vacc = vacc + (w * w) * v_i(q) next to acc; v_(i+1)(p) = vacc / (wsum * wsum), 0.0f if wsum == 0.
+ *   Finish:    unchanged (the filtered variance is not returned).
+ * Memory: 48 bytes per pixel while the call runs, as above: v_i lives in the fourth word of the working colour, where the plain
+ * filter keeps the valid flag. The defaults are the minimiser of the worst case over the same two host renders
+ * (profiles/denoise_var_sweep.txt: RMSE 0.42 / 0.64 of the unfiltered frame's, where the plain filter at its defaults reaches 0.60 / 0.85
+ * on the same inputs). */
+#define YART_DENOISE_VAR_DEFAULT_ITERATIONS 3u
+#define YART_DENOISE_VAR_DEFAULT_SIGMA_LUMA 2.0f
+#define YART_DENOISE_VAR_DEFAULT_SIGMA_NORMAL 0.25f
+#define YART_DENOISE_VAR_DEFAULT_SIGMA_DEPTH 0.1f
+typedef struct YartDenoiseVarParams {
+  uint32_t struct_size;        /* sizeof(YartDenoiseVarParams) */
+  uint32_t iterations;         /* 0 .. 8 */
+  float sigma_luma, sigma_normal, sigma_depth;    /* finite; <= 0: that term is left out */
+  uint32_t flags;              /* YART_DENOISE_* */
+} YartDenoiseVarParams;
+/* DEVICE pointers on `stream`; returns after completion on that stream. d_variance (width * height floats) is required; the other
+ * argument errors are those of yart_hip_denoise_atrous_device: YART_E_INVALID with a message, before any device is touched. */
+int yart_hip_denoise_atrous_var_device(const float* d_rgba, const float* d_variance, const float* d_albedo, const float* d_normal,
+                                       const float* d_depth, uint32_t width, uint32_t height, const YartDenoiseVarParams* params,
+                                       float* d_out_rgba, void* stream);
+/* Same, HOST pointers */
+int yart_hip_denoise_atrous_var_host(const float* rgba, const float* variance, const float* albedo, const float* normal,
+                                     const float* depth, uint32_t width, uint32_t height, const YartDenoiseVarParams* params,
+                                     float* out_rgba);
 
 const char* yart_hip_last_error(void);
 int yart_hip_abi_version(void);

@@ -45,6 +45,13 @@ struct AovFrame {
   std::vector<uint32_t> rays;                                           // rays of the pixel over the whole render
 };
 
+// ... plus the per-pixel sample moments of the same render (YartMomentBuffers): only the requested ones are sized.
+struct MomentFrame : AovFrame {
+  uint32_t momentMask = 0;
+  std::vector<float> mean, variance;                                    // 3 / 1 floats per pixel
+  std::vector<uint32_t> count;                                          // accepted samples
+};
+
 class DeviceScene {
  public:
   explicit DeviceScene(const YartSceneDesc& desc, int device = -1) { requireAbi(); check(yart_hip_scene_create(&desc, device, &h_)); }
@@ -81,6 +88,30 @@ class DeviceScene {
     if (mask & YART_AOV_IDS) { f.ids.resize(n * 4); b.ids = f.ids.data(); }
     if (mask & YART_AOV_RAYS) { f.rays.resize(n); b.rays = f.rays.data(); }
     check(yart_hip_render_aovs(h_, &cam, &params, f.rgba.data(), &b, stats));
+    return f;
+  }
+  // yart_hip_render_moments: renderAovs plus the sample moments of `momentMask` (YART_MOMENT_*) of the frame's own samples
+  MomentFrame renderMoments(const YartCameraDesc& cam, const YartRenderParams& params, uint32_t momentMask = YART_MOMENT_ALL,
+                            uint32_t aovMask = 0, YartStats* stats = nullptr) {
+    MomentFrame f;
+    f.width = cam.width; f.height = cam.height; f.mask = aovMask; f.momentMask = momentMask;
+    const size_t n = size_t(cam.width) * cam.height;
+    f.rgba.resize(n * 4);
+    YartAovBuffers b{};
+    b.struct_size = uint32_t(sizeof(b)); b.mask = aovMask;
+    if (aovMask & YART_AOV_ALBEDO) { f.albedo.resize(n * 3); b.albedo = f.albedo.data(); }
+    if (aovMask & YART_AOV_NORMAL) { f.normal.resize(n * 3); b.normal = f.normal.data(); }
+    if (aovMask & YART_AOV_POSITION) { f.position.resize(n * 3); b.position = f.position.data(); }
+    if (aovMask & YART_AOV_DEPTH) { f.depth.resize(n); b.depth = f.depth.data(); }
+    if (aovMask & YART_AOV_COVERAGE) { f.coverage.resize(n); b.coverage = f.coverage.data(); }
+    if (aovMask & YART_AOV_IDS) { f.ids.resize(n * 4); b.ids = f.ids.data(); }
+    if (aovMask & YART_AOV_RAYS) { f.rays.resize(n); b.rays = f.rays.data(); }
+    YartMomentBuffers m{};
+    m.struct_size = uint32_t(sizeof(m)); m.mask = momentMask;
+    if (momentMask & YART_MOMENT_MEAN) { f.mean.resize(n * 3); m.mean = f.mean.data(); }
+    if (momentMask & YART_MOMENT_VARIANCE) { f.variance.resize(n); m.variance = f.variance.data(); }
+    if (momentMask & YART_MOMENT_COUNT) { f.count.resize(n); m.count = f.count.data(); }
+    check(yart_hip_render_moments(h_, &cam, &params, f.rgba.data(), &b, &m, stats));
     return f;
   }
 
@@ -124,6 +155,27 @@ inline std::vector<float> denoise(const std::vector<float>& rgba, uint32_t width
   check(yart_hip_denoise_atrous_host(rgba.data(), guides.albedo.empty() ? nullptr : guides.albedo.data(),
                                      guides.normal.empty() ? nullptr : guides.normal.data(),
                                      guides.depth.empty() ? nullptr : guides.depth.data(), width, height, &params, out.data()));
+  return out;
+}
+
+// The variance-guided form (yart_hip_denoise_atrous_var_host): `variance` is MomentFrame::variance of the same render.
+inline YartDenoiseVarParams denoiseVarDefaults(bool demodulate = false) {
+  YartDenoiseVarParams p{};
+  p.struct_size = uint32_t(sizeof(p)); p.iterations = YART_DENOISE_VAR_DEFAULT_ITERATIONS;
+  p.sigma_luma = YART_DENOISE_VAR_DEFAULT_SIGMA_LUMA; p.sigma_normal = YART_DENOISE_VAR_DEFAULT_SIGMA_NORMAL;
+  p.sigma_depth = YART_DENOISE_VAR_DEFAULT_SIGMA_DEPTH; p.flags = demodulate ? YART_DENOISE_DEMODULATE : 0u;
+  return p;
+}
+inline std::vector<float> denoiseVar(const std::vector<float>& rgba, const std::vector<float>& variance, uint32_t width, uint32_t height,
+                                     const DenoiseGuides& guides, const YartDenoiseVarParams& params) {
+  const size_t n = size_t(width) * height;
+  if (rgba.size() != n * 4 || variance.size() != n || (!guides.albedo.empty() && guides.albedo.size() != n * 3) ||
+      (!guides.normal.empty() && guides.normal.size() != n * 3) || (!guides.depth.empty() && guides.depth.size() != n))
+    throw Error(YART_E_INVALID, "denoiseVar: a buffer does not have width * height * channels floats");
+  std::vector<float> out(rgba.size());
+  check(yart_hip_denoise_atrous_var_host(rgba.data(), variance.data(), guides.albedo.empty() ? nullptr : guides.albedo.data(),
+                                         guides.normal.empty() ? nullptr : guides.normal.data(),
+                                         guides.depth.empty() ? nullptr : guides.depth.data(), width, height, &params, out.data()));
   return out;
 }
 

@@ -26,6 +26,9 @@ import numpy as np
 from . import yscn
 from .denoise import (DEFAULT_ITERATIONS, DEFAULT_SIGMA_COLOR, DEFAULT_SIGMA_DEPTH, DEFAULT_SIGMA_NORMAL, FLAG_DEMODULATE,
                       atrous_reference)  # noqa: F401 (atrous_reference: the NumPy statement of denoise / denoise_into)
+from .denoise import (DEFAULT_VAR_ITERATIONS, DEFAULT_VAR_SIGMA_DEPTH, DEFAULT_VAR_SIGMA_LUMA, DEFAULT_VAR_SIGMA_NORMAL,
+                      atrous_var_reference)  # noqa: F401 (the NumPy statement of denoise_var / denoise_var_into)
+from .moments import moments_reference  # noqa: F401 (the NumPy statement of render_moments / probe_moments)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libyart_hip.so")
@@ -194,6 +197,30 @@ def reduce_aov_coverage(hit, samples=None):
     return (hit.sum(axis=-1).astype(np.float32) / np.float32(n)).astype(np.float32)
 
 
+class MomentBuffers(C.Structure):
+    """YartMomentBuffers (include/yart_hip.h): the per-pixel sample moments a render fills next to the frame."""
+    _fields_ = [("struct_size", C.c_uint32), ("mask", C.c_uint32),
+                ("mean", C.c_void_p), ("variance", C.c_void_p), ("count", C.c_void_p)]
+
+
+# name -> (YART_MOMENT_* bit, values per pixel, dtype)
+MOMENTS = {"mean": (1, 3, np.float32), "variance": (2, 1, np.float32), "count": (4, 1, np.uint32)}
+MOMENT_ALL = tuple(MOMENTS)
+
+
+class DenoiseVarParams(C.Structure):
+    """YartDenoiseVarParams (include/yart_hip.h): the knobs of the variance-guided à-trous filter."""
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("sigma_luma", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
+
+
+def make_denoise_var_params(iterations=DEFAULT_VAR_ITERATIONS, sigma_luma=DEFAULT_VAR_SIGMA_LUMA,
+                            sigma_normal=DEFAULT_VAR_SIGMA_NORMAL, sigma_depth=DEFAULT_VAR_SIGMA_DEPTH,
+                            demodulate=False) -> DenoiseVarParams:
+    return DenoiseVarParams(C.sizeof(DenoiseVarParams), int(iterations), float(sigma_luma), float(sigma_normal),
+                            float(sigma_depth), FLAG_DEMODULATE if demodulate else 0)
+
+
 class DenoiseParams(C.Structure):
     """YartDenoiseParams (include/yart_hip.h): the knobs of the à-trous filter."""
     _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("sigma_color", C.c_float),
@@ -244,7 +271,9 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_multi_render", "yart_hip_multi_render_tiles", "yart_hip_multi_rccl_selftest",
            "yart_hip_render_aovs", "yart_hip_render_aovs_device", "yart_hip_probe_camera_rays",
            "yart_hip_probe_math", "yart_hip_probe_math_pairs",
-           "yart_hip_denoise_atrous_device", "yart_hip_denoise_atrous_host"]
+           "yart_hip_denoise_atrous_device", "yart_hip_denoise_atrous_host",
+           "yart_hip_render_moments", "yart_hip_render_moments_device", "yart_hip_probe_moments",
+           "yart_hip_denoise_atrous_var_device", "yart_hip_denoise_atrous_var_host"]
 
 LIB_COUNT_PATH = os.path.join(_HERE, "libyart_hip_count.so")   # instrumented twin (exact test counters)
 _libs = {}
@@ -305,6 +334,16 @@ def lib(instrumented: bool = False):
                                                      C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p]
         L.yart_hip_denoise_atrous_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                                    C.POINTER(DenoiseParams), C.c_void_p]
+        L.yart_hip_render_moments.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p,
+                                              C.POINTER(AovBuffers), C.POINTER(MomentBuffers), C.POINTER(Stats)]
+        L.yart_hip_render_moments_device.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p,
+                                                     C.POINTER(AovBuffers), C.POINTER(MomentBuffers), C.c_void_p, C.POINTER(Stats)]
+        L.yart_hip_probe_moments.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]
+        L.yart_hip_denoise_atrous_var_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                         C.c_uint32, C.POINTER(DenoiseVarParams), C.c_void_p, C.c_void_p]
+        L.yart_hip_denoise_atrous_var_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                       C.c_uint32, C.POINTER(DenoiseVarParams), C.c_void_p]
         L.yart_hip_bvh_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.yart_hip_bvh_copy.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         _libs[path] = L
@@ -590,19 +629,83 @@ class DeviceScene:
                                                    C.byref(ab), sp, C.byref(st)), self._L)
         return st.asdict()
 
-    def render_denoised(self, p: dict, iterations=DEFAULT_ITERATIONS, sigma_color=DEFAULT_SIGMA_COLOR,
-                        sigma_normal=DEFAULT_SIGMA_NORMAL, sigma_depth=DEFAULT_SIGMA_DEPTH, demodulate=True, rank=0, world_size=1,
-                        flags=0, device="cuda"):
+    def render_moments(self, p: dict, moments: Sequence[str] = MOMENT_ALL, aovs: Sequence[str] = (), rank=0, world_size=1, flags=0):
+        """``render_aovs`` + per-pixel sample moments (include/yart_hip.h: YartMomentBuffers) of the frame's own samples.
+        Returns (frame HxWx4 float32, {aov name: ndarray}, {moment name: ndarray HxWx3 / HxW}, stats dict); moment names
+        from ``MOMENTS``. yart_amd.moments.moments_reference states the arithmetic in NumPy."""
+        cam, rp, st = make_camera(p), make_params(p, rank, world_size, flags), Stats()
+        out = np.empty((cam.height, cam.width, 4), np.float32)
+        ab, bufs = AovBuffers(), {}
+        ab.struct_size = C.sizeof(AovBuffers)
+        for name in aovs:
+            bit, ch, dt = AOVS[name]
+            bufs[name] = np.empty((cam.height, cam.width, ch) if ch > 1 else (cam.height, cam.width), dt)
+            ab.mask |= bit
+            setattr(ab, name, bufs[name].ctypes.data_as(C.c_void_p))
+        mb, moms = MomentBuffers(), {}
+        mb.struct_size = C.sizeof(MomentBuffers)
+        for name in moments:
+            bit, ch, dt = MOMENTS[name]
+            moms[name] = np.empty((cam.height, cam.width, ch) if ch > 1 else (cam.height, cam.width), dt)
+            mb.mask |= bit
+            setattr(mb, name, moms[name].ctypes.data_as(C.c_void_p))
+        _check(self._L.yart_hip_render_moments(self._h, C.byref(cam), C.byref(rp), out.ctypes.data_as(C.c_void_p),
+                                               C.byref(ab), C.byref(mb), C.byref(st)), self._L)
+        return out, bufs, moms, st.asdict()
+
+    def render_moments_into(self, tensor, aov_tensors: dict, moment_tensors: dict, p: dict, rank=0, world_size=1, flags=0,
+                            stream=None):
+        """``render_aovs_into`` + sample moments written into CUDA/HIP torch tensors: ``moment_tensors`` maps names of
+        ``MOMENTS`` to contiguous device tensors of H*W*channels 4-byte elements (float32; count int32 holding the uint32)."""
+        cam, rp, st = make_camera(p), make_params(p, rank, world_size, flags), Stats()
+        assert tensor.is_cuda and tensor.is_contiguous() and tensor.numel() == cam.width * cam.height * 4
+        ab = AovBuffers()
+        ab.struct_size = C.sizeof(AovBuffers)
+        for name, t in (aov_tensors or {}).items():
+            bit, ch, _ = AOVS[name]
+            assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() == cam.width * cam.height * ch, name
+            ab.mask |= bit
+            setattr(ab, name, C.c_void_p(t.data_ptr()))
+        mb = MomentBuffers()
+        mb.struct_size = C.sizeof(MomentBuffers)
+        for name, t in (moment_tensors or {}).items():
+            bit, ch, _ = MOMENTS[name]
+            assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() == cam.width * cam.height * ch, name
+            mb.mask |= bit
+            setattr(mb, name, C.c_void_p(t.data_ptr()))
+        sp = C.c_void_p(stream) if stream else None
+        _check(self._L.yart_hip_render_moments_device(self._h, C.byref(cam), C.byref(rp), C.c_void_p(tensor.data_ptr()),
+                                                      C.byref(ab), C.byref(mb), sp, C.byref(st)), self._L)
+        return st.asdict()
+
+    def render_denoised(self, p: dict, iterations=None, sigma_color=DEFAULT_SIGMA_COLOR, sigma_normal=None, sigma_depth=None,
+                        demodulate=True, rank=0, world_size=1, flags=0, device="cuda", variance_guided=False,
+                        sigma_luma=DEFAULT_VAR_SIGMA_LUMA):
         """``render_aovs_into`` for albedo, normal and depth, then the à-trous filter (``denoise_into``) on the same device
         buffers, on torch's current stream: no host round trip. Returns (noisy frame, denoised frame, {name: guide}) as torch
-        tensors of ``device`` ((H, W, 4); guides (H, W, 3) / (H, W))."""
+        tensors of ``device`` ((H, W, 4); guides (H, W, 3) / (H, W)).
+        ``variance_guided=True``: ``render_moments_into`` with the variance buffer as well, then the variance-guided filter
+        (``denoise_var_into``) with ``sigma_luma`` in place of ``sigma_color`` (which is not used then); the guides returned
+        then include "variance" (H, W). ``iterations``, ``sigma_normal`` and ``sigma_depth`` left at None take the defaults
+        of the filter that runs (DEFAULT_* of the plain one, DEFAULT_VAR_* of the variance-guided one)."""
         import torch
+        dflt = ((DEFAULT_VAR_ITERATIONS, DEFAULT_VAR_SIGMA_NORMAL, DEFAULT_VAR_SIGMA_DEPTH) if variance_guided else
+                (DEFAULT_ITERATIONS, DEFAULT_SIGMA_NORMAL, DEFAULT_SIGMA_DEPTH))
+        iterations = dflt[0] if iterations is None else iterations
+        sigma_normal = dflt[1] if sigma_normal is None else sigma_normal
+        sigma_depth = dflt[2] if sigma_depth is None else sigma_depth
         w, h = int(p["size"][0]), int(p["size"][1])
         noisy = torch.empty((h, w, 4), dtype=torch.float32, device=device)
         guides = {"albedo": torch.empty((h, w, 3), dtype=torch.float32, device=device),
                   "normal": torch.empty((h, w, 3), dtype=torch.float32, device=device),
                   "depth": torch.empty((h, w), dtype=torch.float32, device=device)}
         stream = torch.cuda.current_stream(noisy.device).cuda_stream
+        if variance_guided:
+            variance = torch.empty((h, w), dtype=torch.float32, device=device)
+            self.render_moments_into(noisy, guides, {"variance": variance}, p, rank, world_size, flags, stream=stream)
+            clean = torch.empty_like(noisy)
+            denoise_var_into(clean, noisy, variance, guides, iterations, sigma_luma, sigma_normal, sigma_depth, demodulate)
+            return noisy, clean, dict(guides, variance=variance)
         self.render_aovs_into(noisy, guides, p, rank, world_size, flags, stream=stream)
         clean = torch.empty_like(noisy)
         denoise_into(clean, noisy, guides, iterations, sigma_color, sigma_normal, sigma_depth, demodulate)
@@ -915,6 +1018,84 @@ def denoise_into(out_tensor, frame_tensor, guides=None, iterations=DEFAULT_ITERA
                                                 w, h, C.byref(dp), C.c_void_p(out_tensor.data_ptr()),
                                                 C.c_void_p(stream) if stream else None), L)
     return out_tensor
+
+
+def denoise_var(frame, variance, albedo=None, normal=None, depth=None, iterations=DEFAULT_VAR_ITERATIONS,
+                sigma_luma=DEFAULT_VAR_SIGMA_LUMA, sigma_normal=DEFAULT_VAR_SIGMA_NORMAL, sigma_depth=DEFAULT_VAR_SIGMA_DEPTH,
+                demodulate=None, out=None):
+    """The variance-guided à-trous filter (include/yart_hip.h: yart_hip_denoise_atrous_var_host): ``denoise`` with the per-pixel
+    ``variance`` (H, W) of ``render_moments`` as a fourth input and ``sigma_luma`` in place of ``sigma_color``.
+    yart_amd.denoise.atrous_var_reference states the same arithmetic in NumPy."""
+    frame = np.ascontiguousarray(frame, np.float32)
+    h, w = frame.shape[:2]
+    assert frame.shape == (h, w, 4)
+    if demodulate is None:
+        demodulate = albedo is not None
+
+    def guide(a, ch):
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(a, np.float32)
+        assert a.size == h * w * ch
+        return a, a.ctypes.data_as(C.c_void_p)
+    (kv, pv), (ka, pa), (kn, pn), (kd, pd) = guide(variance, 1), guide(albedo, 3), guide(normal, 3), guide(depth, 1)
+    if out is None:
+        out = np.empty_like(frame)
+    assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == frame.shape
+    dp = make_denoise_var_params(iterations, sigma_luma, sigma_normal, sigma_depth, demodulate)
+    L = lib()
+    _check(L.yart_hip_denoise_atrous_var_host(frame.ctypes.data_as(C.c_void_p), pv, pa, pn, pd, w, h, C.byref(dp),
+                                              out.ctypes.data_as(C.c_void_p)), L)
+    return out
+
+
+def denoise_var_into(out_tensor, frame_tensor, variance_tensor, guides=None, iterations=DEFAULT_VAR_ITERATIONS,
+                     sigma_luma=DEFAULT_VAR_SIGMA_LUMA, sigma_normal=DEFAULT_VAR_SIGMA_NORMAL, sigma_depth=DEFAULT_VAR_SIGMA_DEPTH,
+                     demodulate=None, stream=None):
+    """``denoise_var`` on CUDA/HIP torch tensors through ``data_ptr()`` (yart_hip_denoise_atrous_var_device): as
+    ``denoise_into``, with ``variance_tensor`` (H*W float32 elements)."""
+    import torch
+    h, w = int(frame_tensor.shape[0]), int(frame_tensor.shape[1])
+    if demodulate is None:
+        demodulate = (guides or {}).get("albedo") is not None
+    ptrs = {}
+    for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1)):
+        t = (guides or {}).get(name)
+        if t is not None:
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == h * w * ch, name
+        ptrs[name] = None if t is None else C.c_void_p(t.data_ptr())
+    unknown = set(guides or {}) - set(ptrs)
+    assert not unknown, f"denoise_var_into: unknown guides {sorted(unknown)}"
+    for t in (frame_tensor, out_tensor):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4)
+    v = variance_tensor
+    assert v.is_cuda and v.is_contiguous() and v.dtype == torch.float32 and v.numel() == h * w, "variance"
+    if stream is None:
+        stream = torch.cuda.current_stream(frame_tensor.device).cuda_stream
+    dp = make_denoise_var_params(iterations, sigma_luma, sigma_normal, sigma_depth, demodulate)
+    L = lib()
+    with torch.cuda.device(frame_tensor.device):
+        _check(L.yart_hip_denoise_atrous_var_device(C.c_void_p(frame_tensor.data_ptr()), C.c_void_p(v.data_ptr()), ptrs["albedo"],
+                                                    ptrs["normal"], ptrs["depth"], w, h, C.byref(dp),
+                                                    C.c_void_p(out_tensor.data_ptr()), C.c_void_p(stream) if stream else None), L)
+    return out_tensor
+
+
+def probe_moments(L_samples, chunks=None, exposure_scale=1.0):
+    """The moment kernels alone (yart_hip_probe_moments), without a scene: ``L_samples`` [n_pixels, spp, 3 or 4] float32
+    per-sample radiance, ``chunks`` sample counts that sum to spp (one accumulate launch each, as a render launches one per
+    wave; None: one chunk). Returns (mean [n, 3] float32, variance [n] float32, count [n] uint32)."""
+    a = np.asarray(L_samples, np.float32)
+    n, spp = a.shape[:2]
+    rec = np.zeros((n, spp, 4), np.float32)
+    rec[..., :3] = a[..., :3]
+    ch = np.ascontiguousarray([spp] if chunks is None else chunks, np.uint32)
+    mean, var, cnt = np.empty((n, 3), np.float32), np.empty(n, np.float32), np.empty(n, np.uint32)
+    L = lib()
+    _check(L.yart_hip_probe_moments(rec.ctypes.data_as(C.c_void_p), n, spp, ch.ctypes.data_as(C.c_void_p), len(ch),
+                                    float(exposure_scale), mean.ctypes.data_as(C.c_void_p), var.ctypes.data_as(C.c_void_p),
+                                    cnt.ctypes.data_as(C.c_void_p)), L)
+    return mean, var, cnt
 
 
 def write_ppm(path, rgb8: np.ndarray):

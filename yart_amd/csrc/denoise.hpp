@@ -111,6 +111,104 @@ YART_HD f4 dnFilterPixel(const Src& src, uint32_t width, uint32_t height, uint32
   return dnF4(accR / wsum, accG / wsum, accB / wsum, cp.w);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Variance-guided form (yart_hip_denoise_atrous_var_*; the spatial filter of SVGF, Schied et al. 2017): the filter
+// above with the colour term measured against the local standard deviation of the luminance and the variance filtered along.
+// Still 48 bytes per pixel: the variance v_i(p) of a valid pixel lives in the fourth word of its working colour, where the
+// plain filter keeps the valid flag; an invalid pixel carries kDnVarInvalid there (all ones: no arithmetic produces that NaN).
+constexpr uint32_t kDnVarInvalid = 0xffffffffu;
+
+struct DnVarConst {
+  float sigmaLuma, inrm, idep; // sigma_luma itself; 1 / (sigma * sigma) of the other two (0 where the term does not exist)
+  uint32_t terms;              // kDn*
+};
+
+YART_HD float dnLuma(float r, float g, float b) { return r * 0.2126f + g * 0.7152f + b * 0.0722f; }   // estimator.hpp luma
+YART_HD float dnKernel3(int a) { return a == 0 ? 0.5f : 0.25f; }   // 3x3 Gaussian: 0.25 centre, 0.125 edge, 0.0625 corner
+
+// Prepare pass of one pixel: dnPrepare, plus v_0 = variance / (ld * ld), ld = luma(d); a variance that is not finite or is
+// negative makes the pixel invalid.
+YART_HD void dnPrepareVar(f4 rgba, float variance, const float* alb3, const float* nrm3, const float* dep, f4& colour, f4& guide) {
+  dnPrepare(rgba, alb3, nrm3, dep, colour, guide);
+  const bool valid = dnBits(colour.w) != 0u && dnFinite(variance) && variance >= 0.0f;
+  const f3 d = dnDivisor(alb3);
+  const float ld = dnLuma(d.x, d.y, d.z);
+  colour.w = valid ? variance / (ld * ld) : __builtin_bit_cast(float, kDnVarInvalid);
+}
+
+// One pixel of iteration i of the variance-guided filter: c_i, v_i -> c_(i+1)(p), v_(i+1)(p) (in .w; the marker if p is invalid)
+template <class Src>
+YART_HD f4 dnFilterPixelVar(const Src& src, uint32_t width, uint32_t height, uint32_t x, uint32_t y, uint32_t i, const DnVarConst& k) {
+  const int s = 1 << i;
+  const size_t p = size_t(y) * width + x;
+  const f4 cp = src.colour(p);
+  const bool validP = dnBits(cp.w) != kDnVarInvalid;
+  const bool guided = (k.terms & (kDnNormal | kDnDepth)) != 0u;
+  f4 gp = dnF4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (guided) gp = src.guide(p);
+  float lyP = 0.0f, den = 1.0f;
+  if (validP && (k.terms & kDnColor)) {
+    // g(p): 3 x 3 Gaussian of v_i at distance 1 (whatever the step), over the valid pixels inside the image
+    float gv = 0.0f, gk = 0.0f;
+    for (int dy = -1; dy <= 1; dy++) {
+      const int qy = int(y) + dy;
+      if (qy < 0 || qy >= int(height)) continue;
+      for (int dx = -1; dx <= 1; dx++) {
+        const int qx = int(x) + dx;
+        if (qx < 0 || qx >= int(width)) continue;
+        const f4 cq = src.colour(size_t(qy) * width + size_t(qx));
+        if (dnBits(cq.w) == kDnVarInvalid) continue;
+        const float kk = dnKernel3(dy) * dnKernel3(dx);
+        gv = gv + kk * cq.w; gk = gk + kk;
+      }
+    }
+    const float g = gk == 0.0f ? 0.0f : gv / gk;
+    den = k.sigmaLuma * sqrtf(g) + 1e-6f;
+    lyP = dnLuma(cp.x, cp.y, cp.z);
+  }
+  float accR = 0.0f, accG = 0.0f, accB = 0.0f, wsum = 0.0f, vacc = 0.0f;
+  for (int dy = -2; dy <= 2; dy++) {
+    const int qy = int(y) + s * dy;
+    if (qy < 0 || qy >= int(height)) continue;
+    for (int dx = -2; dx <= 2; dx++) {
+      const int qx = int(x) + s * dx;
+      if (qx < 0 || qx >= int(width)) continue;
+      const size_t q = size_t(qy) * width + size_t(qx);
+      const f4 cq = src.colour(q);
+      if (dnBits(cq.w) == kDnVarInvalid) continue;
+      const float h = dnKernel(dy) * dnKernel(dx);
+      float e = 0.0f;
+      if (validP) {
+        bool have = false;
+        if (k.terms & kDnColor) {
+          e = fabsf(dnLuma(cq.x, cq.y, cq.z) - lyP) / den; have = true;
+        }
+        if (guided) {
+          const f4 gq = src.guide(q);
+          if (k.terms & kDnNormal) {
+            const float nx = gq.x - gp.x, ny = gq.y - gp.y, nz = gq.z - gp.z;
+            const float dn = (nx * nx + ny * ny) + nz * nz;
+            const float t = dn * k.inrm;
+            e = have ? e + t : t; have = true;
+          }
+          if (k.terms & kDnDepth) {
+            const float dl = gq.w - gp.w;
+            const float t = (dl * dl) * k.idep;
+            e = have ? e + t : t;
+          }
+        }
+      }
+      const float w = h * yexpf(-e);
+      accR = accR + w * cq.x; accG = accG + w * cq.y; accB = accB + w * cq.z;
+      wsum = wsum + w;
+      vacc = vacc + (w * w) * cq.w;
+    }
+  }
+  const float marker = __builtin_bit_cast(float, kDnVarInvalid);
+  if (wsum == 0.0f) return dnF4(0.0f, 0.0f, 0.0f, validP ? 0.0f : marker);
+  return dnF4(accR / wsum, accG / wsum, accB / wsum, validP ? vacc / (wsum * wsum) : marker);
+}
+
 // Finish pass of one pixel: re-modulate, alpha from the input frame
 YART_HD f4 dnFinish(f4 c, const float* alb3, float alpha) {
   const f3 d = dnDivisor(alb3);

@@ -79,3 +79,40 @@ __global__ void __launch_bounds__(kBlock) k_dn_finish(DnFinishArgs a) {
   float* q = a.out + size_t(p) * 4;
   q[0] = o.x; q[1] = o.y; q[2] = o.z; q[3] = o.w;
 }
+
+// Variance-guided form (yart_hip_denoise_atrous_var_*, denoise.hpp dnPrepareVar / dnFilterPixelVar). The same passes, tiles and
+// 48 bytes per pixel: the variance travels in the fourth word of the working colour (where the plain filter keeps the valid
+// flag), so a tap is still two aligned 16-byte loads; the 3 x 3 Gaussian of the variance reads nine words the 25 taps of step 1
+// read anyway. k_dn_finish is shared (it does not look at the fourth word).
+struct DnPrepareVarArgs {
+  const float *rgba, *variance, *albedo, *normal, *depth;
+  f4 *colour, *guide;
+  uint32_t n, pad;
+};
+__global__ void __launch_bounds__(kBlock) k_dn_prepare_var(DnPrepareVarArgs a) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= a.n) return;
+  const float* in = a.rgba + size_t(p) * 4;
+  f4 c, g;
+  dnPrepareVar(dnF4(in[0], in[1], in[2], in[3]), a.variance[p], a.albedo ? a.albedo + size_t(p) * 3 : nullptr,
+               a.normal ? a.normal + size_t(p) * 3 : nullptr, a.depth ? a.depth + p : nullptr, c, g);
+  dnSt(a.colour + p, c);
+  dnSt(a.guide + p, g);
+}
+
+struct DnAtrousVarArgs {
+  const f4 *in, *guide;
+  f4* out;
+  uint32_t width, height, iteration, tilesX;
+  DnVarConst k;
+};
+template <int STEP_CLASS>
+__global__ void __launch_bounds__(kBlock) k_dn_atrous_var(DnAtrousVarArgs a) {
+  constexpr uint32_t kTileW = STEP_CLASS == 0 ? 16u : 64u, kTileH = kBlock / kTileW;
+  const uint32_t ty = blockIdx.x / a.tilesX, tx = blockIdx.x - ty * a.tilesX;
+  const uint32_t x = tx * kTileW + (threadIdx.x % kTileW), y = ty * kTileH + (threadIdx.x / kTileW);
+  if (x >= a.width || y >= a.height) return;
+  DnDeviceSrc src;
+  src.c = a.in; src.g = a.guide;
+  dnSt(a.out + (size_t(y) * a.width + x), dnFilterPixelVar(src, a.width, a.height, x, y, a.iteration, a.k));
+}

@@ -47,6 +47,7 @@
 #include "trace_lean_tlas.hpp"
 #include "tonemap.hpp"
 #include "denoise.hpp"
+#include "moments.hpp"
 #include "trace_ranges.hpp"
 
 using namespace yart_hip;
@@ -391,6 +392,7 @@ __global__ void __launch_bounds__(kBlock) k_tex_quads(TexQuadArgs a) {
 #include "wavefront_kernels.inc"
 #if YART_TU == 0
 #include "aov_kernels.inc"
+#include "moment_kernels.inc"
 #include "denoise_kernels.inc"
 #include "bvh_build_device.inc"
 
@@ -524,6 +526,8 @@ struct YartScene {
   // feature buffers (aov_kernels.inc): running sums / ray counts / ids per pixel of the rank; the records of the megakernel and path-pool
   // pipelines (3 x 16 B per path of the batch); the device side of the host-pointer entry point's buffers
   DevBuf<f4> aovAcc[3], aovRec; DevBuf<uint32_t> aovRays; DevBuf<int32_t> aovIds; DevBuf<uint32_t> aovOut;
+  // sample moments (moment_kernels.inc): the running state per pixel of the rank, and the host entry point's staging buffers
+  DevBuf<MomentState> momState; DevBuf<uint32_t> momOut;
   DevBuf<uint32_t> poolMap;                // path pool: the path (index of L) each slot carries, kWfFreeSlot = free
   uint32_t* poolHost = nullptr;            // pinned: the queue counters of the last rounds (the host's view of "is the batch done")
   ~YartScene() { if (poolHost) (void)hipHostFree(poolHost); }
@@ -726,8 +730,10 @@ struct BatchInfo { uint32_t c0, n, wave, waveSamples, samplesTaken, totalSamples
 typedef std::function<bool(const BatchInfo&)> BatchHook;
 
 // aov: feature buffers to fill as well (device pointers, checked by checkAovs; nullptr: none — nothing below differs from a plain render then)
+// mom: sample moments to fill as well (device pointers, checked by checkMoments; nullptr: none, and nothing below differs either)
 bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRenderParams& p, float* dOut,
-                    hipStream_t stream, YartStats* stats, const BatchHook* hook = nullptr, const YartAovBuffers* aov = nullptr) {
+                    hipStream_t stream, YartStats* stats, const BatchHook* hook = nullptr, const YartAovBuffers* aov = nullptr,
+                    const YartMomentBuffers* mom = nullptr) {
   bool aborted = false;
   auto wall0 = std::chrono::high_resolution_clock::now();
   TraceRange rgRender("yart:render");
@@ -838,7 +844,8 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
     // the resume records' per-wave ranges and the traversal spill area — taken off the budget first.
     const uint64_t perPath = (compact ? 251 : 176) + ((p.flags & YART_FLAG_NO_RESUME) ? 0 : (kResumeWords * 16 + 7) / 8);
     const uint64_t dimsEst = std::min<uint32_t>(256u, (4u + 8u * p.max_depth + 16u + 7u) & ~7u);
-    const uint64_t fixedB = uint64_t(nPix) * dimsEst * 8 + uint64_t(gridMax) * kBlock * (kResumeWords * 16 + uint64_t(spillDepthFor(s.host, true)) * 8);
+    const uint64_t fixedB = uint64_t(nPix) * dimsEst * 8 + uint64_t(gridMax) * kBlock * (kResumeWords * 16 + uint64_t(spillDepthFor(s.host, true)) * 8) +
+                            (mom ? uint64_t(nPix) * sizeof(MomentState) : 0u);      // (sample moments: 48 B per pixel of the rank)
     const uint64_t budget = (uint64_t(freeB) + held) * 8 / 10;
     const uint64_t avail = budget > fixedB ? budget - fixedB : 0;
     if (!pool) {
@@ -879,6 +886,14 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
     if (aov->mask & YART_AOV_COVERAGE) HIP_CHECK(hipMemsetAsync(aov->coverage, 0, wh * sizeof(float), stream));
     if (aov->mask & YART_AOV_IDS) HIP_CHECK(hipMemsetAsync(aov->ids, 0xff, wh * 4 * sizeof(int32_t), stream));
     if (aov->mask & YART_AOV_RAYS) HIP_CHECK(hipMemsetAsync(aov->rays, 0, wh * sizeof(uint32_t), stream));
+  }
+  // sample moments: the running state per pixel of the rank (zero), the caller's buffers cleared as the frame is
+  if (mom) {
+    const size_t np1 = std::max<uint32_t>(nPix, 1u), wh = size_t(W) * H;
+    s.momState.ensure(np1); HIP_CHECK(hipMemsetAsync(s.momState.p, 0, np1 * sizeof(MomentState), stream));
+    if (mom->mask & YART_MOMENT_MEAN) HIP_CHECK(hipMemsetAsync(mom->mean, 0, wh * 3 * sizeof(float), stream));
+    if (mom->mask & YART_MOMENT_VARIANCE) HIP_CHECK(hipMemsetAsync(mom->variance, 0, wh * sizeof(float), stream));
+    if (mom->mask & YART_MOMENT_COUNT) HIP_CHECK(hipMemsetAsync(mom->count, 0, wh * sizeof(uint32_t), stream));
   }
   uint32_t poolSlots = 0;
   if (!mega) {
@@ -1185,6 +1200,14 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
       hipLaunchKernelGGL(k_gmon_blend, dim3((n + kGmonPixPerBlock - 1) / kGmonPixPerBlock), dim3(kBlock), 0, stream, g);
       HIP_CHECK(hipGetLastError());
       tGmon.end(stream);
+      if (mom) {                               // the same records, before the next batch overwrites them
+        MomentArgs ma{};
+        ma.L = s.L.p; ma.state = s.momState.p; ma.nPixels = n; ma.spp = uint32_t(waveSamples); ma.pixBase = c0;
+        ma.exposureScale = cam.exposureScale;
+        TraceRange rgM("yart:moments_accumulate", stream);
+        hipLaunchKernelGGL(k_moments_accumulate, dim3((n + kMomentPixPerBlock - 1) / kMomentPixPerBlock), dim3(kBlock), 0, stream, ma);
+        HIP_CHECK(hipGetLastError());
+      }
       if (aov) {
         hipLaunchKernelGGL(k_aov_add_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, s.aovRays.p + c0, s.pixRays.p + c0, n);
         HIP_CHECK(hipGetLastError());
@@ -1224,6 +1247,14 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
     f.outIds = aov->ids; f.outRays = aov->rays;
     TraceRange rgA("yart:aov_finish", stream);
     hipLaunchKernelGGL(k_aov_finish, dim3((nPix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, f);
+    HIP_CHECK(hipGetLastError());
+  }
+  if (mom && nPix > 0 && !aborted) {
+    MomentFinishArgs f{};
+    f.state = s.momState.p; f.pixels = s.pixels.p; f.nPixels = nPix; f.width = W; f.mask = mom->mask;
+    f.mean = mom->mean; f.variance = mom->variance; f.count = mom->count;
+    TraceRange rgM("yart:moments_finish", stream);
+    hipLaunchKernelGGL(k_moments_finish, dim3((nPix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, f);
     HIP_CHECK(hipGetLastError());
   }
   HIP_CHECK(hipEventRecord(tAll.b, stream));
@@ -1421,22 +1452,58 @@ static bool checkAovs(const YartAovBuffers* in, const YartCameraDesc* cam, const
   return out.mask != 0u;
 }
 
-int yart_hip_render_aovs_device(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, float* d_out_rgba,
-                                const YartAovBuffers* d_aovs, void* stream, YartStats* stats) {
+// Sample moments: the caller's YartMomentBuffers checked (before anything touches a device) and copied into a struct of this
+// build's size; false: nothing is requested
+static bool checkMoments(const YartMomentBuffers* in, const YartRenderParams* params, YartMomentBuffers& out) {
+  out = YartMomentBuffers{};
+  if (in) {
+    require(in->struct_size >= 2 * sizeof(uint32_t), "YartMomentBuffers.struct_size is too small for the struct's head");
+    require((in->mask & ~YART_MOMENT_ALL) == 0u, "YartMomentBuffers.mask has bits that are no YART_MOMENT_* value");
+    const struct { uint32_t bit; size_t off; const char* null; } fields[] = {
+        {YART_MOMENT_MEAN, offsetof(YartMomentBuffers, mean), "YART_MOMENT_MEAN is requested and YartMomentBuffers.mean is null"},
+        {YART_MOMENT_VARIANCE, offsetof(YartMomentBuffers, variance), "YART_MOMENT_VARIANCE is requested and YartMomentBuffers.variance is null"},
+        {YART_MOMENT_COUNT, offsetof(YartMomentBuffers, count), "YART_MOMENT_COUNT is requested and YartMomentBuffers.count is null"}};
+    for (const auto& f : fields) {
+      if (!(in->mask & f.bit)) continue;
+      require(in->struct_size >= f.off + sizeof(void*), "YartMomentBuffers.struct_size ends before a buffer the mask requests");
+      void* ptr = *reinterpret_cast<void* const*>(reinterpret_cast<const char*>(in) + f.off);
+      require(ptr != nullptr, f.null);
+      *reinterpret_cast<void**>(reinterpret_cast<char*>(&out) + f.off) = ptr;
+    }
+    out.struct_size = uint32_t(sizeof(YartMomentBuffers)); out.mask = in->mask;
+  }
+  if (out.mask != 0u && params)
+    require(params->start_sample == 0 && (params->stop_sample == 0 || params->stop_sample == params->samples),
+            "sample moments need the full sample range (start_sample = 0, stop_sample = 0 or samples)");
+  return out.mask != 0u;
+}
+
+int yart_hip_render_moments_device(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, float* d_out_rgba,
+                                   const YartAovBuffers* d_aovs, const YartMomentBuffers* d_moments, void* stream, YartStats* stats) {
   return guarded([&] {
     YartAovBuffers av;
+    YartMomentBuffers mv;
     const bool any = checkAovs(d_aovs, cam, params, av);
+    const bool anyM = checkMoments(d_moments, params, mv);
     require(scene && d_out_rgba, "scene / output pointer is null");
     std::lock_guard<std::mutex> lock(scene->mu);
-    renderToDevice(*scene, *cam, *params, d_out_rgba, static_cast<hipStream_t>(stream), stats, nullptr, any ? &av : nullptr);
+    renderToDevice(*scene, *cam, *params, d_out_rgba, static_cast<hipStream_t>(stream), stats, nullptr, any ? &av : nullptr,
+                   anyM ? &mv : nullptr);
   });
 }
 
-int yart_hip_render_aovs(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, float* out_rgba,
-                         const YartAovBuffers* aovs, YartStats* stats) {
+int yart_hip_render_aovs_device(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, float* d_out_rgba,
+                                const YartAovBuffers* d_aovs, void* stream, YartStats* stats) {
+  return yart_hip_render_moments_device(scene, cam, params, d_out_rgba, d_aovs, nullptr, stream, stats);
+}
+
+int yart_hip_render_moments(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, float* out_rgba,
+                            const YartAovBuffers* aovs, const YartMomentBuffers* moments, YartStats* stats) {
   return guarded([&] {
     YartAovBuffers host;
+    YartMomentBuffers hostM;
     const bool any = checkAovs(aovs, cam, params, host);
+    const bool anyM = checkMoments(moments, params, hostM);
     require(scene && out_rgba, "scene / output pointer is null");
     std::lock_guard<std::mutex> lock(scene->mu);
     auto t0 = std::chrono::high_resolution_clock::now();
@@ -1461,14 +1528,82 @@ int yart_hip_render_aovs(YartScene* scene, const YartCameraDesc* cam, const Yart
         at += f.words * wh;
       }
     }
-    renderToDevice(*scene, *cam, *params, scene->hdr.p, nullptr, stats, nullptr, any ? &dev : nullptr);
+    // the moments likewise (3, 1, 1 words per pixel)
+    const struct { uint32_t bit; size_t words; size_t off; } fieldsM[] = {
+        {YART_MOMENT_MEAN, 3, offsetof(YartMomentBuffers, mean)}, {YART_MOMENT_VARIANCE, 1, offsetof(YartMomentBuffers, variance)},
+        {YART_MOMENT_COUNT, 1, offsetof(YartMomentBuffers, count)}};
+    YartMomentBuffers devM = hostM;
+    if (anyM) {
+      size_t words = 0;
+      for (const auto& f : fieldsM) if (hostM.mask & f.bit) words += f.words * wh;
+      scene->momOut.ensure(words);
+      size_t at = 0;
+      for (const auto& f : fieldsM) if (hostM.mask & f.bit) {
+        *reinterpret_cast<void**>(reinterpret_cast<char*>(&devM) + f.off) = scene->momOut.p + at;
+        at += f.words * wh;
+      }
+    }
+    renderToDevice(*scene, *cam, *params, scene->hdr.p, nullptr, stats, nullptr, any ? &dev : nullptr, anyM ? &devM : nullptr);
     HIP_CHECK(hipMemcpy(out_rgba, scene->hdr.p, n * sizeof(float), hipMemcpyDeviceToHost));
     if (any)
       for (const auto& f : fields) if (host.mask & f.bit)
         HIP_CHECK(hipMemcpy(*reinterpret_cast<void**>(reinterpret_cast<char*>(&host) + f.off),
                             *reinterpret_cast<void**>(reinterpret_cast<char*>(&dev) + f.off), f.words * wh * 4, hipMemcpyDeviceToHost));
+    if (anyM)
+      for (const auto& f : fieldsM) if (hostM.mask & f.bit)
+        HIP_CHECK(hipMemcpy(*reinterpret_cast<void**>(reinterpret_cast<char*>(&hostM) + f.off),
+                            *reinterpret_cast<void**>(reinterpret_cast<char*>(&devM) + f.off), f.words * wh * 4, hipMemcpyDeviceToHost));
     if (stats)
       stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+  });
+}
+
+int yart_hip_render_aovs(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, float* out_rgba,
+                         const YartAovBuffers* aovs, YartStats* stats) {
+  return yart_hip_render_moments(scene, cam, params, out_rgba, aovs, nullptr, stats);
+}
+
+// Diagnostic: the moment kernels on caller-supplied per-sample records (no scene), one accumulate launch per chunk
+int yart_hip_probe_moments(const float* L_rgba, uint32_t n_pixels, uint32_t spp, const uint32_t* chunks, uint32_t n_chunks,
+                           float exposure_scale, float* mean, float* variance, uint32_t* count) {
+  return guarded([&] {
+    require(L_rgba && chunks && mean && variance && count, "probe_moments: null pointer");
+    require(n_pixels > 0 && spp > 0 && n_chunks > 0, "probe_moments: n_pixels, spp or n_chunks is 0");
+    require(uint64_t(n_pixels) * spp <= (1ull << 26), "probe_moments: more than 2^26 records");
+    uint64_t sum = 0;
+    for (uint32_t c = 0; c < n_chunks; c++) { require(chunks[c] > 0, "probe_moments: an empty chunk"); sum += chunks[c]; }
+    require(sum == spp, "probe_moments: the chunks do not sum to spp");
+    int devices = 0;
+    if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0) throw HipError("no HIP device");
+    DevBuf<f4> L; DevBuf<MomentState> state; DevBuf<float> dMean, dVar; DevBuf<uint32_t> dCount;
+    uint32_t largest = 0;
+    for (uint32_t c = 0; c < n_chunks; c++) largest = std::max(largest, chunks[c]);
+    L.ensure(size_t(n_pixels) * largest); state.ensure(n_pixels); dMean.ensure(size_t(n_pixels) * 3); dVar.ensure(n_pixels); dCount.ensure(n_pixels);
+    HIP_CHECK(hipMemset(state.p, 0, size_t(n_pixels) * sizeof(MomentState)));
+    std::vector<f4> wave(size_t(n_pixels) * largest);
+    const f4* all = reinterpret_cast<const f4*>(L_rgba);
+    uint32_t s0 = 0;
+    for (uint32_t c = 0; c < n_chunks; c++) {
+      const uint32_t w = chunks[c];           // the records of this "wave", pixel-major, w per pixel: what a batch holds in its L array
+      for (uint32_t pi = 0; pi < n_pixels; pi++)
+        for (uint32_t k = 0; k < w; k++) wave[size_t(pi) * w + k] = all[size_t(pi) * spp + s0 + k];
+      HIP_CHECK(hipMemcpy(L.p, wave.data(), size_t(n_pixels) * w * sizeof(f4), hipMemcpyHostToDevice));
+      MomentArgs ma{};
+      ma.L = L.p; ma.state = state.p; ma.nPixels = n_pixels; ma.spp = w; ma.pixBase = 0; ma.exposureScale = exposure_scale;
+      hipLaunchKernelGGL(k_moments_accumulate, dim3((n_pixels + kMomentPixPerBlock - 1) / kMomentPixPerBlock), dim3(kBlock), 0, nullptr, ma);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipDeviceSynchronize());
+      s0 += w;
+    }
+    MomentFinishArgs f{};
+    f.state = state.p; f.pixels = nullptr; f.nPixels = n_pixels; f.width = n_pixels; f.mask = YART_MOMENT_ALL;
+    f.mean = dMean.p; f.variance = dVar.p; f.count = dCount.p;
+    hipLaunchKernelGGL(k_moments_finish, dim3((n_pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, f);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(mean, dMean.p, size_t(n_pixels) * 12, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(variance, dVar.p, size_t(n_pixels) * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(count, dCount.p, size_t(n_pixels) * 4, hipMemcpyDeviceToHost));
   });
 }
 
@@ -1928,6 +2063,98 @@ int yart_hip_denoise_atrous_host(const float* rgba, const float* albedo, const f
     if (normal) { nrm.ensure(n * 3); HIP_CHECK(hipMemcpy(nrm.p, normal, n * 12, hipMemcpyHostToDevice)); }
     if (depth) { dep.ensure(n); HIP_CHECK(hipMemcpy(dep.p, depth, n * 4, hipMemcpyHostToDevice)); }
     denoiseRun(c, frame.p, alb.p, nrm.p, dep.p, width, height, frame.p, nullptr);
+    HIP_CHECK(hipMemcpy(out_rgba, frame.p, n * 16, hipMemcpyDeviceToHost));
+  });
+}
+
+// The variance-guided form (denoise_kernels.inc: k_dn_prepare_var, k_dn_atrous_var). The arguments are judged before any device is touched.
+namespace {
+struct DnVarCall { DnVarConst k; uint32_t iterations; bool demodulate; };
+DnVarCall denoiseVarCheck(const void* rgba, const void* variance, const void* albedo, const void* normal, const void* depth, uint32_t width,
+                          uint32_t height, const YartDenoiseVarParams* params, const void* out) {
+  require(rgba && out, "denoise: rgba / out pointer is null");
+  require(variance != nullptr, "denoise: variance pointer is null");
+  require(params != nullptr, "denoise: params pointer is null");
+  require(params->struct_size >= sizeof(YartDenoiseVarParams), "denoise: struct_size is smaller than YartDenoiseVarParams");
+  require(params->iterations <= 8u, "denoise: iterations > 8");
+  require(width > 0 && height > 0, "denoise: width or height is 0");
+  require(uint64_t(width) * height <= (1ull << 28), "denoise: more than 2^28 pixels");
+  require(std::isfinite(params->sigma_luma) && std::isfinite(params->sigma_normal) && std::isfinite(params->sigma_depth),
+          "denoise: a sigma is not finite");
+  require((params->flags & ~uint32_t(YART_DENOISE_DEMODULATE)) == 0u, "denoise: unknown flags bits");
+  DnVarCall c;
+  c.iterations = params->iterations;
+  c.demodulate = (params->flags & YART_DENOISE_DEMODULATE) != 0u;
+  require(!c.demodulate || albedo, "denoise: YART_DENOISE_DEMODULATE without an albedo buffer");
+  c.k.sigmaLuma = params->sigma_luma;
+  c.k.inrm = normal ? dnInvSigma2(params->sigma_normal) : 0.0f;
+  c.k.idep = depth ? dnInvSigma2(params->sigma_depth) : 0.0f;
+  c.k.terms = (params->sigma_luma > 0.0f ? kDnColor : 0u) | (normal && params->sigma_normal > 0.0f ? kDnNormal : 0u) |
+              (depth && params->sigma_depth > 0.0f ? kDnDepth : 0u);
+  return c;
+}
+
+// device pointers; enqueues on `st` and returns after completion
+void denoiseVarRun(const DnVarCall& c, const float* rgba, const float* variance, const float* albedo, const float* normal,
+                   const float* depth, uint32_t width, uint32_t height, float* out, hipStream_t st) {
+  const uint32_t n = width * height;
+  if (c.iterations == 0u) {
+    if (out != rgba) HIP_CHECK(hipMemcpyAsync(out, rgba, size_t(n) * 16, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return;
+  }
+  DevBuf<f4> scratch;                               // colour + variance image 0 | image 1 | guide records: 48 bytes per pixel
+  scratch.ensure(size_t(n) * 3);
+  f4 *img[2] = {scratch.p, scratch.p + n}, *guide = scratch.p + size_t(n) * 2;
+  const dim3 flat((n + kBlock - 1) / kBlock), block(kBlock);
+  DnPrepareVarArgs pa{rgba, variance, c.demodulate ? albedo : nullptr, normal, depth, img[0], guide, n, 0u};
+  hipLaunchKernelGGL(k_dn_prepare_var, flat, block, 0, st, pa);
+  HIP_CHECK(hipGetLastError());
+  for (uint32_t i = 0; i < c.iterations; i++) {
+    DnAtrousVarArgs aa{img[i & 1u], guide, img[(i + 1u) & 1u], width, height, i, 0u, c.k};
+    if (i < 2u) {
+      aa.tilesX = (width + 15u) / 16u;
+      hipLaunchKernelGGL(k_dn_atrous_var<0>, dim3(aa.tilesX * ((height + 15u) / 16u)), block, 0, st, aa);
+    } else {
+      aa.tilesX = (width + 63u) / 64u;
+      hipLaunchKernelGGL(k_dn_atrous_var<1>, dim3(aa.tilesX * ((height + 3u) / 4u)), block, 0, st, aa);
+    }
+    HIP_CHECK(hipGetLastError());
+  }
+  DnFinishArgs fa{img[c.iterations & 1u], rgba, c.demodulate ? albedo : nullptr, out, n, 0u};
+  hipLaunchKernelGGL(k_dn_finish, flat, block, 0, st, fa);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(st));
+}
+}  // namespace
+
+int yart_hip_denoise_atrous_var_device(const float* d_rgba, const float* d_variance, const float* d_albedo, const float* d_normal,
+                                       const float* d_depth, uint32_t width, uint32_t height, const YartDenoiseVarParams* params,
+                                       float* d_out_rgba, void* stream) {
+  return guarded([&] {
+    const DnVarCall c = denoiseVarCheck(d_rgba, d_variance, d_albedo, d_normal, d_depth, width, height, params, d_out_rgba);
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw HipError("no HIP device");
+    denoiseVarRun(c, d_rgba, d_variance, d_albedo, d_normal, d_depth, width, height, d_out_rgba, static_cast<hipStream_t>(stream));
+  });
+}
+
+int yart_hip_denoise_atrous_var_host(const float* rgba, const float* variance, const float* albedo, const float* normal,
+                                     const float* depth, uint32_t width, uint32_t height, const YartDenoiseVarParams* params,
+                                     float* out_rgba) {
+  return guarded([&] {
+    const DnVarCall c = denoiseVarCheck(rgba, variance, albedo, normal, depth, width, height, params, out_rgba);
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw HipError("no HIP device");
+    const size_t n = size_t(width) * height;
+    DevBuf<float> frame, var, alb, nrm, dep;          // the frame is filtered in place on the device
+    frame.ensure(n * 4); var.ensure(n);
+    HIP_CHECK(hipMemcpy(frame.p, rgba, n * 16, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(var.p, variance, n * 4, hipMemcpyHostToDevice));
+    if (albedo && c.demodulate) { alb.ensure(n * 3); HIP_CHECK(hipMemcpy(alb.p, albedo, n * 12, hipMemcpyHostToDevice)); }
+    if (normal) { nrm.ensure(n * 3); HIP_CHECK(hipMemcpy(nrm.p, normal, n * 12, hipMemcpyHostToDevice)); }
+    if (depth) { dep.ensure(n); HIP_CHECK(hipMemcpy(dep.p, depth, n * 4, hipMemcpyHostToDevice)); }
+    denoiseVarRun(c, frame.p, var.p, alb.p, nrm.p, dep.p, width, height, frame.p, nullptr);
     HIP_CHECK(hipMemcpy(out_rgba, frame.p, n * 16, hipMemcpyDeviceToHost));
   });
 }
