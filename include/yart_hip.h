@@ -576,6 +576,89 @@ int yart_hip_denoise_atrous_var_host(const float* rgba, const float* variance, c
                                      const float* depth, uint32_t width, uint32_t height, const YartDenoiseVarParams* params,
                                      float* out_rgba);
 
+/* Temporal accumulation with camera reprojection — the temporal half of SVGF — for a SEQUENCE of frames of one scene: the stage
+ * between yart_hip_render_moments and yart_hip_denoise_atrous_var_device. A scene is immutable after yart_hip_scene_create, so the
+ * only thing that moves between frames is the camera: the position buffer (world-space Hit.p) and the previous frame's
+ * YartCameraDesc are a complete motion description, and no render kernel takes part. Per frame the accumulator takes the frame, its
+ * variance (YART_MOMENT_VARIANCE), its feature buffers and its camera; it projects every pixel's surface point into the previous
+ * frame's camera, fetches the accumulated history there with a validated bilinear tap set, blends, and returns the accumulated
+ * frame, the variance of that estimate and the history length per pixel. Frame and variance are what the variance-guided filter takes.
+ * The handle holds the history for one image size on one device: two images (the pass reads neighbours of one while it writes the
+ * other) of three 16-byte records per pixel — {acc.rgb, variance}, {P.xyz, length}, {n.xyz, node} — 96 BYTES PER PIXEL, allocated
+ * by the first accumulate call (yart_hip_temporal_create touches no device), and the YartCameraDesc of the last accumulated frame.
+ * DEFINITION. Every operation is an individually rounded binary32 operation in the order written (no FMA contraction); dot(a, b) is
+ * (a.x * b.x + a.y * b.y) + a.z * b.z, cross(a, b) = (a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); only
+ * + - * /, floorf and comparisons occur. csrc/temporal.hpp states it; yart_amd/temporal.py temporal_reference is the NumPy
+ * statement the tests compare with, on bits.
+ *   Current pixel p:
+ *     d = alb > 1e-3f ? alb : 1.0f per channel with YART_TEMPORAL_DEMODULATE (the filters' rule), else (1, 1, 1) (albedo is not read)
+ *     c = rgb(p) / d per channel;  ld = luma(d) = (d.r * 0.2126f + d.g * 0.7152f) + d.b * 0.0722f;  v = variance(p) / (ld * ld)
+ *     usable(p)        every component of c is finite, and of albedo(p) when demodulating; variance(p) is finite and >= 0; v is finite
+ *     reprojectable(p) usable(p), coverage(p) == 1.0f, and position(p), normal(p) and depth(p) are finite. (The feature buffers are
+ *                      sums over the hitting samples divided by `samples`: position is a surface point only where every sample hit.)
+ *     !usable(p): out_rgba(p) = rgba(p) and out_variance(p) = variance(p), the input bits; out_length(p) = 0; the pixel's history
+ *                      record is all zero — length 0 — and is nobody's tap.
+ *   Projection of P = position(p) through the PREVIOUS camera's lens centre onto its focus plane, with the derived quantities of
+ *   Camera::calcDerivedProperties (position, topLeftPixel tl, pixelDeltaU dU, pixelDeltaV dV), formed as the renderer forms them:
+ *     nrm = cross(dU, dV);  num = dot(tl - position, nrm);  rel = P - position;  s = num / dot(rel, nrm)
+ *     in front of the camera iff s > 0.0f and s <= FLT_MAX (the denominator has num's sign and is not 0); else no tap counts
+ *     X = (position + rel * s) - tl;  jx = dot(X, dU) / dot(dU, dU);  jy = dot(X, dV) / dot(dV, dV)
+ *     (jx, jy) is in the units of Camera::getRay's jitter: pixel (px, py)'s centre is (float(px), float(py)), its gaussian jitter has mean 0.
+ *     no tap counts unless -1.0f <= jx < float(width) and -1.0f <= jy < float(height)
+ *     x0 = floorf(jx), y0 = floorf(jy);  fx = jx - x0, fy = jy - y0;  taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), in
+ *     this order, with the bilinear weights w = (fx or 1.0f - fx) * (fy or 1.0f - fy)
+ *   A tap q COUNTS iff it is inside the image; its history length is >= 1; its node equals ids(p)[0]; dot(n(p), n_hist(q)) >=
+ *     normal_cos_min; fabsf(dot(n(p), P_hist(q) - P)) <= plane_tolerance * depth(p); and its weight w > 0.0f (a tap of weight 0
+ *     contributes nothing, so it neither shortens the length nor leaves a sum of weights of 0).
+ *   Blend, sums over the counting taps in tap order starting from 0.0f (acc = acc + w * value):
+ *     h = sum(w * c_hist) / sum(w) per channel;  v_h = sum(w * v_hist) / sum(w), the same weights — conservative on purpose:
+ *     neighbouring history pixels are correlated;  N_h = the smallest length of the counting taps
+ *     N = min(N_h + 1, max_history);  a = max(1.0f / float(N), alpha_min);  acc = h + a * (c - h) per channel
+ *     v_acc = (a * a) * v + ((1.0f - a) * (1.0f - a)) * v_h
+ *     No counting tap, p not reprojectable, or an empty history (first frame, or the first after a reset): acc = c, v_acc = v, N = 1.
+ *   Outputs: out_rgba(p) = (acc * d, rgba(p).a);  out_variance(p) = v_acc * (ld * ld);  out_length(p) = N.
+ *   New history record of p: {acc, v_acc}, {P, N}, {n(p), ids(p)[0]} — colour and variance in the demodulated domain.
+ * The defaults minimise the worst case, over 6-frame orbits of the two golden scenes rendered by the host path tracer at 4 spp, of
+ * the last frame's error against 1024 spp relative to not accumulating (tools/temporal_sweep.py, profiles/temporal_sweep.txt: RMSE
+ * 0.60 / 0.71 of the last frame's alone on cornell / material; followed by the variance-guided filter, 0.91 of that filter's alone).
+ * Out of scope: moving geometry, a wider search when all four taps fail, colour clamps against ghosting, yart_hip_multi_*. */
+#define YART_TEMPORAL_DEMODULATE 1u         /* accumulate rgb / d, return acc * d (needs YART_AOV_ALBEDO) */
+#define YART_TEMPORAL_DEFAULT_ALPHA_MIN 0.1f
+#define YART_TEMPORAL_DEFAULT_MAX_HISTORY 8u
+#define YART_TEMPORAL_DEFAULT_NORMAL_COS_MIN 0.8f
+#define YART_TEMPORAL_DEFAULT_PLANE_TOLERANCE 0.01f
+typedef struct YartTemporalParams {
+  uint32_t struct_size;        /* sizeof(YartTemporalParams): lets the struct grow without an ABI bump */
+  float alpha_min;             /* 0 .. 1: the smallest weight of the new frame */
+  uint32_t max_history;        /* >= 1: the cap of the history length */
+  float normal_cos_min;        /* finite */
+  float plane_tolerance;       /* finite; relative to the pixel's depth */
+  uint32_t flags;              /* YART_TEMPORAL_* */
+} YartTemporalParams;
+typedef struct YartTemporal YartTemporal;
+/* width, height > 0 (at most 2^28 pixels); device < 0: the device current at the first accumulate call. No device is touched. */
+int yart_hip_temporal_create(uint32_t width, uint32_t height, int device, YartTemporal** out);
+void yart_hip_temporal_destroy(YartTemporal* temporal);
+/* Forget the history: the next frame is a first frame. */
+int yart_hip_temporal_reset(YartTemporal* temporal);
+/* One frame. DEVICE pointers on `stream` (hipStream_t, may be NULL); returns after completion on that stream. d_rgba: width * height
+ * * 4 floats; d_variance: width * height; d_aovs: position, normal, depth, coverage and ids are required (and albedo with
+ * YART_TEMPORAL_DEMODULATE), as yart_hip_render_moments_device fills them; buffers of other mask bits are not touched.
+ * d_out_variance (width * height floats) and d_out_length (width * height uint32) may each be NULL. d_out_rgba may be d_rgba and
+ * d_out_variance may be d_variance; the outputs may not overlap any other input.
+ * YART_E_INVALID, with a message and before any device is touched: a NULL temporal, cam, d_rgba, d_variance, d_aovs, params or
+ * d_out_rgba; a struct_size smaller than YartTemporalParams; unknown flags bits; a parameter that is not finite; alpha_min outside
+ * [0, 1]; max_history of 0; a camera whose width / height are not the handle's (or with a focal length <= 0); a required feature
+ * buffer missing from d_aovs->mask (or NULL, or beyond its struct_size). YART_E_NO_DEVICE without a HIP device. */
+int yart_hip_temporal_accumulate_device(YartTemporal* temporal, const YartCameraDesc* cam, const float* d_rgba, const float* d_variance,
+                                        const YartAovBuffers* d_aovs, const YartTemporalParams* params, float* d_out_rgba,
+                                        float* d_out_variance, uint32_t* d_out_length, void* stream);
+/* Same, HOST pointers: the buffers are copied to the handle's device, accumulated there (the history stays on the device) and the
+ * outputs copied back. */
+int yart_hip_temporal_accumulate_host(YartTemporal* temporal, const YartCameraDesc* cam, const float* rgba, const float* variance,
+                                      const YartAovBuffers* aovs, const YartTemporalParams* params, float* out_rgba,
+                                      float* out_variance, uint32_t* out_length);
+
 const char* yart_hip_last_error(void);
 int yart_hip_abi_version(void);
 int yart_hip_device_count(void);

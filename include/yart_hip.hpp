@@ -179,6 +179,57 @@ inline std::vector<float> denoiseVar(const std::vector<float>& rgba, const std::
   return out;
 }
 
+// Temporal accumulation with camera reprojection for a sequence of frames of one scene (yart_hip_temporal_*): the stage between a
+// render with moments and denoiseVar. The handle holds the history (96 bytes per pixel on the device) and the last camera.
+inline YartTemporalParams temporalDefaults(bool demodulate = false) {
+  YartTemporalParams p{};
+  p.struct_size = uint32_t(sizeof(p)); p.alpha_min = YART_TEMPORAL_DEFAULT_ALPHA_MIN; p.max_history = YART_TEMPORAL_DEFAULT_MAX_HISTORY;
+  p.normal_cos_min = YART_TEMPORAL_DEFAULT_NORMAL_COS_MIN; p.plane_tolerance = YART_TEMPORAL_DEFAULT_PLANE_TOLERANCE;
+  p.flags = demodulate ? YART_TEMPORAL_DEMODULATE : 0u;
+  return p;
+}
+struct TemporalFeatures {                   // the frame's feature buffers: 3 / 3 / 1 / 1 / 4 (/ 3) values per pixel
+  std::vector<float> position, normal, depth, coverage;
+  std::vector<int32_t> ids;
+  std::vector<float> albedo;                // only with YART_TEMPORAL_DEMODULATE
+};
+struct TemporalFrame { std::vector<float> rgba, variance; std::vector<uint32_t> length; };
+class Temporal {
+ public:
+  Temporal(uint32_t width, uint32_t height, int device = 0) : m_width(width), m_height(height) {
+    check(yart_hip_temporal_create(width, height, device, &m_handle));
+  }
+  ~Temporal() { yart_hip_temporal_destroy(m_handle); }
+  Temporal(const Temporal&) = delete;
+  Temporal& operator=(const Temporal&) = delete;
+  Temporal(Temporal&& o) noexcept : m_handle(o.m_handle), m_width(o.m_width), m_height(o.m_height) { o.m_handle = nullptr; }
+
+  void reset() { check(yart_hip_temporal_reset(m_handle)); }
+  // one frame, host buffers: the accumulated frame, its variance and the history length per pixel
+  TemporalFrame accumulate(const YartCameraDesc& camera, const std::vector<float>& rgba, const std::vector<float>& variance,
+                           const TemporalFeatures& f, const YartTemporalParams& params) {
+    const size_t n = size_t(m_width) * m_height;
+    if (rgba.size() != n * 4 || variance.size() != n || f.position.size() != n * 3 || f.normal.size() != n * 3 || f.depth.size() != n ||
+        f.coverage.size() != n || f.ids.size() != n * 4 || (!f.albedo.empty() && f.albedo.size() != n * 3))
+      throw Error(YART_E_INVALID, "Temporal::accumulate: a buffer does not have width * height * channels values");
+    YartAovBuffers a{};
+    a.struct_size = uint32_t(sizeof(a));
+    a.mask = YART_AOV_POSITION | YART_AOV_NORMAL | YART_AOV_DEPTH | YART_AOV_COVERAGE | YART_AOV_IDS | (f.albedo.empty() ? 0u : YART_AOV_ALBEDO);
+    a.position = const_cast<float*>(f.position.data()); a.normal = const_cast<float*>(f.normal.data());
+    a.depth = const_cast<float*>(f.depth.data()); a.coverage = const_cast<float*>(f.coverage.data());
+    a.ids = const_cast<int32_t*>(f.ids.data()); a.albedo = f.albedo.empty() ? nullptr : const_cast<float*>(f.albedo.data());
+    TemporalFrame out{std::vector<float>(n * 4), std::vector<float>(n), std::vector<uint32_t>(n)};
+    check(yart_hip_temporal_accumulate_host(m_handle, &camera, rgba.data(), variance.data(), &a, &params, out.rgba.data(),
+                                            out.variance.data(), out.length.data()));
+    return out;
+  }
+  YartTemporal* handle() const { return m_handle; }
+
+ private:
+  YartTemporal* m_handle = nullptr;
+  uint32_t m_width, m_height;
+};
+
 // The scene replicated on several GPUs of this node (yart_hip_multi_*): TileRenderer's worker pool with a GPU per worker.
 class MultiDeviceScene {
  public:

@@ -29,6 +29,8 @@ from .denoise import (DEFAULT_ITERATIONS, DEFAULT_SIGMA_COLOR, DEFAULT_SIGMA_DEP
 from .denoise import (DEFAULT_VAR_ITERATIONS, DEFAULT_VAR_SIGMA_DEPTH, DEFAULT_VAR_SIGMA_LUMA, DEFAULT_VAR_SIGMA_NORMAL,
                       atrous_var_reference)  # noqa: F401 (the NumPy statement of denoise_var / denoise_var_into)
 from .moments import moments_reference  # noqa: F401 (the NumPy statement of render_moments / probe_moments)
+from .temporal import (DEFAULT_ALPHA_MIN, DEFAULT_MAX_HISTORY, DEFAULT_NORMAL_COS_MIN, DEFAULT_PLANE_TOLERANCE,
+                       temporal_reference)  # noqa: F401 (the NumPy statement of TemporalAccumulator.accumulate / accumulate_into)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libyart_hip.so")
@@ -221,6 +223,22 @@ def make_denoise_var_params(iterations=DEFAULT_VAR_ITERATIONS, sigma_luma=DEFAUL
                             float(sigma_depth), FLAG_DEMODULATE if demodulate else 0)
 
 
+class TemporalParams(C.Structure):
+    """YartTemporalParams (include/yart_hip.h): the knobs of the temporal accumulator."""
+    _fields_ = [("struct_size", C.c_uint32), ("alpha_min", C.c_float), ("max_history", C.c_uint32),
+                ("normal_cos_min", C.c_float), ("plane_tolerance", C.c_float), ("flags", C.c_uint32)]
+
+
+FLAG_TEMPORAL_DEMODULATE = 1
+TEMPORAL_AOVS = ("position", "normal", "depth", "coverage", "ids")     # + "albedo" when demodulating
+
+
+def make_temporal_params(alpha_min=DEFAULT_ALPHA_MIN, max_history=DEFAULT_MAX_HISTORY, normal_cos_min=DEFAULT_NORMAL_COS_MIN,
+                         plane_tolerance=DEFAULT_PLANE_TOLERANCE, demodulate=False) -> TemporalParams:
+    return TemporalParams(C.sizeof(TemporalParams), float(alpha_min), int(max_history), float(normal_cos_min),
+                          float(plane_tolerance), FLAG_TEMPORAL_DEMODULATE if demodulate else 0)
+
+
 class DenoiseParams(C.Structure):
     """YartDenoiseParams (include/yart_hip.h): the knobs of the à-trous filter."""
     _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("sigma_color", C.c_float),
@@ -273,7 +291,9 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_probe_math", "yart_hip_probe_math_pairs",
            "yart_hip_denoise_atrous_device", "yart_hip_denoise_atrous_host",
            "yart_hip_render_moments", "yart_hip_render_moments_device", "yart_hip_probe_moments",
-           "yart_hip_denoise_atrous_var_device", "yart_hip_denoise_atrous_var_host"]
+           "yart_hip_denoise_atrous_var_device", "yart_hip_denoise_atrous_var_host",
+           "yart_hip_temporal_create", "yart_hip_temporal_destroy", "yart_hip_temporal_reset",
+           "yart_hip_temporal_accumulate_device", "yart_hip_temporal_accumulate_host"]
 
 LIB_COUNT_PATH = os.path.join(_HERE, "libyart_hip_count.so")   # instrumented twin (exact test counters)
 _libs = {}
@@ -344,6 +364,14 @@ def lib(instrumented: bool = False):
                                                          C.c_uint32, C.POINTER(DenoiseVarParams), C.c_void_p, C.c_void_p]
         L.yart_hip_denoise_atrous_var_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                        C.c_uint32, C.POINTER(DenoiseVarParams), C.c_void_p]
+        L.yart_hip_temporal_create.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+        L.yart_hip_temporal_destroy.argtypes = [C.c_void_p]
+        L.yart_hip_temporal_destroy.restype = None
+        L.yart_hip_temporal_reset.argtypes = [C.c_void_p]
+        L.yart_hip_temporal_accumulate_device.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers),
+                                                          C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.yart_hip_temporal_accumulate_host.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers),
+                                                        C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p]
         L.yart_hip_bvh_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.yart_hip_bvh_copy.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         _libs[path] = L
@@ -680,15 +708,22 @@ class DeviceScene:
 
     def render_denoised(self, p: dict, iterations=None, sigma_color=DEFAULT_SIGMA_COLOR, sigma_normal=None, sigma_depth=None,
                         demodulate=True, rank=0, world_size=1, flags=0, device="cuda", variance_guided=False,
-                        sigma_luma=DEFAULT_VAR_SIGMA_LUMA):
+                        sigma_luma=DEFAULT_VAR_SIGMA_LUMA, temporal=None):
         """``render_aovs_into`` for albedo, normal and depth, then the à-trous filter (``denoise_into``) on the same device
         buffers, on torch's current stream: no host round trip. Returns (noisy frame, denoised frame, {name: guide}) as torch
         tensors of ``device`` ((H, W, 4); guides (H, W, 3) / (H, W)).
         ``variance_guided=True``: ``render_moments_into`` with the variance buffer as well, then the variance-guided filter
         (``denoise_var_into``) with ``sigma_luma`` in place of ``sigma_color`` (which is not used then); the guides returned
         then include "variance" (H, W). ``iterations``, ``sigma_normal`` and ``sigma_depth`` left at None take the defaults
-        of the filter that runs (DEFAULT_* of the plain one, DEFAULT_VAR_* of the variance-guided one)."""
+        of the filter that runs (DEFAULT_* of the plain one, DEFAULT_VAR_* of the variance-guided one).
+        ``temporal``: a :class:`TemporalAccumulator` of the frame's size — one frame of a sequence: ``render_moments_into`` with
+        the variance and the feature buffers the accumulator needs, then ``temporal.accumulate_into`` (at the accumulator's own
+        parameters, demodulating as ``demodulate`` says), then the variance-guided filter on the accumulated frame and variance
+        (``variance_guided`` is implied). Returns (noisy frame, denoised frame, guides) with "accumulated" (H, W, 4),
+        "accumulated_variance" (H, W) and "length" (H, W, int32 holding the uint32) among the guides. None: as before."""
         import torch
+        if temporal is not None:
+            variance_guided = True
         dflt = ((DEFAULT_VAR_ITERATIONS, DEFAULT_VAR_SIGMA_NORMAL, DEFAULT_VAR_SIGMA_DEPTH) if variance_guided else
                 (DEFAULT_ITERATIONS, DEFAULT_SIGMA_NORMAL, DEFAULT_SIGMA_DEPTH))
         iterations = dflt[0] if iterations is None else iterations
@@ -700,6 +735,18 @@ class DeviceScene:
                   "normal": torch.empty((h, w, 3), dtype=torch.float32, device=device),
                   "depth": torch.empty((h, w), dtype=torch.float32, device=device)}
         stream = torch.cuda.current_stream(noisy.device).cuda_stream
+        if temporal is not None:
+            variance = torch.empty((h, w), dtype=torch.float32, device=device)
+            feats = dict(guides, position=torch.empty((h, w, 3), dtype=torch.float32, device=device),
+                         coverage=torch.empty((h, w), dtype=torch.float32, device=device),
+                         ids=torch.empty((h, w, 4), dtype=torch.int32, device=device))
+            self.render_moments_into(noisy, feats, {"variance": variance}, p, rank, world_size, flags, stream=stream)
+            acc, acc_var = torch.empty_like(noisy), torch.empty_like(variance)
+            length = torch.empty((h, w), dtype=torch.int32, device=device)
+            temporal.accumulate_into(acc, acc_var, length, p, noisy, variance, feats, demodulate=demodulate, stream=stream)
+            clean = torch.empty_like(noisy)
+            denoise_var_into(clean, acc, acc_var, guides, iterations, sigma_luma, sigma_normal, sigma_depth, demodulate)
+            return noisy, clean, dict(feats, variance=variance, accumulated=acc, accumulated_variance=acc_var, length=length)
         if variance_guided:
             variance = torch.empty((h, w), dtype=torch.float32, device=device)
             self.render_moments_into(noisy, guides, {"variance": variance}, p, rank, world_size, flags, stream=stream)
@@ -1079,6 +1126,124 @@ def denoise_var_into(out_tensor, frame_tensor, variance_tensor, guides=None, ite
                                                     ptrs["normal"], ptrs["depth"], w, h, C.byref(dp),
                                                     C.c_void_p(out_tensor.data_ptr()), C.c_void_p(stream) if stream else None), L)
     return out_tensor
+
+
+class TemporalAccumulator:
+    """Temporal accumulation with camera reprojection for a sequence of frames of one scene (include/yart_hip.h:
+    yart_hip_temporal_*): the stage between ``render_moments`` and ``denoise_var``. Holds the history (96 bytes per pixel on the
+    device, allocated by the first frame) and the last frame's camera. ``alpha_min`` / ``max_history`` / ``normal_cos_min`` /
+    ``plane_tolerance`` are the parameters of every frame unless a call overrides them. ``device`` < 0: the device current at
+    the first frame. yart_amd.temporal.temporal_reference states the same arithmetic in NumPy."""
+
+    def __init__(self, width: int, height: int, device: int = 0, alpha_min=DEFAULT_ALPHA_MIN, max_history=DEFAULT_MAX_HISTORY,
+                 normal_cos_min=DEFAULT_NORMAL_COS_MIN, plane_tolerance=DEFAULT_PLANE_TOLERANCE):
+        self._L = lib()
+        self.width, self.height, self.device = int(width), int(height), int(device)
+        self.params = dict(alpha_min=alpha_min, max_history=max_history, normal_cos_min=normal_cos_min,
+                           plane_tolerance=plane_tolerance)
+        h = C.c_void_p()
+        _check(self._L.yart_hip_temporal_create(self.width, self.height, self.device, C.byref(h)), self._L)
+        self._h = h
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.yart_hip_temporal_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        """Forget the history: the next frame is a first frame."""
+        _check(self._L.yart_hip_temporal_reset(self._h), self._L)
+
+    def _camera(self, cam):
+        return cam if isinstance(cam, CameraDesc) else make_camera(cam)
+
+    def _params(self, demodulate, over):
+        unknown = set(over) - set(self.params)
+        assert not unknown, f"TemporalAccumulator: unknown parameters {sorted(unknown)}"
+        return make_temporal_params(demodulate=demodulate, **dict(self.params, **over))
+
+    def accumulate(self, cam, frame, variance, aovs: dict, demodulate=None, out=None, out_variance=None, **over):
+        """One frame on NumPy arrays (yart_hip_temporal_accumulate_host). ``cam``: the frame's camera (a params dict as
+        ``render`` takes it, or a CameraDesc); ``frame`` (H, W, 4); ``variance`` (H, W); ``aovs``: the feature buffers by name —
+        position, normal, depth, coverage, ids, and albedo when demodulating (``demodulate`` None: whenever albedo is given).
+        ``out`` / ``out_variance`` may be ``frame`` / ``variance``. Returns (accumulated frame, its variance, history length
+        (H, W) uint32)."""
+        h, w = self.height, self.width
+        frame = np.ascontiguousarray(frame, np.float32)
+        variance = np.ascontiguousarray(variance, np.float32)
+        assert frame.shape == (h, w, 4) and variance.size == h * w
+        if demodulate is None:
+            demodulate = aovs.get("albedo") is not None
+        ab, keep = AovBuffers(), []
+        ab.struct_size = C.sizeof(AovBuffers)
+        for name in TEMPORAL_AOVS + (("albedo",) if demodulate else ()):
+            a = aovs.get(name)
+            if a is None:
+                continue
+            bit, ch, dt = AOVS[name]
+            a = np.ascontiguousarray(a, dt)
+            assert a.size == h * w * ch, name
+            keep.append(a)
+            ab.mask |= bit
+            setattr(ab, name, a.ctypes.data_as(C.c_void_p))
+        if out is None:
+            out = np.empty_like(frame)
+        if out_variance is None:
+            out_variance = np.empty((h, w), np.float32)
+        for o, size in ((out, h * w * 4), (out_variance, h * w)):
+            assert o.dtype == np.float32 and o.flags.c_contiguous and o.size == size
+        length = np.empty((h, w), np.uint32)
+        tp = self._params(demodulate, over)
+        _check(self._L.yart_hip_temporal_accumulate_host(self._h, C.byref(self._camera(cam)), frame.ctypes.data_as(C.c_void_p),
+                                                         variance.ctypes.data_as(C.c_void_p), C.byref(ab), C.byref(tp),
+                                                         out.ctypes.data_as(C.c_void_p), out_variance.ctypes.data_as(C.c_void_p),
+                                                         length.ctypes.data_as(C.c_void_p)), self._L)
+        return out, out_variance, length
+
+    def accumulate_into(self, out_tensor, out_variance_tensor, out_length_tensor, cam, frame_tensor, variance_tensor,
+                        aov_tensors: dict, demodulate=None, stream=None, **over):
+        """``accumulate`` on CUDA/HIP torch tensors through ``data_ptr()`` (yart_hip_temporal_accumulate_device), on ``stream``
+        (an integer handle; None: torch's current stream): no host round trip. ``out_variance_tensor`` and
+        ``out_length_tensor`` (H*W 4-byte elements: int32 holding the uint32) may be None; ``out_tensor`` may be
+        ``frame_tensor`` and ``out_variance_tensor`` may be ``variance_tensor``."""
+        import torch
+        h, w = self.height, self.width
+        if demodulate is None:
+            demodulate = aov_tensors.get("albedo") is not None
+        for t in (frame_tensor, out_tensor):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == h * w * 4
+        for t in (variance_tensor, out_variance_tensor, out_length_tensor):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() == h * w)
+        ab = AovBuffers()
+        ab.struct_size = C.sizeof(AovBuffers)
+        for name in TEMPORAL_AOVS + (("albedo",) if demodulate else ()):
+            t = aov_tensors.get(name)
+            if t is None:
+                continue
+            bit, ch, _ = AOVS[name]
+            assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() == h * w * ch, name
+            ab.mask |= bit
+            setattr(ab, name, C.c_void_p(t.data_ptr()))
+        if stream is None:
+            stream = torch.cuda.current_stream(frame_tensor.device).cuda_stream
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        tp = self._params(demodulate, over)
+        with torch.cuda.device(frame_tensor.device):
+            _check(self._L.yart_hip_temporal_accumulate_device(self._h, C.byref(self._camera(cam)), ptr(frame_tensor),
+                                                               ptr(variance_tensor), C.byref(ab), C.byref(tp), ptr(out_tensor),
+                                                               ptr(out_variance_tensor), ptr(out_length_tensor),
+                                                               C.c_void_p(stream) if stream else None), self._L)
+        return out_tensor
 
 
 def probe_moments(L_samples, chunks=None, exposure_scale=1.0):

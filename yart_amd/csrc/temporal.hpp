@@ -1,0 +1,138 @@
+// temporal.hpp — temporal accumulation with camera reprojection (the temporal half of SVGF, Schied et al. 2017): the
+// arithmetic of one pixel, as inline functions for the device kernel (temporal_kernels.inc) and for the host (tests/temporalsim).
+//
+// The definition is the comment above yart_hip_temporal_accumulate_device in include/yart_hip.h; this file states it operation by
+// operation: every operation an individually rounded binary32 operation in the order written (the build has no FMA contraction).
+// Only + - * /, floorf, comparisons and integer min / max: no libm.
+//
+// Per pixel the handle keeps three 16-byte records in each of two history images (96 bytes; the pass reads the neighbours of one
+// image while it writes the other), each record kind in a plane of its own so that neighbouring lanes load neighbouring words:
+//   rec0  {acc.r, acc.g, acc.b, variance}     the accumulated colour (demodulated when the flag is set) and its variance
+//   rec1  {P.x, P.y, P.z, length (u32 bits)}  the world-space point; length 0: the record is nobody's tap
+//   rec2  {n.x, n.y, n.z, node (u32 bits)}    the normal and ids[0]
+#pragma once
+#include "denoise.hpp"
+#include "scene_types.hpp"
+
+namespace yart_hip {
+
+// the previous frame's camera: makeCamera's derived quantities and what the projection forms from them once (host, fp32)
+struct TpCamera {
+  f3 position; float num;      // num = dot(topLeftPixel - position, nrm)
+  f3 topLeft;  float dUU;      // dot(pixelDeltaU, pixelDeltaU)
+  f3 dU;       float dVV;
+  f3 dV;       float pad0;
+  f3 nrm;      float pad1;     // cross(pixelDeltaU, pixelDeltaV)
+};
+inline TpCamera tpCamera(const CameraDev& cd) {
+  TpCamera c{};
+  c.position = cd.position; c.topLeft = cd.topLeftPixel; c.dU = cd.pixelDeltaU; c.dV = cd.pixelDeltaV;
+  c.nrm = cross(c.dU, c.dV);
+  c.num = dot(c.topLeft - c.position, c.nrm);
+  c.dUU = dot(c.dU, c.dU);
+  c.dVV = dot(c.dV, c.dV);
+  return c;
+}
+
+struct TpConst {
+  float alphaMin, normalCosMin, planeTolerance;
+  uint32_t maxHistory;
+  uint32_t width, height;
+  uint32_t haveHistory;        // 0: first frame or after a reset: no tap is read
+  uint32_t pad;
+};
+
+struct TpIn {                  // the current pixel
+  f4 rgba;
+  float variance, depth, coverage;
+  uint32_t node;               // ids[0] as it lies in memory
+  f3 P, n;
+};
+struct TpOut {
+  f4 rgba;                     // to d_out_rgba
+  float variance;              // to d_out_variance
+  uint32_t length;             // to d_out_length
+  f4 rec0, rec1, rec2;         // the pixel's new history record
+};
+
+YART_HD bool tpFinite3(f3 a) { return dnFinite(a.x) && dnFinite(a.y) && dnFinite(a.z); }
+
+// One pixel. Hist decides how a 16-byte record of the previous history image is fetched: hist.rec0(q) / rec1(q) / rec2(q),
+// q = y * width + x. demodulate: the call demodulates, and alb is the pixel's albedo (by value: no array for the kernel to keep).
+template <class Hist>
+YART_HD TpOut tpAccumulatePixel(const Hist& hist, const TpConst& k, const TpCamera& cam, const TpIn& in, bool demodulate, f3 alb) {
+  TpOut o;
+  // dnDivisor: d = alb > 1e-3f ? alb : 1.0f per channel
+  const f3 d = demodulate ? mk3(alb.x > 1e-3f ? alb.x : 1.0f, alb.y > 1e-3f ? alb.y : 1.0f, alb.z > 1e-3f ? alb.z : 1.0f) : mk3(1.0f);
+  const float cr = in.rgba.x / d.x, cg = in.rgba.y / d.y, cb = in.rgba.z / d.z;
+  const float ld = dnLuma(d.x, d.y, d.z);
+  const float ld2 = ld * ld;
+  const float v = in.variance / ld2;
+  bool usable = dnFinite(cr) && dnFinite(cg) && dnFinite(cb) && dnFinite(in.variance) && in.variance >= 0.0f && dnFinite(v);
+  if (demodulate) usable = usable && tpFinite3(alb);
+  if (!usable) {               // passed through; an all-zero record of length 0
+    o.rgba = in.rgba; o.variance = in.variance; o.length = 0u;
+    o.rec0 = o.rec1 = o.rec2 = dnF4(0.0f, 0.0f, 0.0f, 0.0f);
+    return o;
+  }
+  const bool reprojectable = in.coverage == 1.0f && tpFinite3(in.P) && tpFinite3(in.n) && dnFinite(in.depth);
+  float accR = 0.0f, accG = 0.0f, accB = 0.0f, accV = 0.0f, wsum = 0.0f;
+  uint32_t minLen = 0xffffffffu;
+  bool any = false;
+  if (k.haveHistory != 0u && reprojectable) {
+    const f3 rel = in.P - cam.position;
+    const float den = dot(rel, cam.nrm);
+    const float s = cam.num / den;
+    if (s > 0.0f && s <= 3.4028235e38f) {      // in front of the previous camera: den has num's sign and is not 0
+      const f3 X = (cam.position + rel * s) - cam.topLeft;
+      const float jx = dot(X, cam.dU) / cam.dUU, jy = dot(X, cam.dV) / cam.dVV;
+      if (jx >= -1.0f && jx < float(k.width) && jy >= -1.0f && jy < float(k.height)) {   // else no tap is inside the image
+        const float flx = floorf(jx), fly = floorf(jy);
+        const int x0 = int(flx), y0 = int(fly);
+        const float fx = jx - flx, fy = jy - fly;
+        const float gx = 1.0f - fx, gy = 1.0f - fy;
+        const float tol = k.planeTolerance * in.depth;
+        for (int t = 0; t < 4; t++) {          // (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1)
+          const int qx = x0 + (t & 1), qy = y0 + (t >> 1);
+          if (qx < 0 || qx >= int(k.width) || qy < 0 || qy >= int(k.height)) continue;
+          const float w = ((t & 1) ? fx : gx) * ((t >> 1) ? fy : gy);
+          if (!(w > 0.0f)) continue;
+          const size_t q = size_t(qy) * k.width + size_t(qx);
+          const f4 r1 = hist.rec1(q);
+          const uint32_t len = dnBits(r1.w);
+          if (len < 1u) continue;
+          const f4 r2 = hist.rec2(q);
+          if (dnBits(r2.w) != in.node) continue;
+          if (!(dot(in.n, mk3(r2.x, r2.y, r2.z)) >= k.normalCosMin)) continue;
+          const f3 dP = mk3(r1.x, r1.y, r1.z) - in.P;
+          if (!(fabsf(dot(in.n, dP)) <= tol)) continue;
+          const f4 r0 = hist.rec0(q);
+          accR = accR + w * r0.x; accG = accG + w * r0.y; accB = accB + w * r0.z; accV = accV + w * r0.w;
+          wsum = wsum + w;
+          minLen = len < minLen ? len : minLen;
+          any = true;
+        }
+      }
+    }
+  }
+  float outR = cr, outG = cg, outB = cb, outV = v;
+  uint32_t N = 1u;
+  if (any) {
+    const float hr = accR / wsum, hg = accG / wsum, hb = accB / wsum, hv = accV / wsum;
+    N = minLen >= k.maxHistory ? k.maxHistory : minLen + 1u;
+    const float inv = 1.0f / float(N);
+    const float a = inv > k.alphaMin ? inv : k.alphaMin;
+    const float b = 1.0f - a;
+    outR = hr + a * (cr - hr); outG = hg + a * (cg - hg); outB = hb + a * (cb - hb);
+    outV = (a * a) * v + (b * b) * hv;
+  }
+  o.rgba = dnF4(outR * d.x, outG * d.y, outB * d.z, in.rgba.w);
+  o.variance = outV * ld2;
+  o.length = N;
+  o.rec0 = dnF4(outR, outG, outB, outV);
+  o.rec1 = dnF4(in.P.x, in.P.y, in.P.z, __builtin_bit_cast(float, N));
+  o.rec2 = dnF4(in.n.x, in.n.y, in.n.z, __builtin_bit_cast(float, in.node));
+  return o;
+}
+
+}  // namespace yart_hip

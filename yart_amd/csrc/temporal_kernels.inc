@@ -1,0 +1,60 @@
+// temporal_kernels.inc — temporal accumulation with camera reprojection (yart_hip_temporal_*), device side (included by
+// yart_hip.hip, unit 0, after denoise_kernels.inc whose 16-byte load / store it uses). The arithmetic is temporal.hpp; the
+// definition is the header comment of include/yart_hip.h.
+//
+//   k_tp_accumulate   one lane per pixel in the 16 x 16 tile of k_dn_atrous<0>: reads the pixel's frame, variance and feature
+//                     buffers (64 bytes with albedo), projects its surface point into the previous camera, reads up to four taps
+//                     of the previous history image — three aligned 16-byte loads each, the colour record only for a tap that
+//                     counts —, blends, writes the pixel's record into the other history image (48 bytes) and the caller's
+//                     outputs (24 bytes). For any smooth camera move the taps of a tile fall into a tile-sized neighbourhood of
+//                     the previous image, so neighbouring lanes' taps share lines in the CU's vector cache: no LDS tile.
+//                     A first frame (or the first after a reset) reads no tap: TpConst::haveHistory is uniform over the launch.
+//
+// History: two images of three planes of 16-byte records (temporal.hpp), 96 bytes per pixel, owned by the YartTemporal handle.
+// The kernel uses neither LDS nor scratch memory; none of the existing kernels changes.
+
+struct TpDeviceHist {
+  const f4 *r0, *r1, *r2;
+  __device__ __forceinline__ f4 rec0(size_t q) const { return dnLd(r0 + q); }
+  __device__ __forceinline__ f4 rec1(size_t q) const { return dnLd(r1 + q); }
+  __device__ __forceinline__ f4 rec2(size_t q) const { return dnLd(r2 + q); }
+};
+
+struct TpArgs {
+  const float *rgba, *variance, *albedo;           // albedo: only when the call demodulates
+  const float *position, *normal, *depth, *coverage;
+  const int32_t* ids;                              // 4 per pixel; [0] = node
+  const f4* histIn;                                // planes rec0 | rec1 | rec2, n records each
+  f4* histOut;
+  float *outRgba, *outVariance;                    // outRgba may be rgba, outVariance may be variance: a lane reads its own
+  uint32_t* outLength;                             // pixel before it writes it; outVariance / outLength may be null
+  uint32_t n, tilesX;
+  TpConst k;
+  TpCamera cam;
+};
+__global__ void __launch_bounds__(kBlock) k_tp_accumulate(TpArgs a) {
+  const uint32_t ty = blockIdx.x / a.tilesX, tx = blockIdx.x - ty * a.tilesX;
+  const uint32_t x = tx * 16u + (threadIdx.x % 16u), y = ty * 16u + (threadIdx.x / 16u);
+  if (x >= a.k.width || y >= a.k.height) return;
+  const size_t p = size_t(y) * a.k.width + x;
+  TpIn in;
+  in.rgba = dnF4(a.rgba[p * 4], a.rgba[p * 4 + 1], a.rgba[p * 4 + 2], a.rgba[p * 4 + 3]);
+  in.variance = a.variance[p];
+  in.depth = a.depth[p];
+  in.coverage = a.coverage[p];
+  in.node = uint32_t(a.ids[p * 4]);
+  in.P = mk3(a.position[p * 3], a.position[p * 3 + 1], a.position[p * 3 + 2]);
+  in.n = mk3(a.normal[p * 3], a.normal[p * 3 + 1], a.normal[p * 3 + 2]);
+  f3 alb = mk3(1.0f);
+  if (a.albedo) alb = mk3(a.albedo[p * 3], a.albedo[p * 3 + 1], a.albedo[p * 3 + 2]);
+  TpDeviceHist hist;
+  hist.r0 = a.histIn; hist.r1 = a.histIn + a.n; hist.r2 = a.histIn + size_t(a.n) * 2;
+  const TpOut o = tpAccumulatePixel(hist, a.k, a.cam, in, a.albedo != nullptr, alb);
+  dnSt(a.histOut + p, o.rec0);
+  dnSt(a.histOut + a.n + p, o.rec1);
+  dnSt(a.histOut + size_t(a.n) * 2 + p, o.rec2);
+  float* q = a.outRgba + p * 4;                    // the caller's buffers are only known to be 4-byte aligned
+  q[0] = o.rgba.x; q[1] = o.rgba.y; q[2] = o.rgba.z; q[3] = o.rgba.w;
+  if (a.outVariance) a.outVariance[p] = o.variance;
+  if (a.outLength) a.outLength[p] = o.length;
+}

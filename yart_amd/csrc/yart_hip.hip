@@ -47,6 +47,7 @@
 #include "trace_lean_tlas.hpp"
 #include "tonemap.hpp"
 #include "denoise.hpp"
+#include "temporal.hpp"
 #include "moments.hpp"
 #include "trace_ranges.hpp"
 
@@ -394,6 +395,7 @@ __global__ void __launch_bounds__(kBlock) k_tex_quads(TexQuadArgs a) {
 #include "aov_kernels.inc"
 #include "moment_kernels.inc"
 #include "denoise_kernels.inc"
+#include "temporal_kernels.inc"
 #include "bvh_build_device.inc"
 
 namespace {
@@ -2156,6 +2158,157 @@ int yart_hip_denoise_atrous_var_host(const float* rgba, const float* variance, c
     if (depth) { dep.ensure(n); HIP_CHECK(hipMemcpy(dep.p, depth, n * 4, hipMemcpyHostToDevice)); }
     denoiseVarRun(c, frame.p, var.p, alb.p, nrm.p, dep.p, width, height, frame.p, nullptr);
     HIP_CHECK(hipMemcpy(out_rgba, frame.p, n * 16, hipMemcpyDeviceToHost));
+  });
+}
+
+// Temporal accumulation (temporal_kernels.inc: k_tp_accumulate). The arguments are judged before any device is touched; the handle's
+// history — two images of three record planes, 96 bytes per pixel — is allocated by the first call that gets that far.
+}  // extern "C"
+struct YartTemporal {
+  uint32_t width = 0, height = 0;
+  int device = -1;                                  // < 0 until the first accumulate call: the device current then
+  std::mutex mu;
+  DevBuf<f4> hist;                                  // image 0 (rec0 | rec1 | rec2 planes) | image 1
+  uint32_t current = 0;                             // the image that holds the last frame's records
+  bool haveHistory = false;
+  YartCameraDesc camera{};                          // of the last accumulated frame
+};
+namespace {
+struct TpCall { TpConst k; bool demodulate; YartAovBuffers aovs; };
+TpCall temporalCheck(const YartTemporal* t, const YartCameraDesc* cam, const void* rgba, const void* variance, const YartAovBuffers* aovs,
+                     const YartTemporalParams* params, const void* out) {
+  require(t != nullptr, "temporal: handle pointer is null");
+  require(cam != nullptr, "temporal: camera pointer is null");
+  require(rgba && out, "temporal: rgba / out pointer is null");
+  require(variance != nullptr, "temporal: variance pointer is null");
+  require(aovs != nullptr, "temporal: feature buffers (aovs) pointer is null");
+  require(params != nullptr, "temporal: params pointer is null");
+  require(params->struct_size >= sizeof(YartTemporalParams), "temporal: struct_size is smaller than YartTemporalParams");
+  require((params->flags & ~uint32_t(YART_TEMPORAL_DEMODULATE)) == 0u, "temporal: unknown flags bits");
+  require(std::isfinite(params->alpha_min) && std::isfinite(params->normal_cos_min) && std::isfinite(params->plane_tolerance),
+          "temporal: a parameter is not finite");
+  require(params->alpha_min >= 0.0f && params->alpha_min <= 1.0f, "temporal: alpha_min is outside [0, 1]");
+  require(params->max_history >= 1u, "temporal: max_history is 0");
+  require(cam->width == t->width && cam->height == t->height, "temporal: the camera's image size is not the handle's");
+  require(cam->focal_length > 0.0f, "temporal: camera: bad focal length");
+  TpCall c{};
+  c.demodulate = (params->flags & YART_TEMPORAL_DEMODULATE) != 0u;
+  require(aovs->struct_size >= 2 * sizeof(uint32_t), "temporal: YartAovBuffers.struct_size is too small for the struct's head");
+  require((aovs->mask & ~YART_AOV_ALL) == 0u, "temporal: YartAovBuffers.mask has bits that are no YART_AOV_* value");
+  const struct { uint32_t bit; size_t off; bool needed; const char* missing; } fields[] = {
+      {YART_AOV_POSITION, offsetof(YartAovBuffers, position), true, "temporal: the position feature buffer (YART_AOV_POSITION) is missing"},
+      {YART_AOV_NORMAL, offsetof(YartAovBuffers, normal), true, "temporal: the normal feature buffer (YART_AOV_NORMAL) is missing"},
+      {YART_AOV_DEPTH, offsetof(YartAovBuffers, depth), true, "temporal: the depth feature buffer (YART_AOV_DEPTH) is missing"},
+      {YART_AOV_COVERAGE, offsetof(YartAovBuffers, coverage), true, "temporal: the coverage feature buffer (YART_AOV_COVERAGE) is missing"},
+      {YART_AOV_IDS, offsetof(YartAovBuffers, ids), true, "temporal: the ids feature buffer (YART_AOV_IDS) is missing"},
+      {YART_AOV_ALBEDO, offsetof(YartAovBuffers, albedo), c.demodulate, "temporal: YART_TEMPORAL_DEMODULATE without an albedo feature buffer (YART_AOV_ALBEDO)"}};
+  for (const auto& f : fields) {
+    if (!f.needed) continue;
+    require((aovs->mask & f.bit) != 0u && aovs->struct_size >= f.off + sizeof(void*), f.missing);
+    void* ptr = *reinterpret_cast<void* const*>(reinterpret_cast<const char*>(aovs) + f.off);
+    require(ptr != nullptr, f.missing);
+    *reinterpret_cast<void**>(reinterpret_cast<char*>(&c.aovs) + f.off) = ptr;
+  }
+  c.k.alphaMin = params->alpha_min; c.k.normalCosMin = params->normal_cos_min; c.k.planeTolerance = params->plane_tolerance;
+  c.k.maxHistory = params->max_history;
+  c.k.width = t->width; c.k.height = t->height;
+  return c;
+}
+
+// device pointers (c.aovs included); the handle's device is current and its mutex held; returns after completion on `st`
+void temporalRun(YartTemporal& t, TpCall c, const YartCameraDesc& cam, const float* rgba, const float* variance, float* out,
+                 float* outVariance, uint32_t* outLength, hipStream_t st) {
+  const uint32_t n = t.width * t.height;
+  t.hist.ensure(size_t(n) * 6);
+  c.k.haveHistory = t.haveHistory ? 1u : 0u;
+  TpArgs a{};
+  a.rgba = rgba; a.variance = variance; a.albedo = c.demodulate ? c.aovs.albedo : nullptr;
+  a.position = c.aovs.position; a.normal = c.aovs.normal; a.depth = c.aovs.depth; a.coverage = c.aovs.coverage; a.ids = c.aovs.ids;
+  a.histIn = t.hist.p + size_t(t.current) * n * 3;
+  a.histOut = t.hist.p + size_t(t.current ^ 1u) * n * 3;
+  a.outRgba = out; a.outVariance = outVariance; a.outLength = outLength;
+  a.n = n; a.tilesX = (t.width + 15u) / 16u;
+  a.k = c.k;
+  if (t.haveHistory) a.cam = tpCamera(makeCamera(t.camera));
+  hipLaunchKernelGGL(k_tp_accumulate, dim3(a.tilesX * ((t.height + 15u) / 16u)), dim3(kBlock), 0, st, a);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(st));
+  t.current ^= 1u; t.haveHistory = true; t.camera = cam;
+}
+
+void temporalSelectDevice(YartTemporal& t) {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw HipError("no HIP device");
+  if (t.device < 0) HIP_CHECK(hipGetDevice(&t.device));
+  HIP_CHECK(hipSetDevice(t.device));
+}
+}  // namespace
+extern "C" {
+
+int yart_hip_temporal_create(uint32_t width, uint32_t height, int device, YartTemporal** out) {
+  return guarded([&] {
+    require(out != nullptr, "temporal: out pointer is null");
+    require(width > 0 && height > 0, "temporal: width or height is 0");
+    require(uint64_t(width) * height <= (1ull << 28), "temporal: more than 2^28 pixels");
+    auto* t = new YartTemporal;
+    t->width = width; t->height = height; t->device = device;
+    *out = t;
+  });
+}
+
+void yart_hip_temporal_destroy(YartTemporal* temporal) {
+  if (!temporal) return;
+  if (temporal->hist.p && temporal->device >= 0) (void)hipSetDevice(temporal->device);
+  delete temporal;
+}
+
+int yart_hip_temporal_reset(YartTemporal* temporal) {
+  return guarded([&] {
+    require(temporal != nullptr, "temporal: handle pointer is null");
+    std::lock_guard<std::mutex> lock(temporal->mu);
+    temporal->haveHistory = false;
+  });
+}
+
+int yart_hip_temporal_accumulate_device(YartTemporal* temporal, const YartCameraDesc* cam, const float* d_rgba, const float* d_variance,
+                                        const YartAovBuffers* d_aovs, const YartTemporalParams* params, float* d_out_rgba,
+                                        float* d_out_variance, uint32_t* d_out_length, void* stream) {
+  return guarded([&] {
+    const TpCall c = temporalCheck(temporal, cam, d_rgba, d_variance, d_aovs, params, d_out_rgba);
+    std::lock_guard<std::mutex> lock(temporal->mu);
+    temporalSelectDevice(*temporal);
+    temporalRun(*temporal, c, *cam, d_rgba, d_variance, d_out_rgba, d_out_variance, d_out_length, static_cast<hipStream_t>(stream));
+  });
+}
+
+int yart_hip_temporal_accumulate_host(YartTemporal* temporal, const YartCameraDesc* cam, const float* rgba, const float* variance,
+                                      const YartAovBuffers* aovs, const YartTemporalParams* params, float* out_rgba,
+                                      float* out_variance, uint32_t* out_length) {
+  return guarded([&] {
+    TpCall c = temporalCheck(temporal, cam, rgba, variance, aovs, params, out_rgba);
+    std::lock_guard<std::mutex> lock(temporal->mu);
+    temporalSelectDevice(*temporal);
+    const size_t n = size_t(temporal->width) * temporal->height;
+    // frame (4) | variance (1) | position (3) | normal (3) | depth (1) | coverage (1) | ids (4) | albedo (3) | length (1) words per pixel;
+    // frame and variance are accumulated in place
+    DevBuf<float> buf;
+    buf.ensure(n * 21);
+    float* w = buf.p;
+    auto put = [&](const void* src, size_t words) {
+      float* dst = w; w += n * words;
+      if (src) HIP_CHECK(hipMemcpy(dst, src, n * words * 4, hipMemcpyHostToDevice));
+      return dst;
+    };
+    float* dFrame = put(rgba, 4);
+    float* dVar = put(variance, 1);
+    c.aovs.position = put(c.aovs.position, 3); c.aovs.normal = put(c.aovs.normal, 3); c.aovs.depth = put(c.aovs.depth, 1);
+    c.aovs.coverage = put(c.aovs.coverage, 1); c.aovs.ids = reinterpret_cast<int32_t*>(put(c.aovs.ids, 4));
+    c.aovs.albedo = put(c.demodulate ? c.aovs.albedo : nullptr, 3);
+    uint32_t* dLen = reinterpret_cast<uint32_t*>(put(nullptr, 1));
+    temporalRun(*temporal, c, *cam, dFrame, dVar, dFrame, dVar, dLen, nullptr);
+    HIP_CHECK(hipMemcpy(out_rgba, dFrame, n * 16, hipMemcpyDeviceToHost));
+    if (out_variance) HIP_CHECK(hipMemcpy(out_variance, dVar, n * 4, hipMemcpyDeviceToHost));
+    if (out_length) HIP_CHECK(hipMemcpy(out_length, dLen, n * 4, hipMemcpyDeviceToHost));
   });
 }
 
