@@ -381,6 +381,17 @@ int yart_hip_render_moments_device(YartScene* scene, const YartCameraDesc* cam, 
  * variance, count (1 per pixel): host, all required. */
 int yart_hip_probe_moments(const float* L_rgba, uint32_t n_pixels, uint32_t spp, const uint32_t* chunks, uint32_t n_chunks,
                            float exposure_scale, float* mean, float* variance, uint32_t* count);
+/* Diagnostic, no scene: the estimator kernel of the render (one launch, the render's launch geometry) on caller-supplied per-sample
+ * records, on the current device. L_rgba: n_pixels * spp records {r, g, b, ray count as uint32 bits} (host; pixel-major, samples
+ * ascending). kind: YART_ESTIMATOR_*. pixels: n_pixels distinct words x | y << 16 inside the width x height frame, or NULL: pixel i at
+ * (i % width, i / width). hdr_inout (host, width * height * 4): read as the current frame and written back with the listed pixels set
+ * to current * w_current + {estimate, 1} * w_wave; the others are not touched. pix_rays (host, n_pixels, or NULL): each pixel's
+ * ray counts summed mod 2^32. A null L_rgba / hdr_inout, a zero n_pixels / spp / width / height, a width or height above 65536, a kind
+ * outside 0..3, more than 2^26 records, n_pixels > width * height, a pixels[] entry outside the frame and a non-finite
+ * exposure_scale / w_current / w_wave return YART_E_INVALID before any device is touched. */
+int yart_hip_probe_estimator(const float* L_rgba, uint32_t n_pixels, uint32_t spp, int kind, float exposure_scale,
+                             const uint32_t* pixels, uint32_t width, uint32_t height, float w_current, float w_wave,
+                             float* hdr_inout, uint32_t* pix_rays);
 
 /* Several GPUs of one node behind one handle — what the reference's worker pool is to CPU threads
  * (TileRenderer::renderImpl starts threadCount workers that pull tiles, tile-renderer.hpp:150-197; finishTile merges

@@ -291,6 +291,7 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_probe_math", "yart_hip_probe_math_pairs",
            "yart_hip_denoise_atrous_device", "yart_hip_denoise_atrous_host",
            "yart_hip_render_moments", "yart_hip_render_moments_device", "yart_hip_probe_moments",
+           "yart_hip_probe_estimator",
            "yart_hip_denoise_atrous_var_device", "yart_hip_denoise_atrous_var_host",
            "yart_hip_temporal_create", "yart_hip_temporal_destroy", "yart_hip_temporal_reset",
            "yart_hip_temporal_accumulate_device", "yart_hip_temporal_accumulate_host"]
@@ -360,6 +361,8 @@ def lib(instrumented: bool = False):
                                                      C.POINTER(AovBuffers), C.POINTER(MomentBuffers), C.c_void_p, C.POINTER(Stats)]
         L.yart_hip_probe_moments.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float,
                                              C.c_void_p, C.c_void_p, C.c_void_p]
+        L.yart_hip_probe_estimator.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_void_p, C.c_uint32,
+                                               C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         L.yart_hip_denoise_atrous_var_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                          C.c_uint32, C.POINTER(DenoiseVarParams), C.c_void_p, C.c_void_p]
         L.yart_hip_denoise_atrous_var_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -1261,6 +1264,33 @@ def probe_moments(L_samples, chunks=None, exposure_scale=1.0):
                                     float(exposure_scale), mean.ctypes.data_as(C.c_void_p), var.ctypes.data_as(C.c_void_p),
                                     cnt.ctypes.data_as(C.c_void_p)), L)
     return mean, var, cnt
+
+
+def probe_estimator(samples, kind, exposure_scale=1.0, rays=None, pixels=None, size=None, current=None, weights=(0.0, 1.0)):
+    """The estimator kernel alone (yart_hip_probe_estimator: k_gmon_blend with the render's launch geometry), without a scene.
+    ``samples`` [n_pixels, spp, 3] float32 per-sample radiance; ``kind`` 0..3 (YART_ESTIMATOR_*); ``rays`` [n_pixels, spp] uint32
+    ray counts of the records (None: 0). ``pixels`` [n_pixels, 2] distinct (x, y) of a ``size`` = (width, height) frame (None:
+    pixel i at (i % width, i / width); ``size`` None: an n_pixels x 1 frame). ``current`` [height, width, 4] float32 is the frame
+    before the wave (None: zeros) and ``weights`` = (w_current, w_wave) of the blend. Returns (frame [height, width, 4] float32,
+    pix_rays [n_pixels] uint32)."""
+    a = np.asarray(samples, np.float32)
+    n, spp = a.shape[:2]
+    rec = np.zeros((n, spp, 4), np.float32)
+    rec[..., :3] = a[..., :3]
+    if rays is not None:
+        rec.view(np.uint32)[..., 3] = np.asarray(rays, np.uint32).reshape(n, spp)
+    w, h = (n, 1) if size is None else (int(size[0]), int(size[1]))
+    px = None
+    if pixels is not None:
+        xy = np.asarray(pixels, np.uint32).reshape(n, 2)
+        px = np.ascontiguousarray(xy[:, 0] | (xy[:, 1] << np.uint32(16)), np.uint32)
+    frame = np.zeros((h, w, 4), np.float32) if current is None else np.array(current, np.float32, order="C").reshape(h, w, 4)
+    pix_rays = np.empty(n, np.uint32)
+    L = lib()
+    _check(L.yart_hip_probe_estimator(rec.ctypes.data_as(C.c_void_p), n, spp, int(kind), float(exposure_scale),
+                                      None if px is None else px.ctypes.data_as(C.c_void_p), w, h, float(weights[0]),
+                                      float(weights[1]), frame.ctypes.data_as(C.c_void_p), pix_rays.ctypes.data_as(C.c_void_p)), L)
+    return frame, pix_rays
 
 
 def write_ppm(path, rgb8: np.ndarray):

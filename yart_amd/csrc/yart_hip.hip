@@ -1609,6 +1609,45 @@ int yart_hip_probe_moments(const float* L_rgba, uint32_t n_pixels, uint32_t spp,
   });
 }
 
+// Diagnostic: k_gmon_blend on caller-supplied per-sample records (no scene), one launch with the render's launch geometry
+int yart_hip_probe_estimator(const float* L_rgba, uint32_t n_pixels, uint32_t spp, int kind, float exposure_scale,
+                             const uint32_t* pixels, uint32_t width, uint32_t height, float w_current, float w_wave,
+                             float* hdr_inout, uint32_t* pix_rays) {
+  return guarded([&] {
+    require(L_rgba && hdr_inout, "probe_estimator: null pointer");
+    require(n_pixels > 0 && spp > 0, "probe_estimator: n_pixels or spp is 0");
+    require(width > 0 && height > 0, "probe_estimator: width or height is 0");
+    require(width <= 65536u && height <= 65536u, "probe_estimator: width or height above 65536");     // pixels[] packs x | y << 16
+    require(kind >= EST_GMON && kind <= EST_GMONB, "probe_estimator: kind must be one of YART_ESTIMATOR_*");
+    require(uint64_t(n_pixels) * spp <= (1ull << 26), "probe_estimator: more than 2^26 records");
+    require(uint64_t(n_pixels) <= uint64_t(width) * height, "probe_estimator: n_pixels exceeds width * height");
+    require(std::isfinite(exposure_scale), "probe_estimator: exposure_scale is not finite");
+    require(std::isfinite(w_current) && std::isfinite(w_wave), "probe_estimator: a blend weight is not finite");
+    std::vector<uint32_t> px(n_pixels);
+    for (uint32_t i = 0; i < n_pixels; i++) {
+      px[i] = pixels ? pixels[i] : (i % width) | ((i / width) << 16);
+      require((px[i] & 0xffffu) < width && (px[i] >> 16) < height, "probe_estimator: a pixels[] entry is outside the frame");
+    }
+    int devices = 0;
+    if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0) throw HipError("no HIP device");
+    const size_t records = size_t(n_pixels) * spp, frame = size_t(width) * height * 4;
+    DevBuf<f4> L; DevBuf<uint32_t> dPixels, dRays; DevBuf<float> hdr;
+    L.ensure(records); dPixels.ensure(n_pixels); hdr.ensure(frame);
+    if (pix_rays) dRays.ensure(n_pixels);
+    HIP_CHECK(hipMemcpy(L.p, L_rgba, records * sizeof(f4), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dPixels.p, px.data(), size_t(n_pixels) * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(hdr.p, hdr_inout, frame * sizeof(float), hipMemcpyHostToDevice));
+    GmonArgs g{};
+    g.L = L.p; g.pixRays = dRays.p; g.pixels = dPixels.p; g.nPixels = n_pixels; g.spp = spp; g.width = width;
+    g.kind = kind; g.exposureScale = exposure_scale; g.wCurrent = w_current; g.wWave = w_wave; g.hdr = hdr.p;
+    hipLaunchKernelGGL(k_gmon_blend, dim3((n_pixels + kGmonPixPerBlock - 1) / kGmonPixPerBlock), dim3(kBlock), 0, nullptr, g);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(hdr_inout, hdr.p, frame * sizeof(float), hipMemcpyDeviceToHost));
+    if (pix_rays) HIP_CHECK(hipMemcpy(pix_rays, dRays.p, size_t(n_pixels) * 4, hipMemcpyDeviceToHost));
+  });
+}
+
 // One wave of the schedule at a time, and inside a wave one batch at a time (tile-renderer.hpp:200-309: finishTile
 // fires onRenderTileComplete per tile and onRenderWaveComplete after a wave's last tile).
 static int renderProgressive(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, float* out_rgba,
