@@ -551,8 +551,8 @@ int yart_hip_denoise_atrous_host(const float* rgba, const float* albedo, const f
 /* The variance-guided form of the filter above — the spatial filter of SVGF (Schied, Kaplanyan, Wyman, Patney, Chaitanya, Burgess,
  * Liu, Dachsbacher, Lefohn, Salvi 2017) — with the per-pixel variance of yart_hip_render_moments (YART_MOMENT_VARIANCE) as a fourth
  * input: a colour difference is measured against the local standard deviation of the luminance instead of one global sigma_color, and
- * the variance is filtered along. It is the DEFINITION above with these changes and nothing else (csrc/denoise.hpp dnPrepareVar /
- * dnFilterPixelVar state it; yart_amd/denoise.py atrous_var_reference is the NumPy statement the tests compare with, on bits):
+ * the variance is filtered along. It is the DEFINITION above with these changes and nothing else (csrc/denoise.hpp dnPrepare<true> /
+ * dnFilterPixel<true> state it; yart_amd/denoise.py atrous_var_reference is the NumPy statement the tests compare with, on bits):
  *   Prepare:   v_0(p) = variance(p) / (ld * ld), ld = luma(d) = (d.r * 0.2126f + d.g * 0.7152f) + d.b * 0.0722f of the demodulation
  *              divisor d ((1, 1, 1) when not demodulating). valid(p) additionally requires variance(p) to be finite and >= 0.
  *   Iteration, once per centre pixel p:  g(p) = the 3 x 3 Gaussian of v_i around p, ALWAYS at distance 1: weights k3[|dy|] * k3[|dx|],

@@ -9,10 +9,8 @@
 //                          the host path tracer per sample (csrc/integrator.hpp samplePixel, as tests/hostsim `render` runs it: one
 //                          wave, the GMoN estimator) with every sample also reduced by csrc/moments.hpp.
 //                          frame out: w * h * 4 f32 — the very frame hostsim `render` writes; moments out: per pixel 5 words as above
-//   denoisevar <in> <out>  csrc/denoise.hpp's variance-guided filter, driven the way yart_hip.hip drives the kernels.
-//                          in: 9 words {u32 width, height, iterations, flags, guides (1 albedo | 2 normal | 4 depth), in_place,
-//                          f32 sigma_luma, sigma_normal, sigma_depth}, then the frame (w*h*4 f32), the variance (w*h) and the guides
-//                          that are present (w*h*3, w*h*3, w*h); out: the filtered frame
+//   denoisevar <in> <out>  csrc/denoise.hpp's variance-guided filter, driven the way yart_hip.hip drives the kernels
+//                          (tests/denoisesim/dn_host.hpp, which states the file format).
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -27,28 +25,10 @@
 #include "../../yart_amd/csrc/host_scene.hpp"
 #include "../../yart_amd/csrc/integrator.hpp"
 #include "../../yart_amd/csrc/scene_file.hpp"
-#include "../../yart_amd/csrc/denoise.hpp"
 #include "../../yart_amd/csrc/moments.hpp"
+#include "../denoisesim/dn_host.hpp"
 
 using namespace yart_hip;
-
-static std::vector<float> readFloats(const char* path) {
-  FILE* f = std::fopen(path, "rb");
-  if (!f) throw std::runtime_error(std::string("cannot read ") + path);
-  std::vector<float> v;
-  float buf[4096];
-  size_t n;
-  while ((n = std::fread(buf, 4, 4096, f)) > 0) v.insert(v.end(), buf, buf + n);
-  std::fclose(f);
-  return v;
-}
-static void writeWords(const char* path, const void* p, size_t words) {
-  FILE* f = std::fopen(path, "wb");
-  if (!f) throw std::runtime_error(std::string("cannot write ") + path);
-  std::fwrite(p, 4, words, f);
-  std::fclose(f);
-}
-static uint32_t asWord(float f) { return __builtin_bit_cast(uint32_t, f); }
 
 static void putMoments(const MomentState& st, uint32_t* o) {
   float mean[3], variance;
@@ -138,68 +118,12 @@ static int doRender(const char* scenePath, const char* paramPath, const char* fr
   return 0;
 }
 
-struct HostSrc {
-  const f4 *c, *g;
-  f4 colour(size_t q) const { return c[q]; }
-  f4 guide(size_t q) const { return g[q]; }
-};
-
-static int doDenoiseVar(const char* inPath, const char* outPath) {
-  std::vector<float> in = readFloats(inPath);
-  if (in.size() < 9) throw std::runtime_error("short header");
-  const uint32_t w = asWord(in[0]), h = asWord(in[1]), iterations = asWord(in[2]), flags = asWord(in[3]), guides = asWord(in[4]);
-  const uint32_t inPlace = asWord(in[5]);
-  const float sl = in[6], sn = in[7], sd = in[8];
-  if (w == 0 || h == 0 || w > 4096 || h > 4096 || iterations > 8 || guides > 7u || flags > 1u || ((flags & 1u) && !(guides & 1u)))
-    throw std::runtime_error("bad header");
-  const size_t n = size_t(w) * h;
-  const size_t need = 9 + n * 5 + ((guides & 1u) ? n * 3 : 0) + ((guides & 2u) ? n * 3 : 0) + ((guides & 4u) ? n : 0);
-  if (in.size() != need) throw std::runtime_error("input size does not match the header");
-  float* words = in.data() + 9;
-  float* rgba = words; words += n * 4;
-  const float* variance = words; words += n;
-  const float *albedo = nullptr, *normal = nullptr, *depth = nullptr;
-  if (guides & 1u) { albedo = words; words += n * 3; }
-  if (guides & 2u) { normal = words; words += n * 3; }
-  if (guides & 4u) { depth = words; words += n; }
-  std::vector<float> separate(inPlace ? 0 : n * 4);
-  float* out = inPlace ? rgba : separate.data();
-  if (iterations == 0) {
-    if (out != rgba) std::copy(rgba, rgba + n * 4, out);
-  } else {
-    DnVarConst k;
-    k.sigmaLuma = sl;
-    k.inrm = normal ? dnInvSigma2(sn) : 0.0f;
-    k.idep = depth ? dnInvSigma2(sd) : 0.0f;
-    k.terms = (sl > 0.0f ? kDnColor : 0u) | (normal && sn > 0.0f ? kDnNormal : 0u) | (depth && sd > 0.0f ? kDnDepth : 0u);
-    const float* alb = (flags & 1u) ? albedo : nullptr;
-    std::vector<f4> scratch(n * 3);                    // colour + variance image 0 | image 1 | guide records
-    f4 *img[2] = {scratch.data(), scratch.data() + n}, *guide = scratch.data() + 2 * n;
-    for (size_t p = 0; p < n; p++)
-      dnPrepareVar(dnF4(rgba[4 * p], rgba[4 * p + 1], rgba[4 * p + 2], rgba[4 * p + 3]), variance[p], alb ? alb + 3 * p : nullptr,
-                   normal ? normal + 3 * p : nullptr, depth ? depth + p : nullptr, img[0][p], guide[p]);
-    for (uint32_t i = 0; i < iterations; i++) {
-      HostSrc src{img[i & 1u], guide};
-      f4* dst = img[(i + 1u) & 1u];
-      for (uint32_t y = 0; y < h; y++)
-        for (uint32_t x = 0; x < w; x++) dst[size_t(y) * w + x] = dnFilterPixelVar(src, w, h, x, y, i, k);
-    }
-    const f4* last = img[iterations & 1u];
-    for (size_t p = 0; p < n; p++) {
-      const f4 o = dnFinish(last[p], alb ? alb + 3 * p : nullptr, rgba[4 * p + 3]);
-      out[4 * p] = o.x; out[4 * p + 1] = o.y; out[4 * p + 2] = o.z; out[4 * p + 3] = o.w;
-    }
-  }
-  writeWords(outPath, out, n * 4);
-  return 0;
-}
-
 int main(int argc, char** argv) {
   try {
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "reduce" && argc == 4) return doReduce(argv[2], argv[3]);
     if (mode == "render" && argc == 6) return doRender(argv[2], argv[3], argv[4], argv[5]);
-    if (mode == "denoisevar" && argc == 4) return doDenoiseVar(argv[2], argv[3]);
+    if (mode == "denoisevar" && argc == 4) { dnHostRunFile<true>(argv[2], argv[3]); return 0; }
     std::fprintf(stderr, "usage: momentsim reduce <in> <out> | render <scene.yscn> <params.txt> <frame> <moments> | denoisevar <in> <out>\n");
     return 1;
   } catch (const std::exception& e) {

@@ -217,27 +217,33 @@ def momentsim(built, tmp_path_factory):
     return exe
 
 
-def run_sim(exe, tmp, w, h, iterations, gs, sigmas, in_place, env=None):
+def run_sim_on(cmd, tmp, inp, w, h, iterations, gs, sigmas3, in_place, env=None):
+    """Writes the 9-word header, the frame, inp["variance"] if there is one and the guides of `gs`, runs `cmd <in> <out>`."""
     a, n, d, dm = gs
-    inp = inputs(w, h)
-    sig = dict(SIGMAS if sigmas is None else sigmas)
     head = np.array([w, h, iterations, 1 if dm else 0, (1 if a else 0) | (2 if n else 0) | (4 if d else 0), 1 if in_place else 0], np.uint32)
     fin, fout = os.path.join(tmp, "dn.in"), os.path.join(tmp, "dn.out")
     with open(fin, "wb") as f:
         f.write(head.tobytes())
-        f.write(np.array([sig["sigma_luma"], sig["sigma_normal"], sig["sigma_depth"]], np.float32).tobytes())
+        f.write(np.array(sigmas3, np.float32).tobytes())
         f.write(inp["rgba"].tobytes())
-        f.write(inp["variance"].tobytes())
+        if "variance" in inp:
+            f.write(inp["variance"].tobytes())
         for g in guides_of(inp, a, n, d):
             if g is not None:
                 f.write(g.tobytes())
-    r = subprocess.run([exe, "denoisevar", fin, fout], capture_output=True, text=True, env=env)
+    r = subprocess.run(cmd + [fin, fout], capture_output=True, text=True, env=env)
     return r, (np.fromfile(fout, np.float32).reshape(h, w, 4) if r.returncode == 0 else None)
+
+
+def run_sim(exe, tmp, w, h, iterations, gs, sigmas, in_place, env=None):
+    sig = dict(SIGMAS if sigmas is None else sigmas)
+    return run_sim_on([exe, "denoisevar"], tmp, inputs(w, h), w, h, iterations, gs,
+                      [sig["sigma_luma"], sig["sigma_normal"], sig["sigma_depth"]], in_place, env)
 
 
 @pytest.mark.parametrize("w,h", CPU_SIZES)
 def test_host_statement_equals_the_numpy_statement_on_bits(momentsim, tmp_path_factory, tmp_path, w, h):
-    """csrc/denoise.hpp (dnPrepareVar / dnFilterPixelVar) on the host == atrous_var_reference with libm's expf / logf, bit for
+    """csrc/denoise.hpp (dnPrepare<true> / dnFilterPixel<true>) on the host == atrous_var_reference with libm's expf / logf, bit for
     bit: every iteration count, guide subset, demodulation on / off, out of place and in place; the sigma variants that drop terms."""
     for it, gs, sig in grid(w, h):
         want = reference(tmp_path_factory, w, h, it, gs, sig)
@@ -264,6 +270,72 @@ def test_variance_changes_the_result(tmp_path_factory):
     b = atrous_var_reference(inp["rgba"], np.where(np.isfinite(inp["variance"]) & (inp["variance"] >= 0), np.float32(1.0), inp["variance"]),
                              iterations=2, **off)
     assert np.array_equal(bits(a), bits(b))
+
+
+# -- the two forms against each other ------------------------------------------------------------------------------------
+# With the colour term off and every variance finite and non-negative, the variance changes neither which pixels are valid nor
+# any weight: the plain and the variance-guided filter return the same bits. Every other test holds a form to its own NumPy
+# statement; this one holds the two instantiations of the shared body (csrc/denoise.hpp) to each other.
+SAME_SIZES = [(5, 3), (37, 23)]
+SAME_GUIDES = (True, True, True, True)                  # all three guides, demodulated
+SAME_PLAIN = dict(sigma_color=0.0, sigma_normal=0.8, sigma_depth=1.5)
+SAME_VAR = dict(sigma_luma=-1.0, sigma_normal=0.8, sigma_depth=1.5)
+_same_inputs = {}
+
+
+def same_inputs(w, h):
+    """inputs(w, h) with one NaN in the frame (its Inf made finite) and every variance that is not finite or is negative made an
+    exact zero; the albedo keeps its exact zeros."""
+    if (w, h) not in _same_inputs:
+        inp = {k: v.copy() for k, v in inputs(w, h).items()}
+        inp["rgba"][np.isinf(inp["rgba"])] = 7.0
+        bad = ~np.isfinite(inp["variance"]) | (inp["variance"] < 0)
+        inp["variance"][bad] = 0.0
+        assert np.isnan(inp["rgba"]).sum() == 1 and np.isfinite(inp["variance"]).all() and (inp["variance"] >= 0).all()
+        assert (inp["variance"] == 0).any() and (inp["variance"] > 0).any() and (inp["albedo"] == 0).any()
+        for v in inp.values():
+            v.setflags(write=False)
+        _same_inputs[(w, h)] = inp
+    return _same_inputs[(w, h)]
+
+
+def assert_same_bits(plain, var, what):
+    diff = bits(plain) != bits(var)
+    assert not diff.any(), f"{what}: {int(diff.sum())} words differ, first at {np.argwhere(diff)[0].tolist()}"
+    assert np.isfinite(plain).all()
+
+
+@pytest.mark.parametrize("w,h", SAME_SIZES)
+def test_forms_agree_without_a_colour_term_numpy(w, h):
+    from yart_amd.denoise import atrous_reference, atrous_var_reference
+    inp = same_inputs(w, h)
+    guides = guides_of(inp, True, True, True)
+    for it in ITERATIONS:
+        plain = atrous_reference(inp["rgba"], *guides, iterations=it, demodulate=True, **SAME_PLAIN)
+        var = atrous_var_reference(inp["rgba"], inp["variance"], *guides, iterations=it, demodulate=True, **SAME_VAR)
+        assert_same_bits(plain, var, f"NumPy statements {w}x{h} iterations {it}")
+        assert not np.array_equal(bits(plain), bits(inp["rgba"]))
+
+
+@pytest.fixture(scope="module")
+def denoisesim(tmp_path_factory):
+    """tests/denoisesim/denoisesim.cpp: csrc/denoise.hpp's plain statement compiled for the host."""
+    exe = str(tmp_path_factory.mktemp("denoisesim_dnv") / "denoisesim")
+    r = subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-O2", "-o", exe, os.path.join(ROOT, "tests", "denoisesim", "denoisesim.cpp")],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return exe
+
+
+@pytest.mark.parametrize("w,h", SAME_SIZES)
+def test_forms_agree_without_a_colour_term_host(denoisesim, momentsim, tmp_path, w, h):
+    inp = same_inputs(w, h)
+    no_variance = {k: v for k, v in inp.items() if k != "variance"}
+    for it in ITERATIONS:
+        rp, plain = run_sim_on([denoisesim], str(tmp_path), no_variance, w, h, it, SAME_GUIDES, list(SAME_PLAIN.values()), False)
+        rv, var = run_sim_on([momentsim, "denoisevar"], str(tmp_path), inp, w, h, it, SAME_GUIDES, list(SAME_VAR.values()), False)
+        assert rp.returncode == 0 and rv.returncode == 0, rp.stderr + rv.stderr
+        assert_same_bits(plain, var, f"denoisesim / momentsim denoisevar {w}x{h} iterations {it}")
 
 
 # -- quality: the gates of the default parameters ----------------------------------------------------------------------
@@ -327,13 +399,24 @@ def device_denoise(api, w, h, it, gs, sig, in_place):
 @pytest.mark.gpu
 @pytest.mark.parametrize("w,h", GPU_SIZES)
 def test_device_denoise_var_equals_the_numpy_statement_on_bits(gpu_api, tmp_path_factory, w, h):
-    """k_dn_prepare_var / k_dn_atrous_var<0, 1> / k_dn_finish through api.denoise_var == atrous_var_reference with libm's expf /
+    """k_dn_prepare<true> / k_dn_atrous<true, 0 and 1> / k_dn_finish through api.denoise_var == atrous_var_reference with libm's expf /
     logf, bit for bit, over the grid of the host test, out of place and with `out` aliasing the input frame."""
     for it, gs, sig in grid(w, h):
         want = reference(tmp_path_factory, w, h, it, gs, sig)
         for in_place in (False, True):
             got = device_denoise(gpu_api, w, h, it, gs, sig, in_place)
             bit_identical_or_drift(got, want, f"denoise_var {w}x{h} iterations {it} guides {gs} sigmas {sig} in_place {in_place}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h", SAME_SIZES)
+def test_forms_agree_without_a_colour_term_device(gpu_api, w, h):
+    inp = same_inputs(w, h)
+    guides = guides_of(inp, True, True, True)
+    for it in ITERATIONS:
+        plain = gpu_api.denoise(inp["rgba"], *guides, iterations=it, demodulate=True, **SAME_PLAIN)
+        var = gpu_api.denoise_var(inp["rgba"], inp["variance"], *guides, iterations=it, demodulate=True, **SAME_VAR)
+        assert_same_bits(plain, var, f"api.denoise / api.denoise_var {w}x{h} iterations {it}")
 
 
 def run_torch_child(call):

@@ -1010,72 +1010,9 @@ def tonemap(hdr: np.ndarray, look: Optional[str] = "none"):
     return ldr, rgb
 
 
-def denoise(frame, albedo=None, normal=None, depth=None, iterations=DEFAULT_ITERATIONS, sigma_color=DEFAULT_SIGMA_COLOR,
-            sigma_normal=DEFAULT_SIGMA_NORMAL, sigma_depth=DEFAULT_SIGMA_DEPTH, demodulate=None, out=None):
-    """The edge-avoiding à-trous filter (include/yart_hip.h: yart_hip_denoise_atrous_host) of an (H, W, 4) float32 linear-HDR
-    frame on the device, guided by whichever of ``albedo`` (H, W, 3), ``normal`` (H, W, 3) and ``depth`` (H, W) are given;
-    ``demodulate`` divides by the albedo before and multiplies after (None: whenever ``albedo`` is given). ``out``: a C-contiguous float32 array to fill (may be
-    ``frame``). yart_amd.denoise.atrous_reference states the same arithmetic in NumPy."""
-    frame = np.ascontiguousarray(frame, np.float32)
-    h, w = frame.shape[:2]
-    assert frame.shape == (h, w, 4)
-    if demodulate is None:
-        demodulate = albedo is not None
-
-    def guide(a, ch):
-        if a is None:
-            return None, None
-        a = np.ascontiguousarray(a, np.float32)
-        assert a.size == h * w * ch
-        return a, a.ctypes.data_as(C.c_void_p)
-    (ka, pa), (kn, pn), (kd, pd) = guide(albedo, 3), guide(normal, 3), guide(depth, 1)
-    if out is None:
-        out = np.empty_like(frame)
-    assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == frame.shape
-    dp = make_denoise_params(iterations, sigma_color, sigma_normal, sigma_depth, demodulate)
-    L = lib()
-    _check(L.yart_hip_denoise_atrous_host(frame.ctypes.data_as(C.c_void_p), pa, pn, pd, w, h, C.byref(dp),
-                                          out.ctypes.data_as(C.c_void_p)), L)
-    return out
-
-
-def denoise_into(out_tensor, frame_tensor, guides=None, iterations=DEFAULT_ITERATIONS, sigma_color=DEFAULT_SIGMA_COLOR,
-                 sigma_normal=DEFAULT_SIGMA_NORMAL, sigma_depth=DEFAULT_SIGMA_DEPTH, demodulate=None, stream=None):
-    """``denoise`` on CUDA/HIP torch tensors through ``data_ptr()`` (yart_hip_denoise_atrous_device): ``frame_tensor`` and
-    ``out_tensor`` (H, W, 4) float32 (they may be the same tensor), ``guides`` a dict with any of "albedo", "normal" (H*W*3
-    elements) and "depth" (H*W). Runs on ``stream`` (a raw hipStream_t), by default torch's current stream of the frame's
-    device, and returns after completion there."""
-    import torch
-    h, w = int(frame_tensor.shape[0]), int(frame_tensor.shape[1])
-    if demodulate is None:
-        demodulate = (guides or {}).get("albedo") is not None
-    ptrs = {}
-    for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1)):
-        t = (guides or {}).get(name)
-        if t is not None:
-            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == h * w * ch, name
-        ptrs[name] = None if t is None else C.c_void_p(t.data_ptr())
-    unknown = set(guides or {}) - set(ptrs)
-    assert not unknown, f"denoise_into: unknown guides {sorted(unknown)}"
-    for t in (frame_tensor, out_tensor):
-        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4)
-    if stream is None:
-        stream = torch.cuda.current_stream(frame_tensor.device).cuda_stream
-    dp = make_denoise_params(iterations, sigma_color, sigma_normal, sigma_depth, demodulate)
-    L = lib()
-    with torch.cuda.device(frame_tensor.device):
-        _check(L.yart_hip_denoise_atrous_device(C.c_void_p(frame_tensor.data_ptr()), ptrs["albedo"], ptrs["normal"], ptrs["depth"],
-                                                w, h, C.byref(dp), C.c_void_p(out_tensor.data_ptr()),
-                                                C.c_void_p(stream) if stream else None), L)
-    return out_tensor
-
-
-def denoise_var(frame, variance, albedo=None, normal=None, depth=None, iterations=DEFAULT_VAR_ITERATIONS,
-                sigma_luma=DEFAULT_VAR_SIGMA_LUMA, sigma_normal=DEFAULT_VAR_SIGMA_NORMAL, sigma_depth=DEFAULT_VAR_SIGMA_DEPTH,
-                demodulate=None, out=None):
-    """The variance-guided à-trous filter (include/yart_hip.h: yart_hip_denoise_atrous_var_host): ``denoise`` with the per-pixel
-    ``variance`` (H, W) of ``render_moments`` as a fourth input and ``sigma_luma`` in place of ``sigma_color``.
-    yart_amd.denoise.atrous_var_reference states the same arithmetic in NumPy."""
+def _denoise_host(var, frame, variance, albedo, normal, depth, dp, demodulate, out):
+    """``denoise`` (``var`` False: ``variance`` is not looked at) and ``denoise_var``: NumPy arrays through the _host entry point.
+    ``dp(demodulate)`` makes the form's parameter struct."""
     frame = np.ascontiguousarray(frame, np.float32)
     h, w = frame.shape[:2]
     assert frame.shape == (h, w, 4)
@@ -1092,18 +1029,16 @@ def denoise_var(frame, variance, albedo=None, normal=None, depth=None, iteration
     if out is None:
         out = np.empty_like(frame)
     assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == frame.shape
-    dp = make_denoise_var_params(iterations, sigma_luma, sigma_normal, sigma_depth, demodulate)
     L = lib()
-    _check(L.yart_hip_denoise_atrous_var_host(frame.ctypes.data_as(C.c_void_p), pv, pa, pn, pd, w, h, C.byref(dp),
-                                              out.ctypes.data_as(C.c_void_p)), L)
+    fn = L.yart_hip_denoise_atrous_var_host if var else L.yart_hip_denoise_atrous_host
+    _check(fn(frame.ctypes.data_as(C.c_void_p), *([pv] if var else []), pa, pn, pd, w, h, C.byref(dp(demodulate)),
+              out.ctypes.data_as(C.c_void_p)), L)
     return out
 
 
-def denoise_var_into(out_tensor, frame_tensor, variance_tensor, guides=None, iterations=DEFAULT_VAR_ITERATIONS,
-                     sigma_luma=DEFAULT_VAR_SIGMA_LUMA, sigma_normal=DEFAULT_VAR_SIGMA_NORMAL, sigma_depth=DEFAULT_VAR_SIGMA_DEPTH,
-                     demodulate=None, stream=None):
-    """``denoise_var`` on CUDA/HIP torch tensors through ``data_ptr()`` (yart_hip_denoise_atrous_var_device): as
-    ``denoise_into``, with ``variance_tensor`` (H*W float32 elements)."""
+def _denoise_device(var, out_tensor, frame_tensor, variance_tensor, guides, dp, demodulate, stream):
+    """``denoise_into`` (``var`` False: ``variance_tensor`` is not looked at) and ``denoise_var_into``: torch tensors through the
+    _device entry point. ``dp(demodulate)`` makes the form's parameter struct."""
     import torch
     h, w = int(frame_tensor.shape[0]), int(frame_tensor.shape[1])
     if demodulate is None:
@@ -1115,20 +1050,61 @@ def denoise_var_into(out_tensor, frame_tensor, variance_tensor, guides=None, ite
             assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == h * w * ch, name
         ptrs[name] = None if t is None else C.c_void_p(t.data_ptr())
     unknown = set(guides or {}) - set(ptrs)
-    assert not unknown, f"denoise_var_into: unknown guides {sorted(unknown)}"
+    assert not unknown, f"{'denoise_var_into' if var else 'denoise_into'}: unknown guides {sorted(unknown)}"
     for t in (frame_tensor, out_tensor):
         assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4)
-    v = variance_tensor
-    assert v.is_cuda and v.is_contiguous() and v.dtype == torch.float32 and v.numel() == h * w, "variance"
+    first = [C.c_void_p(frame_tensor.data_ptr())]
+    if var:
+        v = variance_tensor
+        assert v.is_cuda and v.is_contiguous() and v.dtype == torch.float32 and v.numel() == h * w, "variance"
+        first.append(C.c_void_p(v.data_ptr()))
     if stream is None:
         stream = torch.cuda.current_stream(frame_tensor.device).cuda_stream
-    dp = make_denoise_var_params(iterations, sigma_luma, sigma_normal, sigma_depth, demodulate)
     L = lib()
+    fn = L.yart_hip_denoise_atrous_var_device if var else L.yart_hip_denoise_atrous_device
     with torch.cuda.device(frame_tensor.device):
-        _check(L.yart_hip_denoise_atrous_var_device(C.c_void_p(frame_tensor.data_ptr()), C.c_void_p(v.data_ptr()), ptrs["albedo"],
-                                                    ptrs["normal"], ptrs["depth"], w, h, C.byref(dp),
-                                                    C.c_void_p(out_tensor.data_ptr()), C.c_void_p(stream) if stream else None), L)
+        _check(fn(*first, ptrs["albedo"], ptrs["normal"], ptrs["depth"], w, h, C.byref(dp(demodulate)),
+                  C.c_void_p(out_tensor.data_ptr()), C.c_void_p(stream) if stream else None), L)
     return out_tensor
+
+
+def denoise(frame, albedo=None, normal=None, depth=None, iterations=DEFAULT_ITERATIONS, sigma_color=DEFAULT_SIGMA_COLOR,
+            sigma_normal=DEFAULT_SIGMA_NORMAL, sigma_depth=DEFAULT_SIGMA_DEPTH, demodulate=None, out=None):
+    """The edge-avoiding à-trous filter (include/yart_hip.h: yart_hip_denoise_atrous_host) of an (H, W, 4) float32 linear-HDR
+    frame on the device, guided by whichever of ``albedo`` (H, W, 3), ``normal`` (H, W, 3) and ``depth`` (H, W) are given;
+    ``demodulate`` divides by the albedo before and multiplies after (None: whenever ``albedo`` is given). ``out``: a C-contiguous float32 array to fill (may be
+    ``frame``). yart_amd.denoise.atrous_reference states the same arithmetic in NumPy."""
+    return _denoise_host(False, frame, None, albedo, normal, depth,
+                         lambda dm: make_denoise_params(iterations, sigma_color, sigma_normal, sigma_depth, dm), demodulate, out)
+
+
+def denoise_into(out_tensor, frame_tensor, guides=None, iterations=DEFAULT_ITERATIONS, sigma_color=DEFAULT_SIGMA_COLOR,
+                 sigma_normal=DEFAULT_SIGMA_NORMAL, sigma_depth=DEFAULT_SIGMA_DEPTH, demodulate=None, stream=None):
+    """``denoise`` on CUDA/HIP torch tensors through ``data_ptr()`` (yart_hip_denoise_atrous_device): ``frame_tensor`` and
+    ``out_tensor`` (H, W, 4) float32 (they may be the same tensor), ``guides`` a dict with any of "albedo", "normal" (H*W*3
+    elements) and "depth" (H*W). Runs on ``stream`` (a raw hipStream_t), by default torch's current stream of the frame's
+    device, and returns after completion there."""
+    return _denoise_device(False, out_tensor, frame_tensor, None, guides,
+                           lambda dm: make_denoise_params(iterations, sigma_color, sigma_normal, sigma_depth, dm), demodulate, stream)
+
+
+def denoise_var(frame, variance, albedo=None, normal=None, depth=None, iterations=DEFAULT_VAR_ITERATIONS,
+                sigma_luma=DEFAULT_VAR_SIGMA_LUMA, sigma_normal=DEFAULT_VAR_SIGMA_NORMAL, sigma_depth=DEFAULT_VAR_SIGMA_DEPTH,
+                demodulate=None, out=None):
+    """The variance-guided à-trous filter (include/yart_hip.h: yart_hip_denoise_atrous_var_host): ``denoise`` with the per-pixel
+    ``variance`` (H, W) of ``render_moments`` as a fourth input and ``sigma_luma`` in place of ``sigma_color``.
+    yart_amd.denoise.atrous_var_reference states the same arithmetic in NumPy."""
+    return _denoise_host(True, frame, variance, albedo, normal, depth,
+                         lambda dm: make_denoise_var_params(iterations, sigma_luma, sigma_normal, sigma_depth, dm), demodulate, out)
+
+
+def denoise_var_into(out_tensor, frame_tensor, variance_tensor, guides=None, iterations=DEFAULT_VAR_ITERATIONS,
+                     sigma_luma=DEFAULT_VAR_SIGMA_LUMA, sigma_normal=DEFAULT_VAR_SIGMA_NORMAL, sigma_depth=DEFAULT_VAR_SIGMA_DEPTH,
+                     demodulate=None, stream=None):
+    """``denoise_var`` on CUDA/HIP torch tensors through ``data_ptr()`` (yart_hip_denoise_atrous_var_device): as
+    ``denoise_into``, with ``variance_tensor`` (H*W float32 elements)."""
+    return _denoise_device(True, out_tensor, frame_tensor, variance_tensor, guides,
+                           lambda dm: make_denoise_var_params(iterations, sigma_luma, sigma_normal, sigma_depth, dm), demodulate, stream)
 
 
 class TemporalAccumulator:

@@ -32,6 +32,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/yart_hip.h"
@@ -2019,56 +2020,69 @@ int yart_hip_tonemap_host(const float* hdr_rgba, uint32_t width, uint32_t height
   });
 }
 
-// Edge-avoiding à-trous filter (denoise_kernels.inc). The arguments are judged here, before any device is touched.
+}  // extern "C"
+// Edge-avoiding à-trous filter (denoise_kernels.inc), plain (VAR = false, YartDenoiseParams) and variance-guided (VAR = true,
+// YartDenoiseVarParams, with a variance buffer). The arguments are judged here, before any device is touched; the last thing the
+// check asks is whether there is a device at all.
 namespace {
 struct DnCall { DnConst k; uint32_t iterations; bool demodulate; };
-DnCall denoiseCheck(const void* rgba, const void* albedo, const void* normal, const void* depth, uint32_t width, uint32_t height,
-                    const YartDenoiseParams* params, const void* out) {
+inline float dnSigmaFirst(const YartDenoiseParams& p) { return p.sigma_color; }
+inline float dnSigmaFirst(const YartDenoiseVarParams& p) { return p.sigma_luma; }
+template <bool VAR>
+using DnParams = std::conditional_t<VAR, YartDenoiseVarParams, YartDenoiseParams>;
+
+template <bool VAR>
+DnCall denoiseCheck(const void* rgba, const void* variance, const void* albedo, const void* normal, const void* depth, uint32_t width,
+                    uint32_t height, const DnParams<VAR>* params, const void* out) {
   require(rgba && out, "denoise: rgba / out pointer is null");
+  if (VAR) require(variance != nullptr, "denoise: variance pointer is null");
   require(params != nullptr, "denoise: params pointer is null");
-  require(params->struct_size >= sizeof(YartDenoiseParams), "denoise: struct_size is smaller than YartDenoiseParams");
+  require(params->struct_size >= sizeof(*params), VAR ? "denoise: struct_size is smaller than YartDenoiseVarParams"
+                                                      : "denoise: struct_size is smaller than YartDenoiseParams");
   require(params->iterations <= 8u, "denoise: iterations > 8");
   require(width > 0 && height > 0, "denoise: width or height is 0");
   require(uint64_t(width) * height <= (1ull << 28), "denoise: more than 2^28 pixels");
-  require(std::isfinite(params->sigma_color) && std::isfinite(params->sigma_normal) && std::isfinite(params->sigma_depth),
+  require(std::isfinite(dnSigmaFirst(*params)) && std::isfinite(params->sigma_normal) && std::isfinite(params->sigma_depth),
           "denoise: a sigma is not finite");
   require((params->flags & ~uint32_t(YART_DENOISE_DEMODULATE)) == 0u, "denoise: unknown flags bits");
   DnCall c;
   c.iterations = params->iterations;
   c.demodulate = (params->flags & YART_DENOISE_DEMODULATE) != 0u;
   require(!c.demodulate || albedo, "denoise: YART_DENOISE_DEMODULATE without an albedo buffer");
-  c.k.icol = dnInvSigma2(params->sigma_color);
-  c.k.inrm = normal ? dnInvSigma2(params->sigma_normal) : 0.0f;
-  c.k.idep = depth ? dnInvSigma2(params->sigma_depth) : 0.0f;
-  c.k.terms = (params->sigma_color > 0.0f ? kDnColor : 0u) | (normal && params->sigma_normal > 0.0f ? kDnNormal : 0u) |
-              (depth && params->sigma_depth > 0.0f ? kDnDepth : 0u);
+  c.k = dnConstants<VAR>(dnSigmaFirst(*params), params->sigma_normal, params->sigma_depth, normal != nullptr, depth != nullptr);
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw HipError("no HIP device");
   return c;
 }
 
-// device pointers; enqueues on `st` and returns after completion
-void denoiseRun(const DnCall& c, const float* rgba, const float* albedo, const float* normal, const float* depth, uint32_t width,
-                uint32_t height, float* out, hipStream_t st) {
+// device pointers (variance: the variance-guided form only); enqueues on `st` and returns after completion
+template <bool VAR>
+void denoiseRun(const DnCall& c, const float* rgba, const float* variance, const float* albedo, const float* normal, const float* depth,
+                uint32_t width, uint32_t height, float* out, hipStream_t st) {
   const uint32_t n = width * height;
   if (c.iterations == 0u) {                         // a plain copy: no demodulation round trip
     if (out != rgba) HIP_CHECK(hipMemcpyAsync(out, rgba, size_t(n) * 16, hipMemcpyDeviceToDevice, st));
     HIP_CHECK(hipStreamSynchronize(st));
     return;
   }
-  DevBuf<f4> scratch;                               // colour image 0 | colour image 1 | guide records: 48 bytes per pixel
+  DevBuf<f4> scratch;                               // working colour image 0 | image 1 | guide records: 48 bytes per pixel
   scratch.ensure(size_t(n) * 3);
   f4 *img[2] = {scratch.p, scratch.p + n}, *guide = scratch.p + size_t(n) * 2;
   const dim3 flat((n + kBlock - 1) / kBlock), block(kBlock);
-  DnPrepareArgs pa{rgba, c.demodulate ? albedo : nullptr, normal, depth, img[0], guide, n, 0u};
-  hipLaunchKernelGGL(k_dn_prepare, flat, block, 0, st, pa);
+  DnPrepareArgs<VAR> pa{};
+  if constexpr (VAR) pa.variance = variance;
+  pa.rgba = rgba; pa.albedo = c.demodulate ? albedo : nullptr; pa.normal = normal; pa.depth = depth;
+  pa.colour = img[0]; pa.guide = guide; pa.n = n;
+  hipLaunchKernelGGL(k_dn_prepare<VAR>, flat, block, 0, st, pa);
   HIP_CHECK(hipGetLastError());
   for (uint32_t i = 0; i < c.iterations; i++) {
     DnAtrousArgs aa{img[i & 1u], guide, img[(i + 1u) & 1u], width, height, i, 0u, c.k};
     if (i < 2u) {
       aa.tilesX = (width + 15u) / 16u;
-      hipLaunchKernelGGL(k_dn_atrous<0>, dim3(aa.tilesX * ((height + 15u) / 16u)), block, 0, st, aa);
+      hipLaunchKernelGGL((k_dn_atrous<VAR, 0>), dim3(aa.tilesX * ((height + 15u) / 16u)), block, 0, st, aa);
     } else {
       aa.tilesX = (width + 63u) / 64u;
-      hipLaunchKernelGGL(k_dn_atrous<1>, dim3(aa.tilesX * ((height + 3u) / 4u)), block, 0, st, aa);
+      hipLaunchKernelGGL((k_dn_atrous<VAR, 1>), dim3(aa.tilesX * ((height + 3u) / 4u)), block, 0, st, aa);
     }
     HIP_CHECK(hipGetLastError());
   }
@@ -2077,106 +2091,52 @@ void denoiseRun(const DnCall& c, const float* rgba, const float* albedo, const f
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(st));
 }
+
+// host pointers: upload the buffers that are present, filter the frame in place on the device, copy it back
+template <bool VAR>
+void denoiseHost(const DnCall& c, const float* rgba, const float* variance, const float* albedo, const float* normal, const float* depth,
+                 uint32_t width, uint32_t height, float* out) {
+  const size_t n = size_t(width) * height;
+  DevBuf<float> frame, var, alb, nrm, dep;
+  const auto upload = [](DevBuf<float>& b, const float* host, size_t floats) {
+    if (!host) return;
+    b.ensure(floats);
+    HIP_CHECK(hipMemcpy(b.p, host, floats * 4, hipMemcpyHostToDevice));
+  };
+  upload(frame, rgba, n * 4);
+  if (VAR) upload(var, variance, n);
+  if (c.demodulate) upload(alb, albedo, n * 3);
+  upload(nrm, normal, n * 3);
+  upload(dep, depth, n);
+  denoiseRun<VAR>(c, frame.p, var.p, alb.p, nrm.p, dep.p, width, height, frame.p, nullptr);
+  HIP_CHECK(hipMemcpy(out, frame.p, n * 16, hipMemcpyDeviceToHost));
+}
 }  // namespace
+extern "C" {
 
 int yart_hip_denoise_atrous_device(const float* d_rgba, const float* d_albedo, const float* d_normal, const float* d_depth,
                                    uint32_t width, uint32_t height, const YartDenoiseParams* params, float* d_out_rgba,
                                    void* stream) {
   return guarded([&] {
-    const DnCall c = denoiseCheck(d_rgba, d_albedo, d_normal, d_depth, width, height, params, d_out_rgba);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw HipError("no HIP device");
-    denoiseRun(c, d_rgba, d_albedo, d_normal, d_depth, width, height, d_out_rgba, static_cast<hipStream_t>(stream));
+    const DnCall c = denoiseCheck<false>(d_rgba, nullptr, d_albedo, d_normal, d_depth, width, height, params, d_out_rgba);
+    denoiseRun<false>(c, d_rgba, nullptr, d_albedo, d_normal, d_depth, width, height, d_out_rgba, static_cast<hipStream_t>(stream));
   });
 }
 
 int yart_hip_denoise_atrous_host(const float* rgba, const float* albedo, const float* normal, const float* depth, uint32_t width,
                                  uint32_t height, const YartDenoiseParams* params, float* out_rgba) {
   return guarded([&] {
-    const DnCall c = denoiseCheck(rgba, albedo, normal, depth, width, height, params, out_rgba);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw HipError("no HIP device");
-    const size_t n = size_t(width) * height;
-    DevBuf<float> frame, alb, nrm, dep;               // the frame is filtered in place on the device
-    frame.ensure(n * 4);
-    HIP_CHECK(hipMemcpy(frame.p, rgba, n * 16, hipMemcpyHostToDevice));
-    if (albedo && c.demodulate) { alb.ensure(n * 3); HIP_CHECK(hipMemcpy(alb.p, albedo, n * 12, hipMemcpyHostToDevice)); }
-    if (normal) { nrm.ensure(n * 3); HIP_CHECK(hipMemcpy(nrm.p, normal, n * 12, hipMemcpyHostToDevice)); }
-    if (depth) { dep.ensure(n); HIP_CHECK(hipMemcpy(dep.p, depth, n * 4, hipMemcpyHostToDevice)); }
-    denoiseRun(c, frame.p, alb.p, nrm.p, dep.p, width, height, frame.p, nullptr);
-    HIP_CHECK(hipMemcpy(out_rgba, frame.p, n * 16, hipMemcpyDeviceToHost));
+    const DnCall c = denoiseCheck<false>(rgba, nullptr, albedo, normal, depth, width, height, params, out_rgba);
+    denoiseHost<false>(c, rgba, nullptr, albedo, normal, depth, width, height, out_rgba);
   });
 }
-
-// The variance-guided form (denoise_kernels.inc: k_dn_prepare_var, k_dn_atrous_var). The arguments are judged before any device is touched.
-namespace {
-struct DnVarCall { DnVarConst k; uint32_t iterations; bool demodulate; };
-DnVarCall denoiseVarCheck(const void* rgba, const void* variance, const void* albedo, const void* normal, const void* depth, uint32_t width,
-                          uint32_t height, const YartDenoiseVarParams* params, const void* out) {
-  require(rgba && out, "denoise: rgba / out pointer is null");
-  require(variance != nullptr, "denoise: variance pointer is null");
-  require(params != nullptr, "denoise: params pointer is null");
-  require(params->struct_size >= sizeof(YartDenoiseVarParams), "denoise: struct_size is smaller than YartDenoiseVarParams");
-  require(params->iterations <= 8u, "denoise: iterations > 8");
-  require(width > 0 && height > 0, "denoise: width or height is 0");
-  require(uint64_t(width) * height <= (1ull << 28), "denoise: more than 2^28 pixels");
-  require(std::isfinite(params->sigma_luma) && std::isfinite(params->sigma_normal) && std::isfinite(params->sigma_depth),
-          "denoise: a sigma is not finite");
-  require((params->flags & ~uint32_t(YART_DENOISE_DEMODULATE)) == 0u, "denoise: unknown flags bits");
-  DnVarCall c;
-  c.iterations = params->iterations;
-  c.demodulate = (params->flags & YART_DENOISE_DEMODULATE) != 0u;
-  require(!c.demodulate || albedo, "denoise: YART_DENOISE_DEMODULATE without an albedo buffer");
-  c.k.sigmaLuma = params->sigma_luma;
-  c.k.inrm = normal ? dnInvSigma2(params->sigma_normal) : 0.0f;
-  c.k.idep = depth ? dnInvSigma2(params->sigma_depth) : 0.0f;
-  c.k.terms = (params->sigma_luma > 0.0f ? kDnColor : 0u) | (normal && params->sigma_normal > 0.0f ? kDnNormal : 0u) |
-              (depth && params->sigma_depth > 0.0f ? kDnDepth : 0u);
-  return c;
-}
-
-// device pointers; enqueues on `st` and returns after completion
-void denoiseVarRun(const DnVarCall& c, const float* rgba, const float* variance, const float* albedo, const float* normal,
-                   const float* depth, uint32_t width, uint32_t height, float* out, hipStream_t st) {
-  const uint32_t n = width * height;
-  if (c.iterations == 0u) {
-    if (out != rgba) HIP_CHECK(hipMemcpyAsync(out, rgba, size_t(n) * 16, hipMemcpyDeviceToDevice, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    return;
-  }
-  DevBuf<f4> scratch;                               // colour + variance image 0 | image 1 | guide records: 48 bytes per pixel
-  scratch.ensure(size_t(n) * 3);
-  f4 *img[2] = {scratch.p, scratch.p + n}, *guide = scratch.p + size_t(n) * 2;
-  const dim3 flat((n + kBlock - 1) / kBlock), block(kBlock);
-  DnPrepareVarArgs pa{rgba, variance, c.demodulate ? albedo : nullptr, normal, depth, img[0], guide, n, 0u};
-  hipLaunchKernelGGL(k_dn_prepare_var, flat, block, 0, st, pa);
-  HIP_CHECK(hipGetLastError());
-  for (uint32_t i = 0; i < c.iterations; i++) {
-    DnAtrousVarArgs aa{img[i & 1u], guide, img[(i + 1u) & 1u], width, height, i, 0u, c.k};
-    if (i < 2u) {
-      aa.tilesX = (width + 15u) / 16u;
-      hipLaunchKernelGGL(k_dn_atrous_var<0>, dim3(aa.tilesX * ((height + 15u) / 16u)), block, 0, st, aa);
-    } else {
-      aa.tilesX = (width + 63u) / 64u;
-      hipLaunchKernelGGL(k_dn_atrous_var<1>, dim3(aa.tilesX * ((height + 3u) / 4u)), block, 0, st, aa);
-    }
-    HIP_CHECK(hipGetLastError());
-  }
-  DnFinishArgs fa{img[c.iterations & 1u], rgba, c.demodulate ? albedo : nullptr, out, n, 0u};
-  hipLaunchKernelGGL(k_dn_finish, flat, block, 0, st, fa);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipStreamSynchronize(st));
-}
-}  // namespace
 
 int yart_hip_denoise_atrous_var_device(const float* d_rgba, const float* d_variance, const float* d_albedo, const float* d_normal,
                                        const float* d_depth, uint32_t width, uint32_t height, const YartDenoiseVarParams* params,
                                        float* d_out_rgba, void* stream) {
   return guarded([&] {
-    const DnVarCall c = denoiseVarCheck(d_rgba, d_variance, d_albedo, d_normal, d_depth, width, height, params, d_out_rgba);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw HipError("no HIP device");
-    denoiseVarRun(c, d_rgba, d_variance, d_albedo, d_normal, d_depth, width, height, d_out_rgba, static_cast<hipStream_t>(stream));
+    const DnCall c = denoiseCheck<true>(d_rgba, d_variance, d_albedo, d_normal, d_depth, width, height, params, d_out_rgba);
+    denoiseRun<true>(c, d_rgba, d_variance, d_albedo, d_normal, d_depth, width, height, d_out_rgba, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -2184,19 +2144,8 @@ int yart_hip_denoise_atrous_var_host(const float* rgba, const float* variance, c
                                      const float* depth, uint32_t width, uint32_t height, const YartDenoiseVarParams* params,
                                      float* out_rgba) {
   return guarded([&] {
-    const DnVarCall c = denoiseVarCheck(rgba, variance, albedo, normal, depth, width, height, params, out_rgba);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw HipError("no HIP device");
-    const size_t n = size_t(width) * height;
-    DevBuf<float> frame, var, alb, nrm, dep;          // the frame is filtered in place on the device
-    frame.ensure(n * 4); var.ensure(n);
-    HIP_CHECK(hipMemcpy(frame.p, rgba, n * 16, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(var.p, variance, n * 4, hipMemcpyHostToDevice));
-    if (albedo && c.demodulate) { alb.ensure(n * 3); HIP_CHECK(hipMemcpy(alb.p, albedo, n * 12, hipMemcpyHostToDevice)); }
-    if (normal) { nrm.ensure(n * 3); HIP_CHECK(hipMemcpy(nrm.p, normal, n * 12, hipMemcpyHostToDevice)); }
-    if (depth) { dep.ensure(n); HIP_CHECK(hipMemcpy(dep.p, depth, n * 4, hipMemcpyHostToDevice)); }
-    denoiseVarRun(c, frame.p, var.p, alb.p, nrm.p, dep.p, width, height, frame.p, nullptr);
-    HIP_CHECK(hipMemcpy(out_rgba, frame.p, n * 16, hipMemcpyDeviceToHost));
+    const DnCall c = denoiseCheck<true>(rgba, variance, albedo, normal, depth, width, height, params, out_rgba);
+    denoiseHost<true>(c, rgba, variance, albedo, normal, depth, width, height, out_rgba);
   });
 }
 
