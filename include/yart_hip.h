@@ -670,6 +670,66 @@ int yart_hip_temporal_accumulate_host(YartTemporal* temporal, const YartCameraDe
                                       const YartAovBuffers* aovs, const YartTemporalParams* params, float* out_rgba,
                                       float* out_variance, uint32_t* out_length);
 
+/* THE MOMENTS FORM of the temporal accumulation — SVGF's variance estimation (Schied et al. 2017, section 4.2) — on the same
+ * YartTemporal handle. The variance the plain form propagates is the within-pixel sample variance of yart_hip_render_moments, which
+ * is 0.0f by definition at 1 spp and has samples - 1 degrees of freedom otherwise. This form estimates the variance of the
+ * accumulated colour's luminance from the frames themselves: per pixel it accumulates, next to the colour, the first and second
+ * moment of the luminance and the sum of the squared frame weights (temporal estimate), and a pixel whose history is too short —
+ * a disocclusion, the first frames after a reset — takes the variance of its 7 x 7 neighbourhood on the same surface (spatial
+ * estimate). Frame and length are those of the plain form, bit for bit; only the variance differs.
+ * A handle is in ONE FORM from its first accumulate after create or reset: calling the other form before yart_hip_temporal_reset is
+ * YART_E_INVALID. In the moments form the history has a fourth plane of 16-byte records per image, rec3 = {m1, m2, w2, 0}: 128 BYTES
+ * PER PIXEL, allocated by the first moments-form call; a plain-form handle still allocates 96.
+ * DEFINITION, in the terms and under the rules of the plain form's (every operation an individually rounded binary32 operation in
+ * the order written, no FMA contraction; only + - * /, floorf, comparisons and integer min / max: no libm). csrc/temporal.hpp
+ * states it (tpAccumulatePixel<true>, tpSpatialVariance); yart_amd/temporal.py temporal_moments_reference is the NumPy statement.
+ *   PASS 1, per pixel p: the plain form — usable / reprojectable, projection, tap set, tap validation, N, a, the colour blend and
+ *   out_rgba / out_length are unchanged — and additionally, with y = luma(c) = (c.r * 0.2126f + c.g * 0.7152f) + c.b * 0.0722f:
+ *     with a counting tap set: h1, h2, hw2 = sum(w * m1_hist) / sum(w), sum(w * m2_hist) / sum(w), sum(w * w2_hist) / sum(w), the
+ *       weights, tap order and sum of weights of h;  m1 = h1 + a * (y - h1);  m2 = h2 + a * (y * y - h2);
+ *       w2 = (a * a) * 1.0f + ((1.0f - a) * (1.0f - a)) * hw2
+ *     without one: m1 = y, m2 = y * y, w2 = 1.0f.   A pixel that is not usable writes an all-zero rec3.
+ *     w2 is the sum of the squared weights the frames have in acc: 1/N for an equal-weight history, and still right when the
+ *     alpha_min floor or the max_history cap binds.
+ *     vt = m2 - m1 * m1;  vt = vt > 0.0f ? vt : 0.0f
+ *     N >= min_moment_history and w2 < 1.0f:  v_acc = vt * (w2 / (1.0f - w2)) — the unbiased weighted-sample estimate of the variance
+ *       of acc's luminance, vt / (N - 1) for equal weights. The pixel is LONG.
+ *     otherwise the pixel is SHORT, and pass 1 stores the plain form's v_acc = (a * a) * v + ((1.0f - a) * (1.0f - a)) * v_h (v
+ *       without a counting tap) as a provisional value: d_variance is the last fallback.
+ *   PASS 2, per SHORT pixel p, on the history image pass 1 wrote (a second kernel): over the 7 x 7 window around p, dy = -3 .. 3
+ *   outer and dx = -3 .. 3 inner, a tap q COUNTS iff it is inside the image; its new length is >= 1; its node equals p's;
+ *   dot(n(p), n(q)) >= normal_cos_min; fabsf(dot(n(p), P(q) - P(p))) <= plane_tolerance * depth(p) — the tap tests of pass 1, on
+ *   the new records; the centre is a tap like any other. Over the counting taps, from 0.0f and 0: s1 = s1 + m1(q), s2 = s2 + m2(q),
+ *   k = k + 1.
+ *     k >= 2:  e1 = s1 / float(k);  e2 = s2 / float(k);  vs = e2 - e1 * e1;  vs = vs > 0.0f ? vs : 0.0f
+ *              v_acc = (vs * (float(k) / float(k - 1))) * w2(p)
+ *     k < 2:   the provisional value stays.
+ *   out_variance(p) = v_acc * (ld * ld), and v_acc is the variance word of p's history record, in both passes.
+ * min_moment_history is SVGF's 4; on the 6-frame orbits of the two golden scenes at 1 spp the moments form followed by the
+ * variance-guided filter is closer to 1024 spp than the plain form followed by it (profiles/temporal_moments_sweep.txt). */
+#define YART_TEMPORAL_DEFAULT_MIN_MOMENT_HISTORY 4u
+typedef struct YartTemporalMomentParams {
+  uint32_t struct_size;        /* sizeof(YartTemporalMomentParams) */
+  float alpha_min;             /* the four of YartTemporalParams, with the same meaning and limits */
+  uint32_t max_history;
+  float normal_cos_min;
+  float plane_tolerance;
+  uint32_t min_moment_history; /* >= 2: below this history length the spatial estimate is used */
+  uint32_t flags;              /* YART_TEMPORAL_DEMODULATE only */
+} YartTemporalMomentParams;
+/* One frame in the moments form. Arguments, aliasing rules and errors of yart_hip_temporal_accumulate_device (d_variance stays
+ * required: the caller has it from yart_hip_render_moments), and YART_E_INVALID as well, before any device is touched, for a
+ * struct_size smaller than YartTemporalMomentParams, a min_moment_history smaller than 2, and a handle whose history is in the plain
+ * form (as the plain call refuses a handle whose history is in the moments form). */
+int yart_hip_temporal_accumulate_moments_device(YartTemporal* temporal, const YartCameraDesc* cam, const float* d_rgba,
+                                                const float* d_variance, const YartAovBuffers* d_aovs,
+                                                const YartTemporalMomentParams* params, float* d_out_rgba, float* d_out_variance,
+                                                uint32_t* d_out_length, void* stream);
+/* Same, HOST pointers */
+int yart_hip_temporal_accumulate_moments_host(YartTemporal* temporal, const YartCameraDesc* cam, const float* rgba, const float* variance,
+                                              const YartAovBuffers* aovs, const YartTemporalMomentParams* params, float* out_rgba,
+                                              float* out_variance, uint32_t* out_length);
+
 const char* yart_hip_last_error(void);
 int yart_hip_abi_version(void);
 int yart_hip_device_count(void);

@@ -180,11 +180,21 @@ inline std::vector<float> denoiseVar(const std::vector<float>& rgba, const std::
 }
 
 // Temporal accumulation with camera reprojection for a sequence of frames of one scene (yart_hip_temporal_*): the stage between a
-// render with moments and denoiseVar. The handle holds the history (96 bytes per pixel on the device) and the last camera.
+// render with moments and denoiseVar. The handle holds the history (96 bytes per pixel on the device; 128 in the moments form) and
+// the last camera. accumulateMoments is the moments form (yart_hip_temporal_accumulate_moments_host): the variance estimated from
+// the accumulated luminance moments, and from the neighbourhood where the history is short; one form per handle between resets.
 inline YartTemporalParams temporalDefaults(bool demodulate = false) {
   YartTemporalParams p{};
   p.struct_size = uint32_t(sizeof(p)); p.alpha_min = YART_TEMPORAL_DEFAULT_ALPHA_MIN; p.max_history = YART_TEMPORAL_DEFAULT_MAX_HISTORY;
   p.normal_cos_min = YART_TEMPORAL_DEFAULT_NORMAL_COS_MIN; p.plane_tolerance = YART_TEMPORAL_DEFAULT_PLANE_TOLERANCE;
+  p.flags = demodulate ? YART_TEMPORAL_DEMODULATE : 0u;
+  return p;
+}
+inline YartTemporalMomentParams temporalMomentDefaults(bool demodulate = false) {
+  YartTemporalMomentParams p{};
+  p.struct_size = uint32_t(sizeof(p)); p.alpha_min = YART_TEMPORAL_DEFAULT_ALPHA_MIN; p.max_history = YART_TEMPORAL_DEFAULT_MAX_HISTORY;
+  p.normal_cos_min = YART_TEMPORAL_DEFAULT_NORMAL_COS_MIN; p.plane_tolerance = YART_TEMPORAL_DEFAULT_PLANE_TOLERANCE;
+  p.min_moment_history = YART_TEMPORAL_DEFAULT_MIN_MOMENT_HISTORY;
   p.flags = demodulate ? YART_TEMPORAL_DEMODULATE : 0u;
   return p;
 }
@@ -208,6 +218,19 @@ class Temporal {
   // one frame, host buffers: the accumulated frame, its variance and the history length per pixel
   TemporalFrame accumulate(const YartCameraDesc& camera, const std::vector<float>& rgba, const std::vector<float>& variance,
                            const TemporalFeatures& f, const YartTemporalParams& params) {
+    return run(yart_hip_temporal_accumulate_host, camera, rgba, variance, f, params);
+  }
+  // the same in the moments form
+  TemporalFrame accumulateMoments(const YartCameraDesc& camera, const std::vector<float>& rgba, const std::vector<float>& variance,
+                                  const TemporalFeatures& f, const YartTemporalMomentParams& params) {
+    return run(yart_hip_temporal_accumulate_moments_host, camera, rgba, variance, f, params);
+  }
+  YartTemporal* handle() const { return m_handle; }
+
+ private:
+  template <class Fn, class Params>
+  TemporalFrame run(Fn fn, const YartCameraDesc& camera, const std::vector<float>& rgba, const std::vector<float>& variance,
+                    const TemporalFeatures& f, const Params& params) {
     const size_t n = size_t(m_width) * m_height;
     if (rgba.size() != n * 4 || variance.size() != n || f.position.size() != n * 3 || f.normal.size() != n * 3 || f.depth.size() != n ||
         f.coverage.size() != n || f.ids.size() != n * 4 || (!f.albedo.empty() && f.albedo.size() != n * 3))
@@ -219,13 +242,9 @@ class Temporal {
     a.depth = const_cast<float*>(f.depth.data()); a.coverage = const_cast<float*>(f.coverage.data());
     a.ids = const_cast<int32_t*>(f.ids.data()); a.albedo = f.albedo.empty() ? nullptr : const_cast<float*>(f.albedo.data());
     TemporalFrame out{std::vector<float>(n * 4), std::vector<float>(n), std::vector<uint32_t>(n)};
-    check(yart_hip_temporal_accumulate_host(m_handle, &camera, rgba.data(), variance.data(), &a, &params, out.rgba.data(),
-                                            out.variance.data(), out.length.data()));
+    check(fn(m_handle, &camera, rgba.data(), variance.data(), &a, &params, out.rgba.data(), out.variance.data(), out.length.data()));
     return out;
   }
-  YartTemporal* handle() const { return m_handle; }
-
- private:
   YartTemporal* m_handle = nullptr;
   uint32_t m_width, m_height;
 };

@@ -29,7 +29,8 @@ from .denoise import (DEFAULT_ITERATIONS, DEFAULT_SIGMA_COLOR, DEFAULT_SIGMA_DEP
 from .denoise import (DEFAULT_VAR_ITERATIONS, DEFAULT_VAR_SIGMA_DEPTH, DEFAULT_VAR_SIGMA_LUMA, DEFAULT_VAR_SIGMA_NORMAL,
                       atrous_var_reference)  # noqa: F401 (the NumPy statement of denoise_var / denoise_var_into)
 from .moments import moments_reference  # noqa: F401 (the NumPy statement of render_moments / probe_moments)
-from .temporal import (DEFAULT_ALPHA_MIN, DEFAULT_MAX_HISTORY, DEFAULT_NORMAL_COS_MIN, DEFAULT_PLANE_TOLERANCE,
+from .temporal import (DEFAULT_ALPHA_MIN, DEFAULT_MAX_HISTORY, DEFAULT_MIN_MOMENT_HISTORY, DEFAULT_NORMAL_COS_MIN,
+                       DEFAULT_PLANE_TOLERANCE, temporal_moments_reference,
                        temporal_reference)  # noqa: F401 (the NumPy statement of TemporalAccumulator.accumulate / accumulate_into)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -229,6 +230,13 @@ class TemporalParams(C.Structure):
                 ("normal_cos_min", C.c_float), ("plane_tolerance", C.c_float), ("flags", C.c_uint32)]
 
 
+class TemporalMomentParams(C.Structure):
+    """YartTemporalMomentParams (include/yart_hip.h): the knobs of the temporal accumulator's moments form."""
+    _fields_ = [("struct_size", C.c_uint32), ("alpha_min", C.c_float), ("max_history", C.c_uint32),
+                ("normal_cos_min", C.c_float), ("plane_tolerance", C.c_float), ("min_moment_history", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
 FLAG_TEMPORAL_DEMODULATE = 1
 TEMPORAL_AOVS = ("position", "normal", "depth", "coverage", "ids")     # + "albedo" when demodulating
 
@@ -237,6 +245,13 @@ def make_temporal_params(alpha_min=DEFAULT_ALPHA_MIN, max_history=DEFAULT_MAX_HI
                          plane_tolerance=DEFAULT_PLANE_TOLERANCE, demodulate=False) -> TemporalParams:
     return TemporalParams(C.sizeof(TemporalParams), float(alpha_min), int(max_history), float(normal_cos_min),
                           float(plane_tolerance), FLAG_TEMPORAL_DEMODULATE if demodulate else 0)
+
+
+def make_temporal_moment_params(alpha_min=DEFAULT_ALPHA_MIN, max_history=DEFAULT_MAX_HISTORY, normal_cos_min=DEFAULT_NORMAL_COS_MIN,
+                                plane_tolerance=DEFAULT_PLANE_TOLERANCE, min_moment_history=DEFAULT_MIN_MOMENT_HISTORY,
+                                demodulate=False) -> TemporalMomentParams:
+    return TemporalMomentParams(C.sizeof(TemporalMomentParams), float(alpha_min), int(max_history), float(normal_cos_min),
+                                float(plane_tolerance), int(min_moment_history), FLAG_TEMPORAL_DEMODULATE if demodulate else 0)
 
 
 class DenoiseParams(C.Structure):
@@ -294,7 +309,8 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_probe_estimator",
            "yart_hip_denoise_atrous_var_device", "yart_hip_denoise_atrous_var_host",
            "yart_hip_temporal_create", "yart_hip_temporal_destroy", "yart_hip_temporal_reset",
-           "yart_hip_temporal_accumulate_device", "yart_hip_temporal_accumulate_host"]
+           "yart_hip_temporal_accumulate_device", "yart_hip_temporal_accumulate_host",
+           "yart_hip_temporal_accumulate_moments_device", "yart_hip_temporal_accumulate_moments_host"]
 
 LIB_COUNT_PATH = os.path.join(_HERE, "libyart_hip_count.so")   # instrumented twin (exact test counters)
 _libs = {}
@@ -375,6 +391,12 @@ def lib(instrumented: bool = False):
                                                           C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.yart_hip_temporal_accumulate_host.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers),
                                                         C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.yart_hip_temporal_accumulate_moments_device.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.c_void_p, C.c_void_p,
+                                                                  C.POINTER(AovBuffers), C.POINTER(TemporalMomentParams), C.c_void_p,
+                                                                  C.c_void_p, C.c_void_p, C.c_void_p]
+        L.yart_hip_temporal_accumulate_moments_host.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.c_void_p, C.c_void_p,
+                                                                C.POINTER(AovBuffers), C.POINTER(TemporalMomentParams), C.c_void_p,
+                                                                C.c_void_p, C.c_void_p]
         L.yart_hip_bvh_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.yart_hip_bvh_copy.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         _libs[path] = L
@@ -721,8 +743,8 @@ class DeviceScene:
         of the filter that runs (DEFAULT_* of the plain one, DEFAULT_VAR_* of the variance-guided one).
         ``temporal``: a :class:`TemporalAccumulator` of the frame's size — one frame of a sequence: ``render_moments_into`` with
         the variance and the feature buffers the accumulator needs, then ``temporal.accumulate_into`` (at the accumulator's own
-        parameters, demodulating as ``demodulate`` says), then the variance-guided filter on the accumulated frame and variance
-        (``variance_guided`` is implied). Returns (noisy frame, denoised frame, guides) with "accumulated" (H, W, 4),
+        parameters and in its own form — plain or moments —, demodulating as ``demodulate`` says), then the variance-guided
+        filter on the accumulated frame and variance (``variance_guided`` is implied). Returns (noisy frame, denoised frame, guides) with "accumulated" (H, W, 4),
         "accumulated_variance" (H, W) and "length" (H, W, int32 holding the uint32) among the guides. None: as before."""
         import torch
         if temporal is not None:
@@ -1112,14 +1134,22 @@ class TemporalAccumulator:
     yart_hip_temporal_*): the stage between ``render_moments`` and ``denoise_var``. Holds the history (96 bytes per pixel on the
     device, allocated by the first frame) and the last frame's camera. ``alpha_min`` / ``max_history`` / ``normal_cos_min`` /
     ``plane_tolerance`` are the parameters of every frame unless a call overrides them. ``device`` < 0: the device current at
-    the first frame. yart_amd.temporal.temporal_reference states the same arithmetic in NumPy."""
+    the first frame. yart_amd.temporal.temporal_reference states the same arithmetic in NumPy.
+    ``moments=True``: the moments form (yart_hip_temporal_accumulate_moments_*; 128 bytes per pixel): the returned variance is
+    estimated from the accumulated luminance moments, and from the 7 x 7 neighbourhood where the history is shorter than
+    ``min_moment_history`` — the form for low sample counts, where the rendered variance is 0 or nearly so.
+    yart_amd.temporal.temporal_moments_reference states it. A handle is in one form between resets."""
 
     def __init__(self, width: int, height: int, device: int = 0, alpha_min=DEFAULT_ALPHA_MIN, max_history=DEFAULT_MAX_HISTORY,
-                 normal_cos_min=DEFAULT_NORMAL_COS_MIN, plane_tolerance=DEFAULT_PLANE_TOLERANCE):
+                 normal_cos_min=DEFAULT_NORMAL_COS_MIN, plane_tolerance=DEFAULT_PLANE_TOLERANCE, moments=False,
+                 min_moment_history=DEFAULT_MIN_MOMENT_HISTORY):
         self._L = lib()
         self.width, self.height, self.device = int(width), int(height), int(device)
+        self.moments = bool(moments)
         self.params = dict(alpha_min=alpha_min, max_history=max_history, normal_cos_min=normal_cos_min,
                            plane_tolerance=plane_tolerance)
+        if self.moments:
+            self.params["min_moment_history"] = min_moment_history
         h = C.c_void_p()
         _check(self._L.yart_hip_temporal_create(self.width, self.height, self.device, C.byref(h)), self._L)
         self._h = h
@@ -1149,10 +1179,11 @@ class TemporalAccumulator:
     def _params(self, demodulate, over):
         unknown = set(over) - set(self.params)
         assert not unknown, f"TemporalAccumulator: unknown parameters {sorted(unknown)}"
-        return make_temporal_params(demodulate=demodulate, **dict(self.params, **over))
+        make = make_temporal_moment_params if self.moments else make_temporal_params
+        return make(demodulate=demodulate, **dict(self.params, **over))
 
     def accumulate(self, cam, frame, variance, aovs: dict, demodulate=None, out=None, out_variance=None, **over):
-        """One frame on NumPy arrays (yart_hip_temporal_accumulate_host). ``cam``: the frame's camera (a params dict as
+        """One frame on NumPy arrays (yart_hip_temporal_accumulate_host, or _moments_host in the moments form). ``cam``: the frame's camera (a params dict as
         ``render`` takes it, or a CameraDesc); ``frame`` (H, W, 4); ``variance`` (H, W); ``aovs``: the feature buffers by name —
         position, normal, depth, coverage, ids, and albedo when demodulating (``demodulate`` None: whenever albedo is given).
         ``out`` / ``out_variance`` may be ``frame`` / ``variance``. Returns (accumulated frame, its variance, history length
@@ -1183,15 +1214,15 @@ class TemporalAccumulator:
             assert o.dtype == np.float32 and o.flags.c_contiguous and o.size == size
         length = np.empty((h, w), np.uint32)
         tp = self._params(demodulate, over)
-        _check(self._L.yart_hip_temporal_accumulate_host(self._h, C.byref(self._camera(cam)), frame.ctypes.data_as(C.c_void_p),
-                                                         variance.ctypes.data_as(C.c_void_p), C.byref(ab), C.byref(tp),
-                                                         out.ctypes.data_as(C.c_void_p), out_variance.ctypes.data_as(C.c_void_p),
-                                                         length.ctypes.data_as(C.c_void_p)), self._L)
+        fn = self._L.yart_hip_temporal_accumulate_moments_host if self.moments else self._L.yart_hip_temporal_accumulate_host
+        _check(fn(self._h, C.byref(self._camera(cam)), frame.ctypes.data_as(C.c_void_p), variance.ctypes.data_as(C.c_void_p),
+                  C.byref(ab), C.byref(tp), out.ctypes.data_as(C.c_void_p), out_variance.ctypes.data_as(C.c_void_p),
+                  length.ctypes.data_as(C.c_void_p)), self._L)
         return out, out_variance, length
 
     def accumulate_into(self, out_tensor, out_variance_tensor, out_length_tensor, cam, frame_tensor, variance_tensor,
                         aov_tensors: dict, demodulate=None, stream=None, **over):
-        """``accumulate`` on CUDA/HIP torch tensors through ``data_ptr()`` (yart_hip_temporal_accumulate_device), on ``stream``
+        """``accumulate`` on CUDA/HIP torch tensors through ``data_ptr()`` (yart_hip_temporal_accumulate[_moments]_device), on ``stream``
         (an integer handle; None: torch's current stream): no host round trip. ``out_variance_tensor`` and
         ``out_length_tensor`` (H*W 4-byte elements: int32 holding the uint32) may be None; ``out_tensor`` may be
         ``frame_tensor`` and ``out_variance_tensor`` may be ``variance_tensor``."""
@@ -1218,10 +1249,10 @@ class TemporalAccumulator:
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         tp = self._params(demodulate, over)
         with torch.cuda.device(frame_tensor.device):
-            _check(self._L.yart_hip_temporal_accumulate_device(self._h, C.byref(self._camera(cam)), ptr(frame_tensor),
-                                                               ptr(variance_tensor), C.byref(ab), C.byref(tp), ptr(out_tensor),
-                                                               ptr(out_variance_tensor), ptr(out_length_tensor),
-                                                               C.c_void_p(stream) if stream else None), self._L)
+            fn = self._L.yart_hip_temporal_accumulate_moments_device if self.moments else self._L.yart_hip_temporal_accumulate_device
+            _check(fn(self._h, C.byref(self._camera(cam)), ptr(frame_tensor), ptr(variance_tensor), C.byref(ab), C.byref(tp),
+                      ptr(out_tensor), ptr(out_variance_tensor), ptr(out_length_tensor), C.c_void_p(stream) if stream else None),
+                   self._L)
         return out_tensor
 
 

@@ -10,6 +10,11 @@
 //   rec0  {acc.r, acc.g, acc.b, variance}     the accumulated colour (demodulated when the flag is set) and its variance
 //   rec1  {P.x, P.y, P.z, length (u32 bits)}  the world-space point; length 0: the record is nobody's tap
 //   rec2  {n.x, n.y, n.z, node (u32 bits)}    the normal and ids[0]
+// The moments form (yart_hip_temporal_accumulate_moments_*, SVGF's variance estimation) keeps a fourth plane, 128 bytes per pixel:
+//   rec3  {m1, m2, w2, 0}                      the accumulated first and second moment of the luminance of the (demodulated)
+//                                              colour and the sum of the squared frame weights of that estimate
+// and runs a second pass, tpSpatialVariance, over the image the first one wrote: a pixel whose history is too short for the
+// temporal estimate takes the variance of m1 over its 7 x 7 neighbourhood on the same surface.
 #pragma once
 #include "denoise.hpp"
 #include "scene_types.hpp"
@@ -39,7 +44,7 @@ struct TpConst {
   uint32_t maxHistory;
   uint32_t width, height;
   uint32_t haveHistory;        // 0: first frame or after a reset: no tap is read
-  uint32_t pad;
+  uint32_t minMomentHistory;   // the moments form only: below this length a pixel is short
 };
 
 struct TpIn {                  // the current pixel
@@ -53,17 +58,23 @@ struct TpOut {
   float variance;              // to d_out_variance
   uint32_t length;             // to d_out_length
   f4 rec0, rec1, rec2;         // the pixel's new history record
+  f4 rec3;                     // the moments form only
 };
 
 YART_HD bool tpFinite3(f3 a) { return dnFinite(a.x) && dnFinite(a.y) && dnFinite(a.z); }
 
-// One pixel. Hist decides how a 16-byte record of the previous history image is fetched: hist.rec0(q) / rec1(q) / rec2(q),
-// q = y * width + x. demodulate: the call demodulates, and alb is the pixel's albedo (by value: no array for the kernel to keep).
-template <class Hist>
+// dnDivisor: d = alb > 1e-3f ? alb : 1.0f per channel
+YART_HD f3 tpDivisor(bool demodulate, f3 alb) {
+  return demodulate ? mk3(alb.x > 1e-3f ? alb.x : 1.0f, alb.y > 1e-3f ? alb.y : 1.0f, alb.z > 1e-3f ? alb.z : 1.0f) : mk3(1.0f);
+}
+
+// One pixel. Hist decides how a 16-byte record of the previous history image is fetched: hist.rec0(q) / rec1(q) / rec2(q) (and
+// rec3(q) with MOMENTS), q = y * width + x. demodulate: the call demodulates, and alb is the pixel's albedo (by value: no array
+// for the kernel to keep). MOMENTS: the moments form — pass 1 of it; a short pixel's o.variance / rec0.w are provisional.
+template <bool MOMENTS, class Hist>
 YART_HD TpOut tpAccumulatePixel(const Hist& hist, const TpConst& k, const TpCamera& cam, const TpIn& in, bool demodulate, f3 alb) {
   TpOut o;
-  // dnDivisor: d = alb > 1e-3f ? alb : 1.0f per channel
-  const f3 d = demodulate ? mk3(alb.x > 1e-3f ? alb.x : 1.0f, alb.y > 1e-3f ? alb.y : 1.0f, alb.z > 1e-3f ? alb.z : 1.0f) : mk3(1.0f);
+  const f3 d = tpDivisor(demodulate, alb);
   const float cr = in.rgba.x / d.x, cg = in.rgba.y / d.y, cb = in.rgba.z / d.z;
   const float ld = dnLuma(d.x, d.y, d.z);
   const float ld2 = ld * ld;
@@ -72,11 +83,12 @@ YART_HD TpOut tpAccumulatePixel(const Hist& hist, const TpConst& k, const TpCame
   if (demodulate) usable = usable && tpFinite3(alb);
   if (!usable) {               // passed through; an all-zero record of length 0
     o.rgba = in.rgba; o.variance = in.variance; o.length = 0u;
-    o.rec0 = o.rec1 = o.rec2 = dnF4(0.0f, 0.0f, 0.0f, 0.0f);
+    o.rec0 = o.rec1 = o.rec2 = o.rec3 = dnF4(0.0f, 0.0f, 0.0f, 0.0f);
     return o;
   }
   const bool reprojectable = in.coverage == 1.0f && tpFinite3(in.P) && tpFinite3(in.n) && dnFinite(in.depth);
   float accR = 0.0f, accG = 0.0f, accB = 0.0f, accV = 0.0f, wsum = 0.0f;
+  float acc1 = 0.0f, acc2 = 0.0f, accW2 = 0.0f;           // MOMENTS: the tap-weighted sums of rec3's words
   uint32_t minLen = 0xffffffffu;
   bool any = false;
   if (k.haveHistory != 0u && reprojectable) {
@@ -108,6 +120,10 @@ YART_HD TpOut tpAccumulatePixel(const Hist& hist, const TpConst& k, const TpCame
           if (!(fabsf(dot(in.n, dP)) <= tol)) continue;
           const f4 r0 = hist.rec0(q);
           accR = accR + w * r0.x; accG = accG + w * r0.y; accB = accB + w * r0.z; accV = accV + w * r0.w;
+          if constexpr (MOMENTS) {
+            const f4 r3 = hist.rec3(q);
+            acc1 = acc1 + w * r3.x; acc2 = acc2 + w * r3.y; accW2 = accW2 + w * r3.z;
+          }
           wsum = wsum + w;
           minLen = len < minLen ? len : minLen;
           any = true;
@@ -117,6 +133,8 @@ YART_HD TpOut tpAccumulatePixel(const Hist& hist, const TpConst& k, const TpCame
   }
   float outR = cr, outG = cg, outB = cb, outV = v;
   uint32_t N = 1u;
+  const float y = MOMENTS ? dnLuma(cr, cg, cb) : 0.0f;
+  float m1 = y, m2 = y * y, w2 = 1.0f;
   if (any) {
     const float hr = accR / wsum, hg = accG / wsum, hb = accB / wsum, hv = accV / wsum;
     N = minLen >= k.maxHistory ? k.maxHistory : minLen + 1u;
@@ -125,6 +143,18 @@ YART_HD TpOut tpAccumulatePixel(const Hist& hist, const TpConst& k, const TpCame
     const float b = 1.0f - a;
     outR = hr + a * (cr - hr); outG = hg + a * (cg - hg); outB = hb + a * (cb - hb);
     outV = (a * a) * v + (b * b) * hv;
+    if (MOMENTS) {
+      const float h1 = acc1 / wsum, h2 = acc2 / wsum, hw2 = accW2 / wsum;
+      m1 = h1 + a * (y - h1);
+      m2 = h2 + a * (y * y - h2);
+      w2 = (a * a) * 1.0f + (b * b) * hw2;
+    }
+  }
+  if (MOMENTS) {
+    float vt = m2 - m1 * m1;
+    vt = vt > 0.0f ? vt : 0.0f;
+    if (N >= k.minMomentHistory && w2 < 1.0f) outV = vt * (w2 / (1.0f - w2));   // else short: the propagated value, for pass 2
+    o.rec3 = dnF4(m1, m2, w2, 0.0f);
   }
   o.rgba = dnF4(outR * d.x, outG * d.y, outB * d.z, in.rgba.w);
   o.variance = outV * ld2;
@@ -133,6 +163,58 @@ YART_HD TpOut tpAccumulatePixel(const Hist& hist, const TpConst& k, const TpCame
   o.rec1 = dnF4(in.P.x, in.P.y, in.P.z, __builtin_bit_cast(float, N));
   o.rec2 = dnF4(in.n.x, in.n.y, in.n.z, __builtin_bit_cast(float, in.node));
   return o;
+}
+
+// the plain form, as its callers have always named it
+template <class Hist>
+YART_HD TpOut tpAccumulatePixel(const Hist& hist, const TpConst& k, const TpCamera& cam, const TpIn& in, bool demodulate, f3 alb) {
+  return tpAccumulatePixel<false, Hist>(hist, k, cam, in, demodulate, alb);
+}
+
+// Pass 2 of the moments form, one pixel (x, y) of the image pass 1 just wrote (hist: rec1 / rec2 / rec3 of that image); depth is
+// the pixel's depth(p). True: the pixel is short and at least two pixels of its 7 x 7 window lie on its surface: vAcc is its
+// spatial estimate, to be written to rec0.w and, times luma(d)^2, to out_variance. False: the pixel keeps what pass 1 wrote.
+constexpr int kTpSpatialRadius = 3;
+template <class Hist>
+YART_HD bool tpSpatialVariance(const Hist& hist, const TpConst& k, uint32_t x, uint32_t y, float depth, float& vAcc) {
+  const size_t p = size_t(y) * k.width + x;
+  const f4 c1 = hist.rec1(p);
+  const uint32_t N = dnBits(c1.w);
+  if (N < 1u) return false;                      // not usable: passed through
+  const f4 c3 = hist.rec3(p);
+  if (N >= k.minMomentHistory && c3.z < 1.0f) return false;                      // long: the temporal estimate stands
+  const f4 c2 = hist.rec2(p);
+  const f3 P = mk3(c1.x, c1.y, c1.z), n = mk3(c2.x, c2.y, c2.z);
+  const uint32_t node = dnBits(c2.w);
+  const float tol = k.planeTolerance * depth;
+  float s1 = 0.0f, s2 = 0.0f;
+  uint32_t cnt = 0u;
+  for (int dy = -kTpSpatialRadius; dy <= kTpSpatialRadius; dy++) {
+    const int qy = int(y) + dy;
+    if (qy < 0 || qy >= int(k.height)) continue;
+    for (int dx = -kTpSpatialRadius; dx <= kTpSpatialRadius; dx++) {
+      const int qx = int(x) + dx;
+      if (qx < 0 || qx >= int(k.width)) continue;
+      const size_t q = size_t(qy) * k.width + size_t(qx);
+      const f4 r1 = hist.rec1(q);
+      if (dnBits(r1.w) < 1u) continue;
+      const f4 r2 = hist.rec2(q);
+      if (dnBits(r2.w) != node) continue;
+      if (!(dot(n, mk3(r2.x, r2.y, r2.z)) >= k.normalCosMin)) continue;
+      const f3 dP = mk3(r1.x, r1.y, r1.z) - P;
+      if (!(fabsf(dot(n, dP)) <= tol)) continue;
+      const f4 r3 = hist.rec3(q);
+      s1 = s1 + r3.x; s2 = s2 + r3.y;
+      cnt++;
+    }
+  }
+  if (cnt < 2u) return false;
+  const float kf = float(cnt);
+  const float e1 = s1 / kf, e2 = s2 / kf;
+  float vs = e2 - e1 * e1;
+  vs = vs > 0.0f ? vs : 0.0f;
+  vAcc = (vs * (kf / float(cnt - 1u))) * c3.z;
+  return true;
 }
 
 }  // namespace yart_hip

@@ -10,21 +10,30 @@
 //                     the previous image, so neighbouring lanes' taps share lines in the CU's vector cache: no LDS tile.
 //                     A first frame (or the first after a reset) reads no tap: TpConst::haveHistory is uniform over the launch.
 //
-// History: two images of three planes of 16-byte records (temporal.hpp), 96 bytes per pixel, owned by the YartTemporal handle.
-// The kernel uses neither LDS nor scratch memory; none of the existing kernels changes.
+//   k_tp_accumulate<true>   the moments form, pass 1: the same, with rec3 — one more aligned 16-byte load per counting tap and
+//                     one more 16-byte store.
+//   k_tp_spatial_variance   the moments form, pass 2, launched after pass 1 on the image it wrote, same tile: a lane whose pixel
+//                     is long (or not usable) returns after two loads of its own records, so a wave without a short pixel ends
+//                     before its first tap load. A short pixel walks its 7 x 7 window through the caches — rec1, then rec2, and
+//                     rec3 only for a tap that counts; a tile's taps fall into 22 x 22 pixels, 1.9 times the tile, the regime
+//                     of k_dn_atrous<·, 0>: no LDS tile — and writes its own rec0.w and out_variance, nothing a neighbour reads.
+//
+// History: two images of three (the moments form: four) planes of 16-byte records (temporal.hpp), 96 (128) bytes per pixel, owned
+// by the YartTemporal handle. The kernels use neither LDS nor scratch memory; none of the existing kernels changes.
 
 struct TpDeviceHist {
-  const f4 *r0, *r1, *r2;
+  const f4 *r0, *r1, *r2, *r3;                     // r3: the moments form only
   __device__ __forceinline__ f4 rec0(size_t q) const { return dnLd(r0 + q); }
   __device__ __forceinline__ f4 rec1(size_t q) const { return dnLd(r1 + q); }
   __device__ __forceinline__ f4 rec2(size_t q) const { return dnLd(r2 + q); }
+  __device__ __forceinline__ f4 rec3(size_t q) const { return dnLd(r3 + q); }
 };
 
 struct TpArgs {
   const float *rgba, *variance, *albedo;           // albedo: only when the call demodulates
   const float *position, *normal, *depth, *coverage;
   const int32_t* ids;                              // 4 per pixel; [0] = node
-  const f4* histIn;                                // planes rec0 | rec1 | rec2, n records each
+  const f4* histIn;                                // planes rec0 | rec1 | rec2 (| rec3), n records each
   f4* histOut;
   float *outRgba, *outVariance;                    // outRgba may be rgba, outVariance may be variance: a lane reads its own
   uint32_t* outLength;                             // pixel before it writes it; outVariance / outLength may be null
@@ -32,6 +41,7 @@ struct TpArgs {
   TpConst k;
   TpCamera cam;
 };
+template <bool MOMENTS>
 __global__ void __launch_bounds__(kBlock) k_tp_accumulate(TpArgs a) {
   const uint32_t ty = blockIdx.x / a.tilesX, tx = blockIdx.x - ty * a.tilesX;
   const uint32_t x = tx * 16u + (threadIdx.x % 16u), y = ty * 16u + (threadIdx.x / 16u);
@@ -49,12 +59,34 @@ __global__ void __launch_bounds__(kBlock) k_tp_accumulate(TpArgs a) {
   if (a.albedo) alb = mk3(a.albedo[p * 3], a.albedo[p * 3 + 1], a.albedo[p * 3 + 2]);
   TpDeviceHist hist;
   hist.r0 = a.histIn; hist.r1 = a.histIn + a.n; hist.r2 = a.histIn + size_t(a.n) * 2;
-  const TpOut o = tpAccumulatePixel(hist, a.k, a.cam, in, a.albedo != nullptr, alb);
+  hist.r3 = MOMENTS ? a.histIn + size_t(a.n) * 3 : nullptr;
+  const TpOut o = tpAccumulatePixel<MOMENTS>(hist, a.k, a.cam, in, a.albedo != nullptr, alb);
   dnSt(a.histOut + p, o.rec0);
   dnSt(a.histOut + a.n + p, o.rec1);
   dnSt(a.histOut + size_t(a.n) * 2 + p, o.rec2);
+  if (MOMENTS) dnSt(a.histOut + size_t(a.n) * 3 + p, o.rec3);
   float* q = a.outRgba + p * 4;                    // the caller's buffers are only known to be 4-byte aligned
   q[0] = o.rgba.x; q[1] = o.rgba.y; q[2] = o.rgba.z; q[3] = o.rgba.w;
   if (a.outVariance) a.outVariance[p] = o.variance;
   if (a.outLength) a.outLength[p] = o.length;
+}
+
+// a: the arguments of the k_tp_accumulate<true> launch it follows; reads a.depth and a.albedo of its own pixel and a.histOut
+__global__ void __launch_bounds__(kBlock) k_tp_spatial_variance(TpArgs a) {
+  const uint32_t ty = blockIdx.x / a.tilesX, tx = blockIdx.x - ty * a.tilesX;
+  const uint32_t x = tx * 16u + (threadIdx.x % 16u), y = ty * 16u + (threadIdx.x / 16u);
+  if (x >= a.k.width || y >= a.k.height) return;
+  const size_t p = size_t(y) * a.k.width + x;
+  TpDeviceHist hist;
+  hist.r0 = a.histOut; hist.r1 = a.histOut + a.n; hist.r2 = a.histOut + size_t(a.n) * 2; hist.r3 = a.histOut + size_t(a.n) * 3;
+  float vAcc;
+  if (!tpSpatialVariance(hist, a.k, x, y, a.depth[p], vAcc)) return;
+  reinterpret_cast<float*>(a.histOut + p)[3] = vAcc;           // rec0.w
+  if (a.outVariance) {
+    f3 alb = mk3(1.0f);
+    if (a.albedo) alb = mk3(a.albedo[p * 3], a.albedo[p * 3 + 1], a.albedo[p * 3 + 2]);
+    const f3 d = tpDivisor(a.albedo != nullptr, alb);
+    const float ld = dnLuma(d.x, d.y, d.z);
+    a.outVariance[p] = vAcc * (ld * ld);
+  }
 }

@@ -2150,33 +2150,43 @@ int yart_hip_denoise_atrous_var_host(const float* rgba, const float* variance, c
 }
 
 // Temporal accumulation (temporal_kernels.inc: k_tp_accumulate). The arguments are judged before any device is touched; the handle's
-// history — two images of three record planes, 96 bytes per pixel — is allocated by the first call that gets that far.
+// history — two images of three record planes, 96 bytes per pixel; four planes, 128 bytes, in the moments form — is allocated by
+// the first call that gets that far. A handle is in one form from its first accumulate to the next reset.
 }  // extern "C"
 struct YartTemporal {
   uint32_t width = 0, height = 0;
   int device = -1;                                  // < 0 until the first accumulate call: the device current then
   std::mutex mu;
-  DevBuf<f4> hist;                                  // image 0 (rec0 | rec1 | rec2 planes) | image 1
+  DevBuf<f4> hist;                                  // image 0 (rec0 | rec1 | rec2 (| rec3) planes) | image 1
+  bool moments = false;                             // the form of the history, while haveHistory
   uint32_t current = 0;                             // the image that holds the last frame's records
   bool haveHistory = false;
   YartCameraDesc camera{};                          // of the last accumulated frame
 };
 namespace {
 struct TpCall { TpConst k; bool demodulate; YartAovBuffers aovs; };
+uint32_t temporalMinMomentHistory(const YartTemporalParams&) { return 0u; }
+uint32_t temporalMinMomentHistory(const YartTemporalMomentParams& p) { return p.min_moment_history; }
+
+// Params: YartTemporalParams, or YartTemporalMomentParams (the same head, and min_moment_history)
+template <class Params>
 TpCall temporalCheck(const YartTemporal* t, const YartCameraDesc* cam, const void* rgba, const void* variance, const YartAovBuffers* aovs,
-                     const YartTemporalParams* params, const void* out) {
+                     const Params* params, const void* out) {
+  constexpr bool MOMENTS = std::is_same<Params, YartTemporalMomentParams>::value;
   require(t != nullptr, "temporal: handle pointer is null");
   require(cam != nullptr, "temporal: camera pointer is null");
   require(rgba && out, "temporal: rgba / out pointer is null");
   require(variance != nullptr, "temporal: variance pointer is null");
   require(aovs != nullptr, "temporal: feature buffers (aovs) pointer is null");
   require(params != nullptr, "temporal: params pointer is null");
-  require(params->struct_size >= sizeof(YartTemporalParams), "temporal: struct_size is smaller than YartTemporalParams");
+  require(params->struct_size >= sizeof(Params), MOMENTS ? "temporal: struct_size is smaller than YartTemporalMomentParams"
+                                                                 : "temporal: struct_size is smaller than YartTemporalParams");
   require((params->flags & ~uint32_t(YART_TEMPORAL_DEMODULATE)) == 0u, "temporal: unknown flags bits");
   require(std::isfinite(params->alpha_min) && std::isfinite(params->normal_cos_min) && std::isfinite(params->plane_tolerance),
           "temporal: a parameter is not finite");
   require(params->alpha_min >= 0.0f && params->alpha_min <= 1.0f, "temporal: alpha_min is outside [0, 1]");
   require(params->max_history >= 1u, "temporal: max_history is 0");
+  if (MOMENTS) require(temporalMinMomentHistory(*params) >= 2u, "temporal: min_moment_history is smaller than 2");
   require(cam->width == t->width && cam->height == t->height, "temporal: the camera's image size is not the handle's");
   require(cam->focal_length > 0.0f, "temporal: camera: bad focal length");
   TpCall c{};
@@ -2199,29 +2209,45 @@ TpCall temporalCheck(const YartTemporal* t, const YartCameraDesc* cam, const voi
   }
   c.k.alphaMin = params->alpha_min; c.k.normalCosMin = params->normal_cos_min; c.k.planeTolerance = params->plane_tolerance;
   c.k.maxHistory = params->max_history;
+  c.k.minMomentHistory = temporalMinMomentHistory(*params);
   c.k.width = t->width; c.k.height = t->height;
   return c;
 }
 
+// the handle's mutex held, before any device is touched
+template <bool MOMENTS>
+void temporalCheckForm(const YartTemporal& t) {
+  require(!t.haveHistory || t.moments == MOMENTS,
+          MOMENTS ? "temporal: the handle's history is in the plain form: reset it before the moments form"
+                  : "temporal: the handle's history is in the moments form: reset it before the plain form");
+}
+
 // device pointers (c.aovs included); the handle's device is current and its mutex held; returns after completion on `st`
+template <bool MOMENTS>
 void temporalRun(YartTemporal& t, TpCall c, const YartCameraDesc& cam, const float* rgba, const float* variance, float* out,
                  float* outVariance, uint32_t* outLength, hipStream_t st) {
   const uint32_t n = t.width * t.height;
-  t.hist.ensure(size_t(n) * 6);
+  constexpr size_t planes = MOMENTS ? 4 : 3;
+  t.hist.ensure(size_t(n) * planes * 2);
   c.k.haveHistory = t.haveHistory ? 1u : 0u;
   TpArgs a{};
   a.rgba = rgba; a.variance = variance; a.albedo = c.demodulate ? c.aovs.albedo : nullptr;
   a.position = c.aovs.position; a.normal = c.aovs.normal; a.depth = c.aovs.depth; a.coverage = c.aovs.coverage; a.ids = c.aovs.ids;
-  a.histIn = t.hist.p + size_t(t.current) * n * 3;
-  a.histOut = t.hist.p + size_t(t.current ^ 1u) * n * 3;
+  a.histIn = t.hist.p + size_t(t.current) * n * planes;
+  a.histOut = t.hist.p + size_t(t.current ^ 1u) * n * planes;
   a.outRgba = out; a.outVariance = outVariance; a.outLength = outLength;
   a.n = n; a.tilesX = (t.width + 15u) / 16u;
   a.k = c.k;
   if (t.haveHistory) a.cam = tpCamera(makeCamera(t.camera));
-  hipLaunchKernelGGL(k_tp_accumulate, dim3(a.tilesX * ((t.height + 15u) / 16u)), dim3(kBlock), 0, st, a);
+  const dim3 grid(a.tilesX * ((t.height + 15u) / 16u));
+  hipLaunchKernelGGL(k_tp_accumulate<MOMENTS>, grid, dim3(kBlock), 0, st, a);
   HIP_CHECK(hipGetLastError());
+  if (MOMENTS) {                                    // pass 2 on the image pass 1 wrote
+    hipLaunchKernelGGL(k_tp_spatial_variance, grid, dim3(kBlock), 0, st, a);
+    HIP_CHECK(hipGetLastError());
+  }
   HIP_CHECK(hipStreamSynchronize(st));
-  t.current ^= 1u; t.haveHistory = true; t.camera = cam;
+  t.current ^= 1u; t.haveHistory = true; t.moments = MOMENTS; t.camera = cam;
 }
 
 void temporalSelectDevice(YartTemporal& t) {
@@ -2258,23 +2284,28 @@ int yart_hip_temporal_reset(YartTemporal* temporal) {
   });
 }
 
-int yart_hip_temporal_accumulate_device(YartTemporal* temporal, const YartCameraDesc* cam, const float* d_rgba, const float* d_variance,
-                                        const YartAovBuffers* d_aovs, const YartTemporalParams* params, float* d_out_rgba,
-                                        float* d_out_variance, uint32_t* d_out_length, void* stream) {
+}  // extern "C"
+namespace {
+template <bool MOMENTS, class Params>
+int temporalAccumulateDevice(YartTemporal* temporal, const YartCameraDesc* cam, const float* d_rgba, const float* d_variance,
+                             const YartAovBuffers* d_aovs, const Params* params, float* d_out_rgba, float* d_out_variance,
+                             uint32_t* d_out_length, void* stream) {
   return guarded([&] {
     const TpCall c = temporalCheck(temporal, cam, d_rgba, d_variance, d_aovs, params, d_out_rgba);
     std::lock_guard<std::mutex> lock(temporal->mu);
+    temporalCheckForm<MOMENTS>(*temporal);
     temporalSelectDevice(*temporal);
-    temporalRun(*temporal, c, *cam, d_rgba, d_variance, d_out_rgba, d_out_variance, d_out_length, static_cast<hipStream_t>(stream));
+    temporalRun<MOMENTS>(*temporal, c, *cam, d_rgba, d_variance, d_out_rgba, d_out_variance, d_out_length, static_cast<hipStream_t>(stream));
   });
 }
 
-int yart_hip_temporal_accumulate_host(YartTemporal* temporal, const YartCameraDesc* cam, const float* rgba, const float* variance,
-                                      const YartAovBuffers* aovs, const YartTemporalParams* params, float* out_rgba,
-                                      float* out_variance, uint32_t* out_length) {
+template <bool MOMENTS, class Params>
+int temporalAccumulateHost(YartTemporal* temporal, const YartCameraDesc* cam, const float* rgba, const float* variance,
+                           const YartAovBuffers* aovs, const Params* params, float* out_rgba, float* out_variance, uint32_t* out_length) {
   return guarded([&] {
     TpCall c = temporalCheck(temporal, cam, rgba, variance, aovs, params, out_rgba);
     std::lock_guard<std::mutex> lock(temporal->mu);
+    temporalCheckForm<MOMENTS>(*temporal);
     temporalSelectDevice(*temporal);
     const size_t n = size_t(temporal->width) * temporal->height;
     // frame (4) | variance (1) | position (3) | normal (3) | depth (1) | coverage (1) | ids (4) | albedo (3) | length (1) words per pixel;
@@ -2293,11 +2324,38 @@ int yart_hip_temporal_accumulate_host(YartTemporal* temporal, const YartCameraDe
     c.aovs.coverage = put(c.aovs.coverage, 1); c.aovs.ids = reinterpret_cast<int32_t*>(put(c.aovs.ids, 4));
     c.aovs.albedo = put(c.demodulate ? c.aovs.albedo : nullptr, 3);
     uint32_t* dLen = reinterpret_cast<uint32_t*>(put(nullptr, 1));
-    temporalRun(*temporal, c, *cam, dFrame, dVar, dFrame, dVar, dLen, nullptr);
+    temporalRun<MOMENTS>(*temporal, c, *cam, dFrame, dVar, dFrame, dVar, dLen, nullptr);
     HIP_CHECK(hipMemcpy(out_rgba, dFrame, n * 16, hipMemcpyDeviceToHost));
     if (out_variance) HIP_CHECK(hipMemcpy(out_variance, dVar, n * 4, hipMemcpyDeviceToHost));
     if (out_length) HIP_CHECK(hipMemcpy(out_length, dLen, n * 4, hipMemcpyDeviceToHost));
   });
+}
+}  // namespace
+extern "C" {
+
+int yart_hip_temporal_accumulate_device(YartTemporal* temporal, const YartCameraDesc* cam, const float* d_rgba, const float* d_variance,
+                                        const YartAovBuffers* d_aovs, const YartTemporalParams* params, float* d_out_rgba,
+                                        float* d_out_variance, uint32_t* d_out_length, void* stream) {
+  return temporalAccumulateDevice<false>(temporal, cam, d_rgba, d_variance, d_aovs, params, d_out_rgba, d_out_variance, d_out_length, stream);
+}
+
+int yart_hip_temporal_accumulate_host(YartTemporal* temporal, const YartCameraDesc* cam, const float* rgba, const float* variance,
+                                      const YartAovBuffers* aovs, const YartTemporalParams* params, float* out_rgba,
+                                      float* out_variance, uint32_t* out_length) {
+  return temporalAccumulateHost<false>(temporal, cam, rgba, variance, aovs, params, out_rgba, out_variance, out_length);
+}
+
+int yart_hip_temporal_accumulate_moments_device(YartTemporal* temporal, const YartCameraDesc* cam, const float* d_rgba,
+                                                const float* d_variance, const YartAovBuffers* d_aovs,
+                                                const YartTemporalMomentParams* params, float* d_out_rgba, float* d_out_variance,
+                                                uint32_t* d_out_length, void* stream) {
+  return temporalAccumulateDevice<true>(temporal, cam, d_rgba, d_variance, d_aovs, params, d_out_rgba, d_out_variance, d_out_length, stream);
+}
+
+int yart_hip_temporal_accumulate_moments_host(YartTemporal* temporal, const YartCameraDesc* cam, const float* rgba, const float* variance,
+                                              const YartAovBuffers* aovs, const YartTemporalMomentParams* params, float* out_rgba,
+                                              float* out_variance, uint32_t* out_length) {
+  return temporalAccumulateHost<true>(temporal, cam, rgba, variance, aovs, params, out_rgba, out_variance, out_length);
 }
 
 int yart_hip_debug_counters(YartScene* scene, uint64_t* out32) {

@@ -6,6 +6,10 @@ every operation a float32 operation in the order the definition gives. It is wha
 ``csrc/temporal.hpp`` compiled for the host) to, bit for bit. :func:`camera_basis` restates the derived camera quantities
 (``csrc/host_scene.hpp`` makeCamera) the projection starts from. No libm: only + - * /, sqrt (correctly rounded), floor and
 comparisons.
+
+:func:`temporal_moments_reference` states the moments form (``yart_hip_temporal_accumulate_moments_*``): the same pass with the
+luminance moments and the sum of squared frame weights accumulated next to the colour, the temporal variance estimate they give,
+and the second pass that estimates the variance of the short pixels from their 7 x 7 neighbourhood.
 """
 from __future__ import annotations
 
@@ -17,6 +21,10 @@ DEFAULT_MAX_HISTORY = 8
 DEFAULT_NORMAL_COS_MIN = 0.8
 DEFAULT_PLANE_TOLERANCE = 0.01
 FLAG_DEMODULATE = 1
+# include/yart_hip.h: YART_TEMPORAL_DEFAULT_MIN_MOMENT_HISTORY (SVGF's value; profiles/temporal_moments_sweep.txt) and the half
+# width of the spatial estimate's window
+DEFAULT_MIN_MOMENT_HISTORY = 4
+SPATIAL_RADIUS = 3
 
 _F = np.float32
 _FLT_MAX = np.float32(3.4028235e38)
@@ -77,7 +85,8 @@ def camera_basis(cam):
 class TemporalHistory:
     """The state of a ``YartTemporal`` handle: the history records of the last accumulated frame — ``colour`` (H, W, 3),
     ``variance`` (H, W), ``position`` (H, W, 3), ``length`` (H, W) uint32, ``normal`` (H, W, 3), ``node`` (H, W) uint32 — and
-    that frame's camera; ``camera`` None: empty (a new handle, or after ``reset``)."""
+    that frame's camera; ``camera`` None: empty (a new handle, or after ``reset``). In the moments form also ``moments``
+    (H, W, 3): m1, m2 and w2 of the accumulated luminance. ``form``: "plain" or "moments" from the first frame after a reset."""
 
     def __init__(self, width, height):
         self.width, self.height = int(width), int(height)
@@ -86,6 +95,7 @@ class TemporalHistory:
     def reset(self):
         self.camera = None
         self.colour = self.variance = self.position = self.length = self.normal = self.node = None
+        self.moments = self.form = None
 
 
 def temporal_reference(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo=None,
@@ -95,6 +105,27 @@ def temporal_reference(history, cam, rgba, variance, position, normal, depth, co
     :func:`camera_fields`), ``rgba`` (H, W, 4), ``variance`` (H, W), ``position`` / ``normal`` (H, W, 3), ``depth`` / ``coverage``
     (H, W), ``ids`` (H, W, 4) int32, ``albedo`` (H, W, 3) or None. ``demodulate``: None = whenever an albedo buffer is given.
     Returns (accumulated frame (H, W, 4) float32, its variance (H, W) float32, history length (H, W) uint32)."""
+    return _accumulate(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo, alpha_min, max_history,
+                       normal_cos_min, plane_tolerance, demodulate, None)
+
+
+def temporal_moments_reference(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo=None,
+                               alpha_min=DEFAULT_ALPHA_MIN, max_history=DEFAULT_MAX_HISTORY,
+                               normal_cos_min=DEFAULT_NORMAL_COS_MIN, plane_tolerance=DEFAULT_PLANE_TOLERANCE,
+                               min_moment_history=DEFAULT_MIN_MOMENT_HISTORY, demodulate=None):
+    """One frame of the moments form; arguments and results as :func:`temporal_reference`, and ``min_moment_history`` (>= 2).
+    The history additionally carries ``moments``; a history is in one form from its first frame to the next ``reset``."""
+    assert int(min_moment_history) >= 2
+    return _accumulate(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo, alpha_min, max_history,
+                       normal_cos_min, plane_tolerance, demodulate, int(min_moment_history))
+
+
+def _accumulate(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo, alpha_min, max_history,
+                normal_cos_min, plane_tolerance, demodulate, min_moment_history):
+    """Pass 1 of both forms (``min_moment_history`` None: the plain form), then pass 2 of the moments form."""
+    moments = min_moment_history is not None
+    form = "moments" if moments else "plain"
+    assert history.camera is None or history.form == form, "the history is in the other form: reset it first"
     if demodulate is None:
         demodulate = albedo is not None
     if demodulate and albedo is None:
@@ -131,6 +162,7 @@ def temporal_reference(history, cam, rgba, variance, position, normal, depth, co
         wsum = np.zeros((h, w), _F)
         min_len = np.full((h, w), 0xffffffff, np.uint32)
         any_tap = np.zeros((h, w), bool)
+        acc_m = np.zeros((h, w, 3), _F)
         if history.camera is not None:
             # -- projection into the previous camera ----------------------------------------------------------------------
             k = camera_basis(history.camera)
@@ -162,6 +194,8 @@ def temporal_reference(history, cam, rgba, variance, position, normal, depth, co
                 counts &= np.abs(_dot(n, (pq - P).astype(_F))) <= tol
                 acc = np.where(counts[..., None], acc + wt[..., None] * history.colour[cy, cx], acc).astype(_F)
                 acc_v = np.where(counts, acc_v + wt * history.variance[cy, cx], acc_v).astype(_F)
+                if moments:
+                    acc_m = np.where(counts[..., None], acc_m + wt[..., None] * history.moments[cy, cx], acc_m).astype(_F)
                 wsum = np.where(counts, wsum + wt, wsum).astype(_F)
                 min_len = np.where(counts & (ln < min_len), ln, min_len)
                 any_tap |= counts
@@ -175,6 +209,18 @@ def temporal_reference(history, cam, rgba, variance, position, normal, depth, co
         b = _F(1.0) - a
         out_c = np.where(any_tap[..., None], hc + a[..., None] * (c - hc), c).astype(_F)
         out_v = np.where(any_tap, (a * a) * v + (b * b) * hv, v).astype(_F)
+        if moments:
+            # -- the luminance moments, the sum of squared frame weights, and the temporal estimate ---------------------------
+            y = _luma(c)
+            yy = y * y
+            hm = acc_m / wsum[..., None]
+            m1 = np.where(any_tap, hm[..., 0] + a * (y - hm[..., 0]), y).astype(_F)
+            m2 = np.where(any_tap, hm[..., 1] + a * (yy - hm[..., 1]), yy).astype(_F)
+            w2 = np.where(any_tap, (a * a) * _F(1.0) + (b * b) * hm[..., 2], _F(1.0)).astype(_F)
+            vt = m2 - m1 * m1
+            vt = np.where(vt > _F(0.0), vt, _F(0.0)).astype(_F)
+            long_ = (N >= np.uint32(min_moment_history)) & (w2 < _F(1.0))
+            out_v = np.where(long_, vt * (w2 / (_F(1.0) - w2)), out_v).astype(_F)
         out = np.empty((h, w, 4), _F)
         out[..., :3] = out_c * d
         out[..., 3] = rgba[..., 3]
@@ -192,4 +238,33 @@ def temporal_reference(history, cam, rgba, variance, position, normal, depth, co
         history.node = np.where(bad, np.uint32(0), node).astype(np.uint32)
         history.length = length.copy()
         history.camera = cam
+        history.form = form
+        if moments:
+            history.moments = np.where(bad[..., None], _F(0), np.stack([m1, m2, w2], -1)).astype(_F)
+            # -- pass 2: the short pixels' variance from their neighbourhood in the image pass 1 wrote ------------------------
+            short = ~bad & ~long_
+            tol = plane_tolerance * depth
+            s1, s2 = np.zeros((h, w), _F), np.zeros((h, w), _F)
+            cnt = np.zeros((h, w), np.uint32)
+            ys, xs = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+            hn, hp = history.normal, history.position
+            for dy in range(-SPATIAL_RADIUS, SPATIAL_RADIUS + 1):
+                for dx in range(-SPATIAL_RADIUS, SPATIAL_RADIUS + 1):
+                    qy, qx = ys + dy, xs + dx
+                    inside = (qx >= 0) & (qx < w) & (qy >= 0) & (qy < h)
+                    cy, cx = np.clip(qy, 0, h - 1), np.clip(qx, 0, w - 1)
+                    counts = short & inside & (history.length[cy, cx] >= 1) & (history.node[cy, cx] == history.node)
+                    counts &= _dot(hn, hn[cy, cx]) >= normal_cos_min
+                    counts &= np.abs(_dot(hn, (hp[cy, cx] - hp).astype(_F))) <= tol
+                    s1 = np.where(counts, s1 + history.moments[cy, cx, 0], s1).astype(_F)
+                    s2 = np.where(counts, s2 + history.moments[cy, cx, 1], s2).astype(_F)
+                    cnt = np.where(counts, cnt + np.uint32(1), cnt).astype(np.uint32)
+            kf = cnt.astype(_F)
+            e1, e2 = s1 / kf, s2 / kf
+            vs = e2 - e1 * e1
+            vs = np.where(vs > _F(0.0), vs, _F(0.0)).astype(_F)
+            spatial = short & (cnt >= 2)
+            v2 = (vs * (kf / (cnt - np.uint32(1)).astype(_F))) * history.moments[..., 2]
+            history.variance = np.where(spatial, v2, history.variance).astype(_F)
+            out_var = np.where(spatial, v2 * ld2, out_var).astype(_F)
     return out, out_var, length
