@@ -366,10 +366,9 @@ int renderMultiProgressive(YartMulti& m, const YartCameraDesc& cam, const YartRe
   const uint32_t n = uint32_t(m.scenes.size());
   const uint32_t stop = params.stop_sample ? params.stop_sample : params.samples;
   YartStats total{};
-  uint64_t remaining = params.samples, wave = 0;
-  uint64_t waveSamples = std::min<uint64_t>(params.first_wave_samples, params.samples);
-  while (waveSamples > 0 && !aborted) {
-    const uint32_t taken = uint32_t(params.samples - remaining);
+  for (WaveSchedule ws(params.samples, params.first_wave_samples, params.max_wave_samples); !aborted && ws.next();) {
+    const uint32_t taken = uint32_t(ws.takenBefore);
+    const uint64_t wave = ws.wave, waveSamples = ws.samples;
     if (taken >= params.start_sample && taken < stop) {
       YartRenderParams q = params;
       q.start_sample = taken; q.stop_sample = uint32_t(taken + waveSamples);
@@ -402,10 +401,6 @@ int renderMultiProgressive(YartMulti& m, const YartCameraDesc& cam, const YartRe
       if (!aborted && on_wave && on_wave(user, &st, uint32_t(wave), uint32_t(waveSamples), uint32_t(taken + waveSamples), params.samples) != 0)
         aborted = true;
     }
-    remaining -= waveSamples;
-    const uint64_t next = (wave > 0 || waveSamples > 1) ? std::min<uint64_t>(waveSamples * 2, params.max_wave_samples) : 1;
-    waveSamples = std::min(next, remaining);
-    wave++;
   }
   total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
   if (stats) *stats = total;

@@ -13,9 +13,9 @@
 //   k_gmon_blend    one wave = one pixel: bucket sums in sample order, GMoN value,
 //                   blend into the HDR buffer (integrator.cpp:17-25, tile-renderer.hpp:220-232).
 //   k_probe_*       diagnostics used by the parity tests.
-// The wavefront (queue-based) pipeline lives in wavefront.hip.inc.
-// This file is compiled four times (csrc/Makefile), YART_TU selecting what a translation unit emits — the kernels are templates and
-// instantiate where they are referenced, so the four objects build in parallel and each holds a quarter of the device code:
+// The wavefront (queue-based) pipeline lives in wavefront_kernels.inc.
+// This file is compiled five times (csrc/Makefile), YART_TU selecting what a translation unit emits — the kernels are templates and
+// instantiate where they are referenced, so the five objects build in parallel and each holds its share of the device code:
 //   0  the C ABI, host orchestration, and every kernel not named below (streaming passes, megakernel, probes, BVH build)
 //   1  the lean closest-hit kernels k_wf_extend_lean<MODE, NODES>          2  the lean any-hit kernels k_wf_shadow_lean<MODE, NODES>
 //   3  the general kernels: retry (resumed walks), one-ray-per-lane lean and general forms        4  the shade kernel k_wf_shade<SORT, FIT, ENV1>
@@ -469,6 +469,7 @@ unsigned long long YART_CAT(texTapRead, YART_TU)() { unsigned long long v = 0; (
 #else  // YART_TU == 0: everything below
 
 }  // namespace
+#include "render_host.hpp"     // (host only: the wave schedule and the buffer tables)
 namespace yart_hip { namespace tu {
 typedef void (*AnyKernel)();
 AnyKernel extendLean(int nodesForm, bool ident);
@@ -726,110 +727,60 @@ struct StageTimer {
     used = 0;
   }
 };
+// The stopwatches of a render: the megakernel; the extend, shade (every streaming pass of the wavefront pipelines) and connect
+// stages; the estimator; and inside those stages the lean closest-hit kernel, the shade kernel and the lean any-hit kernel alone.
+struct StageTimers {
+  StageTimer mega, extend, shade, connect, gmon, lean, shadeK, shadowLean;
+  void resolveAll() { for (StageTimer* t : {&mega, &extend, &shade, &connect, &gmon, &lean, &shadeK, &shadowLean}) t->resolve(); }
+};
 
 // Called after every batch of a wave, once its pixels are final for that wave in the output frame (the stream has been
 // synchronised): the range [c0, c0 + n) of this rank's pixel list. Returning true stops the render after this batch.
 struct BatchInfo { uint32_t c0, n, wave, waveSamples, samplesTaken, totalSamples; };
 typedef std::function<bool(const BatchInfo&)> BatchHook;
 
-// aov: feature buffers to fill as well (device pointers, checked by checkAovs; nullptr: none — nothing below differs from a plain render then)
-// mom: sample moments to fill as well (device pointers, checked by checkMoments; nullptr: none, and nothing below differs either)
-bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRenderParams& p, float* dOut,
-                    hipStream_t stream, YartStats* stats, const BatchHook* hook = nullptr, const YartAovBuffers* aov = nullptr,
-                    const YartMomentBuffers* mom = nullptr) {
-  bool aborted = false;
-  auto wall0 = std::chrono::high_resolution_clock::now();
-  TraceRange rgRender("yart:render");
-  HIP_CHECK(hipSetDevice(s.device));
-  const uint32_t W = camDesc.width, H = camDesc.height;
-  const CameraDev cam = makeCamera(camDesc);
-  const RenderConst rc = makeRenderConst(p);
-  const bool mega = (p.flags & YART_FLAG_MEGAKERNEL) != 0;
-  uint32_t effFlags = p.flags;              // after the defaults (reported in YartStats::pipeline_flags)
-  if (!mega && !(effFlags & YART_FLAG_NO_SHADE_SORT)) effFlags |= YART_FLAG_SHADE_SORT;
-  buildPixelList(s, W, H, p.shard_tile ? p.shard_tile : p.tile_size, p.rank, p.world_size);
-  const uint32_t nPix = uint32_t(s.pixelsHost.size());
+// Everything a render decides before its first wave (makeRenderPlan); the buffers are allocated from it (prepareBuffers) and the
+// batch runners launch from it.
+// aov: feature buffers to fill as well (device pointers, checked by checkAovs; nullptr: none — nothing differs from a plain render then)
+// mom: sample moments to fill as well (device pointers, checked by checkMoments; nullptr: none, and nothing differs either)
+struct RenderPlan {
+  const YartRenderParams* p;
+  const YartAovBuffers* aov;
+  const YartMomentBuffers* mom;
+  uint32_t W, H, nPix;
+  CameraDev cam;
+  RenderConst rc, rcw;                       // rcw: rc with the sampler tables of this render (launchSamplerTables), for the wavefront kernels
+  uint32_t effFlags;                         // after the defaults (reported in YartStats::pipeline_flags)
+  bool mega, pool, compact, general, refill, samplerTables;
+  int nodesForm;
+  uint32_t nodeBitWords;
+  void (*kMega)(MegaArgs);
+  WfKernelFn kExtendFast, kShadowFast, kRetryE, kRetryS, kExtendGen, kExtendGenRetry, kShadowGen, kShadowGenRetry, kShade;
+  int gridMega, gridExtendFast, gridShadowFast, gridExtend, gridShadow, gridShade, gridRetryE, gridRetryS, gridMax;
+  uint32_t chunk, waveCap;                   // pixels per batch; the largest wave of the schedule
+  size_t aovStride;                          // paths of the largest batch: L, and each feature record array of the megakernel / path pool
+  size_t slots;                              // wavefront pipelines: path slots (the batch's paths, or the pool's slots)
+  uint32_t poolSlots, resumeCap;
+};
 
-  const uint64_t startSample = p.start_sample, stopSample = p.stop_sample ? p.stop_sample : p.samples;
-  if (startSample == 0) HIP_CHECK(hipMemsetAsync(dOut, 0, size_t(W) * H * 4 * sizeof(float), stream));
-  s.cursor.ensure(1); s.counters.ensure(kNumCounters); s.pathsLog.ensure(16);
-  HIP_CHECK(hipMemsetAsync(s.pathsLog.p, 0, 16 * sizeof(unsigned long long), stream));
-  HIP_CHECK(hipMemsetAsync(s.counters.p, 0, kNumCounters * sizeof(unsigned long long), stream));
-#if defined(YART_COUNT_TRAVERSAL)
-  { const unsigned long long zero = 0; HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_texTapBytes), &zero, sizeof(zero))); tu::texTapReset1(); tu::texTapReset2(); tu::texTapReset3(); tu::texTapReset4(); }
-#endif
-
-  // lean traversal kernels when the scene allows them (every node transform chain the identity ->
-  // identity-only variant); YART_FLAG_GENERAL_TRACE forces the general kernels for everything
-  const bool general = (p.flags & YART_FLAG_GENERAL_TRACE) != 0;
-  const bool ident = s.host.allIdentity;
-  const bool refill = (p.flags & YART_FLAG_NO_REFILL) == 0;
-  // trace_lean.hpp keeps one 64-bit node candidate mask per ray and uses the all-ones mask as its "new ray"
-  // marker, which a ray that can reach all of exactly 64 nodes would keep: 64 nodes and more go to the chunked form
-  const bool chunked = s.host.nodes.size() >= 64;
-  // 64 nodes and more: candidate windows from the top-level hierarchy (3; measured the fastest form at every size from 65 to 4252
-  // nodes, profiles/r2_many_nodes.txt). Without it (no mesh nodes, more than 16384 nodes = 2 KB of bitset per lane, or debug bit
-  // 262144): chunked masks below kLeanWalkNodes nodes, the per-lane walk from there on (debug bit 65536: the walk at any size)
-  const bool tlasOk = s.dev.nTlas != 0u && s.host.nodes.size() <= 16384u && !(effFlags & (262144u | 65536u));
-  const bool leanLds = !chunked && s.host.nodes.size() <= kLeanSceneNodes && s.host.meshes.size() <= kLeanSceneNodes;
-  const int nodesForm = !chunked ? (leanLds ? 4 : 0) : tlasOk ? 3 : ((effFlags & 65536u) || s.host.nodes.size() >= kLeanWalkNodes) ? 2 : 1;
-  auto pickExtend = [&]() -> void (*)(WfArgs) {
-    if (!refill) return wfKernel(tu::extendFast(ident));
-    return wfKernel(tu::extendLean(nodesForm, ident));
-  };
-  auto pickShadow = [&]() -> void (*)(WfArgs) {
-    if (!refill) return wfKernel(tu::shadowFast(ident));
-    return wfKernel(tu::shadowLean(nodesForm, ident));
-  };
-  auto kExtendFast = pickExtend();
-  auto kShadowFast = pickShadow();
-  auto kRetryE = wfKernel(tu::extendRetry(nodesForm));
-  auto kRetryS = wfKernel(tu::shadowRetry(nodesForm));
-  auto kExtendGen = wfKernel(tu::extendGeneral(false)), kExtendGenRetry = wfKernel(tu::extendGeneral(true));
-  auto kShadowGen = wfKernel(tu::shadowGeneral(false)), kShadowGenRetry = wfKernel(tu::shadowGeneral(true));
-  const auto kMega = aov ? k_render_mega<true> : k_render_mega<false>;
-  const int gridMega = persistentGrid(s, reinterpret_cast<const void*>(kMega), 3);
-  const int gridExtendFast = persistentGrid(s, reinterpret_cast<const void*>(kExtendFast), 8);
-  const int gridShadowFast = persistentGrid(s, reinterpret_cast<const void*>(kShadowFast), 8);
-  const int gridExtend = persistentGrid(s, reinterpret_cast<const void*>(kExtendGen), 8);
-  const int gridShadow = persistentGrid(s, reinterpret_cast<const void*>(kShadowGen), 8);
-  // the shade kernel's LDS copies of the scene's small tables: FIT when the sampler tables are in use (below) and every table fits its slot
-  const bool samplerTables = !mega && !(p.flags & YART_FLAG_DIRECT_SAMPLER) && nPix > 0 && uint64_t(p.samples) <= (1ull << rc.sampler.log2spp);
-  const bool shadeFit = samplerTables && s.dev.nMaterials <= kShadeMatSlots && s.dev.nTextures <= kShadeTexSlots && s.dev.nLights <= kShadeLightSlots &&
-                        s.dev.nEnvs <= kShadeEnvSlots && s.dev.nNodes <= kShadeNodeSlots && s.dev.nInfinite <= kShadeLightSlots;
-  const bool envOnly = shadeFit && s.dev.nArea == 0u && s.dev.nInfinite == 1u && s.dev.nLights == 1u;    // (variant of the FIT kernels only)
-  auto kShade = wfKernel(tu::shade((effFlags & YART_FLAG_SHADE_SORT) != 0, shadeFit, envOnly));
-  const int gridShade = persistentGrid(s, reinterpret_cast<const void*>(kShade), 8, kShadeBlock);
-  const int gridRetryE = persistentGrid(s, reinterpret_cast<const void*>(kRetryE), 8);
-  const int gridRetryS = persistentGrid(s, reinterpret_cast<const void*>(kRetryS), 8);
-  int gridMax = std::max(gridMega, std::max(gridExtend, gridShadow));
-  gridMax = std::max(gridMax, std::max(gridExtendFast, gridShadowFast));
-  gridMax = std::max(gridMax, std::max(gridRetryE, gridRetryS));
-  s.spill.ensure(size_t(gridMax) * kBlock * spillDepthFor(s.host, true));
-  // the lanes' node bitsets of the top-level-hierarchy form (trace_lean_tlas.hpp): all zero between launches
-  const uint32_t nodeBitWords = nodesForm == 3 ? uint32_t((s.host.nodes.size() + 63u) / 64u) : 0u;
-  if (nodeBitWords) {
-    const size_t need = size_t(gridMax) * kBlock * nodeBitWords;
-    if (s.nodeBits.n < need) { s.nodeBits.ensure(need); HIP_CHECK(hipMemsetAsync(s.nodeBits.p, 0, need * 8, stream)); }
-  }
-
-  // Batch = the pixels (x all samples of a wave) rendered together: max_batch_paths, by default kDefaultBatchPaths — a fixed
-  // number, no longer a share of the free device memory (round 3 sized ONE batch to 60 % of it: 150 GB for the C3 frame); only if
-  // that does not fit the device is it cut down to what does. The default pipeline is batch-synchronous: one slot per path of the
-  // batch (251 bytes with the compacted tail state), every bounce one launch per stage over the paths still alive. What a smaller
-  // batch costs (profiles/r4_ab_path_pool.txt): ~10 ms per batch of any size — the tail of every launch, when the GPU waits for
-  // the slowest rays of the last waves — so the C3 frame in 2 / 4 / 8 / 16 batches is 1.4 / 4.5 / 9.7 / 19 % slower than in one.
-  // YART_FLAG_PATH_POOL: the batch runs through a POOL of pool_paths slots with path regeneration instead (168 bytes per slot +
-  // 16 per path of the batch): bounded memory at any frame size, every launch pool-sized until the batch runs out — and ~25 %
-  // slower on the C3 frame, because a wave's lanes then hold paths of every generation (same file).
-  const uint32_t maxWave = std::min(p.max_wave_samples, p.samples);
-  const uint32_t waveCap = std::max(std::min(p.first_wave_samples, p.samples), maxWave);
-  const bool pool = !mega && (p.flags & YART_FLAG_PATH_POOL) != 0;
-  uint32_t resumeCap = 0;
-  const bool compact = !mega && !pool && !(p.flags & YART_FLAG_NO_COMPACTION);
+// Batch = the pixels (x all samples of a wave) rendered together: max_batch_paths, by default kDefaultBatchPaths — a fixed
+// number, no longer a share of the free device memory (round 3 sized ONE batch to 60 % of it: 150 GB for the C3 frame); only if
+// that does not fit the device is it cut down to what does. The default pipeline is batch-synchronous: one slot per path of the
+// batch (251 bytes with the compacted tail state), every bounce one launch per stage over the paths still alive. What a smaller
+// batch costs (profiles/r4_ab_path_pool.txt): ~10 ms per batch of any size — the tail of every launch, when the GPU waits for
+// the slowest rays of the last waves — so the C3 frame in 2 / 4 / 8 / 16 batches is 1.4 / 4.5 / 9.7 / 19 % slower than in one.
+// YART_FLAG_PATH_POOL: the batch runs through a POOL of pool_paths slots with path regeneration instead (168 bytes per slot +
+// 16 per path of the batch): bounded memory at any frame size, every launch pool-sized until the batch runs out — and ~25 %
+// slower on the C3 frame, because a wave's lanes then hold paths of every generation (same file).
+// Returns the paths a batch may hold and — path pool — the slots the device can hold next to the batch's radiance records.
+// Reads the plan's switches, grids and waveCap; the traversal scratch has been allocated (the free memory is looked at here).
+struct BatchBudget { uint64_t maxPaths, poolFit; };
+BatchBudget batchBudget(const YartScene& s, const RenderPlan& pl) {
+  const YartRenderParams& p = *pl.p;
+  const uint32_t nPix = pl.nPix;
   uint64_t maxPaths = p.max_batch_paths ? p.max_batch_paths : kDefaultBatchPaths;
   uint64_t poolFit = ~0ull;                     // path pool: the slots the device can hold next to the batch's radiance records
-  if (!mega) {
+  if (!pl.mega) {
     // (safety only: a device that cannot hold the batch renders smaller ones)
     size_t freeB = 0, totalB = 0;
     HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
@@ -845,421 +796,554 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
     // a tail state of 1/2 of the batch (9 x 16 B + a slot map word) and a slot map of 1/4 = 75 B more; the resume records of an eighth of
     // the paths (kResumeWords x 16 B each = 24 B per path). What does not: the sampler tables (8 B x dims per PIXEL of the rank),
     // the resume records' per-wave ranges and the traversal spill area — taken off the budget first.
-    const uint64_t perPath = (compact ? 251 : 176) + ((p.flags & YART_FLAG_NO_RESUME) ? 0 : (kResumeWords * 16 + 7) / 8);
+    const uint64_t perPath = (pl.compact ? 251 : 176) + ((p.flags & YART_FLAG_NO_RESUME) ? 0 : (kResumeWords * 16 + 7) / 8);
     const uint64_t dimsEst = std::min<uint32_t>(256u, (4u + 8u * p.max_depth + 16u + 7u) & ~7u);
-    const uint64_t fixedB = uint64_t(nPix) * dimsEst * 8 + uint64_t(gridMax) * kBlock * (kResumeWords * 16 + uint64_t(spillDepthFor(s.host, true)) * 8) +
-                            (mom ? uint64_t(nPix) * sizeof(MomentState) : 0u);      // (sample moments: 48 B per pixel of the rank)
+    const uint64_t fixedB = uint64_t(nPix) * dimsEst * 8 + uint64_t(pl.gridMax) * kBlock * (kResumeWords * 16 + uint64_t(spillDepthFor(s.host, true)) * 8) +
+                            (pl.mom ? uint64_t(nPix) * sizeof(MomentState) : 0u);      // (sample moments: 48 B per pixel of the rank)
     const uint64_t budget = (uint64_t(freeB) + held) * 8 / 10;
     const uint64_t avail = budget > fixedB ? budget - fixedB : 0;
-    if (!pool) {
+    if (!pl.pool) {
       const uint64_t fits = std::max<uint64_t>(avail / perPath, 1u << 16);
       maxPaths = std::min<uint64_t>(std::min<uint64_t>(maxPaths, fits), kWfMaxPaths);
     } else {
       // pool: 16 B of radiance per path of the batch + 168 B (+ resume records) per slot of the pool: the batch gets at most half
       // of the budget, the pool what is left
       // (feature buffers: + 48 B of feature record per path of the batch; the default pipeline keeps its records in the shadow-ray arrays)
-      const uint64_t perBatchPath = aov ? 16 + 48 : 16;
+      const uint64_t perBatchPath = pl.aov ? 16 + 48 : 16;
       const uint64_t fits = std::max<uint64_t>(avail / 2 / perBatchPath, 1u << 16);
       maxPaths = std::min<uint64_t>(maxPaths, fits);
-      const uint64_t left = avail > std::min<uint64_t>(maxPaths, uint64_t(nPix ? nPix : 1) * waveCap) * perBatchPath ? avail - std::min<uint64_t>(maxPaths, uint64_t(nPix ? nPix : 1) * waveCap) * perBatchPath : 0;
+      const uint64_t left = avail > std::min<uint64_t>(maxPaths, uint64_t(nPix ? nPix : 1) * pl.waveCap) * perBatchPath ? avail - std::min<uint64_t>(maxPaths, uint64_t(nPix ? nPix : 1) * pl.waveCap) * perBatchPath : 0;
       poolFit = std::max<uint64_t>(left / (176 + (kResumeWords * 16 + 7) / 8), 64);
     }
   }
-  maxPaths = std::min<uint64_t>(maxPaths, (1ull << 31) - 64);
-  uint32_t chunk = uint32_t(std::min<uint64_t>(nPix ? nPix : 1, std::max<uint64_t>(maxPaths / waveCap, 1)));
-  if (nPix > chunk) {                            // batches of equal size (the last one is not a sliver)
-    const uint32_t nb = (nPix + chunk - 1) / chunk;
-    chunk = (nPix + nb - 1) / nb;
+  return {std::min<uint64_t>(maxPaths, (1ull << 31) - 64), poolFit};
+}
+
+// The pixel list of the rank is built (buildPixelList). Allocates the traversal scratch the chosen grids need — spill area and
+// node bitsets, before the batch budget looks at the free memory — and nothing else.
+RenderPlan makeRenderPlan(YartScene& s, const YartCameraDesc& camDesc, const YartRenderParams& p, const YartAovBuffers* aov,
+                          const YartMomentBuffers* mom, hipStream_t stream) {
+  RenderPlan pl{};
+  pl.p = &p; pl.aov = aov; pl.mom = mom;
+  pl.W = camDesc.width; pl.H = camDesc.height; pl.nPix = uint32_t(s.pixelsHost.size());
+  pl.cam = makeCamera(camDesc);
+  pl.rc = pl.rcw = makeRenderConst(p);
+  pl.mega = (p.flags & YART_FLAG_MEGAKERNEL) != 0;
+  pl.effFlags = p.flags;
+  if (!pl.mega && !(pl.effFlags & YART_FLAG_NO_SHADE_SORT)) pl.effFlags |= YART_FLAG_SHADE_SORT;
+
+  // lean traversal kernels when the scene allows them (every node transform chain the identity ->
+  // identity-only variant); YART_FLAG_GENERAL_TRACE forces the general kernels for everything
+  pl.general = (p.flags & YART_FLAG_GENERAL_TRACE) != 0;
+  const bool ident = s.host.allIdentity;
+  pl.refill = (p.flags & YART_FLAG_NO_REFILL) == 0;
+  // trace_lean.hpp keeps one 64-bit node candidate mask per ray and uses the all-ones mask as its "new ray"
+  // marker, which a ray that can reach all of exactly 64 nodes would keep: 64 nodes and more go to the chunked form
+  const bool chunked = s.host.nodes.size() >= 64;
+  // 64 nodes and more: candidate windows from the top-level hierarchy (3; measured the fastest form at every size from 65 to 4252
+  // nodes, profiles/r2_many_nodes.txt). Without it (no mesh nodes, more than 16384 nodes = 2 KB of bitset per lane, or debug bit
+  // 262144): chunked masks below kLeanWalkNodes nodes, the per-lane walk from there on (debug bit 65536: the walk at any size)
+  const bool tlasOk = s.dev.nTlas != 0u && s.host.nodes.size() <= 16384u && !(pl.effFlags & (262144u | 65536u));
+  const bool leanLds = !chunked && s.host.nodes.size() <= kLeanSceneNodes && s.host.meshes.size() <= kLeanSceneNodes;
+  pl.nodesForm = !chunked ? (leanLds ? 4 : 0) : tlasOk ? 3 : ((pl.effFlags & 65536u) || s.host.nodes.size() >= kLeanWalkNodes) ? 2 : 1;
+  pl.kExtendFast = wfKernel(pl.refill ? tu::extendLean(pl.nodesForm, ident) : tu::extendFast(ident));
+  pl.kShadowFast = wfKernel(pl.refill ? tu::shadowLean(pl.nodesForm, ident) : tu::shadowFast(ident));
+  pl.kRetryE = wfKernel(tu::extendRetry(pl.nodesForm));
+  pl.kRetryS = wfKernel(tu::shadowRetry(pl.nodesForm));
+  pl.kExtendGen = wfKernel(tu::extendGeneral(false)); pl.kExtendGenRetry = wfKernel(tu::extendGeneral(true));
+  pl.kShadowGen = wfKernel(tu::shadowGeneral(false)); pl.kShadowGenRetry = wfKernel(tu::shadowGeneral(true));
+  pl.kMega = aov ? k_render_mega<true> : k_render_mega<false>;
+  pl.gridMega = persistentGrid(s, reinterpret_cast<const void*>(pl.kMega), 3);
+  pl.gridExtendFast = persistentGrid(s, reinterpret_cast<const void*>(pl.kExtendFast), 8);
+  pl.gridShadowFast = persistentGrid(s, reinterpret_cast<const void*>(pl.kShadowFast), 8);
+  pl.gridExtend = persistentGrid(s, reinterpret_cast<const void*>(pl.kExtendGen), 8);
+  pl.gridShadow = persistentGrid(s, reinterpret_cast<const void*>(pl.kShadowGen), 8);
+  // the shade kernel's LDS copies of the scene's small tables: FIT when the sampler tables are in use and every table fits its slot
+  // sampler tables (sampler.hpp::SamplerTables) for the wavefront pipeline; they require every
+  // sample index to fit the sampler's log2spp bits (log2Int rounds to nearest, e.g. 90 spp -> 6)
+  pl.samplerTables = !pl.mega && !(p.flags & YART_FLAG_DIRECT_SAMPLER) && pl.nPix > 0 && uint64_t(p.samples) <= (1ull << pl.rc.sampler.log2spp);
+  const bool shadeFit = pl.samplerTables && s.dev.nMaterials <= kShadeMatSlots && s.dev.nTextures <= kShadeTexSlots && s.dev.nLights <= kShadeLightSlots &&
+                        s.dev.nEnvs <= kShadeEnvSlots && s.dev.nNodes <= kShadeNodeSlots && s.dev.nInfinite <= kShadeLightSlots;
+  const bool envOnly = shadeFit && s.dev.nArea == 0u && s.dev.nInfinite == 1u && s.dev.nLights == 1u;    // (variant of the FIT kernels only)
+  pl.kShade = wfKernel(tu::shade((pl.effFlags & YART_FLAG_SHADE_SORT) != 0, shadeFit, envOnly));
+  pl.gridShade = persistentGrid(s, reinterpret_cast<const void*>(pl.kShade), 8, kShadeBlock);
+  pl.gridRetryE = persistentGrid(s, reinterpret_cast<const void*>(pl.kRetryE), 8);
+  pl.gridRetryS = persistentGrid(s, reinterpret_cast<const void*>(pl.kRetryS), 8);
+  pl.gridMax = std::max(pl.gridMega, std::max(pl.gridExtend, pl.gridShadow));
+  pl.gridMax = std::max(pl.gridMax, std::max(pl.gridExtendFast, pl.gridShadowFast));
+  pl.gridMax = std::max(pl.gridMax, std::max(pl.gridRetryE, pl.gridRetryS));
+  s.spill.ensure(size_t(pl.gridMax) * kBlock * spillDepthFor(s.host, true));
+  // the lanes' node bitsets of the top-level-hierarchy form (trace_lean_tlas.hpp): all zero between launches
+  pl.nodeBitWords = pl.nodesForm == 3 ? uint32_t((s.host.nodes.size() + 63u) / 64u) : 0u;
+  if (pl.nodeBitWords) {
+    const size_t need = size_t(pl.gridMax) * kBlock * pl.nodeBitWords;
+    if (s.nodeBits.n < need) { s.nodeBits.ensure(need); HIP_CHECK(hipMemsetAsync(s.nodeBits.p, 0, need * 8, stream)); }
   }
-  s.L.ensure(size_t(chunk) * waveCap);
-  // feature buffers: per-pixel accumulators (zero; ids -1), the caller's buffers cleared as the frame is, and — megakernel / path pool —
-  // the record arrays of the batch
-  const size_t aovStride = size_t(chunk) * waveCap;
-  if (aov) {
-    const size_t np1 = std::max<uint32_t>(nPix, 1u), wh = size_t(W) * H;
-    for (auto& b : s.aovAcc) { b.ensure(np1); HIP_CHECK(hipMemsetAsync(b.p, 0, np1 * sizeof(f4), stream)); }
-    s.aovRays.ensure(np1); HIP_CHECK(hipMemsetAsync(s.aovRays.p, 0, np1 * sizeof(uint32_t), stream));
-    s.aovIds.ensure(np1 * 4); HIP_CHECK(hipMemsetAsync(s.aovIds.p, 0xff, np1 * 4 * sizeof(int32_t), stream));
-    s.pixRays.ensure(np1);
-    if (mega || pool) s.aovRec.ensure(3 * aovStride);
-    if (aov->mask & YART_AOV_ALBEDO) HIP_CHECK(hipMemsetAsync(aov->albedo, 0, wh * 3 * sizeof(float), stream));
-    if (aov->mask & YART_AOV_NORMAL) HIP_CHECK(hipMemsetAsync(aov->normal, 0, wh * 3 * sizeof(float), stream));
-    if (aov->mask & YART_AOV_POSITION) HIP_CHECK(hipMemsetAsync(aov->position, 0, wh * 3 * sizeof(float), stream));
-    if (aov->mask & YART_AOV_DEPTH) HIP_CHECK(hipMemsetAsync(aov->depth, 0, wh * sizeof(float), stream));
-    if (aov->mask & YART_AOV_COVERAGE) HIP_CHECK(hipMemsetAsync(aov->coverage, 0, wh * sizeof(float), stream));
-    if (aov->mask & YART_AOV_IDS) HIP_CHECK(hipMemsetAsync(aov->ids, 0xff, wh * 4 * sizeof(int32_t), stream));
-    if (aov->mask & YART_AOV_RAYS) HIP_CHECK(hipMemsetAsync(aov->rays, 0, wh * sizeof(uint32_t), stream));
+
+  const uint32_t maxWave = std::min(p.max_wave_samples, p.samples);
+  pl.waveCap = std::max(std::min(p.first_wave_samples, p.samples), maxWave);
+  pl.pool = !pl.mega && (p.flags & YART_FLAG_PATH_POOL) != 0;
+  pl.compact = !pl.mega && !pl.pool && !(p.flags & YART_FLAG_NO_COMPACTION);
+  const BatchBudget fit = batchBudget(s, pl);
+  pl.chunk = uint32_t(std::min<uint64_t>(pl.nPix ? pl.nPix : 1, std::max<uint64_t>(fit.maxPaths / pl.waveCap, 1)));
+  if (pl.nPix > pl.chunk) {                      // batches of equal size (the last one is not a sliver)
+    const uint32_t nb = (pl.nPix + pl.chunk - 1) / pl.chunk;
+    pl.chunk = (pl.nPix + nb - 1) / nb;
   }
-  // sample moments: the running state per pixel of the rank (zero), the caller's buffers cleared as the frame is
-  if (mom) {
-    const size_t np1 = std::max<uint32_t>(nPix, 1u), wh = size_t(W) * H;
-    s.momState.ensure(np1); HIP_CHECK(hipMemsetAsync(s.momState.p, 0, np1 * sizeof(MomentState), stream));
-    if (mom->mask & YART_MOMENT_MEAN) HIP_CHECK(hipMemsetAsync(mom->mean, 0, wh * 3 * sizeof(float), stream));
-    if (mom->mask & YART_MOMENT_VARIANCE) HIP_CHECK(hipMemsetAsync(mom->variance, 0, wh * sizeof(float), stream));
-    if (mom->mask & YART_MOMENT_COUNT) HIP_CHECK(hipMemsetAsync(mom->count, 0, wh * sizeof(uint32_t), stream));
-  }
-  uint32_t poolSlots = 0;
-  if (!mega) {
-    const size_t npBatch = size_t(chunk) * waveCap;
-    size_t np = npBatch;
-    if (pool) {
-      const size_t want = std::min<uint64_t>(p.pool_paths ? p.pool_paths : kDefaultPoolPaths, poolFit);
-      np = std::max<size_t>(64, (std::min(want, npBatch) + 63) & ~size_t(63));
-      poolSlots = uint32_t(np);
-      s.poolMap.ensure(np);
-      if (!s.poolHost) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.poolHost), kPoolLag * WC_COUNT * sizeof(uint32_t)));
+  pl.aovStride = size_t(pl.chunk) * pl.waveCap;
+  if (!pl.mega) {
+    pl.slots = pl.aovStride;
+    if (pl.pool) {
+      const size_t want = std::min<uint64_t>(p.pool_paths ? p.pool_paths : kDefaultPoolPaths, fit.poolFit);
+      pl.slots = std::max<size_t>(64, (std::min(want, pl.aovStride) + 63) & ~size_t(63));
+      pl.poolSlots = uint32_t(pl.slots);
     }
-    for (auto& b : s.wf) b.ensure(np);
-    if (compact) {
-      // Two dense "tail" states take the survivors in turn: the first is an array set of half the batch; the second is the BATCH-SIZED
-      // state itself — by the time a second compaction happens the paths live in the first tail and the large arrays hold nothing
-      // that is still read, so the survivors go back to their front (round 5: 36 B per path less than a third array set).
-      for (auto& b : s.wfTail[0]) b.ensure(np / 2 + 64);
-      s.wfTailMap[0].ensure(np / 2 + 64);
-      s.wfTailMap[1].ensure(np / 4 + 64);
-      s.wfDyn.ensure(1);
-    }
-    s.qA.ensure(np); s.qB.ensure(np); s.qS.ensure(np); s.qR.ensure(np); s.wfCounters.ensure(WC_COUNT);
     // resume records of the rays the lean kernels hand to the general ones (traverse.hpp: 192 B each): room for an eighth of
     // the slots (C3 hands over 6-7 % of its rays; a ray that finds no record is restarted, as all of them were before).
     // YART_RESUME_CAP: records (tests of the fallback), 0 = restarts only.
     if (!(p.flags & YART_FLAG_NO_RESUME)) {
       // (+ one range of 64 per wave of the largest grid: a wave takes its records 64 at a time and may leave a range unfinished)
-      size_t cap = std::max<size_t>(np / 8, std::min<size_t>(np, 1u << 16)) + size_t(gridMax) * kBlock;
+      size_t cap = std::max<size_t>(pl.slots / 8, std::min<size_t>(pl.slots, 1u << 16)) + size_t(pl.gridMax) * kBlock;
       if (const char* e = std::getenv("YART_RESUME_CAP")) cap = size_t(std::max<long long>(0, std::atoll(e)));
-      cap = std::min<size_t>(cap, 0x7fffff00u);
-      if (cap) s.resumeRec.ensure(cap * kResumeWords);
-      resumeCap = uint32_t(cap);
+      pl.resumeCap = uint32_t(std::min<size_t>(cap, 0x7fffff00u));
     }
   }
+  return pl;
+}
 
-  Timer tAll;
-  StageTimer tMega, tExtend, tShade, tConnect, tGmon, tLean, tShadeK, tShadowLean;
-  uint32_t waves = 0;
-  uint64_t renderedSamples = 0;
-  HIP_CHECK(hipEventRecord(tAll.a, stream));
-
-  // sampler tables (sampler.hpp::SamplerTables) for the wavefront pipeline; they require every
-  // sample index to fit the sampler's log2spp bits (log2Int rounds to nearest, e.g. 90 spp -> 6)
-  RenderConst rcw = rc;
-  if (samplerTables) {
-    const uint32_t dims = std::min<uint32_t>(256u, (4u + 8u * p.max_depth + 16u + 7u) & ~7u);     // (+ 3 <= kShadeHashSlots)
-    s.smpEntries.ensure(size_t(dims) * nPix); s.smpHash.ensure(dims + 3); s.smpSobol1.ensure(8 * 256);
-    SamplerTabArgs ta{};
-    ta.cfg = rc.sampler; ta.pixels = s.pixels.p; ta.nPixels = nPix; ta.dims = dims;
-    ta.entries = s.smpEntries.p; ta.hash = s.smpHash.p; ta.sobol1 = s.smpSobol1.p;
-    ta.matrix52 = reinterpret_cast<const uint32_t*>(s.dev.lut + LutDev::sobol);
-    TraceRange rg("yart:sampler_tables", stream);
-    tShade.begin(stream);
-    hipLaunchKernelGGL(k_sampler_tables, dim3(s.numCUs * 8), dim3(kBlock), 0, stream, ta);
-    HIP_CHECK(hipGetLastError());
-    tShade.end(stream);
-    rcw.sampler.tab.entries = s.smpEntries.p; rcw.sampler.tab.hash = s.smpHash.p; rcw.sampler.tab.sobol1 = s.smpSobol1.p;
-    rcw.sampler.tab.dims = dims; rcw.sampler.tab.stride = nPix;
+// The scene's buffers a render of this plan needs, grown on demand; the per-pixel accumulators and the caller's feature and moment
+// buffers cleared as the frame is.
+void prepareBuffers(YartScene& s, const RenderPlan& pl, hipStream_t stream) {
+  const size_t np1 = std::max<uint32_t>(pl.nPix, 1u), wh = size_t(pl.W) * pl.H;
+  const auto clear = [&](void* ptr, int byte, size_t bytes) { HIP_CHECK(hipMemsetAsync(ptr, byte, bytes, stream)); };
+  s.L.ensure(pl.aovStride);
+  // feature buffers: per-pixel accumulators (zero; ids -1), the caller's buffers, and — megakernel / path pool — the record arrays of the batch
+  if (pl.aov) {
+    for (auto& b : s.aovAcc) { b.ensure(np1); clear(b.p, 0, np1 * sizeof(f4)); }
+    s.aovRays.ensure(np1); clear(s.aovRays.p, 0, np1 * sizeof(uint32_t));
+    s.aovIds.ensure(np1 * 4); clear(s.aovIds.p, 0xff, np1 * 4 * sizeof(int32_t));
+    s.pixRays.ensure(np1);
+    if (pl.mega || pl.pool) s.aovRec.ensure(3 * pl.aovStride);
+    clearBuffers(kAovTable, *pl.aov, wh, clear);
   }
+  // sample moments: the running state per pixel of the rank (zero), the caller's buffers
+  if (pl.mom) {
+    s.momState.ensure(np1); clear(s.momState.p, 0, np1 * sizeof(MomentState));
+    clearBuffers(kMomentTable, *pl.mom, wh, clear);
+  }
+  if (pl.mega) return;
+  if (pl.pool) {
+    s.poolMap.ensure(pl.slots);
+    if (!s.poolHost) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.poolHost), kPoolLag * WC_COUNT * sizeof(uint32_t)));
+  }
+  for (auto& b : s.wf) b.ensure(pl.slots);
+  if (pl.compact) {
+    // Two dense "tail" states take the survivors in turn: the first is an array set of half the batch; the second is the BATCH-SIZED
+    // state itself — by the time a second compaction happens the paths live in the first tail and the large arrays hold nothing
+    // that is still read, so the survivors go back to their front (round 5: 36 B per path less than a third array set).
+    for (auto& b : s.wfTail[0]) b.ensure(pl.slots / 2 + 64);
+    s.wfTailMap[0].ensure(pl.slots / 2 + 64);
+    s.wfTailMap[1].ensure(pl.slots / 4 + 64);
+    s.wfDyn.ensure(1);
+  }
+  s.qA.ensure(pl.slots); s.qB.ensure(pl.slots); s.qS.ensure(pl.slots); s.qR.ensure(pl.slots); s.wfCounters.ensure(WC_COUNT);
+  if (pl.resumeCap) s.resumeRec.ensure(size_t(pl.resumeCap) * kResumeWords);
+}
 
-  // wave schedule of tile-renderer.hpp:121-124, 284-289
-  uint64_t remaining = p.samples;
-  uint64_t waveSamples = std::min<uint64_t>(p.first_wave_samples, p.samples);
-  uint64_t currentWave = 0;
-  while (waveSamples > 0) {
-    const uint64_t takenBefore = p.samples - remaining, takenAfter = takenBefore + waveSamples;
-    const float wCurrent = float(takenBefore) / float(takenAfter);
-    const float wWave = float(waveSamples) / float(takenAfter);
-    // resumable accumulation: waves outside [start_sample, stop_sample) are not rendered by this call
-    const bool inRange = takenBefore >= startSample && takenBefore < stopSample;
-    if (!inRange && takenBefore < startSample && takenAfter > startSample) throw std::invalid_argument("start_sample is not a wave boundary");
-    if (inRange && takenAfter > stopSample) throw std::invalid_argument("stop_sample is not a wave boundary");
-    if (inRange) { waves++; renderedSamples += waveSamples; }
-    size_t tileDone = 0;                     // blocks of this wave whose ray counts have been summed (tile callbacks only)
-    for (uint32_t c0 = 0; inRange && !aborted && c0 < nPix; c0 += chunk) {
-      const uint32_t n = std::min(chunk, nPix - c0);
-      AovArgs av{};
-      if (aov) {
-        av.acc0 = s.aovAcc[0].p; av.acc1 = s.aovAcc[1].p; av.acc2 = s.aovAcc[2].p; av.accRays = s.aovRays.p; av.ids = s.aovIds.p;
-        av.nPixels = n; av.spp = uint32_t(waveSamples); av.pixBase = c0; av.sampleOffset = uint32_t(takenBefore);
-        if (mega || pool) { av.r0 = s.aovRec.p; av.r1 = s.aovRec.p + aovStride; av.r2 = s.aovRec.p + 2 * aovStride; }
-      }
-      auto aovReduce = [&]() {
-        TraceRange rgA("yart:aov_reduce", stream);
-        hipLaunchKernelGGL(k_aov_reduce, dim3((n * 4u + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, av);
-        HIP_CHECK(hipGetLastError());
-      };
-      if (mega) {
-        HIP_CHECK(hipMemsetAsync(s.cursor.p, 0, sizeof(uint32_t), stream));
-        MegaArgs a{};
-        a.sc = s.dev; a.cam = cam; a.rc = rc; a.pixels = s.pixels.p + c0; a.nPixels = n;
-        a.spp = uint32_t(waveSamples); a.sampleOffset = uint32_t(takenBefore); a.L = s.L.p;
-        a.cursor = s.cursor.p; a.rays = s.counters.p; a.spill = s.spill.p;
-        a.aov0 = av.r0; a.aov1 = av.r1; a.aov2 = av.r2; a.aovIds = av.ids; a.pixBase = c0;
-        TraceRange rgMega("yart:megakernel", stream);
-        tMega.begin(stream);
-        hipLaunchKernelGGL(kMega, dim3(gridMega), dim3(kBlock), 0, stream, a);
-        HIP_CHECK(hipGetLastError());
-        tMega.end(stream);
-        if (aov) aovReduce();
-      } else if (pool) {
-        WfArgs a{};
-        a.sc = s.dev; a.cam = cam; a.rc = rcw; a.pixBase = c0;
-        a.st.ray0 = s.wf[0].p; a.st.ray1 = s.wf[1].p; a.st.thr = s.wf[2].p; a.st.acc = s.wf[3].p;
-        a.st.hit0 = s.wf[4].p; a.st.hit1 = s.wf[5].p; a.st.sh0 = s.wf[6].p; a.st.sh1 = s.wf[7].p; a.st.sh2 = s.wf[8].p;
-        a.qA = s.qA.p; a.qB = s.qB.p; a.qS = s.qS.p; a.qR = s.qR.p; a.counters = s.wfCounters.p;
-        a.pixels = s.pixels.p + c0; a.nPaths = n * uint32_t(waveSamples); a.spp = uint32_t(waveSamples);
-        a.sampleOffset = uint32_t(takenBefore); a.L = s.L.p; a.stats = s.counters.p; a.spill = s.spill.p;
-        a.matClass = s.matClass.p;
-        a.resumeRec = resumeCap ? s.resumeRec.p : nullptr; a.resumeCap = resumeCap;
-        a.sc.nodeBits = s.nodeBits.p; a.sc.nodeBitWords = nodeBitWords;
-        a.slotMap = s.poolMap.p;
-        a.poolSlots = uint32_t(std::min<uint64_t>(poolSlots, (uint64_t(a.nPaths) + 63u) & ~uint64_t(63)));
-        const uint32_t init[WC_COUNT] = {a.poolSlots, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        HIP_CHECK(hipMemcpyAsync(s.wfCounters.p, init, sizeof(init), hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(k_wf_pool_init, dim3(s.numCUs * 4), dim3(kBlock), 0, stream, s.poolMap.p, a.poolSlots);
-        HIP_CHECK(hipGetLastError());
-        // Rounds: every round starts new paths in the free slots and takes every live path one bounce further. The host does not
-        // know when the batch is done; it reads the counters of the round before the previous one (a copy into pinned memory and
-        // an event per round, never waited for) and stops launching when that round left no live path and nothing to start:
-        // two or three empty rounds at the end instead of a host synchronisation per round.
-        struct RoundEvents {                      // (destroyed on every way out of the round loop, a thrown HipError included)
-          hipEvent_t ev[kPoolLag] = {};
-          ~RoundEvents() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
-        } roundEv;
-        hipEvent_t* evRound = roundEv.ev;
-        for (int k = 0; k < kPoolLag; k++) HIP_CHECK(hipEventCreateWithFlags(&evRound[k], hipEventDisableTiming));
-        const uint64_t maxRounds = (uint64_t(a.nPaths) / a.poolSlots + 2u) * (rc.maxDepth + 1u) + 16u;   // (a path lives at most maxDepth rounds)
-        bool done = false;
-        for (uint64_t round = 0; !done; round++) {
-          if (round > maxRounds) throw HipError("path pool: the batch did not finish within its bound of rounds");
-          tShade.begin(stream);
-          hipLaunchKernelGGL(k_wf_refill, dim3(s.numCUs * YART_STREAM_BLOCKS), dim3(kBlock), 0, stream, a);
-          HIP_CHECK(hipGetLastError());
-          tShade.end(stream);
-          {   // the live slots of this round, for the host (WC_NEXT: k_wf_refill)
-            uint32_t* snap = s.poolHost + size_t(round % kPoolLag) * WC_COUNT;
-            HIP_CHECK(hipMemcpyAsync(snap, s.wfCounters.p, WC_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(hipEventRecord(evRound[round % kPoolLag], stream));
-          }
-          tExtend.begin(stream);
-          if (general) {
-            hipLaunchKernelGGL(kExtendGen, dim3(gridExtend), dim3(kBlock), 0, stream, a);
-          } else {
-            tLean.begin(stream);
-            hipLaunchKernelGGL(kExtendFast, dim3(gridExtendFast), dim3(kBlock), 0, stream, a);
-            tLean.end(stream);
-            if (refill) hipLaunchKernelGGL(kRetryE, dim3(gridRetryE), dim3(kBlock), 0, stream, a);
-            else hipLaunchKernelGGL(kExtendGenRetry, dim3(gridExtend), dim3(kBlock), 0, stream, a);
-            hipLaunchKernelGGL(k_wf_reset_retry, dim3(1), dim3(64), 0, stream, s.wfCounters.p);
-          }
-          HIP_CHECK(hipGetLastError());
-          tExtend.end(stream);
-          if (aov) {                             // the paths this round's refill started stand at bounce 0 with their hit records final
-            hipLaunchKernelGGL(k_aov_capture, dim3(s.numCUs * YART_STREAM_BLOCKS), dim3(kBlock), 0, stream, a, av);
-            HIP_CHECK(hipGetLastError());
-          }
-          tShade.begin(stream);
-          tShadeK.begin(stream);
-          hipLaunchKernelGGL(kShade, dim3(gridShade), dim3(kShadeBlock), 0, stream, a);
-          HIP_CHECK(hipGetLastError());
-          tShadeK.end(stream);
-          tShade.end(stream);
-          tConnect.begin(stream);
-          if (general) {
-            hipLaunchKernelGGL(kShadowGen, dim3(gridShadow), dim3(kBlock), 0, stream, a);
-          } else {
-            tShadowLean.begin(stream);
-            hipLaunchKernelGGL(kShadowFast, dim3(gridShadowFast), dim3(kBlock), 0, stream, a);
-            tShadowLean.end(stream);
-            if (refill) hipLaunchKernelGGL(kRetryS, dim3(gridRetryS), dim3(kBlock), 0, stream, a);
-            else hipLaunchKernelGGL(kShadowGenRetry, dim3(gridShadow), dim3(kBlock), 0, stream, a);
-          }
-          HIP_CHECK(hipGetLastError());
-          tConnect.end(stream);
-          tShade.begin(stream);
-          hipLaunchKernelGGL(k_wf_roulette, dim3(s.numCUs * YART_STREAM_BLOCKS), dim3(kBlock), 0, stream, a);
-          HIP_CHECK(hipGetLastError());
-          tShade.end(stream);
-          hipLaunchKernelGGL(k_wf_pool_advance, dim3(1), dim3(64), 0, stream, s.wfCounters.p, a.poolSlots);
-          HIP_CHECK(hipGetLastError());
-          if (round >= 2) {
-            const uint64_t old = round - 2;
-            // (rounds far ahead of the device would only queue launches: wait for the round before the previous one)
-            HIP_CHECK(hipEventSynchronize(evRound[old % kPoolLag]));
-            const uint32_t* c = s.poolHost + size_t(old % kPoolLag) * WC_COUNT;
-            if (c[WC_NEXT] == 0u) done = true;                  // no live slot after its refill: nothing left to start either
-          }
-        }
-        if (aov) aovReduce();
-      } else {
-        WfArgs a{};
-        a.sc = s.dev; a.cam = cam; a.rc = rcw; a.pixBase = c0;
-        a.st.ray0 = s.wf[0].p; a.st.ray1 = s.wf[1].p; a.st.thr = s.wf[2].p; a.st.acc = s.wf[3].p;
-        a.st.hit0 = s.wf[4].p; a.st.hit1 = s.wf[5].p; a.st.sh0 = s.wf[6].p; a.st.sh1 = s.wf[7].p; a.st.sh2 = s.wf[8].p;
-        a.qA = s.qA.p; a.qB = s.qB.p; a.qS = s.qS.p; a.qR = s.qR.p; a.counters = s.wfCounters.p;
-        a.pixels = s.pixels.p + c0; a.nPaths = n * uint32_t(waveSamples); a.spp = uint32_t(waveSamples);
-        a.sampleOffset = uint32_t(takenBefore); a.L = s.L.p; a.stats = s.counters.p; a.spill = s.spill.p;
-        a.matClass = s.matClass.p;
-        a.resumeRec = resumeCap ? s.resumeRec.p : nullptr; a.resumeCap = resumeCap;
-        a.sc.nodeBits = s.nodeBits.p; a.sc.nodeBitWords = nodeBitWords;
-        if (compact) {
-          for (int t = 0; t < 2; t++) {
-            f4** f = &a.tail[t].ray0;                  // the nine pointers of WfState, in declaration order
-            for (int k = 0; k < 9; k++) f[k] = t == 0 ? s.wfTail[0][k].p : s.wf[k].p;      // (second tail: the batch-sized state, see above)
-            a.tailMap[t] = s.wfTailMap[t].p;
-            a.tailCap[t] = a.nPaths / (t == 0 ? 2u : 4u);
-          }
-          WfDyn d0{};
-          d0.st = a.st; d0.slotMap = nullptr; d0.extent = a.nPaths; d0.inTail = 0;
-          HIP_CHECK(hipMemcpyAsync(s.wfDyn.p, &d0, sizeof(d0), hipMemcpyHostToDevice, stream));
-          a.dyn = s.wfDyn.p;
-        }
-        const uint32_t init[WC_COUNT] = {a.nPaths, 0, 0, 0, 0, 0, 0, 0, 0};
-        HIP_CHECK(hipMemcpyAsync(s.wfCounters.p, init, sizeof(init), hipMemcpyHostToDevice, stream));
-        TraceRange rgGen("yart:generate", stream);
-        tShade.begin(stream);
-        hipLaunchKernelGGL(k_wf_generate, dim3(s.numCUs * YART_STREAM_BLOCKS), dim3(kBlock), 0, stream, a);
-        HIP_CHECK(hipGetLastError());
-        tShade.end(stream);
-        rgGen.end();
-        for (uint32_t bounce = 0; bounce < rc.maxDepth; bounce++) {
-          a.bounce = bounce;
-          char rgName[32]; std::snprintf(rgName, sizeof(rgName), "yart:bounce %u", bounce);
-          TraceRange rgBounce(rgName);
-          TraceRange rgExtend("yart:extend", stream);
-          tExtend.begin(stream);
-          if (general) {
-            hipLaunchKernelGGL(kExtendGen, dim3(gridExtend), dim3(kBlock), 0, stream, a);
-          } else {
-            tLean.begin(stream);
-            hipLaunchKernelGGL(kExtendFast, dim3(gridExtendFast), dim3(kBlock), 0, stream, a);
-            tLean.end(stream);
-            if (refill) hipLaunchKernelGGL(kRetryE, dim3(gridRetryE), dim3(kBlock), 0, stream, a);
-            else hipLaunchKernelGGL(kExtendGenRetry, dim3(gridExtend), dim3(kBlock), 0, stream, a);
-            hipLaunchKernelGGL(k_wf_reset_retry, dim3(1), dim3(64), 0, stream, s.wfCounters.p);
-          }
-          HIP_CHECK(hipGetLastError());
-          tExtend.end(stream);
-          rgExtend.end();
-          if (aov && bounce == 0) {
-            // feature records of every path of the batch, written into the shadow-ray arrays (unused until the shade stage below
-            // writes bounce 0's shadow rays) and summed per pixel at once, before that happens
-            TraceRange rgA("yart:aov_capture", stream);
-            av.r0 = a.st.sh0; av.r1 = a.st.sh1; av.r2 = a.st.sh2;
-            hipLaunchKernelGGL(k_aov_capture, dim3(s.numCUs * YART_STREAM_BLOCKS), dim3(kBlock), 0, stream, a, av);
-            HIP_CHECK(hipGetLastError());
-            rgA.end();
-            aovReduce();
-          }
-          TraceRange rgShade("yart:shade", stream);
-          tShade.begin(stream);
-          tShadeK.begin(stream);
-          hipLaunchKernelGGL(kShade, dim3(gridShade), dim3(kShadeBlock), 0, stream, a);
-          HIP_CHECK(hipGetLastError());
-          tShadeK.end(stream);
-          tShade.end(stream);
-          rgShade.end();
-          TraceRange rgShadow("yart:shadow", stream);
-          tConnect.begin(stream);
-          if (general) {
-            hipLaunchKernelGGL(kShadowGen, dim3(gridShadow), dim3(kBlock), 0, stream, a);
-          } else {
-            tShadowLean.begin(stream);
-            hipLaunchKernelGGL(kShadowFast, dim3(gridShadowFast), dim3(kBlock), 0, stream, a);
-            tShadowLean.end(stream);
-            if (refill) hipLaunchKernelGGL(kRetryS, dim3(gridRetryS), dim3(kBlock), 0, stream, a);
-            else hipLaunchKernelGGL(kShadowGenRetry, dim3(gridShadow), dim3(kBlock), 0, stream, a);
-          }
-          HIP_CHECK(hipGetLastError());
-          tConnect.end(stream);
-          rgShadow.end();
-          // Russian roulette of the paths that cast a shadow ray: from the second bounce on (at depth 1 none applies: k_wf_shade
-          // queued them itself), not after the last one (their radiance has been written out by the shadow kernels)
-          if (bounce >= 1 && bounce + 1 < rc.maxDepth) {
-            TraceRange rgR("yart:roulette", stream);
-            tShade.begin(stream);
-            hipLaunchKernelGGL(k_wf_roulette, dim3(s.numCUs * YART_STREAM_BLOCKS), dim3(kBlock), 0, stream, a);
-            HIP_CHECK(hipGetLastError());
-            tShade.end(stream);
-          }
-          hipLaunchKernelGGL(k_wf_advance, dim3(1), dim3(64), 0, stream, s.wfCounters.p, bounce + 1 < 16u ? s.pathsLog.p + bounce + 1 : nullptr);
-          HIP_CHECK(hipGetLastError());
-          std::swap(a.qA, a.qB);
-          if (compact && bounce >= 1 && bounce + 1 < rc.maxDepth) {     // Russian roulette starts thinning at depth 2
-            TraceRange rgC("yart:compact", stream);
-            tShade.begin(stream);
-            hipLaunchKernelGGL(k_wf_compact, dim3(s.numCUs * YART_STREAM_BLOCKS), dim3(kBlock), 0, stream, a);
-            hipLaunchKernelGGL(k_wf_compact_commit, dim3(1), dim3(64), 0, stream, a);
-            HIP_CHECK(hipGetLastError());
-            tShade.end(stream);
-          }
-        }
-      }
-      GmonArgs g{};
-      if (hook && *hook) { s.pixRays.ensure(std::max<uint32_t>(nPix, 1u)); g.pixRays = s.pixRays.p + c0; }
-      if (aov) g.pixRays = s.pixRays.p + c0;
-      g.L = s.L.p; g.pixels = s.pixels.p + c0; g.nPixels = n; g.spp = uint32_t(waveSamples); g.width = W;
-      g.exposureScale = cam.exposureScale; g.wCurrent = wCurrent; g.wWave = wWave; g.hdr = dOut;
-      g.kind = int(p.estimator);
-      TraceRange rgBlend("yart:gmon_blend", stream);
-      tGmon.begin(stream);
-      hipLaunchKernelGGL(k_gmon_blend, dim3((n + kGmonPixPerBlock - 1) / kGmonPixPerBlock), dim3(kBlock), 0, stream, g);
+// The sampler tables of this render, for the wavefront kernels (pl.rcw carries them from here on)
+void launchSamplerTables(YartScene& s, RenderPlan& pl, StageTimers& t, hipStream_t stream) {
+  if (!pl.samplerTables) return;
+  const uint32_t dims = std::min<uint32_t>(256u, (4u + 8u * pl.p->max_depth + 16u + 7u) & ~7u);     // (+ 3 <= kShadeHashSlots)
+  s.smpEntries.ensure(size_t(dims) * pl.nPix); s.smpHash.ensure(dims + 3); s.smpSobol1.ensure(8 * 256);
+  SamplerTabArgs ta{};
+  ta.cfg = pl.rc.sampler; ta.pixels = s.pixels.p; ta.nPixels = pl.nPix; ta.dims = dims;
+  ta.entries = s.smpEntries.p; ta.hash = s.smpHash.p; ta.sobol1 = s.smpSobol1.p;
+  ta.matrix52 = reinterpret_cast<const uint32_t*>(s.dev.lut + LutDev::sobol);
+  TraceRange rg("yart:sampler_tables", stream);
+  t.shade.begin(stream);
+  hipLaunchKernelGGL(k_sampler_tables, dim3(s.numCUs * 8), dim3(kBlock), 0, stream, ta);
+  HIP_CHECK(hipGetLastError());
+  t.shade.end(stream);
+  pl.rcw.sampler.tab.entries = s.smpEntries.p; pl.rcw.sampler.tab.hash = s.smpHash.p; pl.rcw.sampler.tab.sobol1 = s.smpSobol1.p;
+  pl.rcw.sampler.tab.dims = dims; pl.rcw.sampler.tab.stride = pl.nPix;
+}
+
+// One batch of one wave: pixels [c0, c0 + n) of the rank's list, samples [takenBefore, takenBefore + waveSamples) of each
+struct Batch { uint32_t c0, n, waveSamples, takenBefore; };
+
+// feature buffers: the arguments of the batch's capture / reduce kernels (all zero without feature buffers)
+AovArgs aovArgs(const YartScene& s, const RenderPlan& pl, const Batch& b) {
+  AovArgs av{};
+  if (pl.aov) {
+    av.acc0 = s.aovAcc[0].p; av.acc1 = s.aovAcc[1].p; av.acc2 = s.aovAcc[2].p; av.accRays = s.aovRays.p; av.ids = s.aovIds.p;
+    av.nPixels = b.n; av.spp = b.waveSamples; av.pixBase = b.c0; av.sampleOffset = b.takenBefore;
+    if (pl.mega || pl.pool) { av.r0 = s.aovRec.p; av.r1 = s.aovRec.p + pl.aovStride; av.r2 = s.aovRec.p + 2 * pl.aovStride; }
+  }
+  return av;
+}
+void aovReduce(const AovArgs& av, hipStream_t stream) {
+  TraceRange rgA("yart:aov_reduce", stream);
+  hipLaunchKernelGGL(k_aov_reduce, dim3((av.nPixels * 4u + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, av);
+  HIP_CHECK(hipGetLastError());
+}
+
+void runMegaBatch(YartScene& s, const RenderPlan& pl, const Batch& b, StageTimers& t, hipStream_t stream) {
+  const AovArgs av = aovArgs(s, pl, b);
+  HIP_CHECK(hipMemsetAsync(s.cursor.p, 0, sizeof(uint32_t), stream));
+  MegaArgs a{};
+  a.sc = s.dev; a.cam = pl.cam; a.rc = pl.rc; a.pixels = s.pixels.p + b.c0; a.nPixels = b.n;
+  a.spp = b.waveSamples; a.sampleOffset = b.takenBefore; a.L = s.L.p;
+  a.cursor = s.cursor.p; a.rays = s.counters.p; a.spill = s.spill.p;
+  a.aov0 = av.r0; a.aov1 = av.r1; a.aov2 = av.r2; a.aovIds = av.ids; a.pixBase = b.c0;
+  TraceRange rgMega("yart:megakernel", stream);
+  t.mega.begin(stream);
+  hipLaunchKernelGGL(pl.kMega, dim3(pl.gridMega), dim3(kBlock), 0, stream, a);
+  HIP_CHECK(hipGetLastError());
+  t.mega.end(stream);
+  if (pl.aov) aovReduce(av, stream);
+}
+
+// what the path pool and the batch-synchronous pipeline pass to every kernel of a batch
+WfArgs wfArgs(const YartScene& s, const RenderPlan& pl, const Batch& b) {
+  WfArgs a{};
+  a.sc = s.dev; a.cam = pl.cam; a.rc = pl.rcw; a.pixBase = b.c0;
+  a.st.ray0 = s.wf[0].p; a.st.ray1 = s.wf[1].p; a.st.thr = s.wf[2].p; a.st.acc = s.wf[3].p;
+  a.st.hit0 = s.wf[4].p; a.st.hit1 = s.wf[5].p; a.st.sh0 = s.wf[6].p; a.st.sh1 = s.wf[7].p; a.st.sh2 = s.wf[8].p;
+  a.qA = s.qA.p; a.qB = s.qB.p; a.qS = s.qS.p; a.qR = s.qR.p; a.counters = s.wfCounters.p;
+  a.pixels = s.pixels.p + b.c0; a.nPaths = b.n * b.waveSamples; a.spp = b.waveSamples;
+  a.sampleOffset = b.takenBefore; a.L = s.L.p; a.stats = s.counters.p; a.spill = s.spill.p;
+  a.matClass = s.matClass.p;
+  a.resumeRec = pl.resumeCap ? s.resumeRec.p : nullptr; a.resumeCap = pl.resumeCap;
+  a.sc.nodeBits = s.nodeBits.p; a.sc.nodeBitWords = pl.nodeBitWords;
+  return a;
+}
+
+// The extend stage over the queue of `a`: the general kernel, or the lean kernel and then the retry pass over the rays it handed
+// over (the lean retry kernel, or — one-ray-per-lane lean kernels — the general one)
+void extendStage(const RenderPlan& pl, const WfArgs& a, StageTimers& t, hipStream_t stream) {
+  t.extend.begin(stream);
+  if (pl.general) {
+    hipLaunchKernelGGL(pl.kExtendGen, dim3(pl.gridExtend), dim3(kBlock), 0, stream, a);
+  } else {
+    t.lean.begin(stream);
+    hipLaunchKernelGGL(pl.kExtendFast, dim3(pl.gridExtendFast), dim3(kBlock), 0, stream, a);
+    t.lean.end(stream);
+    if (pl.refill) hipLaunchKernelGGL(pl.kRetryE, dim3(pl.gridRetryE), dim3(kBlock), 0, stream, a);
+    else hipLaunchKernelGGL(pl.kExtendGenRetry, dim3(pl.gridExtend), dim3(kBlock), 0, stream, a);
+    hipLaunchKernelGGL(k_wf_reset_retry, dim3(1), dim3(64), 0, stream, a.counters);
+  }
+  HIP_CHECK(hipGetLastError());
+  t.extend.end(stream);
+}
+// The shadow stage, likewise
+void shadowStage(const RenderPlan& pl, const WfArgs& a, StageTimers& t, hipStream_t stream) {
+  t.connect.begin(stream);
+  if (pl.general) {
+    hipLaunchKernelGGL(pl.kShadowGen, dim3(pl.gridShadow), dim3(kBlock), 0, stream, a);
+  } else {
+    t.shadowLean.begin(stream);
+    hipLaunchKernelGGL(pl.kShadowFast, dim3(pl.gridShadowFast), dim3(kBlock), 0, stream, a);
+    t.shadowLean.end(stream);
+    if (pl.refill) hipLaunchKernelGGL(pl.kRetryS, dim3(pl.gridRetryS), dim3(kBlock), 0, stream, a);
+    else hipLaunchKernelGGL(pl.kShadowGenRetry, dim3(pl.gridShadow), dim3(kBlock), 0, stream, a);
+  }
+  HIP_CHECK(hipGetLastError());
+  t.connect.end(stream);
+}
+void shadeStage(const RenderPlan& pl, const WfArgs& a, StageTimers& t, hipStream_t stream) {
+  t.shade.begin(stream);
+  t.shadeK.begin(stream);
+  hipLaunchKernelGGL(pl.kShade, dim3(pl.gridShade), dim3(kShadeBlock), 0, stream, a);
+  HIP_CHECK(hipGetLastError());
+  t.shadeK.end(stream);
+  t.shade.end(stream);
+}
+// a streaming pass of the wavefront pipelines (generate, refill, roulette, compact), on the shade stopwatch
+void streamingPass(const YartScene& s, WfKernelFn k, const WfArgs& a, StageTimers& t, hipStream_t stream) {
+  t.shade.begin(stream);
+  hipLaunchKernelGGL(k, dim3(s.numCUs * YART_STREAM_BLOCKS), dim3(kBlock), 0, stream, a);
+  HIP_CHECK(hipGetLastError());
+  t.shade.end(stream);
+}
+
+void runPoolBatch(YartScene& s, const RenderPlan& pl, const Batch& b, StageTimers& t, hipStream_t stream) {
+  const AovArgs av = aovArgs(s, pl, b);
+  WfArgs a = wfArgs(s, pl, b);
+  a.slotMap = s.poolMap.p;
+  a.poolSlots = uint32_t(std::min<uint64_t>(pl.poolSlots, (uint64_t(a.nPaths) + 63u) & ~uint64_t(63)));
+  const uint32_t init[WC_COUNT] = {a.poolSlots, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  HIP_CHECK(hipMemcpyAsync(s.wfCounters.p, init, sizeof(init), hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(k_wf_pool_init, dim3(s.numCUs * 4), dim3(kBlock), 0, stream, s.poolMap.p, a.poolSlots);
+  HIP_CHECK(hipGetLastError());
+  // Rounds: every round starts new paths in the free slots and takes every live path one bounce further. The host does not
+  // know when the batch is done; it reads the counters of the round before the previous one (a copy into pinned memory and
+  // an event per round, never waited for) and stops launching when that round left no live path and nothing to start:
+  // two or three empty rounds at the end instead of a host synchronisation per round.
+  struct RoundEvents {                      // (destroyed on every way out of the round loop, a thrown HipError included)
+    hipEvent_t ev[kPoolLag] = {};
+    ~RoundEvents() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
+  } roundEv;
+  hipEvent_t* evRound = roundEv.ev;
+  for (int k = 0; k < kPoolLag; k++) HIP_CHECK(hipEventCreateWithFlags(&evRound[k], hipEventDisableTiming));
+  const uint64_t maxRounds = (uint64_t(a.nPaths) / a.poolSlots + 2u) * (pl.rc.maxDepth + 1u) + 16u;   // (a path lives at most maxDepth rounds)
+  bool done = false;
+  for (uint64_t round = 0; !done; round++) {
+    if (round > maxRounds) throw HipError("path pool: the batch did not finish within its bound of rounds");
+    streamingPass(s, k_wf_refill, a, t, stream);
+    {   // the live slots of this round, for the host (WC_NEXT: k_wf_refill)
+      uint32_t* snap = s.poolHost + size_t(round % kPoolLag) * WC_COUNT;
+      HIP_CHECK(hipMemcpyAsync(snap, s.wfCounters.p, WC_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+      HIP_CHECK(hipEventRecord(evRound[round % kPoolLag], stream));
+    }
+    extendStage(pl, a, t, stream);
+    if (pl.aov) {                             // the paths this round's refill started stand at bounce 0 with their hit records final
+      hipLaunchKernelGGL(k_aov_capture, dim3(s.numCUs * YART_STREAM_BLOCKS), dim3(kBlock), 0, stream, a, av);
       HIP_CHECK(hipGetLastError());
-      tGmon.end(stream);
-      if (mom) {                               // the same records, before the next batch overwrites them
-        MomentArgs ma{};
-        ma.L = s.L.p; ma.state = s.momState.p; ma.nPixels = n; ma.spp = uint32_t(waveSamples); ma.pixBase = c0;
-        ma.exposureScale = cam.exposureScale;
-        TraceRange rgM("yart:moments_accumulate", stream);
-        hipLaunchKernelGGL(k_moments_accumulate, dim3((n + kMomentPixPerBlock - 1) / kMomentPixPerBlock), dim3(kBlock), 0, stream, ma);
-        HIP_CHECK(hipGetLastError());
-      }
-      if (aov) {
-        hipLaunchKernelGGL(k_aov_add_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, s.aovRays.p + c0, s.pixRays.p + c0, n);
-        HIP_CHECK(hipGetLastError());
-      }
-      HIP_CHECK(hipStreamSynchronize(stream));
-      rgBlend.end();
-      tMega.resolve(); tExtend.resolve(); tShade.resolve(); tConnect.resolve(); tGmon.resolve(); tLean.resolve(); tShadeK.resolve(); tShadowLean.resolve();
-      if (hook && *hook) {
-        // ray counts of the blocks this batch completed (their pixels' counts of this wave are all in pixRays now)
-        size_t done = tileDone;
-        while (done < s.tiles.size() && s.tiles[done].start + s.tiles[done].count <= c0 + n) done++;
-        if (done > tileDone) {
-          s.tileRays.ensure(s.tiles.size()); s.tileRaysHost.resize(s.tiles.size());
-          hipLaunchKernelGGL(k_tile_rays, dim3(uint32_t(done - tileDone)), dim3(64), 0, stream, s.pixRays.p, s.tileStart.p, s.tileCount.p,
-                             uint32_t(tileDone), uint32_t(done - tileDone), s.tileRays.p);
-          HIP_CHECK(hipGetLastError());
-          HIP_CHECK(hipMemcpyAsync(s.tileRaysHost.data() + tileDone, s.tileRays.p + tileDone, (done - tileDone) * sizeof(unsigned long long),
-                                   hipMemcpyDeviceToHost, stream));
-          HIP_CHECK(hipStreamSynchronize(stream));
-          tileDone = done;
-        }
-        const BatchInfo bi{c0, n, uint32_t(currentWave), uint32_t(waveSamples), uint32_t(takenAfter), p.samples};
-        if ((*hook)(bi)) aborted = true;
-      }
     }
-    if (aborted) break;
-    remaining -= waveSamples;
-    uint64_t next = (currentWave > 0 || waveSamples > 1) ? std::min<uint64_t>(waveSamples * 2, p.max_wave_samples) : 1;
-    waveSamples = std::min(next, remaining);
-    currentWave++;
+    shadeStage(pl, a, t, stream);
+    shadowStage(pl, a, t, stream);
+    streamingPass(s, k_wf_roulette, a, t, stream);
+    hipLaunchKernelGGL(k_wf_pool_advance, dim3(1), dim3(64), 0, stream, s.wfCounters.p, a.poolSlots);
+    HIP_CHECK(hipGetLastError());
+    if (round >= 2) {
+      const uint64_t old = round - 2;
+      // (rounds far ahead of the device would only queue launches: wait for the round before the previous one)
+      HIP_CHECK(hipEventSynchronize(evRound[old % kPoolLag]));
+      const uint32_t* c = s.poolHost + size_t(old % kPoolLag) * WC_COUNT;
+      if (c[WC_NEXT] == 0u) done = true;                  // no live slot after its refill: nothing left to start either
+    }
   }
-  if (aov && nPix > 0 && !aborted) {
+  if (pl.aov) aovReduce(av, stream);
+}
+
+void runWavefrontBatch(YartScene& s, const RenderPlan& pl, const Batch& b, StageTimers& t, hipStream_t stream) {
+  AovArgs av = aovArgs(s, pl, b);
+  WfArgs a = wfArgs(s, pl, b);
+  const uint32_t maxDepth = pl.rc.maxDepth;
+  if (pl.compact) {
+    for (int k = 0; k < 2; k++) {
+      f4** f = &a.tail[k].ray0;                  // the nine pointers of WfState, in declaration order
+      for (int j = 0; j < 9; j++) f[j] = k == 0 ? s.wfTail[0][j].p : s.wf[j].p;      // (second tail: the batch-sized state, see prepareBuffers)
+      a.tailMap[k] = s.wfTailMap[k].p;
+      a.tailCap[k] = a.nPaths / (k == 0 ? 2u : 4u);
+    }
+    WfDyn d0{};
+    d0.st = a.st; d0.slotMap = nullptr; d0.extent = a.nPaths; d0.inTail = 0;
+    HIP_CHECK(hipMemcpyAsync(s.wfDyn.p, &d0, sizeof(d0), hipMemcpyHostToDevice, stream));
+    a.dyn = s.wfDyn.p;
+  }
+  const uint32_t init[WC_COUNT] = {a.nPaths, 0, 0, 0, 0, 0, 0, 0, 0};
+  HIP_CHECK(hipMemcpyAsync(s.wfCounters.p, init, sizeof(init), hipMemcpyHostToDevice, stream));
+  {
+    TraceRange rgGen("yart:generate", stream);
+    streamingPass(s, k_wf_generate, a, t, stream);
+  }
+  for (uint32_t bounce = 0; bounce < maxDepth; bounce++) {
+    a.bounce = bounce;
+    char rgName[32]; std::snprintf(rgName, sizeof(rgName), "yart:bounce %u", bounce);
+    TraceRange rgBounce(rgName);
+    {
+      TraceRange rgExtend("yart:extend", stream);
+      extendStage(pl, a, t, stream);
+    }
+    if (pl.aov && bounce == 0) {
+      // feature records of every path of the batch, written into the shadow-ray arrays (unused until the shade stage below
+      // writes bounce 0's shadow rays) and summed per pixel at once, before that happens
+      {
+        TraceRange rgA("yart:aov_capture", stream);
+        av.r0 = a.st.sh0; av.r1 = a.st.sh1; av.r2 = a.st.sh2;
+        hipLaunchKernelGGL(k_aov_capture, dim3(s.numCUs * YART_STREAM_BLOCKS), dim3(kBlock), 0, stream, a, av);
+        HIP_CHECK(hipGetLastError());
+      }
+      aovReduce(av, stream);
+    }
+    {
+      TraceRange rgShade("yart:shade", stream);
+      shadeStage(pl, a, t, stream);
+    }
+    {
+      TraceRange rgShadow("yart:shadow", stream);
+      shadowStage(pl, a, t, stream);
+    }
+    // Russian roulette of the paths that cast a shadow ray: from the second bounce on (at depth 1 none applies: k_wf_shade
+    // queued them itself), not after the last one (their radiance has been written out by the shadow kernels)
+    const bool thinning = bounce >= 1 && bounce + 1 < maxDepth;
+    if (thinning) {
+      TraceRange rgR("yart:roulette", stream);
+      streamingPass(s, k_wf_roulette, a, t, stream);
+    }
+    hipLaunchKernelGGL(k_wf_advance, dim3(1), dim3(64), 0, stream, s.wfCounters.p, bounce + 1 < 16u ? s.pathsLog.p + bounce + 1 : nullptr);
+    HIP_CHECK(hipGetLastError());
+    std::swap(a.qA, a.qB);
+    if (pl.compact && thinning) {               // Russian roulette starts thinning at depth 2
+      TraceRange rgC("yart:compact", stream);
+      t.shade.begin(stream);
+      hipLaunchKernelGGL(k_wf_compact, dim3(s.numCUs * YART_STREAM_BLOCKS), dim3(kBlock), 0, stream, a);
+      hipLaunchKernelGGL(k_wf_compact_commit, dim3(1), dim3(64), 0, stream, a);
+      HIP_CHECK(hipGetLastError());
+      t.shade.end(stream);
+    }
+  }
+}
+
+// What follows every batch's runner: the batch's samples through the estimator and blended into the frame (weights wCurrent /
+// wWave of the wave), the moments and ray counts summed, the stream synchronised and the stopwatches resolved; then — tile
+// callbacks — the ray counts of the blocks the batch completed and the hook. true: the hook asked to stop.
+struct WaveInfo { uint32_t wave, samplesTaken; float wCurrent, wWave; size_t tileDone; };   // tileDone: blocks of this wave whose ray counts have been summed
+bool finishBatch(YartScene& s, const RenderPlan& pl, const Batch& b, WaveInfo& w, float* dOut, StageTimers& t, const BatchHook* hook,
+                 hipStream_t stream) {
+  const uint32_t c0 = b.c0, n = b.n;
+  const bool hooked = hook && *hook;
+  GmonArgs g{};
+  if (hooked) { s.pixRays.ensure(std::max<uint32_t>(pl.nPix, 1u)); g.pixRays = s.pixRays.p + c0; }
+  if (pl.aov) g.pixRays = s.pixRays.p + c0;
+  g.L = s.L.p; g.pixels = s.pixels.p + c0; g.nPixels = n; g.spp = b.waveSamples; g.width = pl.W;
+  g.exposureScale = pl.cam.exposureScale; g.wCurrent = w.wCurrent; g.wWave = w.wWave; g.hdr = dOut;
+  g.kind = int(pl.p->estimator);
+  {
+    TraceRange rgBlend("yart:gmon_blend", stream);
+    t.gmon.begin(stream);
+    hipLaunchKernelGGL(k_gmon_blend, dim3((n + kGmonPixPerBlock - 1) / kGmonPixPerBlock), dim3(kBlock), 0, stream, g);
+    HIP_CHECK(hipGetLastError());
+    t.gmon.end(stream);
+    if (pl.mom) {                            // the same records, before the next batch overwrites them
+      MomentArgs ma{};
+      ma.L = s.L.p; ma.state = s.momState.p; ma.nPixels = n; ma.spp = b.waveSamples; ma.pixBase = c0;
+      ma.exposureScale = pl.cam.exposureScale;
+      TraceRange rgM("yart:moments_accumulate", stream);
+      hipLaunchKernelGGL(k_moments_accumulate, dim3((n + kMomentPixPerBlock - 1) / kMomentPixPerBlock), dim3(kBlock), 0, stream, ma);
+      HIP_CHECK(hipGetLastError());
+    }
+    if (pl.aov) {
+      hipLaunchKernelGGL(k_aov_add_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, s.aovRays.p + c0, s.pixRays.p + c0, n);
+      HIP_CHECK(hipGetLastError());
+    }
+    HIP_CHECK(hipStreamSynchronize(stream));
+  }
+  t.resolveAll();
+  if (!hooked) return false;
+  // ray counts of the blocks this batch completed (their pixels' counts of this wave are all in pixRays now)
+  size_t done = w.tileDone;
+  while (done < s.tiles.size() && s.tiles[done].start + s.tiles[done].count <= c0 + n) done++;
+  if (done > w.tileDone) {
+    s.tileRays.ensure(s.tiles.size()); s.tileRaysHost.resize(s.tiles.size());
+    hipLaunchKernelGGL(k_tile_rays, dim3(uint32_t(done - w.tileDone)), dim3(64), 0, stream, s.pixRays.p, s.tileStart.p, s.tileCount.p,
+                       uint32_t(w.tileDone), uint32_t(done - w.tileDone), s.tileRays.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(s.tileRaysHost.data() + w.tileDone, s.tileRays.p + w.tileDone, (done - w.tileDone) * sizeof(unsigned long long),
+                             hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    w.tileDone = done;
+  }
+  return (*hook)(BatchInfo{c0, n, w.wave, b.waveSamples, w.samplesTaken, pl.p->samples});
+}
+
+// After the last wave: the accumulators of the feature buffers and the moments written to the caller's buffers
+void launchFinishKernels(const YartScene& s, const RenderPlan& pl, hipStream_t stream) {
+  if (pl.nPix == 0) return;
+  if (pl.aov) {
+    const YartAovBuffers* aov = pl.aov;
     AovFinishArgs f{};
     f.acc0 = s.aovAcc[0].p; f.acc1 = s.aovAcc[1].p; f.acc2 = s.aovAcc[2].p; f.accRays = s.aovRays.p; f.ids = s.aovIds.p;
-    f.pixels = s.pixels.p; f.nPixels = nPix; f.width = W; f.samples = p.samples; f.mask = aov->mask;
+    f.pixels = s.pixels.p; f.nPixels = pl.nPix; f.width = pl.W; f.samples = pl.p->samples; f.mask = aov->mask;
     f.albedo = aov->albedo; f.normal = aov->normal; f.position = aov->position; f.depth = aov->depth; f.coverage = aov->coverage;
     f.outIds = aov->ids; f.outRays = aov->rays;
     TraceRange rgA("yart:aov_finish", stream);
-    hipLaunchKernelGGL(k_aov_finish, dim3((nPix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, f);
+    hipLaunchKernelGGL(k_aov_finish, dim3((pl.nPix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, f);
     HIP_CHECK(hipGetLastError());
   }
-  if (mom && nPix > 0 && !aborted) {
+  if (pl.mom) {
+    const YartMomentBuffers* mom = pl.mom;
     MomentFinishArgs f{};
-    f.state = s.momState.p; f.pixels = s.pixels.p; f.nPixels = nPix; f.width = W; f.mask = mom->mask;
+    f.state = s.momState.p; f.pixels = s.pixels.p; f.nPixels = pl.nPix; f.width = pl.W; f.mask = mom->mask;
     f.mean = mom->mean; f.variance = mom->variance; f.count = mom->count;
     TraceRange rgM("yart:moments_finish", stream);
-    hipLaunchKernelGGL(k_moments_finish, dim3((nPix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, f);
+    hipLaunchKernelGGL(k_moments_finish, dim3((pl.nPix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, f);
     HIP_CHECK(hipGetLastError());
   }
+}
+
+// YartStats of a finished render (ms_total is the caller's); cnt: the device counters, renderedSamples: per pixel
+YartStats makeStats(const YartScene& s, const RenderPlan& pl, const StageTimers& t, const unsigned long long* cnt, float msAll,
+                    uint32_t waves, uint64_t renderedSamples) {
+  YartStats st{};
+  st.samples = uint64_t(pl.nPix) * renderedSamples;
+  st.rays = cnt[0];
+  st.traversals = cnt[1]; st.box_tests = cnt[2]; st.tri_tests = cnt[3]; st.shaded_hits = cnt[4];
+  st.ms_device = msAll;
+  st.ms_traverse = pl.mega ? t.mega.ms : t.extend.ms + t.connect.ms;
+  st.launches_traverse = pl.mega ? t.mega.launches : t.extend.launches + t.connect.launches;
+  st.ms_extend = t.extend.ms; st.ms_shade = t.shade.ms; st.ms_connect = t.connect.ms; st.ms_gmon = t.gmon.ms;
+  st.ms_extend_lean = t.lean.ms; st.launches_extend_lean = t.lean.launches;
+  st.lean_traversals = cnt[5]; st.lean_box_tests = cnt[6]; st.lean_tri_tests = cnt[7];
+  st.ms_shade_kernel = t.shadeK.ms; st.launches_shade_kernel = t.shadeK.launches;
+  st.ms_shadow_lean = t.shadowLean.ms; st.launches_shadow_lean = t.shadowLean.launches;
+  st.shadow_lean_traversals = cnt[24]; st.shadow_lean_box_tests = cnt[25]; st.shadow_lean_tri_tests = cnt[26];
+  st.shade_entries = cnt[28]; st.retry_extend_traversals = cnt[29]; st.retry_shadow_traversals = cnt[30];
+  st.pipeline_flags = pl.effFlags;
+  {
+    unsigned long long paths[16] = {0};
+    HIP_CHECK(hipMemcpy(paths, s.pathsLog.p, sizeof(paths), hipMemcpyDeviceToHost));
+    for (int b = 0; b < 16; b++) st.paths_at_bounce[b] = paths[b];
+    st.paths_at_bounce[0] = pl.mega || pl.pool ? 0 : uint64_t(pl.nPix) * renderedSamples;     // (every path enters bounce 0)
+  }
+#if defined(YART_COUNT_TRAVERSAL)
+  {
+    unsigned long long tb = 0;
+    HIP_CHECK(hipMemcpyFromSymbol(&tb, HIP_SYMBOL(g_texTapBytes), sizeof(tb)));
+    tb += tu::texTapRead1() + tu::texTapRead2() + tu::texTapRead3() + tu::texTapRead4();
+    st.texture_tap_bytes = tb;
+  }
+#endif
+  st.launches_extend = t.extend.launches; st.launches_connect = t.connect.launches;
+  st.waves = waves;
+  return st;
+}
+
+// Plan, buffers, sampler tables; then wave by wave (resumable accumulation: only the waves inside [start_sample, stop_sample))
+// and batch by batch through the plan's pipeline; then the finish kernels and the statistics. true: the hook stopped the render.
+bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRenderParams& p, float* dOut,
+                    hipStream_t stream, YartStats* stats, const BatchHook* hook = nullptr, const YartAovBuffers* aov = nullptr,
+                    const YartMomentBuffers* mom = nullptr) {
+  bool aborted = false;
+  auto wall0 = std::chrono::high_resolution_clock::now();
+  TraceRange rgRender("yart:render");
+  HIP_CHECK(hipSetDevice(s.device));
+  buildPixelList(s, camDesc.width, camDesc.height, p.shard_tile ? p.shard_tile : p.tile_size, p.rank, p.world_size);
+  const uint64_t startSample = p.start_sample, stopSample = p.stop_sample ? p.stop_sample : p.samples;
+  if (startSample == 0) HIP_CHECK(hipMemsetAsync(dOut, 0, size_t(camDesc.width) * camDesc.height * 4 * sizeof(float), stream));
+  s.cursor.ensure(1); s.counters.ensure(kNumCounters); s.pathsLog.ensure(16);
+  HIP_CHECK(hipMemsetAsync(s.pathsLog.p, 0, 16 * sizeof(unsigned long long), stream));
+  HIP_CHECK(hipMemsetAsync(s.counters.p, 0, kNumCounters * sizeof(unsigned long long), stream));
+#if defined(YART_COUNT_TRAVERSAL)
+  { const unsigned long long zero = 0; HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_texTapBytes), &zero, sizeof(zero))); tu::texTapReset1(); tu::texTapReset2(); tu::texTapReset3(); tu::texTapReset4(); }
+#endif
+  RenderPlan pl = makeRenderPlan(s, camDesc, p, aov, mom, stream);
+  prepareBuffers(s, pl, stream);
+
+  Timer tAll;
+  StageTimers t;
+  uint32_t waves = 0;
+  uint64_t renderedSamples = 0;
+  HIP_CHECK(hipEventRecord(tAll.a, stream));
+  launchSamplerTables(s, pl, t, stream);
+  const auto runBatch = pl.mega ? runMegaBatch : pl.pool ? runPoolBatch : runWavefrontBatch;
+
+  for (WaveSchedule ws(p.samples, p.first_wave_samples, p.max_wave_samples); !aborted && ws.next();) {
+    // resumable accumulation: waves outside [start_sample, stop_sample) are not rendered by this call
+    const bool inRange = ws.takenBefore >= startSample && ws.takenBefore < stopSample;
+    if (!inRange && ws.takenBefore < startSample && ws.takenAfter > startSample) throw std::invalid_argument("start_sample is not a wave boundary");
+    if (inRange && ws.takenAfter > stopSample) throw std::invalid_argument("stop_sample is not a wave boundary");
+    if (!inRange) continue;
+    waves++; renderedSamples += ws.samples;
+    WaveInfo w{uint32_t(ws.wave), uint32_t(ws.takenAfter), float(ws.takenBefore) / float(ws.takenAfter), float(ws.samples) / float(ws.takenAfter), 0};
+    for (uint32_t c0 = 0; !aborted && c0 < pl.nPix; c0 += pl.chunk) {
+      const Batch b{c0, std::min(pl.chunk, pl.nPix - c0), uint32_t(ws.samples), uint32_t(ws.takenBefore)};
+      runBatch(s, pl, b, t, stream);
+      aborted = finishBatch(s, pl, b, w, dOut, t, hook, stream);
+    }
+  }
+  if (!aborted) launchFinishKernels(s, pl, stream);
   HIP_CHECK(hipEventRecord(tAll.b, stream));
   HIP_CHECK(hipEventSynchronize(tAll.b));
   float msAll = 0; HIP_CHECK(hipEventElapsedTime(&msAll, tAll.a, tAll.b));
@@ -1267,37 +1351,7 @@ bool renderToDevice(YartScene& s, const YartCameraDesc& camDesc, const YartRende
   HIP_CHECK(hipMemcpy(cnt, s.counters.p, sizeof(cnt), hipMemcpyDeviceToHost));
   for (int i = 0; i < kNumCounters; i++) s.lastCounters[i] = cnt[i];
   if (stats) {
-    *stats = YartStats{};
-    stats->samples = uint64_t(nPix) * renderedSamples;
-    stats->rays = cnt[0];
-    stats->traversals = cnt[1]; stats->box_tests = cnt[2]; stats->tri_tests = cnt[3]; stats->shaded_hits = cnt[4];
-    stats->ms_device = msAll;
-    stats->ms_traverse = mega ? tMega.ms : tExtend.ms + tConnect.ms;
-    stats->launches_traverse = mega ? tMega.launches : tExtend.launches + tConnect.launches;
-    stats->ms_extend = tExtend.ms; stats->ms_shade = tShade.ms; stats->ms_connect = tConnect.ms; stats->ms_gmon = tGmon.ms;
-    stats->ms_extend_lean = tLean.ms; stats->launches_extend_lean = tLean.launches;
-    stats->lean_traversals = cnt[5]; stats->lean_box_tests = cnt[6]; stats->lean_tri_tests = cnt[7];
-    stats->ms_shade_kernel = tShadeK.ms; stats->launches_shade_kernel = tShadeK.launches;
-    stats->ms_shadow_lean = tShadowLean.ms; stats->launches_shadow_lean = tShadowLean.launches;
-    stats->shadow_lean_traversals = cnt[24]; stats->shadow_lean_box_tests = cnt[25]; stats->shadow_lean_tri_tests = cnt[26];
-    stats->shade_entries = cnt[28]; stats->retry_extend_traversals = cnt[29]; stats->retry_shadow_traversals = cnt[30];
-    stats->pipeline_flags = effFlags;
-    {
-      unsigned long long pl[16] = {0};
-      HIP_CHECK(hipMemcpy(pl, s.pathsLog.p, sizeof(pl), hipMemcpyDeviceToHost));
-      for (int b = 0; b < 16; b++) stats->paths_at_bounce[b] = pl[b];
-      stats->paths_at_bounce[0] = mega || pool ? 0 : uint64_t(nPix) * renderedSamples;     // (every path enters bounce 0)
-    }
-#if defined(YART_COUNT_TRAVERSAL)
-    {
-      unsigned long long tb = 0;
-      HIP_CHECK(hipMemcpyFromSymbol(&tb, HIP_SYMBOL(g_texTapBytes), sizeof(tb)));
-      tb += tu::texTapRead1() + tu::texTapRead2() + tu::texTapRead3() + tu::texTapRead4();
-      stats->texture_tap_bytes = tb;
-    }
-#endif
-    stats->launches_extend = tExtend.launches; stats->launches_connect = tConnect.launches;
-    stats->waves = waves;
+    *stats = makeStats(s, pl, t, cnt, msAll, waves, renderedSamples);
     stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - wall0).count();
   }
   return aborted;
@@ -1428,26 +1482,7 @@ int yart_hip_render(YartScene* scene, const YartCameraDesc* cam, const YartRende
 // build's size; false: nothing is requested (a plain render)
 static bool checkAovs(const YartAovBuffers* in, const YartCameraDesc* cam, const YartRenderParams* params, YartAovBuffers& out) {
   out = YartAovBuffers{};
-  if (in) {
-    require(in->struct_size >= 2 * sizeof(uint32_t), "YartAovBuffers.struct_size is too small for the struct's head");
-    require((in->mask & ~YART_AOV_ALL) == 0u, "YartAovBuffers.mask has bits that are no YART_AOV_* value");
-    const struct { uint32_t bit; size_t off; const char* null; } fields[] = {
-        {YART_AOV_ALBEDO, offsetof(YartAovBuffers, albedo), "YART_AOV_ALBEDO is requested and YartAovBuffers.albedo is null"},
-        {YART_AOV_NORMAL, offsetof(YartAovBuffers, normal), "YART_AOV_NORMAL is requested and YartAovBuffers.normal is null"},
-        {YART_AOV_POSITION, offsetof(YartAovBuffers, position), "YART_AOV_POSITION is requested and YartAovBuffers.position is null"},
-        {YART_AOV_DEPTH, offsetof(YartAovBuffers, depth), "YART_AOV_DEPTH is requested and YartAovBuffers.depth is null"},
-        {YART_AOV_COVERAGE, offsetof(YartAovBuffers, coverage), "YART_AOV_COVERAGE is requested and YartAovBuffers.coverage is null"},
-        {YART_AOV_IDS, offsetof(YartAovBuffers, ids), "YART_AOV_IDS is requested and YartAovBuffers.ids is null"},
-        {YART_AOV_RAYS, offsetof(YartAovBuffers, rays), "YART_AOV_RAYS is requested and YartAovBuffers.rays is null"}};
-    for (const auto& f : fields) {
-      if (!(in->mask & f.bit)) continue;
-      require(in->struct_size >= f.off + sizeof(void*), "YartAovBuffers.struct_size ends before a buffer the mask requests");
-      void* ptr = *reinterpret_cast<void* const*>(reinterpret_cast<const char*>(in) + f.off);
-      require(ptr != nullptr, f.null);
-      *reinterpret_cast<void**>(reinterpret_cast<char*>(&out) + f.off) = ptr;
-    }
-    out.struct_size = uint32_t(sizeof(YartAovBuffers)); out.mask = in->mask;
-  }
+  if (in) checkAndCopyBuffers(kAovTable, *in, out);
   validate(cam, params);
   if (out.mask != 0u)
     require(params->start_sample == 0 && (params->stop_sample == 0 || params->stop_sample == params->samples),
@@ -1459,22 +1494,7 @@ static bool checkAovs(const YartAovBuffers* in, const YartCameraDesc* cam, const
 // build's size; false: nothing is requested
 static bool checkMoments(const YartMomentBuffers* in, const YartRenderParams* params, YartMomentBuffers& out) {
   out = YartMomentBuffers{};
-  if (in) {
-    require(in->struct_size >= 2 * sizeof(uint32_t), "YartMomentBuffers.struct_size is too small for the struct's head");
-    require((in->mask & ~YART_MOMENT_ALL) == 0u, "YartMomentBuffers.mask has bits that are no YART_MOMENT_* value");
-    const struct { uint32_t bit; size_t off; const char* null; } fields[] = {
-        {YART_MOMENT_MEAN, offsetof(YartMomentBuffers, mean), "YART_MOMENT_MEAN is requested and YartMomentBuffers.mean is null"},
-        {YART_MOMENT_VARIANCE, offsetof(YartMomentBuffers, variance), "YART_MOMENT_VARIANCE is requested and YartMomentBuffers.variance is null"},
-        {YART_MOMENT_COUNT, offsetof(YartMomentBuffers, count), "YART_MOMENT_COUNT is requested and YartMomentBuffers.count is null"}};
-    for (const auto& f : fields) {
-      if (!(in->mask & f.bit)) continue;
-      require(in->struct_size >= f.off + sizeof(void*), "YartMomentBuffers.struct_size ends before a buffer the mask requests");
-      void* ptr = *reinterpret_cast<void* const*>(reinterpret_cast<const char*>(in) + f.off);
-      require(ptr != nullptr, f.null);
-      *reinterpret_cast<void**>(reinterpret_cast<char*>(&out) + f.off) = ptr;
-    }
-    out.struct_size = uint32_t(sizeof(YartMomentBuffers)); out.mask = in->mask;
-  }
+  if (in) checkAndCopyBuffers(kMomentTable, *in, out);
   if (out.mask != 0u && params)
     require(params->start_sample == 0 && (params->stop_sample == 0 || params->stop_sample == params->samples),
             "sample moments need the full sample range (start_sample = 0, stop_sample = 0 or samples)");
@@ -1514,48 +1534,22 @@ int yart_hip_render_moments(YartScene* scene, const YartCameraDesc* cam, const Y
     const size_t wh = size_t(cam->width) * cam->height, n = wh * 4;
     scene->hdr.ensure(n);
     if (params->start_sample > 0) HIP_CHECK(hipMemcpy(scene->hdr.p, out_rgba, n * sizeof(float), hipMemcpyHostToDevice));
-    // the requested buffers side by side in one device allocation (4-byte words: 3, 3, 3, 1, 1, 4, 1 per pixel)
-    const struct { uint32_t bit; size_t words; size_t off; } fields[] = {
-        {YART_AOV_ALBEDO, 3, offsetof(YartAovBuffers, albedo)}, {YART_AOV_NORMAL, 3, offsetof(YartAovBuffers, normal)},
-        {YART_AOV_POSITION, 3, offsetof(YartAovBuffers, position)}, {YART_AOV_DEPTH, 1, offsetof(YartAovBuffers, depth)},
-        {YART_AOV_COVERAGE, 1, offsetof(YartAovBuffers, coverage)}, {YART_AOV_IDS, 4, offsetof(YartAovBuffers, ids)},
-        {YART_AOV_RAYS, 1, offsetof(YartAovBuffers, rays)}};
+    // the requested buffers side by side in one device allocation each (render_host.hpp: kAovTable, kMomentTable)
     YartAovBuffers dev = host;
     if (any) {
-      size_t words = 0;
-      for (const auto& f : fields) if (host.mask & f.bit) words += f.words * wh;
-      scene->aovOut.ensure(words);
-      size_t at = 0;
-      for (const auto& f : fields) if (host.mask & f.bit) {
-        *reinterpret_cast<void**>(reinterpret_cast<char*>(&dev) + f.off) = scene->aovOut.p + at;
-        at += f.words * wh;
-      }
+      scene->aovOut.ensure(layOutBuffers(kAovTable, host.mask, wh, nullptr, dev));
+      layOutBuffers(kAovTable, host.mask, wh, scene->aovOut.p, dev);
     }
-    // the moments likewise (3, 1, 1 words per pixel)
-    const struct { uint32_t bit; size_t words; size_t off; } fieldsM[] = {
-        {YART_MOMENT_MEAN, 3, offsetof(YartMomentBuffers, mean)}, {YART_MOMENT_VARIANCE, 1, offsetof(YartMomentBuffers, variance)},
-        {YART_MOMENT_COUNT, 1, offsetof(YartMomentBuffers, count)}};
     YartMomentBuffers devM = hostM;
     if (anyM) {
-      size_t words = 0;
-      for (const auto& f : fieldsM) if (hostM.mask & f.bit) words += f.words * wh;
-      scene->momOut.ensure(words);
-      size_t at = 0;
-      for (const auto& f : fieldsM) if (hostM.mask & f.bit) {
-        *reinterpret_cast<void**>(reinterpret_cast<char*>(&devM) + f.off) = scene->momOut.p + at;
-        at += f.words * wh;
-      }
+      scene->momOut.ensure(layOutBuffers(kMomentTable, hostM.mask, wh, nullptr, devM));
+      layOutBuffers(kMomentTable, hostM.mask, wh, scene->momOut.p, devM);
     }
     renderToDevice(*scene, *cam, *params, scene->hdr.p, nullptr, stats, nullptr, any ? &dev : nullptr, anyM ? &devM : nullptr);
     HIP_CHECK(hipMemcpy(out_rgba, scene->hdr.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    if (any)
-      for (const auto& f : fields) if (host.mask & f.bit)
-        HIP_CHECK(hipMemcpy(*reinterpret_cast<void**>(reinterpret_cast<char*>(&host) + f.off),
-                            *reinterpret_cast<void**>(reinterpret_cast<char*>(&dev) + f.off), f.words * wh * 4, hipMemcpyDeviceToHost));
-    if (anyM)
-      for (const auto& f : fieldsM) if (hostM.mask & f.bit)
-        HIP_CHECK(hipMemcpy(*reinterpret_cast<void**>(reinterpret_cast<char*>(&hostM) + f.off),
-                            *reinterpret_cast<void**>(reinterpret_cast<char*>(&devM) + f.off), f.words * wh * 4, hipMemcpyDeviceToHost));
+    const auto toHost = [](void* dst, const void* src, size_t bytes) { HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); };
+    if (any) copyBuffers(kAovTable, host, dev, wh, toHost);
+    if (anyM) copyBuffers(kMomentTable, hostM, devM, wh, toHost);
     if (stats)
       stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
   });
@@ -1667,12 +1661,9 @@ static int renderProgressive(YartScene* scene, const YartCameraDesc* cam, const 
     if (params->start_sample > 0) HIP_CHECK(hipMemcpy(scene->hdr.p, out_rgba, n * sizeof(float), hipMemcpyHostToDevice));
     else if (on_tile) std::memset(out_rgba, 0, n * sizeof(float));       // tiles arrive one by one: the rest of the frame is defined
     YartStats total{};
-    // the wave schedule of tile-renderer.hpp:264-289 (renderToDevice walks the same one): w0 = min(first, samples),
-    // then min(2 w, max) — a first wave of one sample is followed by another single one
-    uint64_t remaining = params->samples, wave = 0;
-    uint64_t waveSamples = std::min<uint64_t>(params->first_wave_samples, params->samples);
-    while (waveSamples > 0 && !aborted) {
-      const uint32_t taken = uint32_t(params->samples - remaining);
+    for (WaveSchedule ws(params->samples, params->first_wave_samples, params->max_wave_samples); !aborted && ws.next();) {
+      const uint32_t taken = uint32_t(ws.takenBefore);
+      const uint64_t wave = ws.wave, waveSamples = ws.samples;
       if (taken >= params->start_sample && taken < stop) {
         YartRenderParams q = *params;
         q.start_sample = taken; q.stop_sample = uint32_t(taken + waveSamples);
@@ -1710,10 +1701,6 @@ static int renderProgressive(YartScene* scene, const YartCameraDesc* cam, const 
         else if (on_wave && on_wave(user, &st, uint32_t(wave), uint32_t(waveSamples), uint32_t(taken + waveSamples), params->samples) != 0)
           aborted = true;
       }
-      remaining -= waveSamples;
-      const uint64_t next = (wave > 0 || waveSamples > 1) ? std::min<uint64_t>(waveSamples * 2, params->max_wave_samples) : 1;
-      waveSamples = std::min(next, remaining);
-      wave++;
     }
     total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
     if (stats) *stats = total;
@@ -2165,6 +2152,15 @@ struct YartTemporal {
 };
 namespace {
 struct TpCall { TpConst k; bool demodulate; YartAovBuffers aovs; };
+// the feature buffers an accumulate call reads, in the order they are checked and staged (albedo: with YART_TEMPORAL_DEMODULATE only)
+struct TemporalField { uint32_t bit; bool demodulateOnly; const char* missing; };
+constexpr TemporalField kTemporalFields[] = {
+    {YART_AOV_POSITION, false, "temporal: the position feature buffer (YART_AOV_POSITION) is missing"},
+    {YART_AOV_NORMAL, false, "temporal: the normal feature buffer (YART_AOV_NORMAL) is missing"},
+    {YART_AOV_DEPTH, false, "temporal: the depth feature buffer (YART_AOV_DEPTH) is missing"},
+    {YART_AOV_COVERAGE, false, "temporal: the coverage feature buffer (YART_AOV_COVERAGE) is missing"},
+    {YART_AOV_IDS, false, "temporal: the ids feature buffer (YART_AOV_IDS) is missing"},
+    {YART_AOV_ALBEDO, true, "temporal: YART_TEMPORAL_DEMODULATE without an albedo feature buffer (YART_AOV_ALBEDO)"}};
 uint32_t temporalMinMomentHistory(const YartTemporalParams&) { return 0u; }
 uint32_t temporalMinMomentHistory(const YartTemporalMomentParams& p) { return p.min_moment_history; }
 
@@ -2191,22 +2187,9 @@ TpCall temporalCheck(const YartTemporal* t, const YartCameraDesc* cam, const voi
   require(cam->focal_length > 0.0f, "temporal: camera: bad focal length");
   TpCall c{};
   c.demodulate = (params->flags & YART_TEMPORAL_DEMODULATE) != 0u;
-  require(aovs->struct_size >= 2 * sizeof(uint32_t), "temporal: YartAovBuffers.struct_size is too small for the struct's head");
-  require((aovs->mask & ~YART_AOV_ALL) == 0u, "temporal: YartAovBuffers.mask has bits that are no YART_AOV_* value");
-  const struct { uint32_t bit; size_t off; bool needed; const char* missing; } fields[] = {
-      {YART_AOV_POSITION, offsetof(YartAovBuffers, position), true, "temporal: the position feature buffer (YART_AOV_POSITION) is missing"},
-      {YART_AOV_NORMAL, offsetof(YartAovBuffers, normal), true, "temporal: the normal feature buffer (YART_AOV_NORMAL) is missing"},
-      {YART_AOV_DEPTH, offsetof(YartAovBuffers, depth), true, "temporal: the depth feature buffer (YART_AOV_DEPTH) is missing"},
-      {YART_AOV_COVERAGE, offsetof(YartAovBuffers, coverage), true, "temporal: the coverage feature buffer (YART_AOV_COVERAGE) is missing"},
-      {YART_AOV_IDS, offsetof(YartAovBuffers, ids), true, "temporal: the ids feature buffer (YART_AOV_IDS) is missing"},
-      {YART_AOV_ALBEDO, offsetof(YartAovBuffers, albedo), c.demodulate, "temporal: YART_TEMPORAL_DEMODULATE without an albedo feature buffer (YART_AOV_ALBEDO)"}};
-  for (const auto& f : fields) {
-    if (!f.needed) continue;
-    require((aovs->mask & f.bit) != 0u && aovs->struct_size >= f.off + sizeof(void*), f.missing);
-    void* ptr = *reinterpret_cast<void* const*>(reinterpret_cast<const char*>(aovs) + f.off);
-    require(ptr != nullptr, f.missing);
-    *reinterpret_cast<void**>(reinterpret_cast<char*>(&c.aovs) + f.off) = ptr;
-  }
+  checkBufferHead(kAovTable, *aovs, "temporal: ");
+  for (const TemporalField& f : kTemporalFields)
+    if (!f.demodulateOnly || c.demodulate) require(takeBufferField(*aovs, kAovTable.field(f.bit), c.aovs), f.missing);
   c.k.alphaMin = params->alpha_min; c.k.normalCosMin = params->normal_cos_min; c.k.planeTolerance = params->plane_tolerance;
   c.k.maxHistory = params->max_history;
   c.k.minMomentHistory = temporalMinMomentHistory(*params);
@@ -2320,9 +2303,10 @@ int temporalAccumulateHost(YartTemporal* temporal, const YartCameraDesc* cam, co
     };
     float* dFrame = put(rgba, 4);
     float* dVar = put(variance, 1);
-    c.aovs.position = put(c.aovs.position, 3); c.aovs.normal = put(c.aovs.normal, 3); c.aovs.depth = put(c.aovs.depth, 1);
-    c.aovs.coverage = put(c.aovs.coverage, 1); c.aovs.ids = reinterpret_cast<int32_t*>(put(c.aovs.ids, 4));
-    c.aovs.albedo = put(c.demodulate ? c.aovs.albedo : nullptr, 3);
+    for (const TemporalField& tf : kTemporalFields) {        // (albedo without YART_TEMPORAL_DEMODULATE: null in c.aovs, room but no copy)
+      const BufferField& f = kAovTable.field(tf.bit);
+      setFieldPtr(c.aovs, f, put(fieldPtr(c.aovs, f), f.words));
+    }
     uint32_t* dLen = reinterpret_cast<uint32_t*>(put(nullptr, 1));
     temporalRun<MOMENTS>(*temporal, c, *cam, dFrame, dVar, dFrame, dVar, dLen, nullptr);
     HIP_CHECK(hipMemcpy(out_rgba, dFrame, n * 16, hipMemcpyDeviceToHost));
