@@ -152,7 +152,7 @@ typedef struct YartRenderParams {
 
 #define YART_FLAG_MEGAKERNEL 1u     /* single-kernel integrator instead of the wavefront pipeline */
 #define YART_FLAG_NO_REFILL 16u     /* one-ray-per-lane lean kernels instead of the ones with in-wave ray
-                                       replacement (trace_lean.hpp) */
+                                       replacement (csrc/trace_lean.hpp: traceLean) */
 #define YART_FLAG_SHADE_SORT 2u     /* bucket each wave's 256 shade-queue entries by lobe class before shading them: the default
                                        since round 2 (measured: shade stage -8.4 % on the McLaren-class scene, -0.5 % on the
                                        Sponza-class one; round 1 bucketed by material index and lost 5 % there) */

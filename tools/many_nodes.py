@@ -1,5 +1,5 @@
 """GPU-box measurement: cost of scenes with many scene-graph nodes (instanced meshes) — the lean kernels' per-ray pass over
-the node boxes is linear in the node count (trace_lean.hpp part (A); chunked form from 64 nodes on)."""
+the node boxes is linear in the node count (trace_lean.hpp part (A), the kNodesMask form; the kNodesChunked form from 64 nodes on)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

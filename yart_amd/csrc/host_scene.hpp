@@ -506,10 +506,10 @@ inline HostImage buildHostImage(const YartSceneDesc& d, MeshBvhFn bvhFn = nullpt
       h[c] = finite ? float(mx[c] + pad) : kInf;
     }
     // .w of the pair: bits of the node's pre-order subtree [i, skip) as a 64-bit mask (scenes of fewer than
-    // 64 nodes; trace_lean.hpp keeps a per-ray candidate mask)
+    // 64 nodes; the kNodesMask form of trace_lean.hpp keeps a per-ray candidate mask)
     uint64_t sub = 0;
     if (nn < 64) for (uint32_t k = i; k < nd.skip; k++) sub |= 1ull << k;
-    // scenes of 64 nodes and more (trace_lean_chunked.hpp walks the node list per lane): lo.w = the node's skip link, so a
+    // scenes of 64 nodes and more (the kNodesWalk form of trace_lean.hpp walks the node list per lane): lo.w = the node's skip link, so a
     // missed box needs no second load
     const uint32_t subLo = nn < 64 ? uint32_t(sub) : nd.skip, subHi = uint32_t(sub >> 32);
     std::memcpy(&lo.w, &subLo, 4); std::memcpy(&hi.w, &subHi, 4);
@@ -518,7 +518,7 @@ inline HostImage buildHostImage(const YartSceneDesc& d, MeshBvhFn bvhFn = nullpt
 
   // ---- spatial hierarchy over the mesh nodes' padded world boxes (scenes of 64 nodes and more): median splits of the box
   // centres along the widest axis, one node per leaf. Any tree would do: a ray's query only has to return every mesh node whose
-  // box it hits (trace_lean_tlas.hpp), the exact tests then run in the reference's pre-order.
+  // box it hits (the kNodesTlas form of trace_lean.hpp), the exact tests then run in the reference's pre-order.
   if (nn >= 64) {
     std::vector<uint32_t> ids;
     for (uint32_t i = 0; i < nn; i++) if (im.nodes[i].mesh >= 0) ids.push_back(i);

@@ -195,7 +195,7 @@ struct SceneDev {
   const float* envData;
   const uint32_t* envGuide;
   const f4* nodeWorld;       // 2 per scene node: padded WORLD-space AABB of the node's subtree (min, max)
-  // scenes of many nodes (trace_lean_tlas.hpp): a spatial hierarchy over the mesh nodes' nodeWorld boxes — a filter only, the
+  // scenes of many nodes (trace_lean.hpp, kNodesTlas): a spatial hierarchy over the mesh nodes' nodeWorld boxes — a filter only, the
   // exact tests still run in the reference's pre-order — and the lanes' node bitsets (scratch, set per launch): nodeBitWords
   // 64-bit words per lane, word w of thread t at nodeBits[w * threads + t]
   const struct TlasNode* tlas;

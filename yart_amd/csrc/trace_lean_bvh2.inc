@@ -1,4 +1,4 @@
-// trace_lean_bvh2.inc — part (C) of the lean tracers (traceLean / Chunked / Walk / Tlas): the while-while BVH
+// trace_lean_bvh2.inc — part (C) of the lean tracer (trace_lean.hpp::traceLean, its only include site): the while-while BVH
 // traversal, step for step and test for test the reference's (cpu/ray-integrator.cpp:84-160: near child first,
 // far child pushed with its entry distance, pop-cull d < hit.t, leaf triangles in index order), written for the
 // scalar unit: the step is straight-line, the lane state the loop changes is integers in VGPRs (cur = link word,
@@ -109,7 +109,7 @@
           else if (stackIdx == 0u || (NEE && kFast && meshDidHit && !meshHasAlpha)) live = 0u;
           else stackPop(stk, --stackIdx, cur, d);
         }
-        if (uint32_t(__popcll(__ballot(live != 0u))) < 64u - kRefillHere + 1u) break;
+        if (uint32_t(__popcll(__ballot(live != 0u))) < 64u - kRefill + 1u) break;
       }
 #undef LEAN2_VISIT
       // lanes that left their BVH in this round (testBVH returned, or the ray goes to the general kernel)

@@ -76,7 +76,7 @@ typedef __attribute__((address_space(3))) uint64_t lds_u64;
 #else
 typedef uint64_t lds_u64;
 #endif
-// Walks the lean kernels hand to the general ones are RESUMED, not restarted (trace_lean.hpp): one record per handed-over ray.
+// Walks the lean kernels hand to the general ones are RESUMED, not restarted (trace_lean.hpp, the kNodesMask forms): one record per handed-over ray.
 //   word 0: path slot, scene node, flags (bit 0 didHit, bit 1 meshDidHit, bits 8.. stack entries), link word of the leaf
 //   word 1: the leaf's entry distance, hit.t, candidate mask      word 2 (closest-hit rays that have a hit): hit.u, hit.v, hit.tri,
 //   hit.node | hit.backSide << 20                                  words 3..10: the traversal stack, two entries per word

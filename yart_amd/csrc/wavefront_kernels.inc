@@ -158,7 +158,7 @@ __device__ __forceinline__ void samplerToLds(SamplerConfig& c, SamplerLds& l, bo
 }
 constexpr uint32_t kLeanSceneNodes = 16;
 struct LeanSceneLds { uint32_t node[kLeanSceneNodes * sizeof(NodeDev) / 4], world[kLeanSceneNodes * 8], mesh[kLeanSceneNodes * sizeof(MeshDev) / 4]; };
-// (NODES == 4: the host has checked that the scene fits — the copies' being in LDS is then known at compile time: ds_read with constant
+// (NODES == kNodesMaskLds: the host has checked that the scene fits — the copies' being in LDS is then known at compile time: ds_read with constant
 // addresses instead of flat loads through pointers that might be either; extend lean 65.7 -> 62.0 ms, shadow lean 67.0 -> 63.7)
 __device__ __forceinline__ void leanSceneToLds(SceneDev& sc, LeanSceneLds& l, uint32_t nMeshes) {
   ldsCopyWords(l.node, sc.nodes, sc.nNodes * uint32_t(sizeof(NodeDev) / 4));
@@ -381,8 +381,8 @@ __global__ void __launch_bounds__(kBlock, leanWaves(MODE)) k_wf_extend_lean(WfAr
   WfTally tally;
   const WfState st = a.st;
   stk.rec = a.resumeRec; stk.recCursor = &a.counters[WC_RESUME]; stk.recCap = a.resumeCap;
-  __shared__ __attribute__((aligned(16))) LeanSceneLds sceneLds;        // (used by the NODES == 4 form only)
-  if (NODES == 4) leanSceneToLds(a.sc, sceneLds, a.sc.nMeshes);
+  __shared__ __attribute__((aligned(16))) LeanSceneLds sceneLds;        // (used by the kNodesMaskLds form only)
+  if (NODES == kNodesMaskLds) leanSceneToLds(a.sc, sceneLds, a.sc.nMeshes);
   traceLeanAny<false, MODE, NODES>(a.sc, a.rc.sampler, stk, a.qA, a.counters[WC_ACTIVE], &a.counters[WC_CUR_EXTEND],
       [&](uint32_t slot) {
         const f4 r0 = wfLd(st.ray0 + slot), r1 = wfLd(st.ray1 + slot);
@@ -416,8 +416,8 @@ __global__ void __launch_bounds__(kBlock, leanWaves(MODE)) k_wf_shadow_lean(WfAr
   const WfState st = a.st;
   uint32_t nRays = 0;
   stk.rec = a.resumeRec; stk.recCursor = &a.counters[WC_RESUME]; stk.recCap = a.resumeCap;
-  __shared__ __attribute__((aligned(16))) LeanSceneLds sceneLds;        // (used by the NODES == 4 form only)
-  if (NODES == 4) leanSceneToLds(a.sc, sceneLds, a.sc.nMeshes);
+  __shared__ __attribute__((aligned(16))) LeanSceneLds sceneLds;        // (used by the kNodesMaskLds form only)
+  if (NODES == kNodesMaskLds) leanSceneToLds(a.sc, sceneLds, a.sc.nMeshes);
   traceLeanAny<true, MODE, NODES>(a.sc, a.rc.sampler, stk, a.qS, a.counters[WC_SHADOW], &a.counters[WC_CUR_SHADOW],
       [&](uint32_t slot) {
         const f4 r0 = wfLd(st.ray0 + slot), s0 = wfLd(st.sh0 + slot);
@@ -456,8 +456,8 @@ __global__ void __launch_bounds__(kBlock, YART_RETRY_WAVES) k_wf_extend_retry_le
   WfTally tally;
   const WfState st = a.st;
   stk.rec = a.resumeRec; stk.recCursor = &a.counters[WC_RESUME]; stk.recCap = a.resumeCap;
-  __shared__ __attribute__((aligned(16))) LeanSceneLds sceneLds;        // (used by the NODES == 4 form only)
-  if (NODES == 4) leanSceneToLds(a.sc, sceneLds, a.sc.nMeshes);
+  __shared__ __attribute__((aligned(16))) LeanSceneLds sceneLds;        // (used by the kNodesMaskLds form only)
+  if (NODES == kNodesMaskLds) leanSceneToLds(a.sc, sceneLds, a.sc.nMeshes);
   __shared__ uint64_t sHash[264];                          // the alpha tests' draws read one hashDim value each
   if (a.rc.sampler.tab.hash != nullptr && a.rc.sampler.tab.dims + 3u <= 264u) {
     for (uint32_t k = threadIdx.x; k < a.rc.sampler.tab.dims + 3u; k += blockDim.x) sHash[k] = a.rc.sampler.tab.hash[k];
@@ -496,8 +496,8 @@ __global__ void __launch_bounds__(kBlock, YART_RETRY_WAVES) k_wf_shadow_retry_le
   const WfState st = a.st;
   uint32_t nRays = 0;
   stk.rec = a.resumeRec; stk.recCursor = &a.counters[WC_RESUME]; stk.recCap = a.resumeCap;
-  __shared__ __attribute__((aligned(16))) LeanSceneLds sceneLds;        // (used by the NODES == 4 form only)
-  if (NODES == 4) leanSceneToLds(a.sc, sceneLds, a.sc.nMeshes);
+  __shared__ __attribute__((aligned(16))) LeanSceneLds sceneLds;        // (used by the kNodesMaskLds form only)
+  if (NODES == kNodesMaskLds) leanSceneToLds(a.sc, sceneLds, a.sc.nMeshes);
   __shared__ uint64_t sHash[264];                          // the alpha tests' draws read one hashDim value each
   if (a.rc.sampler.tab.hash != nullptr && a.rc.sampler.tab.dims + 3u <= 264u) {
     for (uint32_t k = threadIdx.x; k < a.rc.sampler.tab.dims + 3u; k += blockDim.x) sHash[k] = a.rc.sampler.tab.hash[k];

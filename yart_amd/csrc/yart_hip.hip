@@ -43,9 +43,6 @@
 #include "gltf_reader.hpp"
 #include "wavefront.hpp"
 #include "trace_lean.hpp"
-#include "trace_lean_chunked.hpp"
-#include "trace_lean_walk.hpp"
-#include "trace_lean_tlas.hpp"
 #include "tonemap.hpp"
 #include "denoise.hpp"
 #include "temporal.hpp"
@@ -419,25 +416,24 @@ static size_t spillDepthFor(const HostImage& im, bool wholeStack) {
 namespace yart_hip { namespace tu {
 typedef void (*AnyKernel)();
 #define YART_ANY(K) reinterpret_cast<AnyKernel>(static_cast<void (*)(WfArgs)>(K))
-#define YART_PICK_LEAN(KERNEL, M)                                                                                             \
-  (nodesForm == 4 ? (ident ? YART_ANY((KERNEL<(M) | TRAV_IDENTITY, 4>)) : YART_ANY((KERNEL<(M), 4>)))                         \
-   : nodesForm == 3 ? (ident ? YART_ANY((KERNEL<(M) | TRAV_IDENTITY, 3>)) : YART_ANY((KERNEL<(M), 3>)))                       \
-   : nodesForm == 2 ? (ident ? YART_ANY((KERNEL<(M) | TRAV_IDENTITY, 2>)) : YART_ANY((KERNEL<(M), 2>)))                       \
-   : nodesForm == 1 ? (ident ? YART_ANY((KERNEL<(M) | TRAV_IDENTITY, 1>)) : YART_ANY((KERNEL<(M), 1>)))                       \
-                    : (ident ? YART_ANY((KERNEL<(M) | TRAV_IDENTITY, 0>)) : YART_ANY((KERNEL<(M), 0>))))
+#define YART_LEAN_FORM(KERNEL, M, N) (ident ? YART_ANY((KERNEL<(M) | TRAV_IDENTITY, N>)) : YART_ANY((KERNEL<(M), N>)))
+#define YART_PICK_LEAN(KERNEL, M)                                                                        \
+  (nodesForm == kNodesMaskLds ? YART_LEAN_FORM(KERNEL, M, kNodesMaskLds)                                 \
+   : nodesForm == kNodesTlas ? YART_LEAN_FORM(KERNEL, M, kNodesTlas)                                     \
+   : nodesForm == kNodesWalk ? YART_LEAN_FORM(KERNEL, M, kNodesWalk)                                     \
+   : nodesForm == kNodesChunked ? YART_LEAN_FORM(KERNEL, M, kNodesChunked)                               \
+                                : YART_LEAN_FORM(KERNEL, M, kNodesMask))
+#define YART_PICK_RETRY(KERNEL)                                                                          \
+  (nodesForm == kNodesMaskLds ? YART_ANY(KERNEL<kNodesMaskLds>) : nodesForm == kNodesTlas ? YART_ANY(KERNEL<kNodesTlas>)   \
+   : nodesForm == kNodesWalk ? YART_ANY(KERNEL<kNodesWalk>) : nodesForm == kNodesChunked ? YART_ANY(KERNEL<kNodesChunked>) \
+                                                                                         : YART_ANY(KERNEL<kNodesMask>))
 #if YART_TU == 1
 AnyKernel extendLean(int nodesForm, bool ident) { return YART_PICK_LEAN(k_wf_extend_lean, TRAV_FAST); }
 #elif YART_TU == 2
 AnyKernel shadowLean(int nodesForm, bool ident) { return YART_PICK_LEAN(k_wf_shadow_lean, TRAV_FAST); }
 #elif YART_TU == 3
-AnyKernel extendRetry(int nodesForm) {
-  return nodesForm == 4 ? YART_ANY(k_wf_extend_retry_lean<4>) : nodesForm == 3 ? YART_ANY(k_wf_extend_retry_lean<3>)
-       : nodesForm == 2 ? YART_ANY(k_wf_extend_retry_lean<2>) : nodesForm == 1 ? YART_ANY(k_wf_extend_retry_lean<1>) : YART_ANY(k_wf_extend_retry_lean<0>);
-}
-AnyKernel shadowRetry(int nodesForm) {
-  return nodesForm == 4 ? YART_ANY(k_wf_shadow_retry_lean<4>) : nodesForm == 3 ? YART_ANY(k_wf_shadow_retry_lean<3>)
-       : nodesForm == 2 ? YART_ANY(k_wf_shadow_retry_lean<2>) : nodesForm == 1 ? YART_ANY(k_wf_shadow_retry_lean<1>) : YART_ANY(k_wf_shadow_retry_lean<0>);
-}
+AnyKernel extendRetry(int nodesForm) { return YART_PICK_RETRY(k_wf_extend_retry_lean); }
+AnyKernel shadowRetry(int nodesForm) { return YART_PICK_RETRY(k_wf_shadow_retry_lean); }
 AnyKernel extendFast(bool ident) { return ident ? YART_ANY((k_wf_extend_fast<TRAV_FAST | TRAV_IDENTITY>)) : YART_ANY(k_wf_extend_fast<TRAV_FAST>); }
 AnyKernel shadowFast(bool ident) { return ident ? YART_ANY((k_wf_shadow_fast<TRAV_FAST | TRAV_IDENTITY>)) : YART_ANY(k_wf_shadow_fast<TRAV_FAST>); }
 AnyKernel extendGeneral(bool retry) { return retry ? YART_ANY(k_wf_extend<true>) : YART_ANY(k_wf_extend<false>); }
@@ -455,7 +451,9 @@ void shadeRegionsTake(unsigned long long* v48) {          // (measurement builds
 }
 #endif
 #endif
+#undef YART_PICK_RETRY
 #undef YART_PICK_LEAN
+#undef YART_LEAN_FORM
 #undef YART_ANY
 #if defined(YART_COUNT_TRAVERSAL)
 // (instrumented build: every unit tallies the texel bytes of ITS kernels' lookups; unit 0 sums them)
@@ -837,15 +835,16 @@ RenderPlan makeRenderPlan(YartScene& s, const YartCameraDesc& camDesc, const Yar
   pl.general = (p.flags & YART_FLAG_GENERAL_TRACE) != 0;
   const bool ident = s.host.allIdentity;
   pl.refill = (p.flags & YART_FLAG_NO_REFILL) == 0;
-  // trace_lean.hpp keeps one 64-bit node candidate mask per ray and uses the all-ones mask as its "new ray"
-  // marker, which a ray that can reach all of exactly 64 nodes would keep: 64 nodes and more go to the chunked form
+  // the kNodesMask form of trace_lean.hpp keeps one 64-bit node candidate mask per ray and uses the all-ones mask as its "new ray"
+  // marker, which a ray that can reach all of exactly 64 nodes would keep: 64 nodes and more go to the windowed forms
   const bool chunked = s.host.nodes.size() >= 64;
-  // 64 nodes and more: candidate windows from the top-level hierarchy (3; measured the fastest form at every size from 65 to 4252
+  // 64 nodes and more: candidate windows from the top-level hierarchy (kNodesTlas; measured the fastest form at every size from 65 to 4252
   // nodes, profiles/r2_many_nodes.txt). Without it (no mesh nodes, more than 16384 nodes = 2 KB of bitset per lane, or debug bit
-  // 262144): chunked masks below kLeanWalkNodes nodes, the per-lane walk from there on (debug bit 65536: the walk at any size)
+  // 262144): chunked masks (kNodesChunked) below kLeanWalkNodes nodes, the per-lane walk (kNodesWalk) from there on (debug bit 65536: the walk at any size)
   const bool tlasOk = s.dev.nTlas != 0u && s.host.nodes.size() <= 16384u && !(pl.effFlags & (262144u | 65536u));
   const bool leanLds = !chunked && s.host.nodes.size() <= kLeanSceneNodes && s.host.meshes.size() <= kLeanSceneNodes;
-  pl.nodesForm = !chunked ? (leanLds ? 4 : 0) : tlasOk ? 3 : ((pl.effFlags & 65536u) || s.host.nodes.size() >= kLeanWalkNodes) ? 2 : 1;
+  pl.nodesForm = !chunked ? (leanLds ? kNodesMaskLds : kNodesMask) : tlasOk ? kNodesTlas
+               : ((pl.effFlags & 65536u) || s.host.nodes.size() >= kLeanWalkNodes) ? kNodesWalk : kNodesChunked;
   pl.kExtendFast = wfKernel(pl.refill ? tu::extendLean(pl.nodesForm, ident) : tu::extendFast(ident));
   pl.kShadowFast = wfKernel(pl.refill ? tu::shadowLean(pl.nodesForm, ident) : tu::shadowFast(ident));
   pl.kRetryE = wfKernel(tu::extendRetry(pl.nodesForm));
@@ -873,8 +872,8 @@ RenderPlan makeRenderPlan(YartScene& s, const YartCameraDesc& camDesc, const Yar
   pl.gridMax = std::max(pl.gridMax, std::max(pl.gridExtendFast, pl.gridShadowFast));
   pl.gridMax = std::max(pl.gridMax, std::max(pl.gridRetryE, pl.gridRetryS));
   s.spill.ensure(size_t(pl.gridMax) * kBlock * spillDepthFor(s.host, true));
-  // the lanes' node bitsets of the top-level-hierarchy form (trace_lean_tlas.hpp): all zero between launches
-  pl.nodeBitWords = pl.nodesForm == 3 ? uint32_t((s.host.nodes.size() + 63u) / 64u) : 0u;
+  // the lanes' node bitsets of the top-level-hierarchy form (kNodesTlas, trace_lean.hpp): all zero between launches
+  pl.nodeBitWords = pl.nodesForm == kNodesTlas ? uint32_t((s.host.nodes.size() + 63u) / 64u) : 0u;
   if (pl.nodeBitWords) {
     const size_t need = size_t(pl.gridMax) * kBlock * pl.nodeBitWords;
     if (s.nodeBits.n < need) { s.nodeBits.ensure(need); HIP_CHECK(hipMemsetAsync(s.nodeBits.p, 0, need * 8, stream)); }
