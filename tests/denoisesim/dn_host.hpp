@@ -2,7 +2,7 @@
 // variance-guided one), never part of libyart_hip.so.
 //
 // yart_amd/csrc/denoise.hpp — the arithmetic of the à-trous filter that the device kernels call — compiled as host C++ and driven
-// the way yart_hip.hip drives the kernels: prepare pass, the iterations between two working images, finish pass, with the library's
+// the way csrc/postprocess.inc drives the kernels: prepare pass, the iterations between two working images, finish pass, with the library's
 // 48 bytes per pixel. VAR chooses the form, as in denoise.hpp.
 //   in:  9 words {u32 width, height, iterations, flags, guides (1 albedo | 2 normal | 4 depth), in_place,
 //                 f32 sigma_color (VAR: sigma_luma), sigma_normal, sigma_depth}, then the frame (w*h*4 f32), with VAR the variance

@@ -9,7 +9,7 @@
 //                          the host path tracer per sample (csrc/integrator.hpp samplePixel, as tests/hostsim `render` runs it: one
 //                          wave, the GMoN estimator) with every sample also reduced by csrc/moments.hpp.
 //                          frame out: w * h * 4 f32 — the very frame hostsim `render` writes; moments out: per pixel 5 words as above
-//   denoisevar <in> <out>  csrc/denoise.hpp's variance-guided filter, driven the way yart_hip.hip drives the kernels
+//   denoisevar <in> <out>  csrc/denoise.hpp's variance-guided filter, driven the way csrc/postprocess.inc drives the kernels
 //                          (tests/denoisesim/dn_host.hpp, which states the file format).
 #include <algorithm>
 #include <atomic>

@@ -2,7 +2,7 @@
 //
 // The product's device headers compiled as host C++ (as tests/hostsim, tests/aovsim, tests/denoisesim and tests/momentsim
 // compile them):
-//   accumulate <in> <out>   csrc/temporal.hpp over a sequence of frames, driven the way yart_hip.hip drives the kernel (two history
+//   accumulate <in> <out>   csrc/temporal.hpp over a sequence of frames, driven the way csrc/postprocess.inc drives the kernel (two history
 //                           images of three record planes, the previous frame's camera through makeCamera / tpCamera).
 //                           in: 9 words {u32 width, height, frames, flags (1 demodulate), in_place, max_history, f32 alpha_min,
 //                           normal_cos_min, plane_tolerance}, then per frame {u32 reset_before, YartCameraDesc (17 words), rgba

@@ -1,7 +1,7 @@
 // temporalsim_moments.cpp — TEST INFRASTRUCTURE for tests/test_temporal_moments.py, never part of libyart_hip.so.
 //
 // The moments form of the temporal accumulation (csrc/temporal.hpp: tpAccumulatePixel<true>, then tpSpatialVariance) compiled as
-// host C++ over a sequence of frames, driven the way yart_hip.hip drives the two kernels: two history images of four record planes,
+// host C++ over a sequence of frames, driven the way csrc/postprocess.inc drives the two kernels: two history images of four record planes,
 // the previous frame's camera through makeCamera / tpCamera, pass 2 over the whole image after pass 1 has written all of it.
 //
 //   temporalsim_moments <in> <out>

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Instruction mix of the kernels in a device assembly file (hipcc ... -S --offload-device-only -o x.s yart_hip.hip):
+"""Instruction mix of the kernels in a device assembly file (hipcc ... -S --offload-device-only -o x.s yart_hip.hip, or
+-DYART_TU=1..4 ... wavefront_units.hip for the path kernels):
 per kernel, static counts by class (VALU / transcendental-and-quarter-rate / fp64 / SALU / VMEM / LDS / scratch) and
 the register / scratch figures of its .amdhsa block.   tools/isa_stats.py x.s [kernel-substring ...]"""
 import re

@@ -1,5 +1,5 @@
 // bvh_build_device.inc — the reference's binned-SAH BVH build (core/bvh.hpp:41-184, 273-347) on the device, with the
-// node array and the index permutation of bvh_build.hpp byte for byte (included by yart_hip.hip; SURVEY §8(f) rank 3).
+// node array and the index permutation of bvh_build.hpp byte for byte (included by yart_hip.hip, unit 0; SURVEY §8(f) rank 3).
 //
 // Why an exact device build is possible at all: every quantity the reference's recursion decides on is either an
 // order-free fold (bounds are min / max folds, bin counts are integer sums) or a function of one node's index range, and

@@ -1,5 +1,5 @@
 // denoise_kernels.inc — edge-avoiding à-trous filter (yart_hip_denoise_atrous_* and yart_hip_denoise_atrous_var_*), device side
-// (included by yart_hip.hip, unit 0, next to aov_kernels.inc). The arithmetic is denoise.hpp; the definition is the header comment
+// (included by postprocess.inc, unit 0, with the filter's host driver and entries). The arithmetic is denoise.hpp; the definition is the header comment
 // of include/yart_hip.h. VAR chooses the form (denoise.hpp): false the plain filter, true the variance-guided one. Both forms have
 // the same passes, tiles and 48 bytes per pixel: the variance travels in the fourth word of the working colour (where the plain
 // filter keeps the valid flag), so a tap is two aligned 16-byte loads in either; the 3 x 3 Gaussian of the variance reads nine words

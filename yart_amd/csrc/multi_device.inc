@@ -1,4 +1,4 @@
-// multi_device.inc — several GPUs of one node behind one C-ABI handle (included by yart_hip.hip).
+// multi_device.inc — several GPUs of one node behind one C-ABI handle (included by yart_hip.hip, unit 0).
 //
 // Stands where the reference's worker pool stands: TileRenderer::renderImpl starts `threadCount` threads that pull
 // tiles (tile-renderer.hpp:150-197) and finishTile merges every finished tile into the one m_hdrBuffer (:225-241).

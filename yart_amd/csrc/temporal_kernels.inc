@@ -1,5 +1,5 @@
 // temporal_kernels.inc — temporal accumulation with camera reprojection (yart_hip_temporal_*), device side (included by
-// yart_hip.hip, unit 0, after denoise_kernels.inc whose 16-byte load / store it uses). The arithmetic is temporal.hpp; the
+// postprocess.inc, unit 0, after denoise_kernels.inc whose 16-byte load / store it uses). The arithmetic is temporal.hpp; the
 // definition is the header comment of include/yart_hip.h.
 //
 //   k_tp_accumulate   one lane per pixel in the 16 x 16 tile of k_dn_atrous<0>: reads the pixel's frame, variance and feature

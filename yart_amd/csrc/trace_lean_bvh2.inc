@@ -1,4 +1,4 @@
-// trace_lean_bvh2.inc — part (C) of the lean tracer (trace_lean.hpp::traceLean, its only include site): the while-while BVH
+// trace_lean_bvh2.inc — part (C) of the lean tracer (trace_lean.hpp::traceLean, its only include site; every unit): the while-while BVH
 // traversal, step for step and test for test the reference's (cpu/ray-integrator.cpp:84-160: near child first,
 // far child pushed with its entry distance, pop-cull d < hit.t, leaf triangles in index order), written for the
 // scalar unit: the step is straight-line, the lane state the loop changes is integers in VGPRs (cur = link word,

@@ -1,4 +1,4 @@
-// trace_lean_scene.inc — part (B) of the lean tracer (trace_lean.hpp::traceLean): the scene-graph walk of the lanes that stand
+// trace_lean_scene.inc — part (B) of the lean tracer (trace_lean.hpp::traceLean, which includes it twice; every unit): the scene-graph walk of the lanes that stand
 // between two meshes, to the point where each of them has entered a mesh, finished its ray or (kNodesChunked, kNodesTlas)
 // stands before its next candidate window. One text for all forms: each form's way to the next node it has to look at
 // comes first, under `if constexpr`, then the node visit all forms share.

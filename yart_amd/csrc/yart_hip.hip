@@ -1,4 +1,4 @@
-// yart_hip.hip — gfx950 kernels and the C ABI of libyart_hip.so.
+// yart_hip.hip — unit 0 of libyart_hip.so: the frame kernels, the host side of a render and the C ABI.
 //
 // Stands where reference cpu/tile-renderer.hpp:118-309 (TileRenderer::renderImpl /
 // finishTile) and cpu/integrator.cpp:5-28 (Integrator::render) stand: tiles of the
@@ -12,18 +12,27 @@
 //                   64 paths at a time from an atomic cursor; LDS traversal stack.
 //   k_gmon_blend    one wave = one pixel: bucket sums in sample order, GMoN value,
 //                   blend into the HDR buffer (integrator.cpp:17-25, tile-renderer.hpp:220-232).
-//   k_probe_*       diagnostics used by the parity tests.
-// The wavefront (queue-based) pipeline lives in wavefront_kernels.inc.
-// This file is compiled five times (csrc/Makefile), YART_TU selecting what a translation unit emits — the kernels are templates and
-// instantiate where they are referenced, so the five objects build in parallel and each holds its share of the device code:
-//   0  the C ABI, host orchestration, and every kernel not named below (streaming passes, megakernel, probes, BVH build)
-//   1  the lean closest-hit kernels k_wf_extend_lean<MODE, NODES>          2  the lean any-hit kernels k_wf_shadow_lean<MODE, NODES>
-//   3  the general kernels: retry (resumed walks), one-ray-per-lane lean and general forms        4  the shade kernel k_wf_shade<SORT, FIT, ENV1>
-// Units 1-4 export their kernels as type-erased host stubs (yart_hip::tu::*, below); unit 0 launches them through those pointers.
-#ifndef YART_TU
-#define YART_TU 0
-#endif
-#include <hip/hip_runtime.h>
+//   k_tile_rays     ray counts per pixel block (tile callbacks);  k_tex_quads  the textures' 2x2 footprint records, at upload.
+// Host side in this file: YartScene and its upload, the render plan, the batch runners and the wave loop (renderToDevice), and the
+// scene, render, multi-device, debug and BVH entries of the C ABI.
+//
+// The library is five translation units (csrc/Makefile), so that the device code builds in parallel. Which file a unit compiles
+// decides what it emits; every kernel is emitted in exactly one unit:
+//   unit 0     yart_hip.hip (this file), with
+//                stream_kernels.inc     the streaming passes of the wavefront pipelines and the sampler tables
+//                aov_kernels.inc, moment_kernels.inc, bvh_build_device.inc      feature buffers, sample moments, the device BVH build
+//                multi_device.inc       several GPUs behind one handle, with its pixel pack / unpack / copy kernels
+//                postprocess.inc        tonemap / encode, the a-trous denoiser (denoise_kernels.inc) and temporal accumulation
+//                                       (temporal_kernels.inc): kernels, drivers and entries
+//                probes.inc             the diagnostic kernels k_probe_* and the yart_hip_probe_* entries
+//   units 1-4  wavefront_units.hip under -DYART_TU=1..4: the path kernels, which are templates and are emitted where they are
+//              instantiated — 1 the lean closest-hit kernels k_wf_extend_lean<MODE, NODES>, 2 the lean any-hit kernels
+//              k_wf_shadow_lean<MODE, NODES>, 3 the retry (resumed walks), one-ray-per-lane lean and general kernels, 4 the shade
+//              kernel k_wf_shade<SORT, FIT, ENV1>
+//   all five   hip_common.hpp (constants, HIP_CHECK, DevBuf), wavefront_kernels.inc (WfArgs, the queue helpers, the path
+//              kernels' templates: unit 0 needs the types and instantiates none) and kernel_units.hpp (yart_hip::tu: the
+//              type-erased host stubs through which unit 0 launches the kernels of units 1-4)
+#include "hip_common.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -43,63 +52,23 @@
 #include "gltf_reader.hpp"
 #include "wavefront.hpp"
 #include "trace_lean.hpp"
-#include "tonemap.hpp"
-#include "denoise.hpp"
-#include "temporal.hpp"
 #include "moments.hpp"
 #include "trace_ranges.hpp"
+#include "kernel_units.hpp"
 
 using namespace yart_hip;
 
 namespace {
 
-constexpr int kBlock = 256;            // 4 waves per workgroup
-#ifndef YART_STREAM_BLOCKS
-#define YART_STREAM_BLOCKS 8           // workgroups per CU of the streaming kernels (generate, post, compact); shade + post stage at 1080p x 64 spp: 4 -> 105.5, 8 -> 106.1, 16 -> 106.4, 32 -> 106.6 ms
-#endif
-constexpr int kLdsStack = 24;          // traversal stack entries kept in LDS per lane (8 B each)
-constexpr int kSpillDepth = int(kRefStackDepth) - kLdsStack;
-constexpr int kSpillDepthMax = int(kRefStackDepth);   // spill area sized for the shallowest LDS stack
 constexpr uint64_t kDefaultBatchPaths = 1ull << 28;   // YartRenderParams::max_batch_paths = 0: 268 M paths (batch-synchronous: 67 GB; path pool: 4.3 GB of per-sample records)
 constexpr uint64_t kDefaultPoolPaths = 1ull << 25;    // YartRenderParams::pool_paths = 0: 33.5 M slots, 5.6 GB
 constexpr int kPoolLag = 4;                            // the host looks at the counters of the round before the previous one (ring of 4)
-constexpr int kNumCounters = 32;       // [0] rays, [1..4] instrumented tallies, [8..31] debug statistics
 
 thread_local std::string g_lastError;
-
-struct HipError : std::runtime_error { using std::runtime_error::runtime_error; };
-#define HIP_CHECK(expr)                                                                     \
-  do {                                                                                      \
-    hipError_t _e = (expr);                                                                 \
-    if (_e != hipSuccess)                                                                   \
-      throw HipError(std::string(#expr) + ": " + hipGetErrorString(_e));                    \
-  } while (0)
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-  void ensure(size_t count) {
-    if (count <= n) return;
-    release();
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)));
-    n = count;
-  }
-  void upload(const std::vector<T>& v) {
-    ensure(std::max<size_t>(v.size(), 1));
-    if (!v.empty()) HIP_CHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  }
-};
 
 // ---------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------
-#if YART_TU == 0
 struct MegaArgs {
   SceneDev sc;
   CameraDev cam;
@@ -246,114 +215,6 @@ __global__ void __launch_bounds__(64) k_tile_rays(const uint32_t* pixRays, const
   if (threadIdx.x == 0) out[t] = r;
 }
 
-// AgX tonemap of an RGBA32F frame (alpha kept as 1, tile-renderer.hpp:234-237) and the 8-bit
-// encoding of output/ppm.cpp; one lane per pixel, 16 B in / 16 B (or 3 B) out: HBM-bound.
-__global__ void __launch_bounds__(kBlock) k_tonemap_agx(const f4* in, f4* out, uint32_t n, int look) {
-  const AgxLook lk = agxLook(look);
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const f4 v = in[i];
-    const f3 c = agxTonemap(mk3(v.x, v.y, v.z), lk);
-    f4 o; o.x = c.x; o.y = c.y; o.z = c.z; o.w = 1.0f;
-    out[i] = o;
-  }
-}
-__global__ void __launch_bounds__(kBlock) k_encode_rgb8(const f4* in, uint8_t* out, uint32_t n) {
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const f4 v = in[i];
-    out[3 * size_t(i)] = ppmByte(v.x); out[3 * size_t(i) + 1] = ppmByte(v.y); out[3 * size_t(i) + 2] = ppmByte(v.z);
-  }
-}
-
-struct ProbeSampleArgs {
-  SceneDev sc; CameraDev cam; RenderConst rc;
-  const uint32_t* xys; uint32_t n; float* out; unsigned long long* rays; uint64_t* spill;
-};
-__global__ void __launch_bounds__(kBlock) k_probe_samples(ProbeSampleArgs a) {
-  __shared__ uint64_t ldsStack[kLdsStack * kBlock];
-  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
-  PathCtx cx;
-  cx.sc = &a.sc;
-  cx.sobol = reinterpret_cast<const uint32_t*>(a.sc.lut + LutDev::sobol);
-  cx.stk.lds = (lds_u64*)(ldsStack + threadIdx.x); cx.stk.ldsStride = kBlock; cx.stk.ldsDepth = kLdsStack;
-  cx.stk.spill = a.spill + gtid; cx.stk.spillStride = gridDim.x * blockDim.x;
-  cx.rc = a.rc;
-  if (gtid >= a.n) return;
-  uint32_t rays = 0;
-  f3 L = samplePixel(cx, a.cam, a.xys[gtid * 3], a.xys[gtid * 3 + 1], a.xys[gtid * 3 + 2], rays);
-  a.out[gtid * 3] = L.x; a.out[gtid * 3 + 1] = L.y; a.out[gtid * 3 + 2] = L.z;
-  atomicAdd(a.rays, (unsigned long long) rays);
-}
-
-// the sampler alone (diagnostic): per case startPixelSample + a pattern of draws (1 = get1D, 2 = get2D); with `tab` set the
-// draws go through the per-render sampler tables exactly as the wavefront kernels' do
-struct ProbeSamplerArgs { SamplerConfig cfg; const uint32_t* sobol; const uint32_t* cases; uint32_t n, nDraws, nOut, pad; const uint8_t* pattern; float* out; };
-__global__ void __launch_bounds__(kBlock) k_probe_sampler(ProbeSamplerArgs a) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= a.n) return;
-  Sampler s;
-  startPixelSample(s, a.cfg, a.cases[3 * i], a.cases[3 * i + 1], a.cases[3 * i + 2]);
-  s.pix = i;                                                 // (sampler tables: one pixel column per case)
-  float* o = a.out + size_t(i) * a.nOut;
-  for (uint32_t k = 0; k < a.nDraws; k++) {
-    if (a.pattern[k] == 2) { const f2 v = get2D(s, a.cfg, a.sobol); *o++ = v.x; *o++ = v.y; }
-    else *o++ = get1D(s, a.cfg);
-  }
-}
-
-struct ProbeHitArgs { SceneDev sc; const float* rays; uint32_t n; float* out; uint64_t* spill; };
-__global__ void __launch_bounds__(kBlock) k_probe_hits(ProbeHitArgs a) {
-  __shared__ uint64_t ldsStack[kLdsStack * kBlock];
-  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
-  TravStack stk;
-  stk.lds = (lds_u64*)(ldsStack + threadIdx.x); stk.ldsStride = kBlock; stk.ldsDepth = kLdsStack;
-  stk.spill = a.spill + gtid; stk.spillStride = gridDim.x * blockDim.x;
-  if (gtid >= a.n) return;
-  const float* r = a.rays + size_t(gtid) * 6;
-  f3 o = mk3(r[0], r[1], r[2]), d = mk3(r[3], r[4], r[5]);
-  HitRec hr; hr.t = kInf; hr.u = hr.v = 0; hr.tri = 0; hr.node = 0; hr.backSide = 0;
-  f3 att = mk3(1.0f);
-  Sampler dummy; dummy.dim = 0; dummy.morton = 0;
-  AlphaCtx ac; ac.sampler = &dummy; ac.cfg.log2spp = 0; ac.cfg.nBase4Digits = 6;
-  bool hit = traverseScene<false>(a.sc, o, d, 0.001f, hr, att, stk, ac);
-  float* q = a.out + size_t(gtid) * 16;
-  for (int i = 0; i < 16; i++) q[i] = 0.0f;
-  q[0] = hit ? 1.0f : 0.0f;
-  if (hit) {
-    Hit h = finalizeHit(a.sc, hr, o, d);
-    q[1] = h.t; q[2] = hr.u; q[3] = hr.v;
-    q[4] = h.p.x; q[5] = h.p.y; q[6] = h.p.z; q[7] = h.n.x; q[8] = h.n.y; q[9] = h.n.z;
-    q[10] = h.tg.x; q[11] = h.tg.y; q[12] = h.tg.z;
-    q[13] = float(localTri(a.sc, hr)); q[14] = float(h.lightIdx); q[15] = h.backSide ? 1.0f : 0.0f;
-  }
-}
-
-// the math the frames rest on, one function at a time (diagnostic, yart_hip_probe_math[_pairs]): the very inline functions the
-// render kernels call (ymath.hpp, libm_pow.hpp via tonemap.hpp) and the fp32 divide / sqrt / bit reversal as this build compiles them
-struct ProbeMathArgs { int fn; uint32_t firstBits; uint64_t n; float y; const float* a; const float* b; float* out; };
-YART_HD float probeMathEval(int fn, float a, float b) {   // (host + device only so that the host pass resolves the names)
-  switch (fn) {
-    case YART_MATH_SINF: return ysinf(a);
-    case YART_MATH_COSF: return ycosf(a);
-    case YART_MATH_SINF_2PI: return ysinf2pi(a);
-    case YART_MATH_COSF_2PI: return ycosf2pi(a);
-    case YART_MATH_LOGF: return ylogf(a);
-    case YART_MATH_EXPF: return yexpf(a);
-    case YART_MATH_LOG2F: return ylog2f(a);
-    case YART_MATH_POWF: return ypowf(a, b);
-    case YART_MATH_DIV: return a / b;
-    case YART_MATH_SQRT: return sqrtf(a);
-    default: return __builtin_bit_cast(float, reverseBits32(__builtin_bit_cast(uint32_t, a)));   // YART_MATH_BREV
-  }
-}
-__global__ void __launch_bounds__(kBlock) k_probe_math(ProbeMathArgs q) {
-  const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
-  for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < q.n; i += stride) {
-    const float a = q.a ? q.a[i] : __builtin_bit_cast(float, q.firstBits + uint32_t(i));
-    const float b = q.b ? q.b[i] : q.y;
-    q.out[i] = probeMathEval(q.fn, a, b);
-  }
-}
-
 // 2x2 footprint records of one texture (scene_types.hpp TexDev::quadOffset), expanded on the device at upload from the plain
 // texel arrays: record (x, y) = the four taps texture.cpp:21-35 reads for a lookup whose base texel is (x, y)
 struct TexQuadArgs { const uint8_t* u8; const float* f32; TexDev t; uint8_t* out; };
@@ -386,17 +247,12 @@ __global__ void __launch_bounds__(kBlock) k_tex_quads(TexQuadArgs a) {
   }
 }
 
-#endif  // YART_TU == 0
-
-#include "wavefront_kernels.inc"
-#if YART_TU == 0
+#include "wavefront_kernels.inc"     // what every unit shares, and the path kernels' templates (instantiated in units 1-4 only)
+#include "stream_kernels.inc"
 #include "aov_kernels.inc"
 #include "moment_kernels.inc"
-#include "denoise_kernels.inc"
-#include "temporal_kernels.inc"
 #include "bvh_build_device.inc"
 
-namespace {
 static_assert(devbvh::kMaxLevels == int(kMaxStackBound), "the stack bound's cap is the device builder's level limit");
 // Spill entries per lane for a scene: what they always were (the reference's 64-entry stack) unless one of the scene's trees
 // needs more (host_scene.hpp: HostImage::stackBound, at most kMaxStackBound — deeper meshes do not get past scene creation).
@@ -407,86 +263,7 @@ static size_t spillDepthFor(const HostImage& im, bool wholeStack) {
   return size_t(std::max<int>(kSpillDepth, int(im.stackBound) - kLdsStack));
 }
 }  // namespace
-#endif
-
-#if YART_TU != 0
-}  // namespace
-
-// the kernels of this unit, for unit 0 (function pointers to the host stubs; the argument type is the same struct in every unit)
-namespace yart_hip { namespace tu {
-typedef void (*AnyKernel)();
-#define YART_ANY(K) reinterpret_cast<AnyKernel>(static_cast<void (*)(WfArgs)>(K))
-#define YART_LEAN_FORM(KERNEL, M, N) (ident ? YART_ANY((KERNEL<(M) | TRAV_IDENTITY, N>)) : YART_ANY((KERNEL<(M), N>)))
-#define YART_PICK_LEAN(KERNEL, M)                                                                        \
-  (nodesForm == kNodesMaskLds ? YART_LEAN_FORM(KERNEL, M, kNodesMaskLds)                                 \
-   : nodesForm == kNodesTlas ? YART_LEAN_FORM(KERNEL, M, kNodesTlas)                                     \
-   : nodesForm == kNodesWalk ? YART_LEAN_FORM(KERNEL, M, kNodesWalk)                                     \
-   : nodesForm == kNodesChunked ? YART_LEAN_FORM(KERNEL, M, kNodesChunked)                               \
-                                : YART_LEAN_FORM(KERNEL, M, kNodesMask))
-#define YART_PICK_RETRY(KERNEL)                                                                          \
-  (nodesForm == kNodesMaskLds ? YART_ANY(KERNEL<kNodesMaskLds>) : nodesForm == kNodesTlas ? YART_ANY(KERNEL<kNodesTlas>)   \
-   : nodesForm == kNodesWalk ? YART_ANY(KERNEL<kNodesWalk>) : nodesForm == kNodesChunked ? YART_ANY(KERNEL<kNodesChunked>) \
-                                                                                         : YART_ANY(KERNEL<kNodesMask>))
-#if YART_TU == 1
-AnyKernel extendLean(int nodesForm, bool ident) { return YART_PICK_LEAN(k_wf_extend_lean, TRAV_FAST); }
-#elif YART_TU == 2
-AnyKernel shadowLean(int nodesForm, bool ident) { return YART_PICK_LEAN(k_wf_shadow_lean, TRAV_FAST); }
-#elif YART_TU == 3
-AnyKernel extendRetry(int nodesForm) { return YART_PICK_RETRY(k_wf_extend_retry_lean); }
-AnyKernel shadowRetry(int nodesForm) { return YART_PICK_RETRY(k_wf_shadow_retry_lean); }
-AnyKernel extendFast(bool ident) { return ident ? YART_ANY((k_wf_extend_fast<TRAV_FAST | TRAV_IDENTITY>)) : YART_ANY(k_wf_extend_fast<TRAV_FAST>); }
-AnyKernel shadowFast(bool ident) { return ident ? YART_ANY((k_wf_shadow_fast<TRAV_FAST | TRAV_IDENTITY>)) : YART_ANY(k_wf_shadow_fast<TRAV_FAST>); }
-AnyKernel extendGeneral(bool retry) { return retry ? YART_ANY(k_wf_extend<true>) : YART_ANY(k_wf_extend<false>); }
-AnyKernel shadowGeneral(bool retry) { return retry ? YART_ANY(k_wf_shadow<true>) : YART_ANY(k_wf_shadow<false>); }
-#elif YART_TU == 4
-AnyKernel shade(bool sort, bool fit, bool env1) {
-  return sort ? (env1 ? YART_ANY((k_wf_shade<true, true, true>)) : fit ? YART_ANY((k_wf_shade<true, true, false>)) : YART_ANY((k_wf_shade<true, false, false>)))
-              : (env1 ? YART_ANY((k_wf_shade<false, true, true>)) : fit ? YART_ANY((k_wf_shade<false, true, false>)) : YART_ANY((k_wf_shade<false, false, false>)));
-}
-#if defined(YART_SHADE_REGIONS)
-void shadeRegionsTake(unsigned long long* v48) {          // (measurement builds: the kernel's region counters live in this unit)
-  (void)hipMemcpyFromSymbol(v48, HIP_SYMBOL(g_shadeRegion), 48 * sizeof(unsigned long long));
-  const unsigned long long zero[48] = {0};
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_shadeRegion), zero, sizeof(zero));
-}
-#endif
-#endif
-#undef YART_PICK_RETRY
-#undef YART_PICK_LEAN
-#undef YART_LEAN_FORM
-#undef YART_ANY
-#if defined(YART_COUNT_TRAVERSAL)
-// (instrumented build: every unit tallies the texel bytes of ITS kernels' lookups; unit 0 sums them)
-#define YART_CAT2(a, b) a##b
-#define YART_CAT(a, b) YART_CAT2(a, b)
-void YART_CAT(texTapReset, YART_TU)() { const unsigned long long zero = 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_texTapBytes), &zero, sizeof(zero)); }
-unsigned long long YART_CAT(texTapRead, YART_TU)() { unsigned long long v = 0; (void)hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_texTapBytes), sizeof(v)); return v; }
-#endif
-}}  // namespace yart_hip::tu
-
-#else  // YART_TU == 0: everything below
-
-}  // namespace
 #include "render_host.hpp"     // (host only: the wave schedule and the buffer tables)
-namespace yart_hip { namespace tu {
-typedef void (*AnyKernel)();
-AnyKernel extendLean(int nodesForm, bool ident);
-AnyKernel shadowLean(int nodesForm, bool ident);
-AnyKernel extendRetry(int nodesForm);
-AnyKernel shadowRetry(int nodesForm);
-AnyKernel extendFast(bool ident);
-AnyKernel shadowFast(bool ident);
-AnyKernel extendGeneral(bool retry);
-AnyKernel shadowGeneral(bool retry);
-AnyKernel shade(bool sort, bool fit, bool env1);
-#if defined(YART_SHADE_REGIONS)
-void shadeRegionsTake(unsigned long long* v48);
-#endif
-#if defined(YART_COUNT_TRAVERSAL)
-void texTapReset1(); void texTapReset2(); void texTapReset3(); void texTapReset4();
-unsigned long long texTapRead1(); unsigned long long texTapRead2(); unsigned long long texTapRead3(); unsigned long long texTapRead4();
-#endif
-}}
 namespace {
 typedef void (*WfKernelFn)(WfArgs);
 inline WfKernelFn wfKernel(yart_hip::tu::AnyKernel k) { return reinterpret_cast<WfKernelFn>(k); }
@@ -1559,89 +1336,6 @@ int yart_hip_render_aovs(YartScene* scene, const YartCameraDesc* cam, const Yart
   return yart_hip_render_moments(scene, cam, params, out_rgba, aovs, nullptr, stats);
 }
 
-// Diagnostic: the moment kernels on caller-supplied per-sample records (no scene), one accumulate launch per chunk
-int yart_hip_probe_moments(const float* L_rgba, uint32_t n_pixels, uint32_t spp, const uint32_t* chunks, uint32_t n_chunks,
-                           float exposure_scale, float* mean, float* variance, uint32_t* count) {
-  return guarded([&] {
-    require(L_rgba && chunks && mean && variance && count, "probe_moments: null pointer");
-    require(n_pixels > 0 && spp > 0 && n_chunks > 0, "probe_moments: n_pixels, spp or n_chunks is 0");
-    require(uint64_t(n_pixels) * spp <= (1ull << 26), "probe_moments: more than 2^26 records");
-    uint64_t sum = 0;
-    for (uint32_t c = 0; c < n_chunks; c++) { require(chunks[c] > 0, "probe_moments: an empty chunk"); sum += chunks[c]; }
-    require(sum == spp, "probe_moments: the chunks do not sum to spp");
-    int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0) throw HipError("no HIP device");
-    DevBuf<f4> L; DevBuf<MomentState> state; DevBuf<float> dMean, dVar; DevBuf<uint32_t> dCount;
-    uint32_t largest = 0;
-    for (uint32_t c = 0; c < n_chunks; c++) largest = std::max(largest, chunks[c]);
-    L.ensure(size_t(n_pixels) * largest); state.ensure(n_pixels); dMean.ensure(size_t(n_pixels) * 3); dVar.ensure(n_pixels); dCount.ensure(n_pixels);
-    HIP_CHECK(hipMemset(state.p, 0, size_t(n_pixels) * sizeof(MomentState)));
-    std::vector<f4> wave(size_t(n_pixels) * largest);
-    const f4* all = reinterpret_cast<const f4*>(L_rgba);
-    uint32_t s0 = 0;
-    for (uint32_t c = 0; c < n_chunks; c++) {
-      const uint32_t w = chunks[c];           // the records of this "wave", pixel-major, w per pixel: what a batch holds in its L array
-      for (uint32_t pi = 0; pi < n_pixels; pi++)
-        for (uint32_t k = 0; k < w; k++) wave[size_t(pi) * w + k] = all[size_t(pi) * spp + s0 + k];
-      HIP_CHECK(hipMemcpy(L.p, wave.data(), size_t(n_pixels) * w * sizeof(f4), hipMemcpyHostToDevice));
-      MomentArgs ma{};
-      ma.L = L.p; ma.state = state.p; ma.nPixels = n_pixels; ma.spp = w; ma.pixBase = 0; ma.exposureScale = exposure_scale;
-      hipLaunchKernelGGL(k_moments_accumulate, dim3((n_pixels + kMomentPixPerBlock - 1) / kMomentPixPerBlock), dim3(kBlock), 0, nullptr, ma);
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipDeviceSynchronize());
-      s0 += w;
-    }
-    MomentFinishArgs f{};
-    f.state = state.p; f.pixels = nullptr; f.nPixels = n_pixels; f.width = n_pixels; f.mask = YART_MOMENT_ALL;
-    f.mean = dMean.p; f.variance = dVar.p; f.count = dCount.p;
-    hipLaunchKernelGGL(k_moments_finish, dim3((n_pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, f);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(mean, dMean.p, size_t(n_pixels) * 12, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(variance, dVar.p, size_t(n_pixels) * 4, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(count, dCount.p, size_t(n_pixels) * 4, hipMemcpyDeviceToHost));
-  });
-}
-
-// Diagnostic: k_gmon_blend on caller-supplied per-sample records (no scene), one launch with the render's launch geometry
-int yart_hip_probe_estimator(const float* L_rgba, uint32_t n_pixels, uint32_t spp, int kind, float exposure_scale,
-                             const uint32_t* pixels, uint32_t width, uint32_t height, float w_current, float w_wave,
-                             float* hdr_inout, uint32_t* pix_rays) {
-  return guarded([&] {
-    require(L_rgba && hdr_inout, "probe_estimator: null pointer");
-    require(n_pixels > 0 && spp > 0, "probe_estimator: n_pixels or spp is 0");
-    require(width > 0 && height > 0, "probe_estimator: width or height is 0");
-    require(width <= 65536u && height <= 65536u, "probe_estimator: width or height above 65536");     // pixels[] packs x | y << 16
-    require(kind >= EST_GMON && kind <= EST_GMONB, "probe_estimator: kind must be one of YART_ESTIMATOR_*");
-    require(uint64_t(n_pixels) * spp <= (1ull << 26), "probe_estimator: more than 2^26 records");
-    require(uint64_t(n_pixels) <= uint64_t(width) * height, "probe_estimator: n_pixels exceeds width * height");
-    require(std::isfinite(exposure_scale), "probe_estimator: exposure_scale is not finite");
-    require(std::isfinite(w_current) && std::isfinite(w_wave), "probe_estimator: a blend weight is not finite");
-    std::vector<uint32_t> px(n_pixels);
-    for (uint32_t i = 0; i < n_pixels; i++) {
-      px[i] = pixels ? pixels[i] : (i % width) | ((i / width) << 16);
-      require((px[i] & 0xffffu) < width && (px[i] >> 16) < height, "probe_estimator: a pixels[] entry is outside the frame");
-    }
-    int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0) throw HipError("no HIP device");
-    const size_t records = size_t(n_pixels) * spp, frame = size_t(width) * height * 4;
-    DevBuf<f4> L; DevBuf<uint32_t> dPixels, dRays; DevBuf<float> hdr;
-    L.ensure(records); dPixels.ensure(n_pixels); hdr.ensure(frame);
-    if (pix_rays) dRays.ensure(n_pixels);
-    HIP_CHECK(hipMemcpy(L.p, L_rgba, records * sizeof(f4), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dPixels.p, px.data(), size_t(n_pixels) * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(hdr.p, hdr_inout, frame * sizeof(float), hipMemcpyHostToDevice));
-    GmonArgs g{};
-    g.L = L.p; g.pixRays = dRays.p; g.pixels = dPixels.p; g.nPixels = n_pixels; g.spp = spp; g.width = width;
-    g.kind = kind; g.exposureScale = exposure_scale; g.wCurrent = w_current; g.wWave = w_wave; g.hdr = hdr.p;
-    hipLaunchKernelGGL(k_gmon_blend, dim3((n_pixels + kGmonPixPerBlock - 1) / kGmonPixPerBlock), dim3(kBlock), 0, nullptr, g);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(hdr_inout, hdr.p, frame * sizeof(float), hipMemcpyDeviceToHost));
-    if (pix_rays) HIP_CHECK(hipMemcpy(pix_rays, dRays.p, size_t(n_pixels) * 4, hipMemcpyDeviceToHost));
-  });
-}
-
 // One wave of the schedule at a time, and inside a wave one batch at a time (tile-renderer.hpp:200-309: finishTile
 // fires onRenderTileComplete per tile and onRenderWaveComplete after a wave's last tile).
 static int renderProgressive(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, float* out_rgba,
@@ -1804,543 +1498,6 @@ int yart_hip_multi_render_tiles(YartMulti* multi, const YartCameraDesc* cam, con
   return rc == YART_OK && aborted ? YART_ABORTED : rc;
 }
 
-int yart_hip_probe_samples(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params,
-                           uint32_t n, const uint32_t* xys, float* out_rgb, uint64_t* out_rays) {
-  return guarded([&] {
-    require(scene && xys && out_rgb, "null pointer");
-    validate(cam, params);
-    if (n == 0) return;
-    std::lock_guard<std::mutex> lock(scene->mu);
-    YartScene& s = *scene;
-    HIP_CHECK(hipSetDevice(s.device));
-    const int grid = int((n + kBlock - 1) / kBlock);
-    s.spill.ensure(size_t(grid) * kBlock * spillDepthFor(s.host, false));
-    s.probeIn.ensure(size_t(n) * 3); s.probeOut.ensure(size_t(n) * 3); s.counters.ensure(8);
-    HIP_CHECK(hipMemcpy(s.probeIn.p, xys, size_t(n) * 3 * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemset(s.counters.p, 0, 8 * sizeof(unsigned long long)));
-    ProbeSampleArgs a{};
-    a.sc = s.dev; a.cam = makeCamera(*cam); a.rc = makeRenderConst(*params);
-    a.xys = s.probeIn.p; a.n = n; a.out = s.probeOut.p; a.rays = s.counters.p; a.spill = s.spill.p;
-    hipLaunchKernelGGL(k_probe_samples, dim3(grid), dim3(kBlock), 0, nullptr, a);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(out_rgb, s.probeOut.p, size_t(n) * 3 * 4, hipMemcpyDeviceToHost));
-    if (out_rays) {
-      unsigned long long r = 0;
-      HIP_CHECK(hipMemcpy(&r, s.counters.p, sizeof(r), hipMemcpyDeviceToHost));
-      *out_rays = r;
-    }
-  });
-}
-
-int yart_hip_probe_hits(YartScene* scene, uint32_t n, const float* rays, float* out) {
-  return guarded([&] {
-    require(scene && rays && out, "null pointer");
-    if (n == 0) return;
-    std::lock_guard<std::mutex> lock(scene->mu);
-    YartScene& s = *scene;
-    HIP_CHECK(hipSetDevice(s.device));
-    const int grid = int((n + kBlock - 1) / kBlock);
-    s.spill.ensure(size_t(grid) * kBlock * spillDepthFor(s.host, false));
-    DevBuf<float> in, res;
-    in.ensure(size_t(n) * 6); res.ensure(size_t(n) * 16);
-    HIP_CHECK(hipMemcpy(in.p, rays, size_t(n) * 6 * 4, hipMemcpyHostToDevice));
-    ProbeHitArgs a{};
-    a.sc = s.dev; a.rays = in.p; a.n = n; a.out = res.p; a.spill = s.spill.p;
-    hipLaunchKernelGGL(k_probe_hits, dim3(grid), dim3(kBlock), 0, nullptr, a);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(out, res.p, size_t(n) * 16 * 4, hipMemcpyDeviceToHost));
-  });
-}
-
-int yart_hip_probe_camera_rays(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, uint32_t n,
-                               const uint32_t* xys, float* out_rays) {
-  return guarded([&] {
-    require(scene && xys && out_rays && n > 0, "probe_camera_rays: null pointer or n == 0");
-    validate(cam, params);
-    for (uint32_t i = 0; i < n; i++)
-      require(xys[3 * i] < cam->width && xys[3 * i + 1] < cam->height && xys[3 * i + 2] < params->samples, "probe_camera_rays: pixel / sample out of range");
-    YartScene& s = *scene;
-    std::lock_guard<std::mutex> lk(s.mu);
-    HIP_CHECK(hipSetDevice(s.device));
-    DevBuf<uint32_t> dIn; DevBuf<float> dOut;
-    dIn.upload(std::vector<uint32_t>(xys, xys + size_t(n) * 3));
-    dOut.ensure(size_t(n) * 6);
-    ProbeCameraArgs a{};
-    a.cam = makeCamera(*cam); a.rc = makeRenderConst(*params);
-    a.sobol = reinterpret_cast<const uint32_t*>(s.dev.lut + LutDev::sobol);
-    a.xys = dIn.p; a.n = n; a.out = dOut.p;
-    hipLaunchKernelGGL(k_probe_camera_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, a);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(out_rays, dOut.p, size_t(n) * 6 * sizeof(float), hipMemcpyDeviceToHost));
-  });
-}
-
-int yart_hip_probe_sampler(YartScene* scene, uint32_t spp, uint32_t tile, uint32_t n, const uint32_t* cases, uint32_t n_draws,
-                           const uint8_t* pattern, int use_tables, float* out) {
-  return guarded([&] {
-    require(scene && cases && pattern && out && n > 0 && n_draws > 0 && n_draws <= 64 && spp > 0 && tile > 0, "probe_sampler: bad argument");
-    YartScene& s = *scene;
-    std::lock_guard<std::mutex> lk(s.mu);
-    HIP_CHECK(hipSetDevice(s.device));
-    uint32_t nOut = 0;
-    for (uint32_t k = 0; k < n_draws; k++) { require(pattern[k] == 1 || pattern[k] == 2, "probe_sampler: pattern entries are 1 or 2"); nOut += pattern[k]; }
-    for (uint32_t i = 0; i < n; i++) require(cases[3 * i] < 65536u && cases[3 * i + 1] < 65536u && cases[3 * i + 2] < spp, "probe_sampler: pixel / sample out of range");
-    DevBuf<uint32_t> dCases; DevBuf<uint8_t> dPat; DevBuf<float> dOut;
-    dCases.upload(std::vector<uint32_t>(cases, cases + size_t(n) * 3)); dPat.upload(std::vector<uint8_t>(pattern, pattern + n_draws));
-    dOut.ensure(size_t(n) * nOut);
-    ProbeSamplerArgs a{};
-    a.cfg = makeSamplerConfig(spp, tile);
-    a.sobol = reinterpret_cast<const uint32_t*>(s.dev.lut + LutDev::sobol);
-    a.cases = dCases.p; a.n = n; a.nDraws = n_draws; a.nOut = nOut; a.pattern = dPat.p; a.out = dOut.p;
-    DevBuf<uint32_t> dPix; DevBuf<uint64_t> entries, hash; DevBuf<uint32_t> sobol1;
-    if (use_tables) {
-      // the tables of a render whose pixel list is the cases' pixels (k_sampler_tables, as renderToDevice builds them)
-      require(uint64_t(spp) <= (1ull << a.cfg.log2spp), "probe_sampler: the sampler tables need spp <= 2^log2spp");
-      std::vector<uint32_t> pix(n);
-      for (uint32_t i = 0; i < n; i++) pix[i] = cases[3 * i] | (cases[3 * i + 1] << 16);
-      dPix.upload(pix);
-      const uint32_t dims = 256u;
-      entries.ensure(size_t(dims) * n); hash.ensure(dims + 3); sobol1.ensure(8 * 256);
-      SamplerTabArgs ta{};
-      ta.cfg = a.cfg; ta.pixels = dPix.p; ta.nPixels = n; ta.dims = dims; ta.entries = entries.p; ta.hash = hash.p; ta.sobol1 = sobol1.p;
-      ta.matrix52 = a.sobol;
-      hipLaunchKernelGGL(k_sampler_tables, dim3(64), dim3(kBlock), 0, nullptr, ta);
-      HIP_CHECK(hipGetLastError());
-      a.cfg.tab.entries = entries.p; a.cfg.tab.hash = hash.p; a.cfg.tab.sobol1 = sobol1.p; a.cfg.tab.dims = dims; a.cfg.tab.stride = n;
-    }
-    hipLaunchKernelGGL(k_probe_sampler, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, a);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(out, dOut.p, size_t(n) * nOut * 4, hipMemcpyDeviceToHost));
-  });
-}
-
-namespace {
-constexpr uint64_t kProbeMathMax = 1ull << 28;   // results per call: 1 GiB of device memory
-void probeMath(int fn, uint32_t firstBits, uint64_t n, float y, const float* a, const float* b, float* out) {
-  HIP_CHECK(hipSetDevice(0));
-  DevBuf<float> dA, dB, dOut;
-  dOut.ensure(size_t(n));
-  if (a) { dA.ensure(size_t(n)); HIP_CHECK(hipMemcpy(dA.p, a, size_t(n) * 4, hipMemcpyHostToDevice)); }
-  if (b) { dB.ensure(size_t(n)); HIP_CHECK(hipMemcpy(dB.p, b, size_t(n) * 4, hipMemcpyHostToDevice)); }
-  ProbeMathArgs q{};
-  q.fn = fn; q.firstBits = firstBits; q.n = n; q.y = y; q.a = dA.p; q.b = dB.p; q.out = dOut.p;
-  const uint64_t blocks = std::min<uint64_t>((n + kBlock - 1) / kBlock, 1u << 16);
-  hipLaunchKernelGGL(k_probe_math, dim3(uint32_t(blocks)), dim3(kBlock), 0, nullptr, q);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipDeviceSynchronize());
-  HIP_CHECK(hipMemcpy(out, dOut.p, size_t(n) * 4, hipMemcpyDeviceToHost));
-}
-}  // namespace
-
-int yart_hip_probe_math(int fn, uint32_t first_bits, uint64_t count, float y, float* out_host) {
-  return guarded([&] {
-    require(fn >= 0 && fn < YART_MATH_COUNT, "probe_math: unknown function");
-    require(fn != YART_MATH_DIV, "probe_math: the divide takes explicit operands (yart_hip_probe_math_pairs)");
-    require(out_host && count > 0 && count <= kProbeMathMax, "probe_math: null output, count == 0 or count > 2^28");
-    require(uint64_t(first_bits) + count <= (1ull << 32), "probe_math: the range runs past the last bit pattern");
-    probeMath(fn, first_bits, count, y, nullptr, nullptr, out_host);
-  });
-}
-
-int yart_hip_probe_math_pairs(int fn, uint64_t n, const float* a, const float* b, float* out_host) {
-  return guarded([&] {
-    require(fn >= 0 && fn < YART_MATH_COUNT, "probe_math_pairs: unknown function");
-    require(a && out_host && n > 0 && n <= kProbeMathMax, "probe_math_pairs: null pointer, n == 0 or n > 2^28");
-    require(b || (fn != YART_MATH_DIV && fn != YART_MATH_POWF), "probe_math_pairs: this function takes a second operand");
-    probeMath(fn, 0, n, 0.0f, a, b, out_host);
-  });
-}
-
-int yart_hip_tonemap_agx(const float* d_hdr_rgba, uint32_t width, uint32_t height, int look, float* d_ldr_rgba,
-                         void* stream) {
-  return guarded([&] {
-    require(d_hdr_rgba && d_ldr_rgba && width > 0 && height > 0 && look >= 0 && look <= 2, "tonemap: bad argument");
-    const uint32_t n = width * height;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(k_tonemap_agx, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
-                       reinterpret_cast<const f4*>(d_hdr_rgba), reinterpret_cast<f4*>(d_ldr_rgba), n, look);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(st));
-  });
-}
-
-int yart_hip_encode_rgb8(const float* d_rgba, uint32_t width, uint32_t height, uint8_t* d_rgb8, void* stream) {
-  return guarded([&] {
-    require(d_rgba && d_rgb8 && width > 0 && height > 0, "encode: bad argument");
-    const uint32_t n = width * height;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(k_encode_rgb8, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
-                       reinterpret_cast<const f4*>(d_rgba), d_rgb8, n);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(st));
-  });
-}
-
-int yart_hip_tonemap_host(const float* hdr_rgba, uint32_t width, uint32_t height, int look, float* ldr_rgba,
-                          uint8_t* rgb8) {
-  return guarded([&] {
-    require(hdr_rgba && width > 0 && height > 0 && look >= -1 && look <= 2, "tonemap: bad argument");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw HipError("no HIP device");
-    const size_t n = size_t(width) * height;
-    DevBuf<float> in, out; DevBuf<uint8_t> bytes;
-    in.ensure(n * 4); out.ensure(n * 4); bytes.ensure(n * 3);
-    HIP_CHECK(hipMemcpy(in.p, hdr_rgba, n * 16, hipMemcpyHostToDevice));
-    const float* src = in.p;
-    if (look >= 0) {                                           // look -1: no tonemapper (tile-renderer.hpp:238-240)
-      hipLaunchKernelGGL(k_tonemap_agx, dim3((uint32_t(n) + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr,
-                         reinterpret_cast<const f4*>(in.p), reinterpret_cast<f4*>(out.p), uint32_t(n), look);
-      HIP_CHECK(hipGetLastError());
-      src = out.p;
-    }
-    hipLaunchKernelGGL(k_encode_rgb8, dim3((uint32_t(n) + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr,
-                       reinterpret_cast<const f4*>(src), bytes.p, uint32_t(n));
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    if (ldr_rgba) HIP_CHECK(hipMemcpy(ldr_rgba, src, n * 16, hipMemcpyDeviceToHost));
-    if (rgb8) HIP_CHECK(hipMemcpy(rgb8, bytes.p, n * 3, hipMemcpyDeviceToHost));
-  });
-}
-
-}  // extern "C"
-// Edge-avoiding à-trous filter (denoise_kernels.inc), plain (VAR = false, YartDenoiseParams) and variance-guided (VAR = true,
-// YartDenoiseVarParams, with a variance buffer). The arguments are judged here, before any device is touched; the last thing the
-// check asks is whether there is a device at all.
-namespace {
-struct DnCall { DnConst k; uint32_t iterations; bool demodulate; };
-inline float dnSigmaFirst(const YartDenoiseParams& p) { return p.sigma_color; }
-inline float dnSigmaFirst(const YartDenoiseVarParams& p) { return p.sigma_luma; }
-template <bool VAR>
-using DnParams = std::conditional_t<VAR, YartDenoiseVarParams, YartDenoiseParams>;
-
-template <bool VAR>
-DnCall denoiseCheck(const void* rgba, const void* variance, const void* albedo, const void* normal, const void* depth, uint32_t width,
-                    uint32_t height, const DnParams<VAR>* params, const void* out) {
-  require(rgba && out, "denoise: rgba / out pointer is null");
-  if (VAR) require(variance != nullptr, "denoise: variance pointer is null");
-  require(params != nullptr, "denoise: params pointer is null");
-  require(params->struct_size >= sizeof(*params), VAR ? "denoise: struct_size is smaller than YartDenoiseVarParams"
-                                                      : "denoise: struct_size is smaller than YartDenoiseParams");
-  require(params->iterations <= 8u, "denoise: iterations > 8");
-  require(width > 0 && height > 0, "denoise: width or height is 0");
-  require(uint64_t(width) * height <= (1ull << 28), "denoise: more than 2^28 pixels");
-  require(std::isfinite(dnSigmaFirst(*params)) && std::isfinite(params->sigma_normal) && std::isfinite(params->sigma_depth),
-          "denoise: a sigma is not finite");
-  require((params->flags & ~uint32_t(YART_DENOISE_DEMODULATE)) == 0u, "denoise: unknown flags bits");
-  DnCall c;
-  c.iterations = params->iterations;
-  c.demodulate = (params->flags & YART_DENOISE_DEMODULATE) != 0u;
-  require(!c.demodulate || albedo, "denoise: YART_DENOISE_DEMODULATE without an albedo buffer");
-  c.k = dnConstants<VAR>(dnSigmaFirst(*params), params->sigma_normal, params->sigma_depth, normal != nullptr, depth != nullptr);
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw HipError("no HIP device");
-  return c;
-}
-
-// device pointers (variance: the variance-guided form only); enqueues on `st` and returns after completion
-template <bool VAR>
-void denoiseRun(const DnCall& c, const float* rgba, const float* variance, const float* albedo, const float* normal, const float* depth,
-                uint32_t width, uint32_t height, float* out, hipStream_t st) {
-  const uint32_t n = width * height;
-  if (c.iterations == 0u) {                         // a plain copy: no demodulation round trip
-    if (out != rgba) HIP_CHECK(hipMemcpyAsync(out, rgba, size_t(n) * 16, hipMemcpyDeviceToDevice, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    return;
-  }
-  DevBuf<f4> scratch;                               // working colour image 0 | image 1 | guide records: 48 bytes per pixel
-  scratch.ensure(size_t(n) * 3);
-  f4 *img[2] = {scratch.p, scratch.p + n}, *guide = scratch.p + size_t(n) * 2;
-  const dim3 flat((n + kBlock - 1) / kBlock), block(kBlock);
-  DnPrepareArgs<VAR> pa{};
-  if constexpr (VAR) pa.variance = variance;
-  pa.rgba = rgba; pa.albedo = c.demodulate ? albedo : nullptr; pa.normal = normal; pa.depth = depth;
-  pa.colour = img[0]; pa.guide = guide; pa.n = n;
-  hipLaunchKernelGGL(k_dn_prepare<VAR>, flat, block, 0, st, pa);
-  HIP_CHECK(hipGetLastError());
-  for (uint32_t i = 0; i < c.iterations; i++) {
-    DnAtrousArgs aa{img[i & 1u], guide, img[(i + 1u) & 1u], width, height, i, 0u, c.k};
-    if (i < 2u) {
-      aa.tilesX = (width + 15u) / 16u;
-      hipLaunchKernelGGL((k_dn_atrous<VAR, 0>), dim3(aa.tilesX * ((height + 15u) / 16u)), block, 0, st, aa);
-    } else {
-      aa.tilesX = (width + 63u) / 64u;
-      hipLaunchKernelGGL((k_dn_atrous<VAR, 1>), dim3(aa.tilesX * ((height + 3u) / 4u)), block, 0, st, aa);
-    }
-    HIP_CHECK(hipGetLastError());
-  }
-  DnFinishArgs fa{img[c.iterations & 1u], rgba, c.demodulate ? albedo : nullptr, out, n, 0u};
-  hipLaunchKernelGGL(k_dn_finish, flat, block, 0, st, fa);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipStreamSynchronize(st));
-}
-
-// host pointers: upload the buffers that are present, filter the frame in place on the device, copy it back
-template <bool VAR>
-void denoiseHost(const DnCall& c, const float* rgba, const float* variance, const float* albedo, const float* normal, const float* depth,
-                 uint32_t width, uint32_t height, float* out) {
-  const size_t n = size_t(width) * height;
-  DevBuf<float> frame, var, alb, nrm, dep;
-  const auto upload = [](DevBuf<float>& b, const float* host, size_t floats) {
-    if (!host) return;
-    b.ensure(floats);
-    HIP_CHECK(hipMemcpy(b.p, host, floats * 4, hipMemcpyHostToDevice));
-  };
-  upload(frame, rgba, n * 4);
-  if (VAR) upload(var, variance, n);
-  if (c.demodulate) upload(alb, albedo, n * 3);
-  upload(nrm, normal, n * 3);
-  upload(dep, depth, n);
-  denoiseRun<VAR>(c, frame.p, var.p, alb.p, nrm.p, dep.p, width, height, frame.p, nullptr);
-  HIP_CHECK(hipMemcpy(out, frame.p, n * 16, hipMemcpyDeviceToHost));
-}
-}  // namespace
-extern "C" {
-
-int yart_hip_denoise_atrous_device(const float* d_rgba, const float* d_albedo, const float* d_normal, const float* d_depth,
-                                   uint32_t width, uint32_t height, const YartDenoiseParams* params, float* d_out_rgba,
-                                   void* stream) {
-  return guarded([&] {
-    const DnCall c = denoiseCheck<false>(d_rgba, nullptr, d_albedo, d_normal, d_depth, width, height, params, d_out_rgba);
-    denoiseRun<false>(c, d_rgba, nullptr, d_albedo, d_normal, d_depth, width, height, d_out_rgba, static_cast<hipStream_t>(stream));
-  });
-}
-
-int yart_hip_denoise_atrous_host(const float* rgba, const float* albedo, const float* normal, const float* depth, uint32_t width,
-                                 uint32_t height, const YartDenoiseParams* params, float* out_rgba) {
-  return guarded([&] {
-    const DnCall c = denoiseCheck<false>(rgba, nullptr, albedo, normal, depth, width, height, params, out_rgba);
-    denoiseHost<false>(c, rgba, nullptr, albedo, normal, depth, width, height, out_rgba);
-  });
-}
-
-int yart_hip_denoise_atrous_var_device(const float* d_rgba, const float* d_variance, const float* d_albedo, const float* d_normal,
-                                       const float* d_depth, uint32_t width, uint32_t height, const YartDenoiseVarParams* params,
-                                       float* d_out_rgba, void* stream) {
-  return guarded([&] {
-    const DnCall c = denoiseCheck<true>(d_rgba, d_variance, d_albedo, d_normal, d_depth, width, height, params, d_out_rgba);
-    denoiseRun<true>(c, d_rgba, d_variance, d_albedo, d_normal, d_depth, width, height, d_out_rgba, static_cast<hipStream_t>(stream));
-  });
-}
-
-int yart_hip_denoise_atrous_var_host(const float* rgba, const float* variance, const float* albedo, const float* normal,
-                                     const float* depth, uint32_t width, uint32_t height, const YartDenoiseVarParams* params,
-                                     float* out_rgba) {
-  return guarded([&] {
-    const DnCall c = denoiseCheck<true>(rgba, variance, albedo, normal, depth, width, height, params, out_rgba);
-    denoiseHost<true>(c, rgba, variance, albedo, normal, depth, width, height, out_rgba);
-  });
-}
-
-// Temporal accumulation (temporal_kernels.inc: k_tp_accumulate). The arguments are judged before any device is touched; the handle's
-// history — two images of three record planes, 96 bytes per pixel; four planes, 128 bytes, in the moments form — is allocated by
-// the first call that gets that far. A handle is in one form from its first accumulate to the next reset.
-}  // extern "C"
-struct YartTemporal {
-  uint32_t width = 0, height = 0;
-  int device = -1;                                  // < 0 until the first accumulate call: the device current then
-  std::mutex mu;
-  DevBuf<f4> hist;                                  // image 0 (rec0 | rec1 | rec2 (| rec3) planes) | image 1
-  bool moments = false;                             // the form of the history, while haveHistory
-  uint32_t current = 0;                             // the image that holds the last frame's records
-  bool haveHistory = false;
-  YartCameraDesc camera{};                          // of the last accumulated frame
-};
-namespace {
-struct TpCall { TpConst k; bool demodulate; YartAovBuffers aovs; };
-// the feature buffers an accumulate call reads, in the order they are checked and staged (albedo: with YART_TEMPORAL_DEMODULATE only)
-struct TemporalField { uint32_t bit; bool demodulateOnly; const char* missing; };
-constexpr TemporalField kTemporalFields[] = {
-    {YART_AOV_POSITION, false, "temporal: the position feature buffer (YART_AOV_POSITION) is missing"},
-    {YART_AOV_NORMAL, false, "temporal: the normal feature buffer (YART_AOV_NORMAL) is missing"},
-    {YART_AOV_DEPTH, false, "temporal: the depth feature buffer (YART_AOV_DEPTH) is missing"},
-    {YART_AOV_COVERAGE, false, "temporal: the coverage feature buffer (YART_AOV_COVERAGE) is missing"},
-    {YART_AOV_IDS, false, "temporal: the ids feature buffer (YART_AOV_IDS) is missing"},
-    {YART_AOV_ALBEDO, true, "temporal: YART_TEMPORAL_DEMODULATE without an albedo feature buffer (YART_AOV_ALBEDO)"}};
-uint32_t temporalMinMomentHistory(const YartTemporalParams&) { return 0u; }
-uint32_t temporalMinMomentHistory(const YartTemporalMomentParams& p) { return p.min_moment_history; }
-
-// Params: YartTemporalParams, or YartTemporalMomentParams (the same head, and min_moment_history)
-template <class Params>
-TpCall temporalCheck(const YartTemporal* t, const YartCameraDesc* cam, const void* rgba, const void* variance, const YartAovBuffers* aovs,
-                     const Params* params, const void* out) {
-  constexpr bool MOMENTS = std::is_same<Params, YartTemporalMomentParams>::value;
-  require(t != nullptr, "temporal: handle pointer is null");
-  require(cam != nullptr, "temporal: camera pointer is null");
-  require(rgba && out, "temporal: rgba / out pointer is null");
-  require(variance != nullptr, "temporal: variance pointer is null");
-  require(aovs != nullptr, "temporal: feature buffers (aovs) pointer is null");
-  require(params != nullptr, "temporal: params pointer is null");
-  require(params->struct_size >= sizeof(Params), MOMENTS ? "temporal: struct_size is smaller than YartTemporalMomentParams"
-                                                                 : "temporal: struct_size is smaller than YartTemporalParams");
-  require((params->flags & ~uint32_t(YART_TEMPORAL_DEMODULATE)) == 0u, "temporal: unknown flags bits");
-  require(std::isfinite(params->alpha_min) && std::isfinite(params->normal_cos_min) && std::isfinite(params->plane_tolerance),
-          "temporal: a parameter is not finite");
-  require(params->alpha_min >= 0.0f && params->alpha_min <= 1.0f, "temporal: alpha_min is outside [0, 1]");
-  require(params->max_history >= 1u, "temporal: max_history is 0");
-  if (MOMENTS) require(temporalMinMomentHistory(*params) >= 2u, "temporal: min_moment_history is smaller than 2");
-  require(cam->width == t->width && cam->height == t->height, "temporal: the camera's image size is not the handle's");
-  require(cam->focal_length > 0.0f, "temporal: camera: bad focal length");
-  TpCall c{};
-  c.demodulate = (params->flags & YART_TEMPORAL_DEMODULATE) != 0u;
-  checkBufferHead(kAovTable, *aovs, "temporal: ");
-  for (const TemporalField& f : kTemporalFields)
-    if (!f.demodulateOnly || c.demodulate) require(takeBufferField(*aovs, kAovTable.field(f.bit), c.aovs), f.missing);
-  c.k.alphaMin = params->alpha_min; c.k.normalCosMin = params->normal_cos_min; c.k.planeTolerance = params->plane_tolerance;
-  c.k.maxHistory = params->max_history;
-  c.k.minMomentHistory = temporalMinMomentHistory(*params);
-  c.k.width = t->width; c.k.height = t->height;
-  return c;
-}
-
-// the handle's mutex held, before any device is touched
-template <bool MOMENTS>
-void temporalCheckForm(const YartTemporal& t) {
-  require(!t.haveHistory || t.moments == MOMENTS,
-          MOMENTS ? "temporal: the handle's history is in the plain form: reset it before the moments form"
-                  : "temporal: the handle's history is in the moments form: reset it before the plain form");
-}
-
-// device pointers (c.aovs included); the handle's device is current and its mutex held; returns after completion on `st`
-template <bool MOMENTS>
-void temporalRun(YartTemporal& t, TpCall c, const YartCameraDesc& cam, const float* rgba, const float* variance, float* out,
-                 float* outVariance, uint32_t* outLength, hipStream_t st) {
-  const uint32_t n = t.width * t.height;
-  constexpr size_t planes = MOMENTS ? 4 : 3;
-  t.hist.ensure(size_t(n) * planes * 2);
-  c.k.haveHistory = t.haveHistory ? 1u : 0u;
-  TpArgs a{};
-  a.rgba = rgba; a.variance = variance; a.albedo = c.demodulate ? c.aovs.albedo : nullptr;
-  a.position = c.aovs.position; a.normal = c.aovs.normal; a.depth = c.aovs.depth; a.coverage = c.aovs.coverage; a.ids = c.aovs.ids;
-  a.histIn = t.hist.p + size_t(t.current) * n * planes;
-  a.histOut = t.hist.p + size_t(t.current ^ 1u) * n * planes;
-  a.outRgba = out; a.outVariance = outVariance; a.outLength = outLength;
-  a.n = n; a.tilesX = (t.width + 15u) / 16u;
-  a.k = c.k;
-  if (t.haveHistory) a.cam = tpCamera(makeCamera(t.camera));
-  const dim3 grid(a.tilesX * ((t.height + 15u) / 16u));
-  hipLaunchKernelGGL(k_tp_accumulate<MOMENTS>, grid, dim3(kBlock), 0, st, a);
-  HIP_CHECK(hipGetLastError());
-  if (MOMENTS) {                                    // pass 2 on the image pass 1 wrote
-    hipLaunchKernelGGL(k_tp_spatial_variance, grid, dim3(kBlock), 0, st, a);
-    HIP_CHECK(hipGetLastError());
-  }
-  HIP_CHECK(hipStreamSynchronize(st));
-  t.current ^= 1u; t.haveHistory = true; t.moments = MOMENTS; t.camera = cam;
-}
-
-void temporalSelectDevice(YartTemporal& t) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw HipError("no HIP device");
-  if (t.device < 0) HIP_CHECK(hipGetDevice(&t.device));
-  HIP_CHECK(hipSetDevice(t.device));
-}
-}  // namespace
-extern "C" {
-
-int yart_hip_temporal_create(uint32_t width, uint32_t height, int device, YartTemporal** out) {
-  return guarded([&] {
-    require(out != nullptr, "temporal: out pointer is null");
-    require(width > 0 && height > 0, "temporal: width or height is 0");
-    require(uint64_t(width) * height <= (1ull << 28), "temporal: more than 2^28 pixels");
-    auto* t = new YartTemporal;
-    t->width = width; t->height = height; t->device = device;
-    *out = t;
-  });
-}
-
-void yart_hip_temporal_destroy(YartTemporal* temporal) {
-  if (!temporal) return;
-  if (temporal->hist.p && temporal->device >= 0) (void)hipSetDevice(temporal->device);
-  delete temporal;
-}
-
-int yart_hip_temporal_reset(YartTemporal* temporal) {
-  return guarded([&] {
-    require(temporal != nullptr, "temporal: handle pointer is null");
-    std::lock_guard<std::mutex> lock(temporal->mu);
-    temporal->haveHistory = false;
-  });
-}
-
-}  // extern "C"
-namespace {
-template <bool MOMENTS, class Params>
-int temporalAccumulateDevice(YartTemporal* temporal, const YartCameraDesc* cam, const float* d_rgba, const float* d_variance,
-                             const YartAovBuffers* d_aovs, const Params* params, float* d_out_rgba, float* d_out_variance,
-                             uint32_t* d_out_length, void* stream) {
-  return guarded([&] {
-    const TpCall c = temporalCheck(temporal, cam, d_rgba, d_variance, d_aovs, params, d_out_rgba);
-    std::lock_guard<std::mutex> lock(temporal->mu);
-    temporalCheckForm<MOMENTS>(*temporal);
-    temporalSelectDevice(*temporal);
-    temporalRun<MOMENTS>(*temporal, c, *cam, d_rgba, d_variance, d_out_rgba, d_out_variance, d_out_length, static_cast<hipStream_t>(stream));
-  });
-}
-
-template <bool MOMENTS, class Params>
-int temporalAccumulateHost(YartTemporal* temporal, const YartCameraDesc* cam, const float* rgba, const float* variance,
-                           const YartAovBuffers* aovs, const Params* params, float* out_rgba, float* out_variance, uint32_t* out_length) {
-  return guarded([&] {
-    TpCall c = temporalCheck(temporal, cam, rgba, variance, aovs, params, out_rgba);
-    std::lock_guard<std::mutex> lock(temporal->mu);
-    temporalCheckForm<MOMENTS>(*temporal);
-    temporalSelectDevice(*temporal);
-    const size_t n = size_t(temporal->width) * temporal->height;
-    // frame (4) | variance (1) | position (3) | normal (3) | depth (1) | coverage (1) | ids (4) | albedo (3) | length (1) words per pixel;
-    // frame and variance are accumulated in place
-    DevBuf<float> buf;
-    buf.ensure(n * 21);
-    float* w = buf.p;
-    auto put = [&](const void* src, size_t words) {
-      float* dst = w; w += n * words;
-      if (src) HIP_CHECK(hipMemcpy(dst, src, n * words * 4, hipMemcpyHostToDevice));
-      return dst;
-    };
-    float* dFrame = put(rgba, 4);
-    float* dVar = put(variance, 1);
-    for (const TemporalField& tf : kTemporalFields) {        // (albedo without YART_TEMPORAL_DEMODULATE: null in c.aovs, room but no copy)
-      const BufferField& f = kAovTable.field(tf.bit);
-      setFieldPtr(c.aovs, f, put(fieldPtr(c.aovs, f), f.words));
-    }
-    uint32_t* dLen = reinterpret_cast<uint32_t*>(put(nullptr, 1));
-    temporalRun<MOMENTS>(*temporal, c, *cam, dFrame, dVar, dFrame, dVar, dLen, nullptr);
-    HIP_CHECK(hipMemcpy(out_rgba, dFrame, n * 16, hipMemcpyDeviceToHost));
-    if (out_variance) HIP_CHECK(hipMemcpy(out_variance, dVar, n * 4, hipMemcpyDeviceToHost));
-    if (out_length) HIP_CHECK(hipMemcpy(out_length, dLen, n * 4, hipMemcpyDeviceToHost));
-  });
-}
-}  // namespace
-extern "C" {
-
-int yart_hip_temporal_accumulate_device(YartTemporal* temporal, const YartCameraDesc* cam, const float* d_rgba, const float* d_variance,
-                                        const YartAovBuffers* d_aovs, const YartTemporalParams* params, float* d_out_rgba,
-                                        float* d_out_variance, uint32_t* d_out_length, void* stream) {
-  return temporalAccumulateDevice<false>(temporal, cam, d_rgba, d_variance, d_aovs, params, d_out_rgba, d_out_variance, d_out_length, stream);
-}
-
-int yart_hip_temporal_accumulate_host(YartTemporal* temporal, const YartCameraDesc* cam, const float* rgba, const float* variance,
-                                      const YartAovBuffers* aovs, const YartTemporalParams* params, float* out_rgba,
-                                      float* out_variance, uint32_t* out_length) {
-  return temporalAccumulateHost<false>(temporal, cam, rgba, variance, aovs, params, out_rgba, out_variance, out_length);
-}
-
-int yart_hip_temporal_accumulate_moments_device(YartTemporal* temporal, const YartCameraDesc* cam, const float* d_rgba,
-                                                const float* d_variance, const YartAovBuffers* d_aovs,
-                                                const YartTemporalMomentParams* params, float* d_out_rgba, float* d_out_variance,
-                                                uint32_t* d_out_length, void* stream) {
-  return temporalAccumulateDevice<true>(temporal, cam, d_rgba, d_variance, d_aovs, params, d_out_rgba, d_out_variance, d_out_length, stream);
-}
-
-int yart_hip_temporal_accumulate_moments_host(YartTemporal* temporal, const YartCameraDesc* cam, const float* rgba, const float* variance,
-                                              const YartAovBuffers* aovs, const YartTemporalMomentParams* params, float* out_rgba,
-                                              float* out_variance, uint32_t* out_length) {
-  return temporalAccumulateHost<true>(temporal, cam, rgba, variance, aovs, params, out_rgba, out_variance, out_length);
-}
-
 int yart_hip_debug_counters(YartScene* scene, uint64_t* out32) {
   return guarded([&] {
     require(scene && out32, "null pointer");
@@ -2387,13 +1544,19 @@ int yart_hip_bvh_copy(YartScene* scene, uint32_t mesh, uint32_t* nodes_out, uint
   });
 }
 
+// the arguments yart_hip_bvh_build_device and yart_hip_bvh_build_host share
+static void checkBvhBuildArgs(const float* positions, uint32_t n_verts, const uint32_t* faces, uint32_t face_stride, uint32_t n_faces,
+                              const uint32_t* nodes_out, const uint32_t* indices_out, const uint32_t* n_nodes) {
+  require(positions && faces && nodes_out && indices_out && n_nodes, "null pointer");
+  require(n_faces >= 1 && n_faces <= kLinkIndexMask && face_stride >= 3, "bvh build: bad triangle count or stride");
+  for (size_t k = 0; k < size_t(n_faces) * face_stride; k += face_stride)
+    for (int c = 0; c < 3; c++) require(faces[k + c] < n_verts, "bvh build: vertex index out of range");
+}
+
 int yart_hip_bvh_build_device(int device, const float* positions, uint32_t n_verts, const uint32_t* faces, uint32_t face_stride,
                               uint32_t n_faces, uint32_t* nodes_out, uint32_t* indices_out, uint32_t* n_nodes, double* ms_device) {
   return guarded([&] {
-    require(positions && faces && nodes_out && indices_out && n_nodes, "null pointer");
-    require(n_faces >= 1 && n_faces <= kLinkIndexMask && face_stride >= 3, "bvh build: bad triangle count or stride");
-    for (size_t k = 0; k < size_t(n_faces) * face_stride; k += face_stride)
-      for (int c = 0; c < 3; c++) require(faces[k + c] < n_verts, "bvh build: vertex index out of range");
+    checkBvhBuildArgs(positions, n_verts, faces, face_stride, n_faces, nodes_out, indices_out, n_nodes);
     std::vector<BvhNode> nodes;
     std::vector<uint32_t> indices;
     require(devbvh::build(device, positions, n_verts, faces, face_stride, n_faces, nodes, indices, ms_device),
@@ -2407,10 +1570,7 @@ int yart_hip_bvh_build_device(int device, const float* positions, uint32_t n_ver
 int yart_hip_bvh_build_host(const float* positions, uint32_t n_verts, const uint32_t* faces, uint32_t face_stride, uint32_t n_faces,
                             uint32_t threads, uint32_t* nodes_out, uint32_t* indices_out, uint32_t* n_nodes, double* ms_host) {
   return guarded([&] {
-    require(positions && faces && nodes_out && indices_out && n_nodes, "null pointer");
-    require(n_faces >= 1 && n_faces <= kLinkIndexMask && face_stride >= 3, "bvh build: bad triangle count or stride");
-    for (size_t k = 0; k < size_t(n_faces) * face_stride; k += face_stride)
-      for (int c = 0; c < 3; c++) require(faces[k + c] < n_verts, "bvh build: vertex index out of range");
+    checkBvhBuildArgs(positions, n_verts, faces, face_stride, n_faces, nodes_out, indices_out, n_nodes);
     const auto t0 = std::chrono::steady_clock::now();
     SahBvhBuilder b;
     b.setThreads(threads);
@@ -2423,4 +1583,6 @@ int yart_hip_bvh_build_host(const float* positions, uint32_t n_verts, const uint
 }
 
 }  // extern "C"
-#endif  // YART_TU == 0
+
+#include "postprocess.inc"
+#include "probes.inc"
