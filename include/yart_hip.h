@@ -588,9 +588,11 @@ int yart_hip_denoise_atrous_var_host(const float* rgba, const float* variance, c
                                      float* out_rgba);
 
 /* Temporal accumulation with camera reprojection — the temporal half of SVGF — for a SEQUENCE of frames of one scene: the stage
- * between yart_hip_render_moments and yart_hip_denoise_atrous_var_device. A scene is immutable after yart_hip_scene_create, so the
- * only thing that moves between frames is the camera: the position buffer (world-space Hit.p) and the previous frame's
- * YartCameraDesc are a complete motion description, and no render kernel takes part. Per frame the accumulator takes the frame, its
+ * between yart_hip_render_moments and yart_hip_denoise_atrous_var_device. A scene is immutable after yart_hip_scene_create, so
+ * between frames of ONE scene only the camera moves: the position buffer (world-space Hit.p) and the previous frame's
+ * YartCameraDesc are a complete motion description, and no render kernel takes part. A caller who animates geometry re-creates the
+ * scene per frame with other YartNodeDesc::fwd / inv and says how each node moved with yart_hip_temporal_set_motion (below, PER-NODE
+ * MOTION). Per frame the accumulator takes the frame, its
  * variance (YART_MOMENT_VARIANCE), its feature buffers and its camera; it projects every pixel's surface point into the previous
  * frame's camera, fetches the accumulated history there with a validated bilinear tap set, blends, and returns the accumulated
  * frame, the variance of that estimate and the history length per pixel. Frame and variance are what the variance-guided filter takes.
@@ -632,7 +634,18 @@ int yart_hip_denoise_atrous_var_host(const float* rgba, const float* variance, c
  * The defaults minimise the worst case, over 6-frame orbits of the two golden scenes rendered by the host path tracer at 4 spp, of
  * the last frame's error against 1024 spp relative to not accumulating (tools/temporal_sweep.py, profiles/temporal_sweep.txt: RMSE
  * 0.60 / 0.71 of the last frame's alone on cornell / material; followed by the variance-guided filter, 0.91 of that filter's alone).
- * Out of scope: moving geometry, a wider search when all four taps fail, colour clamps against ghosting, yart_hip_multi_*. */
+ * PER-NODE MOTION (yart_hip_temporal_set_motion). Node indices are stable across re-created scenes and ids(p)[0] is the node index.
+ * A motion is one record per scene node: the map from THIS frame's world space to the PREVIOUS frame's for points rigidly attached
+ * to that node, 24 floats read as six 16-byte words — {M row 0}, {M row 1}, {M row 2}: the 3 x 4 point transform; {Nm row 0, kind},
+ * {Nm row 1, 0}, {Nm row 2, 0}: the 3 x 3 normal transform, kind a uint32 in word 15: 0 static (the other 23 words are ignored), 1
+ * moving. The definition above changes for a MOVING pixel p only — a motion is pending, uint32(ids(p)[0]) < n_nodes, and that record's
+ * kind == 1; any other pixel runs exactly the operations above (nothing is multiplied by an identity: -0 stays -0):
+ *     P' = (dot(M row i .xyz, P) + M row i .w), i = 0 .. 2;   n' = (dot(Nm row i, n(p))), i = 0 .. 2   — the rules and the dot above
+ *     reprojectable(p) additionally needs P' and n' finite;  the projection uses P' in place of P: rel = P' - position
+ *     a tap q counts iff ... dot(n', n_hist(q)) >= normal_cos_min; fabsf(dot(n', P_hist(q) - P')) <= plane_tolerance * depth(p) ...
+ *   Node equality, the weights, the blend, N, a, the moments and the new history record — {P, N}, {n(p), node}, the CURRENT values —
+ *   are unchanged, and so is pass 2 of the moments form, which works on the new records only.
+ * Out of scope: deforming meshes, a wider search when all four taps fail, colour clamps against ghosting, yart_hip_multi_*. */
 #define YART_TEMPORAL_DEMODULATE 1u         /* accumulate rgb / d, return acc * d (needs YART_AOV_ALBEDO) */
 #define YART_TEMPORAL_DEFAULT_ALPHA_MIN 0.1f
 #define YART_TEMPORAL_DEFAULT_MAX_HISTORY 8u
@@ -650,8 +663,20 @@ typedef struct YartTemporal YartTemporal;
 /* width, height > 0 (at most 2^28 pixels); device < 0: the device current at the first accumulate call. No device is touched. */
 int yart_hip_temporal_create(uint32_t width, uint32_t height, int device, YartTemporal** out);
 void yart_hip_temporal_destroy(YartTemporal* temporal);
-/* Forget the history: the next frame is a first frame. */
+/* Forget the history: the next frame is a first frame. A pending motion is forgotten too. */
 int yart_hip_temporal_reset(YartTemporal* temporal);
+/* Per-node motion for the NEXT accumulate call on the handle (PER-NODE MOTION above). The records are copied into the handle and no
+ * device is touched. The motion applies to the next accumulate call — either form, device or host entry — that passes its own
+ * argument checks; that call uploads the records on its stream before its kernel and consumes the motion: the call after it runs
+ * without one. motion == NULL clears a pending motion, as yart_hip_temporal_reset does.
+ * YART_E_INVALID, with a message and nothing left pending: a NULL temporal; a struct_size smaller than YartTemporalMotion; n_nodes
+ * of 0 or >= 2^20; NULL records; a kind other than 0 or 1; a word of a kind == 1 record that is not finite. */
+typedef struct YartTemporalMotion {
+  uint32_t struct_size;        /* sizeof(YartTemporalMotion) */
+  uint32_t n_nodes;            /* 1 .. 2^20 - 1 */
+  const float* records;        /* HOST, n_nodes * 24 floats */
+} YartTemporalMotion;
+int yart_hip_temporal_set_motion(YartTemporal* temporal, const YartTemporalMotion* motion);
 /* One frame. DEVICE pointers on `stream` (hipStream_t, may be NULL); returns after completion on that stream. d_rgba: width * height
  * * 4 floats; d_variance: width * height; d_aovs: position, normal, depth, coverage and ids are required (and albedo with
  * YART_TEMPORAL_DEMODULATE), as yart_hip_render_moments_device fills them; buffers of other mask bits are not touched.

@@ -215,6 +215,14 @@ class Temporal {
   Temporal(Temporal&& o) noexcept : m_handle(o.m_handle), m_width(o.m_width), m_height(o.m_height) { o.m_handle = nullptr; }
 
   void reset() { check(yart_hip_temporal_reset(m_handle)); }
+  // per-node motion for the next accumulate call (yart_hip_temporal_set_motion): 24 floats per scene node; empty: clear a pending one
+  void setMotion(const std::vector<float>& records) {
+    if (records.empty()) { check(yart_hip_temporal_set_motion(m_handle, nullptr)); return; }
+    if (records.size() % 24 != 0) throw Error(YART_E_INVALID, "Temporal::setMotion: records are not 24 floats per node");
+    YartTemporalMotion m{};
+    m.struct_size = uint32_t(sizeof(m)); m.n_nodes = uint32_t(records.size() / 24); m.records = records.data();
+    check(yart_hip_temporal_set_motion(m_handle, &m));
+  }
   // one frame, host buffers: the accumulated frame, its variance and the history length per pixel
   TemporalFrame accumulate(const YartCameraDesc& camera, const std::vector<float>& rgba, const std::vector<float>& variance,
                            const TemporalFeatures& f, const YartTemporalParams& params) {

@@ -30,7 +30,7 @@ from .denoise import (DEFAULT_VAR_ITERATIONS, DEFAULT_VAR_SIGMA_DEPTH, DEFAULT_V
                       atrous_var_reference)  # noqa: F401 (the NumPy statement of denoise_var / denoise_var_into)
 from .moments import moments_reference  # noqa: F401 (the NumPy statement of render_moments / probe_moments)
 from .temporal import (DEFAULT_ALPHA_MIN, DEFAULT_MAX_HISTORY, DEFAULT_MIN_MOMENT_HISTORY, DEFAULT_NORMAL_COS_MIN,
-                       DEFAULT_PLANE_TOLERANCE, temporal_moments_reference,
+                       DEFAULT_PLANE_TOLERANCE, MOTION_WORDS, node_motion, temporal_moments_reference,
                        temporal_reference)  # noqa: F401 (the NumPy statement of TemporalAccumulator.accumulate / accumulate_into)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -237,6 +237,11 @@ class TemporalMomentParams(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+class TemporalMotion(C.Structure):
+    """YartTemporalMotion (include/yart_hip.h): the per-node motion records for the next accumulate call."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_nodes", C.c_uint32), ("records", C.c_void_p)]
+
+
 FLAG_TEMPORAL_DEMODULATE = 1
 TEMPORAL_AOVS = ("position", "normal", "depth", "coverage", "ids")     # + "albedo" when demodulating
 
@@ -310,7 +315,8 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_denoise_atrous_var_device", "yart_hip_denoise_atrous_var_host",
            "yart_hip_temporal_create", "yart_hip_temporal_destroy", "yart_hip_temporal_reset",
            "yart_hip_temporal_accumulate_device", "yart_hip_temporal_accumulate_host",
-           "yart_hip_temporal_accumulate_moments_device", "yart_hip_temporal_accumulate_moments_host"]
+           "yart_hip_temporal_accumulate_moments_device", "yart_hip_temporal_accumulate_moments_host",
+           "yart_hip_temporal_set_motion"]
 
 LIB_COUNT_PATH = os.path.join(_HERE, "libyart_hip_count.so")   # instrumented twin (exact test counters)
 _libs = {}
@@ -387,6 +393,7 @@ def lib(instrumented: bool = False):
         L.yart_hip_temporal_destroy.argtypes = [C.c_void_p]
         L.yart_hip_temporal_destroy.restype = None
         L.yart_hip_temporal_reset.argtypes = [C.c_void_p]
+        L.yart_hip_temporal_set_motion.argtypes = [C.c_void_p, C.POINTER(TemporalMotion)]
         L.yart_hip_temporal_accumulate_device.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers),
                                                           C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.yart_hip_temporal_accumulate_host.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers),
@@ -733,7 +740,7 @@ class DeviceScene:
 
     def render_denoised(self, p: dict, iterations=None, sigma_color=DEFAULT_SIGMA_COLOR, sigma_normal=None, sigma_depth=None,
                         demodulate=True, rank=0, world_size=1, flags=0, device="cuda", variance_guided=False,
-                        sigma_luma=DEFAULT_VAR_SIGMA_LUMA, temporal=None):
+                        sigma_luma=DEFAULT_VAR_SIGMA_LUMA, temporal=None, motion=None):
         """``render_aovs_into`` for albedo, normal and depth, then the à-trous filter (``denoise_into``) on the same device
         buffers, on torch's current stream: no host round trip. Returns (noisy frame, denoised frame, {name: guide}) as torch
         tensors of ``device`` ((H, W, 4); guides (H, W, 3) / (H, W)).
@@ -745,8 +752,11 @@ class DeviceScene:
         the variance and the feature buffers the accumulator needs, then ``temporal.accumulate_into`` (at the accumulator's own
         parameters and in its own form — plain or moments —, demodulating as ``demodulate`` says), then the variance-guided
         filter on the accumulated frame and variance (``variance_guided`` is implied). Returns (noisy frame, denoised frame, guides) with "accumulated" (H, W, 4),
-        "accumulated_variance" (H, W) and "length" (H, W, int32 holding the uint32) among the guides. None: as before."""
+        "accumulated_variance" (H, W) and "length" (H, W, int32 holding the uint32) among the guides. None: as before.
+        ``motion`` (with ``temporal``): how this scene's nodes moved since the previous frame's scene — the records of
+        yart_amd.temporal.node_motion(previous nodes, these nodes) —, handed to ``temporal.accumulate_into``."""
         import torch
+        assert motion is None or temporal is not None, "render_denoised: motion needs a temporal accumulator"
         if temporal is not None:
             variance_guided = True
         dflt = ((DEFAULT_VAR_ITERATIONS, DEFAULT_VAR_SIGMA_NORMAL, DEFAULT_VAR_SIGMA_DEPTH) if variance_guided else
@@ -768,7 +778,8 @@ class DeviceScene:
             self.render_moments_into(noisy, feats, {"variance": variance}, p, rank, world_size, flags, stream=stream)
             acc, acc_var = torch.empty_like(noisy), torch.empty_like(variance)
             length = torch.empty((h, w), dtype=torch.int32, device=device)
-            temporal.accumulate_into(acc, acc_var, length, p, noisy, variance, feats, demodulate=demodulate, stream=stream)
+            temporal.accumulate_into(acc, acc_var, length, p, noisy, variance, feats, demodulate=demodulate, stream=stream,
+                                     motion=motion)
             clean = torch.empty_like(noisy)
             denoise_var_into(clean, acc, acc_var, guides, iterations, sigma_luma, sigma_normal, sigma_depth, demodulate)
             return noisy, clean, dict(feats, variance=variance, accumulated=acc, accumulated_variance=acc_var, length=length)
@@ -1170,8 +1181,19 @@ class TemporalAccumulator:
             pass
 
     def reset(self):
-        """Forget the history: the next frame is a first frame."""
+        """Forget the history (and a pending motion): the next frame is a first frame."""
         _check(self._L.yart_hip_temporal_reset(self._h), self._L)
+
+    def set_motion(self, motion):
+        """Per-node motion for the next ``accumulate`` / ``accumulate_into`` (yart_hip_temporal_set_motion), which consumes it:
+        an (n_nodes, 24) float32 array as yart_amd.temporal.node_motion builds it. None clears a pending motion."""
+        if motion is None:
+            _check(self._L.yart_hip_temporal_set_motion(self._h, None), self._L)
+            return
+        rec = np.ascontiguousarray(motion)
+        assert rec.dtype == np.float32 and rec.size % MOTION_WORDS == 0, "motion: (n_nodes, 24) float32 records"
+        tm = TemporalMotion(C.sizeof(TemporalMotion), rec.size // MOTION_WORDS, rec.ctypes.data_as(C.c_void_p))
+        _check(self._L.yart_hip_temporal_set_motion(self._h, C.byref(tm)), self._L)
 
     def _camera(self, cam):
         return cam if isinstance(cam, CameraDesc) else make_camera(cam)
@@ -1182,11 +1204,12 @@ class TemporalAccumulator:
         make = make_temporal_moment_params if self.moments else make_temporal_params
         return make(demodulate=demodulate, **dict(self.params, **over))
 
-    def accumulate(self, cam, frame, variance, aovs: dict, demodulate=None, out=None, out_variance=None, **over):
+    def accumulate(self, cam, frame, variance, aovs: dict, demodulate=None, out=None, out_variance=None, motion=None, **over):
         """One frame on NumPy arrays (yart_hip_temporal_accumulate_host, or _moments_host in the moments form). ``cam``: the frame's camera (a params dict as
         ``render`` takes it, or a CameraDesc); ``frame`` (H, W, 4); ``variance`` (H, W); ``aovs``: the feature buffers by name —
         position, normal, depth, coverage, ids, and albedo when demodulating (``demodulate`` None: whenever albedo is given).
-        ``out`` / ``out_variance`` may be ``frame`` / ``variance``. Returns (accumulated frame, its variance, history length
+        ``out`` / ``out_variance`` may be ``frame`` / ``variance``. ``motion``: this frame's per-node motion records
+        (``set_motion`` is called first); None: whatever is pending. Returns (accumulated frame, its variance, history length
         (H, W) uint32)."""
         h, w = self.height, self.width
         frame = np.ascontiguousarray(frame, np.float32)
@@ -1214,6 +1237,8 @@ class TemporalAccumulator:
             assert o.dtype == np.float32 and o.flags.c_contiguous and o.size == size
         length = np.empty((h, w), np.uint32)
         tp = self._params(demodulate, over)
+        if motion is not None:
+            self.set_motion(motion)
         fn = self._L.yart_hip_temporal_accumulate_moments_host if self.moments else self._L.yart_hip_temporal_accumulate_host
         _check(fn(self._h, C.byref(self._camera(cam)), frame.ctypes.data_as(C.c_void_p), variance.ctypes.data_as(C.c_void_p),
                   C.byref(ab), C.byref(tp), out.ctypes.data_as(C.c_void_p), out_variance.ctypes.data_as(C.c_void_p),
@@ -1221,11 +1246,12 @@ class TemporalAccumulator:
         return out, out_variance, length
 
     def accumulate_into(self, out_tensor, out_variance_tensor, out_length_tensor, cam, frame_tensor, variance_tensor,
-                        aov_tensors: dict, demodulate=None, stream=None, **over):
+                        aov_tensors: dict, demodulate=None, stream=None, motion=None, **over):
         """``accumulate`` on CUDA/HIP torch tensors through ``data_ptr()`` (yart_hip_temporal_accumulate[_moments]_device), on ``stream``
         (an integer handle; None: torch's current stream): no host round trip. ``out_variance_tensor`` and
         ``out_length_tensor`` (H*W 4-byte elements: int32 holding the uint32) may be None; ``out_tensor`` may be
-        ``frame_tensor`` and ``out_variance_tensor`` may be ``variance_tensor``."""
+        ``frame_tensor`` and ``out_variance_tensor`` may be ``variance_tensor``. ``motion``: as ``accumulate`` takes it (a
+        NumPy array: the records are host data)."""
         import torch
         h, w = self.height, self.width
         if demodulate is None:
@@ -1248,6 +1274,8 @@ class TemporalAccumulator:
             stream = torch.cuda.current_stream(frame_tensor.device).cuda_stream
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         tp = self._params(demodulate, over)
+        if motion is not None:
+            self.set_motion(motion)
         with torch.cuda.device(frame_tensor.device):
             fn = self._L.yart_hip_temporal_accumulate_moments_device if self.moments else self._L.yart_hip_temporal_accumulate_device
             _check(fn(self._h, C.byref(self._camera(cam)), ptr(frame_tensor), ptr(variance_tensor), C.byref(ab), C.byref(tp),

@@ -225,6 +225,9 @@ struct YartTemporal {
   uint32_t current = 0;                             // the image that holds the last frame's records
   bool haveHistory = false;
   YartCameraDesc camera{};                          // of the last accumulated frame
+  std::vector<float> motion;                        // yart_hip_temporal_set_motion: the pending records, 24 floats per node; empty: none
+  std::vector<float> motionTaken;                   // what the running call consumed: the source of its upload
+  DevBuf<f4> motionDev;
 };
 namespace {
 struct TpCall { TpConst k; bool demodulate; YartAovBuffers aovs; };
@@ -281,6 +284,12 @@ void temporalCheckForm(const YartTemporal& t) {
                   : "temporal: the handle's history is in the moments form: reset it before the plain form");
 }
 
+// the handle's mutex held, after the call's last argument check and before any device is touched: the call consumes the pending motion
+void temporalTakeMotion(YartTemporal& t) {
+  t.motionTaken.clear();
+  t.motionTaken.swap(t.motion);
+}
+
 // device pointers (c.aovs included); the handle's device is current and its mutex held; returns after completion on `st`
 template <bool MOMENTS>
 void temporalRun(YartTemporal& t, TpCall c, const YartCameraDesc& cam, const float* rgba, const float* variance, float* out,
@@ -299,7 +308,15 @@ void temporalRun(YartTemporal& t, TpCall c, const YartCameraDesc& cam, const flo
   a.k = c.k;
   if (t.haveHistory) a.cam = tpCamera(makeCamera(t.camera));
   const dim3 grid(a.tilesX * ((t.height + 15u) / 16u));
-  hipLaunchKernelGGL(k_tp_accumulate<MOMENTS>, grid, dim3(kBlock), 0, st, a);
+  if (!t.motionTaken.empty()) {                     // on `st`, before the kernel that reads it
+    const size_t words = t.motionTaken.size() / 4;
+    t.motionDev.ensure(words);
+    HIP_CHECK(hipMemcpyAsync(t.motionDev.p, t.motionTaken.data(), words * sizeof(f4), hipMemcpyHostToDevice, st));
+    const TpDeviceMotion motion{t.motionDev.p, uint32_t(words / kTpMotionWords)};
+    hipLaunchKernelGGL((k_tp_accumulate<MOMENTS, true>), grid, dim3(kBlock), 0, st, a, motion);
+  } else {
+    hipLaunchKernelGGL((k_tp_accumulate<MOMENTS, false>), grid, dim3(kBlock), 0, st, a, TpNoMotion{});
+  }
   HIP_CHECK(hipGetLastError());
   if (MOMENTS) {                                    // pass 2 on the image pass 1 wrote
     hipLaunchKernelGGL(k_tp_spatial_variance, grid, dim3(kBlock), 0, st, a);
@@ -340,6 +357,29 @@ int yart_hip_temporal_reset(YartTemporal* temporal) {
     require(temporal != nullptr, "temporal: handle pointer is null");
     std::lock_guard<std::mutex> lock(temporal->mu);
     temporal->haveHistory = false;
+    temporal->motion.clear();
+  });
+}
+
+int yart_hip_temporal_set_motion(YartTemporal* temporal, const YartTemporalMotion* motion) {
+  return guarded([&] {
+    require(temporal != nullptr, "temporal: handle pointer is null");
+    std::lock_guard<std::mutex> lock(temporal->mu);
+    temporal->motion.clear();                       // a refused motion leaves nothing pending
+    if (!motion) return;
+    require(motion->struct_size >= sizeof(YartTemporalMotion), "temporal: struct_size is smaller than YartTemporalMotion");
+    require(motion->n_nodes >= 1u && motion->n_nodes < kTpMotionMaxNodes, "temporal: motion: n_nodes is 0 or not below 2^20");
+    require(motion->records != nullptr, "temporal: motion: records pointer is null");
+    constexpr size_t kWords = kTpMotionWords * 4;
+    for (uint32_t i = 0; i < motion->n_nodes; i++) {
+      const float* r = motion->records + size_t(i) * kWords;
+      const uint32_t kind = dnBits(r[15]);
+      require(kind <= 1u, "temporal: motion: a record's kind is neither 0 (static) nor 1 (moving)");
+      if (kind == 0u) continue;
+      for (size_t j = 0; j < kWords; j++)
+        require(j == 15 || std::isfinite(r[j]), "temporal: motion: a word of a moving node's record is not finite");
+    }
+    temporal->motion.assign(motion->records, motion->records + size_t(motion->n_nodes) * kWords);
   });
 }
 
@@ -353,6 +393,7 @@ int temporalAccumulateDevice(YartTemporal* temporal, const YartCameraDesc* cam, 
     const TpCall c = temporalCheck(temporal, cam, d_rgba, d_variance, d_aovs, params, d_out_rgba);
     std::lock_guard<std::mutex> lock(temporal->mu);
     temporalCheckForm<MOMENTS>(*temporal);
+    temporalTakeMotion(*temporal);
     temporalSelectDevice(*temporal);
     temporalRun<MOMENTS>(*temporal, c, *cam, d_rgba, d_variance, d_out_rgba, d_out_variance, d_out_length, static_cast<hipStream_t>(stream));
   });
@@ -365,6 +406,7 @@ int temporalAccumulateHost(YartTemporal* temporal, const YartCameraDesc* cam, co
     TpCall c = temporalCheck(temporal, cam, rgba, variance, aovs, params, out_rgba);
     std::lock_guard<std::mutex> lock(temporal->mu);
     temporalCheckForm<MOMENTS>(*temporal);
+    temporalTakeMotion(*temporal);
     temporalSelectDevice(*temporal);
     const size_t n = size_t(temporal->width) * temporal->height;
     // frame (4) | variance (1) | position (3) | normal (3) | depth (1) | coverage (1) | ids (4) | albedo (3) | length (1) words per pixel;

@@ -68,11 +68,49 @@ YART_HD f3 tpDivisor(bool demodulate, f3 alb) {
   return demodulate ? mk3(alb.x > 1e-3f ? alb.x : 1.0f, alb.y > 1e-3f ? alb.y : 1.0f, alb.z > 1e-3f ? alb.z : 1.0f) : mk3(1.0f);
 }
 
+// Per-node motion (yart_hip_temporal_set_motion): one record of six 16-byte words per scene node, the map from this frame's world
+// space to the previous frame's for points rigidly attached to the node:
+//   words 0 .. 2  {M row i}            the 3 x 4 point transform: P' = dot(M row i .xyz, P) + M row i .w
+//   words 3 .. 5  {Nm row i, kind | 0} the 3 x 3 normal transform: n' = dot(Nm row i, n); kind (u32 bits, word 3 only) 0 static, 1 moving
+// A Motion decides how a word is fetched: motion.nodes() and motion.word(node, i). A pixel is MOVING when its node is below
+// nodes() and its record's kind is 1; it is projected, and its taps are validated, with P' and n'. Any other pixel runs the
+// operations it ran before there was a motion: nothing is multiplied by an identity (-0 stays -0).
+constexpr uint32_t kTpMotionWords = 6;           // 16-byte words per record
+constexpr uint32_t kTpMotionMaxNodes = 1u << 20; // exclusive
+struct TpNoMotion {                              // no motion is pending: compiles to the code without one
+  static constexpr bool kNone = true;
+  YART_HD uint32_t nodes() const { return 0u; }
+  YART_HD f4 word(uint32_t, uint32_t) const { return dnF4(0.0f, 0.0f, 0.0f, 0.0f); }
+};
+
+// What a pixel is projected with and what its taps are tested with: P' and n' of a moving pixel, P and n of any other.
+struct TpMoved { f3 P, n; bool finite; };
+template <class Motion>
+YART_HD TpMoved tpMoved(const Motion& motion, const TpIn& in) {
+  if constexpr (!Motion::kNone) {
+    if (in.node < motion.nodes()) {
+      const f4 n0 = motion.word(in.node, 3u);    // first: it carries kind
+      if (dnBits(n0.w) == 1u) {
+        const f4 m0 = motion.word(in.node, 0u), m1 = motion.word(in.node, 1u), m2 = motion.word(in.node, 2u);
+        const f4 n1 = motion.word(in.node, 4u), n2 = motion.word(in.node, 5u);
+        TpMoved mv;
+        mv.P = mk3(dot(mk3(m0.x, m0.y, m0.z), in.P) + m0.w, dot(mk3(m1.x, m1.y, m1.z), in.P) + m1.w,
+                   dot(mk3(m2.x, m2.y, m2.z), in.P) + m2.w);
+        mv.n = mk3(dot(mk3(n0.x, n0.y, n0.z), in.n), dot(mk3(n1.x, n1.y, n1.z), in.n), dot(mk3(n2.x, n2.y, n2.z), in.n));
+        mv.finite = tpFinite3(mv.P) && tpFinite3(mv.n);
+        return mv;
+      }
+    }
+  }
+  return TpMoved{in.P, in.n, true};
+}
+
 // One pixel. Hist decides how a 16-byte record of the previous history image is fetched: hist.rec0(q) / rec1(q) / rec2(q) (and
 // rec3(q) with MOMENTS), q = y * width + x. demodulate: the call demodulates, and alb is the pixel's albedo (by value: no array
 // for the kernel to keep). MOMENTS: the moments form — pass 1 of it; a short pixel's o.variance / rec0.w are provisional.
-template <bool MOMENTS, class Hist>
-YART_HD TpOut tpAccumulatePixel(const Hist& hist, const TpConst& k, const TpCamera& cam, const TpIn& in, bool demodulate, f3 alb) {
+template <bool MOMENTS, class Hist, class Motion>
+YART_HD TpOut tpAccumulatePixel(const Hist& hist, const Motion& motion, const TpConst& k, const TpCamera& cam, const TpIn& in,
+                                bool demodulate, f3 alb) {
   TpOut o;
   const f3 d = tpDivisor(demodulate, alb);
   const float cr = in.rgba.x / d.x, cg = in.rgba.y / d.y, cb = in.rgba.z / d.z;
@@ -86,13 +124,15 @@ YART_HD TpOut tpAccumulatePixel(const Hist& hist, const TpConst& k, const TpCame
     o.rec0 = o.rec1 = o.rec2 = o.rec3 = dnF4(0.0f, 0.0f, 0.0f, 0.0f);
     return o;
   }
-  const bool reprojectable = in.coverage == 1.0f && tpFinite3(in.P) && tpFinite3(in.n) && dnFinite(in.depth);
+  const TpMoved mv = tpMoved(motion, in);
+  const f3 P = mv.P, n = mv.n;
+  const bool reprojectable = in.coverage == 1.0f && tpFinite3(in.P) && tpFinite3(in.n) && dnFinite(in.depth) && mv.finite;
   float accR = 0.0f, accG = 0.0f, accB = 0.0f, accV = 0.0f, wsum = 0.0f;
   float acc1 = 0.0f, acc2 = 0.0f, accW2 = 0.0f;           // MOMENTS: the tap-weighted sums of rec3's words
   uint32_t minLen = 0xffffffffu;
   bool any = false;
   if (k.haveHistory != 0u && reprojectable) {
-    const f3 rel = in.P - cam.position;
+    const f3 rel = P - cam.position;
     const float den = dot(rel, cam.nrm);
     const float s = cam.num / den;
     if (s > 0.0f && s <= 3.4028235e38f) {      // in front of the previous camera: den has num's sign and is not 0
@@ -115,9 +155,9 @@ YART_HD TpOut tpAccumulatePixel(const Hist& hist, const TpConst& k, const TpCame
           if (len < 1u) continue;
           const f4 r2 = hist.rec2(q);
           if (dnBits(r2.w) != in.node) continue;
-          if (!(dot(in.n, mk3(r2.x, r2.y, r2.z)) >= k.normalCosMin)) continue;
-          const f3 dP = mk3(r1.x, r1.y, r1.z) - in.P;
-          if (!(fabsf(dot(in.n, dP)) <= tol)) continue;
+          if (!(dot(n, mk3(r2.x, r2.y, r2.z)) >= k.normalCosMin)) continue;
+          const f3 dP = mk3(r1.x, r1.y, r1.z) - P;
+          if (!(fabsf(dot(n, dP)) <= tol)) continue;
           const f4 r0 = hist.rec0(q);
           accR = accR + w * r0.x; accG = accG + w * r0.y; accB = accB + w * r0.z; accV = accV + w * r0.w;
           if constexpr (MOMENTS) {
@@ -165,10 +205,15 @@ YART_HD TpOut tpAccumulatePixel(const Hist& hist, const TpConst& k, const TpCame
   return o;
 }
 
+// without a motion, as the callers from before there was one name it
+template <bool MOMENTS, class Hist>
+YART_HD TpOut tpAccumulatePixel(const Hist& hist, const TpConst& k, const TpCamera& cam, const TpIn& in, bool demodulate, f3 alb) {
+  return tpAccumulatePixel<MOMENTS, Hist, TpNoMotion>(hist, TpNoMotion{}, k, cam, in, demodulate, alb);
+}
 // the plain form, as its callers have always named it
 template <class Hist>
 YART_HD TpOut tpAccumulatePixel(const Hist& hist, const TpConst& k, const TpCamera& cam, const TpIn& in, bool demodulate, f3 alb) {
-  return tpAccumulatePixel<false, Hist>(hist, k, cam, in, demodulate, alb);
+  return tpAccumulatePixel<false, Hist, TpNoMotion>(hist, TpNoMotion{}, k, cam, in, demodulate, alb);
 }
 
 // Pass 2 of the moments form, one pixel (x, y) of the image pass 1 just wrote (hist: rec1 / rec2 / rec3 of that image); depth is

@@ -10,6 +10,11 @@
 //                     the previous image, so neighbouring lanes' taps share lines in the CU's vector cache: no LDS tile.
 //                     A first frame (or the first after a reset) reads no tap: TpConst::haveHistory is uniform over the launch.
 //
+//   k_tp_accumulate<·, true>   with a pending per-node motion (yart_hip_temporal_set_motion): a lane whose node has a record loads
+//                     the record's word 3, which carries kind, and the other five 16-byte words only when the node moves — six
+//                     aligned loads; a tile's lanes mostly share a node, so all but the first are line hits. Launched only for
+//                     the call that consumes a motion: the <·, false> kernels are the code from before there was one.
+//
 //   k_tp_accumulate<true>   the moments form, pass 1: the same, with rec3 — one more aligned 16-byte load per counting tap and
 //                     one more 16-byte store.
 //   k_tp_spatial_variance   the moments form, pass 2, launched after pass 1 on the image it wrote, same tile: a lane whose pixel
@@ -29,6 +34,14 @@ struct TpDeviceHist {
   __device__ __forceinline__ f4 rec3(size_t q) const { return dnLd(r3 + q); }
 };
 
+struct TpDeviceMotion {
+  static constexpr bool kNone = false;
+  const f4* rec;                                   // kTpMotionWords words per node
+  uint32_t n;
+  __device__ __forceinline__ uint32_t nodes() const { return n; }
+  __device__ __forceinline__ f4 word(uint32_t node, uint32_t i) const { return dnLd(rec + size_t(node) * kTpMotionWords + i); }
+};
+
 struct TpArgs {
   const float *rgba, *variance, *albedo;           // albedo: only when the call demodulates
   const float *position, *normal, *depth, *coverage;
@@ -41,8 +54,11 @@ struct TpArgs {
   TpConst k;
   TpCamera cam;
 };
-template <bool MOMENTS>
-__global__ void __launch_bounds__(kBlock) k_tp_accumulate(TpArgs a) {
+// MOTION: the launch has a per-node motion, `motion`; else the second argument is empty and the code is that of a kernel without it
+template <bool MOTION>
+using TpMotionArg = typename std::conditional<MOTION, TpDeviceMotion, TpNoMotion>::type;
+template <bool MOMENTS, bool MOTION>
+__global__ void __launch_bounds__(kBlock) k_tp_accumulate(TpArgs a, TpMotionArg<MOTION> motion) {
   const uint32_t ty = blockIdx.x / a.tilesX, tx = blockIdx.x - ty * a.tilesX;
   const uint32_t x = tx * 16u + (threadIdx.x % 16u), y = ty * 16u + (threadIdx.x / 16u);
   if (x >= a.k.width || y >= a.k.height) return;
@@ -60,7 +76,7 @@ __global__ void __launch_bounds__(kBlock) k_tp_accumulate(TpArgs a) {
   TpDeviceHist hist;
   hist.r0 = a.histIn; hist.r1 = a.histIn + a.n; hist.r2 = a.histIn + size_t(a.n) * 2;
   hist.r3 = MOMENTS ? a.histIn + size_t(a.n) * 3 : nullptr;
-  const TpOut o = tpAccumulatePixel<MOMENTS>(hist, a.k, a.cam, in, a.albedo != nullptr, alb);
+  const TpOut o = tpAccumulatePixel<MOMENTS>(hist, motion, a.k, a.cam, in, a.albedo != nullptr, alb);
   dnSt(a.histOut + p, o.rec0);
   dnSt(a.histOut + a.n + p, o.rec1);
   dnSt(a.histOut + size_t(a.n) * 2 + p, o.rec2);
@@ -71,7 +87,7 @@ __global__ void __launch_bounds__(kBlock) k_tp_accumulate(TpArgs a) {
   if (a.outLength) a.outLength[p] = o.length;
 }
 
-// a: the arguments of the k_tp_accumulate<true> launch it follows; reads a.depth and a.albedo of its own pixel and a.histOut
+// a: the arguments of the k_tp_accumulate<true, ·> launch it follows; reads a.depth and a.albedo of its own pixel and a.histOut
 __global__ void __launch_bounds__(kBlock) k_tp_spatial_variance(TpArgs a) {
   const uint32_t ty = blockIdx.x / a.tilesX, tx = blockIdx.x - ty * a.tilesX;
   const uint32_t x = tx * 16u + (threadIdx.x % 16u), y = ty * 16u + (threadIdx.x / 16u);

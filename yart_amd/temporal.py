@@ -10,6 +10,9 @@ comparisons.
 :func:`temporal_moments_reference` states the moments form (``yart_hip_temporal_accumulate_moments_*``): the same pass with the
 luminance moments and the sum of squared frame weights accumulated next to the colour, the temporal variance estimate they give,
 and the second pass that estimates the variance of the short pixels from their 7 x 7 neighbourhood.
+
+Both take ``motion``: the per-node motion records of ``yart_hip_temporal_set_motion`` — how each scene node moved since the
+previous frame — which :func:`node_motion` builds from the node lists of the two frames' scenes.
 """
 from __future__ import annotations
 
@@ -25,6 +28,11 @@ FLAG_DEMODULATE = 1
 # width of the spatial estimate's window
 DEFAULT_MIN_MOMENT_HISTORY = 4
 SPATIAL_RADIUS = 3
+# include/yart_hip.h: YartTemporalMotion — floats per record, the word that holds kind, the kinds, and the (exclusive) node limit
+MOTION_WORDS = 24
+MOTION_KIND_WORD = 15
+MOTION_STATIC, MOTION_MOVING = 0, 1
+MOTION_MAX_NODES = 1 << 20
 
 _F = np.float32
 _FLT_MAX = np.float32(3.4028235e38)
@@ -82,6 +90,58 @@ def camera_basis(cam):
     return dict(position=position.astype(_F), top_left=tl, dU=du, dV=dv)
 
 
+def motion_records(motion):
+    """``motion`` as the (n_nodes, 24) float32 array of records, checked as ``yart_hip_temporal_set_motion`` checks it."""
+    rec = np.ascontiguousarray(motion)
+    assert rec.dtype == np.float32, "motion records are float32 (kind is a uint32 stored as bits)"
+    rec = rec.reshape(-1, MOTION_WORDS)
+    assert 1 <= len(rec) < MOTION_MAX_NODES, "n_nodes is 0 or not below 2^20"
+    kind = rec[:, MOTION_KIND_WORD].view(np.uint32)
+    assert (kind <= MOTION_MOVING).all(), "a record's kind is neither 0 nor 1"
+    words = np.delete(rec[kind == MOTION_MOVING], MOTION_KIND_WORD, axis=1)
+    assert np.isfinite(words).all(), "a word of a moving node's record is not finite"
+    return rec
+
+
+def _node_field(node, name, index):
+    if isinstance(node, dict):
+        return node[name]
+    return getattr(node, name) if hasattr(node, name) else node[index]
+
+
+def node_motion(nodes_prev, nodes_cur):
+    """The per-node motion records from the node lists of the previous and the current frame's scene (``yscn.Scene.nodes``, or
+    anything with ``parent`` and ``fwd`` — attributes, keys, or (parent, fwd) pairs —, a parent before its children): the
+    (n_nodes, 24) float32 array ``TemporalAccumulator.accumulate(..., motion=)`` and the references take.
+    In float64: W_k = W_parent(k) · fwd_k is node k's object-to-world transform — csrc/traverse.hpp objectRay takes a world ray
+    to object space with the chain's ``inv`` root first (row-major matrices, column vectors: ymath.hpp mulPoint), so object to
+    world is the ``fwd`` chain with the root on the left. M = W_prev · W_cur^-1 takes a point attached to the node from this
+    frame's world space to the previous frame's; with L its linear part, Nm = L^-T · |det L|^(1/3) takes the normal — exact (a
+    unit n' for a unit n) for rigid motion and uniform scale; any other motion leaves n' non-unit, which shifts the normal test.
+    kind = 0 (static, the other words 0) exactly when the node's ``fwd`` chain up to the root is the same in both lists, word
+    for word; else 1."""
+    assert len(nodes_prev) == len(nodes_cur), "the two frames' scenes do not have the same nodes"
+    n = len(nodes_cur)
+    rec = np.zeros((n, MOTION_WORDS), _F)
+    kind = rec[:, MOTION_KIND_WORD].view(np.uint32)
+    world, same = [[None] * n, [None] * n], [None] * n
+    for k in range(n):
+        parent = int(_node_field(nodes_cur[k], "parent", 0))
+        assert parent == int(_node_field(nodes_prev[k], "parent", 0)) and parent < k, "node %d: another or a later parent" % k
+        fwd = [np.asarray(_node_field(nodes[k], "fwd", 1), _F).reshape(4, 4) for nodes in (nodes_prev, nodes_cur)]
+        same[k] = bool((fwd[0].view(np.uint32) == fwd[1].view(np.uint32)).all()) and (parent < 0 or same[parent])
+        for j in (0, 1):
+            world[j][k] = fwd[j].astype(np.float64) if parent < 0 else world[j][parent] @ fwd[j].astype(np.float64)
+        if same[k]:
+            continue
+        m = world[0][k] @ np.linalg.inv(world[1][k])
+        lin = m[:3, :3]
+        rec[k, :12] = m[:3].reshape(12)
+        rec[k, 12:].reshape(3, 4)[:, :3] = np.linalg.inv(lin).T * abs(np.linalg.det(lin)) ** (1.0 / 3.0)
+        kind[k] = MOTION_MOVING
+    return rec
+
+
 class TemporalHistory:
     """The state of a ``YartTemporal`` handle: the history records of the last accumulated frame — ``colour`` (H, W, 3),
     ``variance`` (H, W), ``position`` (H, W, 3), ``length`` (H, W) uint32, ``normal`` (H, W, 3), ``node`` (H, W) uint32 — and
@@ -100,28 +160,31 @@ class TemporalHistory:
 
 def temporal_reference(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo=None,
                        alpha_min=DEFAULT_ALPHA_MIN, max_history=DEFAULT_MAX_HISTORY, normal_cos_min=DEFAULT_NORMAL_COS_MIN,
-                       plane_tolerance=DEFAULT_PLANE_TOLERANCE, demodulate=None):
+                       plane_tolerance=DEFAULT_PLANE_TOLERANCE, demodulate=None, motion=None):
     """One frame: ``history`` (a :class:`TemporalHistory`, updated in place), ``cam`` the frame's camera (see
     :func:`camera_fields`), ``rgba`` (H, W, 4), ``variance`` (H, W), ``position`` / ``normal`` (H, W, 3), ``depth`` / ``coverage``
     (H, W), ``ids`` (H, W, 4) int32, ``albedo`` (H, W, 3) or None. ``demodulate``: None = whenever an albedo buffer is given.
+    ``motion``: None, or the (n_nodes, 24) float32 per-node motion records of this frame (``kind`` as bits in column 15; see
+    :func:`node_motion`): a pixel whose ``ids[0]`` is below n_nodes and whose record's kind is 1 is projected, and its taps are
+    validated, with P' = M P and n' = Nm n; every other pixel is untouched by it.
     Returns (accumulated frame (H, W, 4) float32, its variance (H, W) float32, history length (H, W) uint32)."""
     return _accumulate(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo, alpha_min, max_history,
-                       normal_cos_min, plane_tolerance, demodulate, None)
+                       normal_cos_min, plane_tolerance, demodulate, None, motion)
 
 
 def temporal_moments_reference(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo=None,
                                alpha_min=DEFAULT_ALPHA_MIN, max_history=DEFAULT_MAX_HISTORY,
                                normal_cos_min=DEFAULT_NORMAL_COS_MIN, plane_tolerance=DEFAULT_PLANE_TOLERANCE,
-                               min_moment_history=DEFAULT_MIN_MOMENT_HISTORY, demodulate=None):
+                               min_moment_history=DEFAULT_MIN_MOMENT_HISTORY, demodulate=None, motion=None):
     """One frame of the moments form; arguments and results as :func:`temporal_reference`, and ``min_moment_history`` (>= 2).
     The history additionally carries ``moments``; a history is in one form from its first frame to the next ``reset``."""
     assert int(min_moment_history) >= 2
     return _accumulate(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo, alpha_min, max_history,
-                       normal_cos_min, plane_tolerance, demodulate, int(min_moment_history))
+                       normal_cos_min, plane_tolerance, demodulate, int(min_moment_history), motion)
 
 
 def _accumulate(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo, alpha_min, max_history,
-                normal_cos_min, plane_tolerance, demodulate, min_moment_history):
+                normal_cos_min, plane_tolerance, demodulate, min_moment_history, motion=None):
     """Pass 1 of both forms (``min_moment_history`` None: the plain form), then pass 2 of the moments form."""
     moments = min_moment_history is not None
     form = "moments" if moments else "plain"
@@ -157,6 +220,17 @@ def _accumulate(history, cam, rgba, variance, position, normal, depth, coverage,
         if alb is not None:
             usable &= np.isfinite(alb).all(-1)
         reproj = usable & (coverage == _F(1.0)) & np.isfinite(P).all(-1) & np.isfinite(n).all(-1) & np.isfinite(depth)
+        Pq, nq = P, n                 # what is projected and what the taps are tested with: P', n' of a moving pixel
+        if motion is not None:
+            rec = motion_records(motion)
+            in_range = node < np.uint32(len(rec))
+            r = rec[np.where(in_range, node, np.uint32(0))]
+            moving = in_range & (r[..., MOTION_KIND_WORD].view(np.uint32) == np.uint32(MOTION_MOVING))
+            Pm = np.stack([_dot(r[..., 4 * i:4 * i + 3], P) + r[..., 4 * i + 3] for i in range(3)], -1).astype(_F)
+            nm = np.stack([_dot(r[..., 12 + 4 * i:15 + 4 * i], n) for i in range(3)], -1).astype(_F)
+            reproj &= ~moving | (np.isfinite(Pm).all(-1) & np.isfinite(nm).all(-1))
+            Pq = np.where(moving[..., None], Pm, P).astype(_F)
+            nq = np.where(moving[..., None], nm, n).astype(_F)
         acc = np.zeros((h, w, 3), _F)
         acc_v = np.zeros((h, w), _F)
         wsum = np.zeros((h, w), _F)
@@ -169,7 +243,7 @@ def _accumulate(history, cam, rgba, variance, position, normal, depth, coverage,
             nrm = _cross(k["dU"], k["dV"])
             num = _dot((k["top_left"] - k["position"]).astype(_F), nrm)
             duu, dvv = _dot(k["dU"], k["dU"]), _dot(k["dV"], k["dV"])
-            rel = (P - k["position"]).astype(_F)
+            rel = (Pq - k["position"]).astype(_F)
             s = num / _dot(rel, nrm)
             ok = reproj & (s > 0) & (s <= _FLT_MAX)
             X = ((k["position"] + rel * s[..., None]) - k["top_left"]).astype(_F)
@@ -188,10 +262,10 @@ def _accumulate(history, cam, rgba, variance, position, normal, depth, coverage,
                 inside = ok & (qx >= 0) & (qx < w) & (qy >= 0) & (qy < h)
                 cx, cy = np.clip(qx, 0, w - 1), np.clip(qy, 0, h - 1)
                 ln = history.length[cy, cx]
-                nq, pq = history.normal[cy, cx], history.position[cy, cx]
+                nh, ph = history.normal[cy, cx], history.position[cy, cx]
                 counts = inside & (wt > 0) & (ln >= 1) & (history.node[cy, cx] == node)
-                counts &= _dot(n, nq) >= normal_cos_min
-                counts &= np.abs(_dot(n, (pq - P).astype(_F))) <= tol
+                counts &= _dot(nq, nh) >= normal_cos_min
+                counts &= np.abs(_dot(nq, (ph - Pq).astype(_F))) <= tol
                 acc = np.where(counts[..., None], acc + wt[..., None] * history.colour[cy, cx], acc).astype(_F)
                 acc_v = np.where(counts, acc_v + wt * history.variance[cy, cx], acc_v).astype(_F)
                 if moments:
