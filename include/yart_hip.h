@@ -229,6 +229,42 @@ int yart_hip_scene_create_flags(const YartSceneDesc* desc, int device, uint32_t 
 int yart_hip_scene_load(const char* path, int device, YartScene** out);
 void yart_hip_scene_destroy(YartScene* scene);
 
+/* New node and light transforms for a scene that is on the device — the next frame of a rigid animation without
+ * yart_hip_scene_destroy + yart_hip_scene_create. Re-derived, on the device unless noted: the nodes' transforms, identity flags and
+ * children-inclusive boxes, their padded world boxes, the boxes of the top-level hierarchy (scenes of 64 nodes and more; refitted
+ * in the tree the scene has, or with YART_UPDATE_REBUILD_TOP rebuilt on the host by scene creation's code), and on the host the
+ * lights' transforms, the area lights' area and power, the power CDF and the total power. The scene then renders the bits a scene
+ * freshly created from the same description renders. Nothing else is rebuilt or uploaded: BVHs, vertex / leaf / texture arrays,
+ * materials and environment tables stay. A scene graph of more than 64 levels is re-derived on the host and uploaded.
+ * nodes: n_nodes records, parent and mesh as at create, fwd / inv the new transforms. lights: n_lights = 0 leaves the lights
+ * untouched, else every record as at create except fwd / inv (a light that lies on a moved node moves only if its record does).
+ * Returns after the work has completed on `stream`. Takes the scene's lock like a render: it must not be called from a wave or tile
+ * callback of the same scene.
+ * YART_E_INVALID, with the scene and the device exactly as they were (everything is checked before the first write): scene, update
+ * or nodes NULL; struct_size too small; unknown flags; n_nodes not the scene's; a node's parent or mesh changed; n_lights neither 0
+ * nor the scene's; a light field other than fwd / inv changed; a matrix word of a node or light not finite; a mesh of the scene
+ * whose vertex box is not finite; a `stats` whose struct_size is below 8 (its first two fields).
+ * stats: the caller sets stats->struct_size = sizeof(YartSceneUpdateStats) before the call; that many bytes are written.
+ * Any other failure (YART_E_HIP: a copy or a launch failed after the first write) leaves the device arrays and the library's host
+ * copy in an unspecified state: the scene is unusable and is to be destroyed.
+ * Stream order: the copies and kernels of the update are enqueued on `stream`; the caller orders them against renders of this
+ * scene that are still running on OTHER streams (yart_hip_render*_device). A scene's first update (and the first refit after a
+ * YART_UPDATE_REBUILD_TOP) also uploads its topology tables with blocking copies on the null stream.
+ * Out of scope — re-create the scene: deforming meshes, a changed topology (nodes added, removed, re-parented or re-meshed),
+ * materials / emission, and the replicas of a YartMulti. */
+#define YART_UPDATE_REBUILD_TOP 1u   /* rebuild the top-level hierarchy (host, create's own code) instead of refitting its boxes */
+typedef struct YartSceneUpdate {
+  uint32_t struct_size;              /* sizeof(YartSceneUpdate) */
+  uint32_t n_nodes;                  /* the scene's node count */
+  const YartNodeDesc* nodes;         /* parent and mesh as at create; fwd / inv: the new transforms */
+  uint32_t n_lights;                 /* 0: lights untouched; else the scene's light count */
+  const YartLightDesc* lights;       /* every field as at create except fwd / inv */
+  uint32_t flags;                    /* YART_UPDATE_* */
+} YartSceneUpdate;
+/* launches: kernels launched; ms_total: wall time of the call; ms_device: from the first copy to the last on the stream */
+typedef struct YartSceneUpdateStats { uint32_t struct_size, launches; double ms_total, ms_device; } YartSceneUpdateStats;
+int yart_hip_scene_update(YartScene* scene, const YartSceneUpdate* update, void* stream, YartSceneUpdateStats* stats /* may be NULL */);
+
 /* glTF 2.0 / GLB import — what `gltf::load(path)` (src/gltf/gltf.cpp:319-358) followed
  * by the frontend's environment set-up (src/main.cpp:78-86) gives the renderer: materials with the KHR
  * transmission / ior / anisotropy / clearcoat / volume / emissive_strength extensions (gltf.cpp:62-176),
@@ -464,6 +500,10 @@ int yart_hip_probe_camera_rays(YartScene* scene, const YartCameraDesc* cam, cons
 /* the 32 device counter words of the last render on this scene ([0] rays, [1..4] exact
  * traversal tallies in the instrumented build, [8..] kernel-phase statistics in debug builds) */
 int yart_hip_debug_counters(YartScene* scene, uint64_t* out32);
+/* diagnostic read-back of what yart_hip_scene_update re-derives, from the device: the NodeDev records (176 bytes per node), the
+ * nodeWorld pairs (8 floats per node), the TlasNode records (32 bytes each; *n_tlas_out of them, 0 for a scene of fewer than 64
+ * nodes; room for 2 * nodes - 1). Any output pointer may be NULL. */
+int yart_hip_probe_scene_graph(YartScene* scene, void* nodes_out, float* node_world_out, void* tlas_out, uint32_t* n_tlas_out);
 /* measurement builds (-DYART_SHADE_REGIONS=1, tools/shade_regions.py) only: wave cycles [0..15], visits [16..31] and
  * active lanes [32..47] per code region of the shade kernel since the last call; YART_E_INVALID in the product build */
 int yart_hip_debug_shade_regions(uint64_t* out48);

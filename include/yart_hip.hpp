@@ -71,6 +71,20 @@ class DeviceScene {
   DeviceScene& operator=(const DeviceScene&) = delete;
   ~DeviceScene() { yart_hip_scene_destroy(h_); }
   YartScene* handle() const { return h_; }
+  // yart_hip_scene_update: new transforms for the scene's nodes (parent / mesh as at create) and, if any are given, its lights
+  // (every other field as at create); rebuildTop: YART_UPDATE_REBUILD_TOP. Returns the update's statistics.
+  YartSceneUpdateStats update(const std::vector<YartNodeDesc>& nodes, const std::vector<YartLightDesc>& lights = {}, bool rebuildTop = false,
+                              void* stream = nullptr) {
+    YartSceneUpdate u{};
+    u.struct_size = uint32_t(sizeof(u));
+    u.n_nodes = uint32_t(nodes.size()); u.nodes = nodes.data();
+    u.n_lights = uint32_t(lights.size()); u.lights = lights.empty() ? nullptr : lights.data();
+    u.flags = rebuildTop ? YART_UPDATE_REBUILD_TOP : 0u;
+    YartSceneUpdateStats st{};
+    st.struct_size = uint32_t(sizeof(st));
+    check(yart_hip_scene_update(h_, &u, stream, &st));
+    return st;
+  }
   // yart_hip_render_aovs: the frame plus the feature buffers of `mask` (YART_AOV_*), from the same camera samples. Several GPUs:
   // one call per device with params.rank / world_size, then add the buffers (ids: by max).
   AovFrame renderAovs(const YartCameraDesc& cam, const YartRenderParams& params, uint32_t mask = YART_AOV_ALL, YartStats* stats = nullptr) {

@@ -92,6 +92,24 @@ class LightDesc(C.Structure):
                 ("fwd", C.c_float * 16), ("inv", C.c_float * 16)]
 
 
+class SceneUpdate(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_nodes", C.c_uint32), ("nodes", C.POINTER(NodeDesc)),
+                ("n_lights", C.c_uint32), ("lights", C.POINTER(LightDesc)), ("flags", C.c_uint32)]
+
+
+class SceneUpdateStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_double), ("ms_device", C.c_double)]
+
+
+UPDATE_REBUILD_TOP = 1
+# the records of DeviceScene.scene_graph(): csrc/scene_types.hpp NodeDev and TlasNode
+NODE_DTYPE = np.dtype([("fwd", np.float32, 16), ("inv", np.float32, 16), ("bmin", np.float32, 3), ("mesh", np.int32),
+                       ("bmax", np.float32, 3), ("skip", np.uint32), ("parent", np.int32), ("depth", np.uint32),
+                       ("flags", np.uint32), ("pad", np.uint32)])
+TLAS_DTYPE = np.dtype([("lo", np.float32, 3), ("a", np.uint32), ("hi", np.float32, 3), ("b", np.uint32)])
+NODE_WORLD_DTYPE = np.dtype([("lo", np.float32, 3), ("lo_w", np.uint32), ("hi", np.float32, 3), ("hi_w", np.uint32)])
+
+
 class SceneDesc(C.Structure):
     _fields_ = [("n_textures", C.c_uint32), ("n_materials", C.c_uint32), ("n_meshes", C.c_uint32),
                 ("n_nodes", C.c_uint32), ("n_lights", C.c_uint32),
@@ -316,7 +334,8 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_temporal_create", "yart_hip_temporal_destroy", "yart_hip_temporal_reset",
            "yart_hip_temporal_accumulate_device", "yart_hip_temporal_accumulate_host",
            "yart_hip_temporal_accumulate_moments_device", "yart_hip_temporal_accumulate_moments_host",
-           "yart_hip_temporal_set_motion"]
+           "yart_hip_temporal_set_motion",
+           "yart_hip_scene_update", "yart_hip_probe_scene_graph"]
 
 LIB_COUNT_PATH = os.path.join(_HERE, "libyart_hip_count.so")   # instrumented twin (exact test counters)
 _libs = {}
@@ -404,6 +423,8 @@ def lib(instrumented: bool = False):
         L.yart_hip_temporal_accumulate_moments_host.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.c_void_p, C.c_void_p,
                                                                 C.POINTER(AovBuffers), C.POINTER(TemporalMomentParams), C.c_void_p,
                                                                 C.c_void_p, C.c_void_p]
+        L.yart_hip_scene_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdate), C.c_void_p, C.POINTER(SceneUpdateStats)]
+        L.yart_hip_probe_scene_graph.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         L.yart_hip_bvh_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.yart_hip_bvh_copy.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         _libs[path] = L
@@ -503,6 +524,18 @@ def make_params(p: dict, rank=0, world_size=1, flags=0) -> RenderParams:
     return r
 
 
+def _motion_snapshot(nodes):
+    """(parent, copy of fwd as binary32) per node: what yart_amd.temporal.node_motion needs of a node list, detached from it"""
+    return [(int(n.parent), np.array(n.fwd, np.float32, copy=True)) for n in nodes]
+
+
+def describe_scene(s: "yscn.Scene"):
+    """A :class:`yscn.Scene` as the C ABI's YartSceneDesc -> (desc, keep): `keep` owns every array the descriptor points into
+    and must outlive the calls that read `desc` (yart_hip_scene_create copies what it needs)."""
+    keep = []
+    return DeviceScene._describe_into(s, keep), keep
+
+
 class DeviceScene:
     """Owns a ``YartScene*`` (device-resident flattened scene + BVHs)."""
 
@@ -513,6 +546,10 @@ class DeviceScene:
         self._h = C.c_void_p()
         self._keep = []
         self._L = lib(instrumented)
+        # what the scene last held, where it is known: (parent, copy of fwd) per node — a snapshot, so that a caller who moves the
+        # nodes of their own yscn.Scene in place and hands them to update(motion=True) is compared with what was, not with itself
+        self._nodes, self._n_nodes = None, None
+        self.last_update = None                     # statistics of the last update(): dict(launches, ms_total, ms_device)
         if isinstance(scene, (str, os.PathLike)) and is_gltf_path(scene):
             o = import_options(env_hdr, env_radius, uniform_env)
             _check(self._L.yart_hip_scene_load_gltf(os.fspath(scene).encode(), C.byref(o), device, C.byref(self._h)),
@@ -521,6 +558,7 @@ class DeviceScene:
             _check(self._L.yart_hip_scene_load(os.fspath(scene).encode(), device, C.byref(self._h)), self._L)
         else:
             desc = self._describe(scene)
+            self._nodes, self._n_nodes = _motion_snapshot(scene.nodes), len(scene.nodes)
             if host_bvh:      # YART_SCENE_HOST_BVH: the meshes' BVHs from the host builder instead of the device build (same bytes)
                 self._L.yart_hip_scene_create_flags.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
                 _check(self._L.yart_hip_scene_create_flags(C.byref(desc), device, 2, C.byref(self._h)), self._L)
@@ -529,7 +567,10 @@ class DeviceScene:
         self._keep = []     # the library copies everything it needs
 
     def _describe(self, s: yscn.Scene) -> SceneDesc:
-        keep = self._keep
+        return self._describe_into(s, self._keep)
+
+    @staticmethod
+    def _describe_into(s: yscn.Scene, keep) -> SceneDesc:
 
         def ptr(a, dtype):
             a = np.ascontiguousarray(a, dtype=dtype); keep.append(a)
@@ -556,6 +597,47 @@ class DeviceScene:
         keep += [tex, mats, meshes, nodes, lights]
         return SceneDesc(len(s.textures), len(s.materials), len(s.meshes), len(s.nodes), len(s.lights),
                          tex, mats, meshes, nodes, lights)
+
+    # -- animation ----------------------------------------------------------------
+    def update(self, nodes, lights=None, rebuild_top=False, motion=False, stream=None):
+        """yart_hip_scene_update: new transforms for the scene in place. ``nodes`` / ``lights``: the node / light lists of a
+        :class:`yscn.Scene` — parent and mesh, and every light field but fwd / inv, as at create; ``lights=None`` leaves the lights
+        untouched. ``rebuild_top``: rebuild the top-level hierarchy instead of refitting its boxes. With ``motion=True`` returns
+        ``yart_amd.temporal.node_motion(the node list the scene held before, nodes)``. The call's statistics are in
+        ``self.last_update``."""
+        nodes = list(nodes)
+        nd = (NodeDesc * max(len(nodes), 1))()
+        for i, n in enumerate(nodes):
+            nd[i] = NodeDesc(n.parent, n.mesh, _f(n.fwd, 16), _f(n.inv, 16))
+        lights = list(lights) if lights is not None else []
+        ld = (LightDesc * max(len(lights), 1))()
+        for i, l in enumerate(lights):
+            ld[i] = LightDesc(l.type, l.mesh, l.tri, int(l.two_sided), l.texture, l.radius, _f(l.emission, 3), _f(l.fwd, 16), _f(l.inv, 16))
+        up = SceneUpdate(C.sizeof(SceneUpdate), len(nodes), nd, len(lights), ld if lights else None, UPDATE_REBUILD_TOP if rebuild_top else 0)
+        st = SceneUpdateStats(C.sizeof(SceneUpdateStats))
+        if motion and self._nodes is None:
+            raise YartError(YART_E_INVALID, "update(motion=True): the scene was loaded from a file, its previous node list is not known")
+        _check(self._L.yart_hip_scene_update(self._h, C.byref(up), stream, C.byref(st)), self._L)
+        self.last_update = dict(launches=st.launches, ms_total=st.ms_total, ms_device=st.ms_device)
+        previous, self._nodes, self._n_nodes = self._nodes, _motion_snapshot(nodes), len(nodes)
+        if motion:
+            from . import temporal
+            return temporal.node_motion(previous, self._nodes)
+        return None
+
+    def scene_graph(self):
+        """yart_hip_probe_scene_graph: what an update re-derives, read back from the device: (nodes, node_world, tlas) as
+        structured arrays of NODE_DTYPE, NODE_WORLD_DTYPE and TLAS_DTYPE (tlas: empty for a scene of fewer than 64 nodes). Only for a scene
+        made from a :class:`yscn.Scene` (or updated since): for one loaded from a file the node count is not known here, and
+        the call raises."""
+        n = C.c_uint32()
+        if self._n_nodes is None:                       # (the probe does not report the node count: scenes made from a yscn.Scene only)
+            raise YartError(YART_E_INVALID, "scene_graph(): the scene was loaded from a file, its node count is not known")
+        nodes, world = np.zeros(self._n_nodes, NODE_DTYPE), np.zeros(self._n_nodes, NODE_WORLD_DTYPE)
+        tlas = np.zeros(max(2 * self._n_nodes - 1, 1), TLAS_DTYPE)
+        _check(self._L.yart_hip_probe_scene_graph(self._h, nodes.ctypes.data_as(C.c_void_p), world.ctypes.data_as(C.c_void_p),
+                                                  tlas.ctypes.data_as(C.c_void_p), C.byref(n)), self._L)
+        return nodes, world, tlas[:n.value].copy()
 
     @property
     def handle(self):
@@ -859,9 +941,7 @@ class MultiDeviceScene:
             o = import_options(env_hdr, env_radius, uniform_env)
             _check(self._L.yart_hip_multi_load(os.fspath(scene).encode(), C.byref(o), devs, len(devices), C.byref(self._h)), self._L)
         else:
-            helper = DeviceScene.__new__(DeviceScene)
-            helper._keep = []
-            desc = DeviceScene._describe(helper, scene)
+            desc, _keep = describe_scene(scene)
             _check(self._L.yart_hip_multi_create(C.byref(desc), devs, len(devices), C.byref(self._h)), self._L)
 
     @property

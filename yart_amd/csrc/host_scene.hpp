@@ -22,6 +22,7 @@
 #include "bvh_build.hpp"
 #include "sampler.hpp"
 #include "scene_types.hpp"
+#include "scene_update.hpp"
 
 namespace yart_hip {
 
@@ -69,6 +70,10 @@ struct HostImage {
   // parametric.cpp:226-251 picks among them per hit) over the instanced triangles: a cheap stand-in for how mixed the
   // shade queue of this scene is. Below kShadeSortShare the shade kernel buckets its entries by material by default.
   float dominantLobeShare = 1.0f;
+  // What yart_hip_scene_update checks and starts from: every mesh's vertex box (a node's own box before its children are folded
+  // in) and the lights as they were described at create. (The nodes' parent / mesh are in `nodes`.)
+  std::vector<SuBox> meshBox;
+  std::vector<YartLightDesc> lightDesc;
 
   SceneDev view() const {
     SceneDev s{};
@@ -184,6 +189,72 @@ inline void checkStackBound(uint32_t need, uint32_t mesh) {
   if (need > kMaxStackBound)
     throw std::invalid_argument("mesh " + std::to_string(mesh) + ": its BVH is " + std::to_string(need) +
                                 " levels deep, the traversal stack holds at most " + std::to_string(kMaxStackBound));
+}
+
+// The top-level hierarchy of a scene of 64 nodes and more (empty otherwise), from the nodes' padded world boxes; returns its height.
+// Scene creation calls it, and yart_hip_scene_update under YART_UPDATE_REBUILD_TOP.
+inline uint32_t buildTopLevel(const std::vector<NodeDev>& nodes, const std::vector<f4>& nodeWorld, std::vector<TlasNode>& tlas) {
+  // spatial hierarchy over the mesh nodes' padded world boxes (scenes of 64 nodes and more): median splits of the box
+  // centres along the widest axis, one node per leaf. Any tree would do: a ray's query only has to return every mesh node whose
+  // box it hits (the kNodesTlas form of trace_lean.hpp), the exact tests then run in the reference's pre-order.
+  uint32_t height = 0;
+  const uint32_t nn = uint32_t(nodes.size());
+  tlas.clear();
+  if (nn >= 64) {
+    std::vector<uint32_t> ids;
+    for (uint32_t i = 0; i < nn; i++) if (nodes[i].mesh >= 0) ids.push_back(i);
+    if (!ids.empty()) {
+      // (a node whose padded world box is not finite — lo = -inf, hi = +inf — would give a NaN centre, and a comparator over
+      // NaNs is not a strict weak ordering: undefined behaviour in std::nth_element. Such centres count as 0; the hierarchy
+      // only filters, any split is valid.)
+      auto centre = [&](uint32_t n, int c) {
+        const float v = 0.5f * ((&nodeWorld[2 * n].x)[c] + (&nodeWorld[2 * n + 1].x)[c]);
+        return std::isfinite(v) ? v : 0.0f;
+      };
+      tlas.resize(2 * ids.size() - 1);
+      uint32_t used = 1;
+      // (median splits: a range of n ids is ceil(log2 n) levels high, 32 at the very most — far below the 64 entries every
+      // scene's stack has; checked below all the same, since the query pushes on the lane's traversal stack unguarded)
+      std::function<void(uint32_t, uint32_t, uint32_t, uint32_t)> build = [&](uint32_t at, uint32_t lo, uint32_t hi, uint32_t level) {
+        height = std::max(height, level);
+        TlasNode t{};
+        for (int c = 0; c < 3; c++) { t.lo[c] = kInf; t.hi[c] = -kInf; }
+        float cmin[3] = {kInf, kInf, kInf}, cmax[3] = {-kInf, -kInf, -kInf};
+        for (uint32_t k = lo; k < hi; k++)
+          for (int c = 0; c < 3; c++) {
+            t.lo[c] = std::min(t.lo[c], (&nodeWorld[2 * ids[k]].x)[c]); t.hi[c] = std::max(t.hi[c], (&nodeWorld[2 * ids[k] + 1].x)[c]);
+            cmin[c] = std::min(cmin[c], centre(ids[k], c)); cmax[c] = std::max(cmax[c], centre(ids[k], c));
+          }
+        if (hi - lo == 1) { t.a = ids[lo]; t.b = 1; tlas[at] = t; return; }
+        int axis = 0;
+        for (int c = 1; c < 3; c++) if (cmax[c] - cmin[c] > cmax[axis] - cmin[axis]) axis = c;
+        const uint32_t mid = lo + (hi - lo) / 2;
+        std::nth_element(ids.begin() + lo, ids.begin() + mid, ids.begin() + hi,
+                         [&](uint32_t x, uint32_t y) { const float cx = centre(x, axis), cy = centre(y, axis); return cx < cy || (cx == cy && x < y); });
+        t.a = used; t.b = 0; used += 2;
+        tlas[at] = t;
+        build(t.a, lo, mid, level + 1); build(t.a + 1, mid, hi, level + 1);
+      };
+      build(0, 0, uint32_t(ids.size()), 0);
+      require(height <= 32u, "top-level hierarchy: higher than a median split can make it");
+    }
+  }
+  return height;
+}
+
+// An area light's area and power from its transform and its triangle's object-space vertices (AreaLight ctor, light.cpp:16-38), and
+// its entry of the power CDF: a sequential binary32 running sum in light order (light-sampler.cpp:43-47). Scene creation and
+// yart_hip_scene_update both derive the lights through these two.
+inline void deriveAreaLight(LightDev& ld, f3 p0, f3 p1, f3 p2) {
+  f3 t0 = mulPoint(ld.xf.fwd, p0);
+  f3 t1 = mulPoint(ld.xf.fwd, p1);
+  f3 t2 = mulPoint(ld.xf.fwd, p2);
+  ld.area = triangleAreaHost(t0, t1, t2);                                   // light.cpp:26-33
+  ld.power = length(ld.emission) * ld.area * kPi * (ld.twoSided ? 2.0f : 1.0f);   // :36-38
+}
+inline void addAreaPower(float power, float& cdfEntry, float& totalPower) {
+  cdfEntry = totalPower + power;                                            // light-sampler.cpp:46-47
+  totalPower += power;
 }
 
 inline HostImage buildHostImage(const YartSceneDesc& d, MeshBvhFn bvhFn = nullptr, void* bvhCtx = nullptr) {
@@ -391,6 +462,13 @@ inline HostImage buildHostImage(const YartSceneDesc& d, MeshBvhFn bvhFn = nullpt
       st.material = tv.w; st.light = m.face_light ? m.face_light[f] : -1;
       im.shadeTris.push_back(st);
     }
+    {
+      Bounds3 vb;                                                 // Node(Mesh*), scene.hpp:17-22: the box of the mesh's vertices
+      for (uint32_t v = 0; v < m.n_vertices; v++) vb.expand(m.positions + size_t(v) * 3);
+      SuBox sb;
+      for (int c = 0; c < 3; c++) { sb.mn[c] = vb.mn[c]; sb.mx[c] = vb.mx[c]; }
+      im.meshBox.push_back(sb);
+    }
     for (uint32_t v = 0; v < m.n_vertices; v++) {
       f4 p; p.x = m.positions[3 * v]; p.y = m.positions[3 * v + 1]; p.z = m.positions[3 * v + 2]; p.w = 0;
       f4 n; n.x = m.normals[3 * v]; n.y = m.normals[3 * v + 1]; n.z = m.normals[3 * v + 2]; n.w = 0;
@@ -430,10 +508,8 @@ inline HostImage buildHostImage(const YartSceneDesc& d, MeshBvhFn bvhFn = nullpt
     }
     require(nn < (1u << 20), "more than 2^20 scene nodes are not supported");   // wavefront.hpp::wfHitWord
     if (nd.depth > im.maxNodeDepth) im.maxNodeDepth = nd.depth;
-    if (n.mesh >= 0) {                                          // Node(Mesh*), scene.hpp:17-22
-      const YartMeshDesc& m = d.meshes[n.mesh];
-      for (uint32_t v = 0; v < m.n_vertices; v++) nb[i].expand(m.positions + size_t(v) * 3);
-    }
+    if (n.mesh >= 0)                                            // Node(Mesh*), scene.hpp:17-22
+      for (int c = 0; c < 3; c++) { nb[i].mn[c] = im.meshBox[n.mesh].mn[c]; nb[i].mx[c] = im.meshBox[n.mesh].mx[c]; }
   }
   for (uint32_t i = nn; i-- > 1;) {                             // appendChild bottom-up, scene.hpp:48-52
     const NodeDev& c = im.nodes[i];
@@ -516,49 +592,8 @@ inline HostImage buildHostImage(const YartSceneDesc& d, MeshBvhFn bvhFn = nullpt
     im.nodeWorld[2 * i] = lo; im.nodeWorld[2 * i + 1] = hi;
   }
 
-  // ---- spatial hierarchy over the mesh nodes' padded world boxes (scenes of 64 nodes and more): median splits of the box
-  // centres along the widest axis, one node per leaf. Any tree would do: a ray's query only has to return every mesh node whose
-  // box it hits (the kNodesTlas form of trace_lean.hpp), the exact tests then run in the reference's pre-order.
-  if (nn >= 64) {
-    std::vector<uint32_t> ids;
-    for (uint32_t i = 0; i < nn; i++) if (im.nodes[i].mesh >= 0) ids.push_back(i);
-    if (!ids.empty()) {
-      // (a node whose padded world box is not finite — lo = -inf, hi = +inf — would give a NaN centre, and a comparator over
-      // NaNs is not a strict weak ordering: undefined behaviour in std::nth_element. Such centres count as 0; the hierarchy
-      // only filters, any split is valid.)
-      auto centre = [&](uint32_t n, int c) {
-        const float v = 0.5f * ((&im.nodeWorld[2 * n].x)[c] + (&im.nodeWorld[2 * n + 1].x)[c]);
-        return std::isfinite(v) ? v : 0.0f;
-      };
-      im.tlas.resize(2 * ids.size() - 1);
-      uint32_t used = 1;
-      // (median splits: a range of n ids is ceil(log2 n) levels high, 32 at the very most — far below the 64 entries every
-      // scene's stack has; checked below all the same, since the query pushes on the lane's traversal stack unguarded)
-      std::function<void(uint32_t, uint32_t, uint32_t, uint32_t)> build = [&](uint32_t at, uint32_t lo, uint32_t hi, uint32_t level) {
-        im.tlasHeight = std::max(im.tlasHeight, level);
-        TlasNode t{};
-        for (int c = 0; c < 3; c++) { t.lo[c] = kInf; t.hi[c] = -kInf; }
-        float cmin[3] = {kInf, kInf, kInf}, cmax[3] = {-kInf, -kInf, -kInf};
-        for (uint32_t k = lo; k < hi; k++)
-          for (int c = 0; c < 3; c++) {
-            t.lo[c] = std::min(t.lo[c], (&im.nodeWorld[2 * ids[k]].x)[c]); t.hi[c] = std::max(t.hi[c], (&im.nodeWorld[2 * ids[k] + 1].x)[c]);
-            cmin[c] = std::min(cmin[c], centre(ids[k], c)); cmax[c] = std::max(cmax[c], centre(ids[k], c));
-          }
-        if (hi - lo == 1) { t.a = ids[lo]; t.b = 1; im.tlas[at] = t; return; }
-        int axis = 0;
-        for (int c = 1; c < 3; c++) if (cmax[c] - cmin[c] > cmax[axis] - cmin[axis]) axis = c;
-        const uint32_t mid = lo + (hi - lo) / 2;
-        std::nth_element(ids.begin() + lo, ids.begin() + mid, ids.begin() + hi,
-                         [&](uint32_t x, uint32_t y) { const float cx = centre(x, axis), cy = centre(y, axis); return cx < cy || (cx == cy && x < y); });
-        t.a = used; t.b = 0; used += 2;
-        im.tlas[at] = t;
-        build(t.a, lo, mid, level + 1); build(t.a + 1, mid, hi, level + 1);
-      };
-      build(0, 0, uint32_t(ids.size()), 0);
-      require(im.tlasHeight <= 32u, "top-level hierarchy: higher than a median split can make it");
-      im.stackBound = std::max(im.stackBound, im.tlasHeight);
-    }
-  }
+  im.tlasHeight = buildTopLevel(im.nodes, im.nodeWorld, im.tlas);
+  im.stackBound = std::max(im.stackBound, im.tlasHeight);
   if (im.tlas.empty()) im.tlas.resize(1);
 
   // ---- lights (light.cpp, light-sampler.cpp:32-50) ------------------------------
@@ -574,14 +609,10 @@ inline HostImage buildHostImage(const YartSceneDesc& d, MeshBvhFn bvhFn = nullpt
               "area light: mesh / triangle out of range");
       const YartMeshDesc& m = d.meshes[l.mesh];
       auto P = [&](uint32_t v) { return mk3(m.positions[3 * v], m.positions[3 * v + 1], m.positions[3 * v + 2]); };
-      f3 t0 = mulPoint(ld.xf.fwd, P(m.faces[4 * l.tri]));
-      f3 t1 = mulPoint(ld.xf.fwd, P(m.faces[4 * l.tri + 1]));
-      f3 t2 = mulPoint(ld.xf.fwd, P(m.faces[4 * l.tri + 2]));
-      ld.area = triangleAreaHost(t0, t1, t2);                                   // light.cpp:26-33
-      ld.power = length(ld.emission) * ld.area * kPi * (l.two_sided ? 2.0f : 1.0f);   // :36-38
+      deriveAreaLight(ld, P(m.faces[4 * l.tri]), P(m.faces[4 * l.tri + 1]), P(m.faces[4 * l.tri + 2]));
       im.areaLights.push_back(i);
-      im.areaPowerCdf.push_back(im.totalPower + ld.power);                      // light-sampler.cpp:46-47
-      im.totalPower += ld.power;
+      im.areaPowerCdf.push_back(0.0f);
+      addAreaPower(ld.power, im.areaPowerCdf.back(), im.totalPower);
     } else if (l.type == LIGHT_UNIFORM_INF) {
       ld.power = 4.0f * kPi * kPi * l.radius * l.radius * length(ld.emission);   // light.cpp:98-103
       im.infiniteLights.push_back(i);
@@ -682,6 +713,7 @@ inline HostImage buildHostImage(const YartSceneDesc& d, MeshBvhFn bvhFn = nullpt
       require(false, "light: unknown type");
     }
     im.lights.push_back(ld);
+    im.lightDesc.push_back(l);
   }
   // hit.lightIdx (per-mesh numbering) is used as a global light index by the reference
   // (mis-integrator.cpp:65): validate it stays in range.
@@ -731,6 +763,26 @@ inline HostImage buildHostImage(const YartSceneDesc& d, MeshBvhFn bvhFn = nullpt
     im.dominantLobeShare = total > 0 ? float(top / total) : 1.0f;
   }
   return im;
+}
+
+// yart_hip_scene_update: the lights of an image from new transforms (every other field as at create; n: the image's light count).
+// Area and power of the area lights, the power CDF in light order and the total power, by the functions scene creation uses; the
+// triangles' vertices are the image's own copies.
+inline void rederiveLights(HostImage& h, const YartLightDesc* lights, uint32_t n) {
+  float total = 0.0f;
+  uint32_t area = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    LightDev& ld = h.lights[i];
+    std::memcpy(ld.xf.fwd, lights[i].fwd, 64); std::memcpy(ld.xf.inv, lights[i].inv, 64);
+    h.lightDesc[i] = lights[i];
+    if (ld.type != LIGHT_AREA) continue;
+    const MeshDev& m = h.meshes[ld.mesh];
+    const u4 tv = h.triVerts[m.triOffset + ld.tri];
+    auto P = [&](uint32_t v) { const f4 p = h.vPos[m.vertOffset + v]; return mk3(p.x, p.y, p.z); };
+    deriveAreaLight(ld, P(tv.x), P(tv.y), P(tv.z));
+    addAreaPower(ld.power, h.areaPowerCdf[area++], total);
+  }
+  h.totalPower = total;
 }
 
 // Camera::calcDerivedProperties (camera.hpp:25-59) after moveAndLookAt (:123-130)

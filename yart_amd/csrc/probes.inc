@@ -128,6 +128,20 @@ int yart_hip_probe_samples(YartScene* scene, const YartCameraDesc* cam, const Ya
   });
 }
 
+int yart_hip_probe_scene_graph(YartScene* scene, void* nodes_out, float* node_world_out, void* tlas_out, uint32_t* n_tlas_out) {
+  return guarded([&] {
+    require(scene, "probe_scene_graph: scene pointer is null");
+    std::lock_guard<std::mutex> lock(scene->mu);
+    YartScene& s = *scene;
+    HIP_CHECK(hipSetDevice(s.device));
+    const size_t nn = s.host.nodes.size();
+    if (nodes_out) HIP_CHECK(hipMemcpy(nodes_out, s.nodes.p, nn * sizeof(NodeDev), hipMemcpyDeviceToHost));
+    if (node_world_out) HIP_CHECK(hipMemcpy(node_world_out, s.nodeWorld.p, nn * 2u * sizeof(f4), hipMemcpyDeviceToHost));
+    if (tlas_out && s.dev.nTlas) HIP_CHECK(hipMemcpy(tlas_out, s.tlas.p, size_t(s.dev.nTlas) * sizeof(TlasNode), hipMemcpyDeviceToHost));
+    if (n_tlas_out) *n_tlas_out = s.dev.nTlas;
+  });
+}
+
 int yart_hip_probe_hits(YartScene* scene, uint32_t n, const float* rays, float* out) {
   return guarded([&] {
     require(scene && rays && out, "null pointer");

@@ -279,6 +279,18 @@ struct Timer {
 
 }  // namespace
 
+// What yart_hip_scene_update keeps per scene (scene_update_kernels.inc): tables of the topology, built at the first update, and
+// the staging buffers of the uploaded transforms.
+struct SceneUpdateTables {
+  bool ready = false, tlasReady = false;
+  uint32_t levels = 0;                                  // levels of the scene graph (deepest node's depth + 1)
+  DevBuf<uint32_t> parents, childOff, childIdx;         // nodes with children by level; their children as a CSR list
+  std::vector<uint32_t> levelFirst, levelBig, levelSmall;   // per level: its range of `parents` (kSuFanOut and more children first)
+  DevBuf<SuBox> meshBox;
+  DevBuf<uint32_t> tlasOrder; std::vector<uint32_t> tlasFirst;   // the top-level tree's nodes by level
+  DevBuf<uint32_t> stageDesc, stageFlags;
+};
+
 struct YartScene {
   int device = 0;
   HostImage host;
@@ -317,6 +329,7 @@ struct YartScene {
   std::vector<TileRec> tiles;
   unsigned long long lastCounters[32] = {0};
   uint32_t pixW = 0, pixH = 0, pixTile = 0, pixRank = 0, pixWorld = 0;
+  SceneUpdateTables su;
   std::mutex mu;
 };
 
@@ -1585,4 +1598,5 @@ int yart_hip_bvh_build_host(const float* positions, uint32_t n_verts, const uint
 }  // extern "C"
 
 #include "postprocess.inc"
+#include "scene_update_kernels.inc"
 #include "probes.inc"
