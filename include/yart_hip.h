@@ -250,8 +250,8 @@ void yart_hip_scene_destroy(YartScene* scene);
  * Stream order: the copies and kernels of the update are enqueued on `stream`; the caller orders them against renders of this
  * scene that are still running on OTHER streams (yart_hip_render*_device). A scene's first update (and the first refit after a
  * YART_UPDATE_REBUILD_TOP) also uploads its topology tables with blocking copies on the null stream.
- * Out of scope — re-create the scene: deforming meshes, a changed topology (nodes added, removed, re-parented or re-meshed),
- * materials / emission, and the replicas of a YartMulti. */
+ * Out of scope — re-create the scene: a changed topology (nodes added, removed, re-parented or re-meshed), materials / emission,
+ * and the replicas of a YartMulti. Deforming meshes: yart_hip_scene_update_meshes below. */
 #define YART_UPDATE_REBUILD_TOP 1u   /* rebuild the top-level hierarchy (host, create's own code) instead of refitting its boxes */
 typedef struct YartSceneUpdate {
   uint32_t struct_size;              /* sizeof(YartSceneUpdate) */
@@ -264,6 +264,48 @@ typedef struct YartSceneUpdate {
 /* launches: kernels launched; ms_total: wall time of the call; ms_device: from the first copy to the last on the stream */
 typedef struct YartSceneUpdateStats { uint32_t struct_size, launches; double ms_total, ms_device; } YartSceneUpdateStats;
 int yart_hip_scene_update(YartScene* scene, const YartSceneUpdate* update, void* stream, YartSceneUpdateStats* stats /* may be NULL */);
+
+/* New vertices for meshes of a scene that is on the device — the next frame of a skinned character, a cloth or a morphing height
+ * field without yart_hip_scene_destroy + yart_hip_scene_create: textures, footprint records, environment tables, materials and every
+ * mesh that is not listed stay where they are. Per listed mesh the positions (and normals / tangents, if given) are uploaded and the
+ * vertex arrays rewritten; the mesh's BVH is REBUILT on the device by the builder scene creation uses (not refitted: the contract is
+ * the bits the reference renders, and its Mesh constructor builds the tree from the vertices it is given — a refitted tree changes
+ * the traversal order, and with it the stochastic alpha-test draws and equal-t ties); leaf records, link words (alpha bit, span),
+ * the mesh's alpha flag and, with normals / tangents, the shading records are re-derived on the device; the node array is repacked
+ * when a tree's node count changed; the traversal stack bound is re-derived (it sizes the spill area of the next render, growing or
+ * shrinking). On the host, from the caller's positions: the mesh's vertex box (exact in the sign of zeros) and area, power, power CDF
+ * and total power of area lights on a listed mesh. Then the nodes' boxes, world boxes and the top-level hierarchy are re-derived by
+ * yart_hip_scene_update's own chain with the scene's current transforms (flags: YART_UPDATE_REBUILD_TOP as there). Afterwards the
+ * scene holds, and renders, the bits of a scene freshly created from the same description; yart_hip_bvh_info / yart_hip_bvh_copy
+ * return the new tree, a later yart_hip_scene_update starts from the new boxes. The two entries combine in either order for a frame
+ * that moves nodes and deforms meshes. Faces, materials, uvs, face_light, the node list and the transforms are unchanged.
+ * Locking, `stream` and `stats` as for yart_hip_scene_update (the build reads a few counter words back per tree level: `stream` is
+ * synchronised that often). Scratch memory of the build is kept in the scene and grown on demand: an animation allocates nothing
+ * per frame once its largest mesh has been built and a node count has changed twice.
+ * YART_E_INVALID, with the scene and the device exactly as they were: scene, update or meshes NULL; struct_size too small; unknown
+ * flags; n_meshes 0 or more than the scene's mesh count; a mesh index out of range or listed twice; n_vertices not the mesh's;
+ * positions NULL; a position, normal or tangent word not finite; a rebuilt tree deeper than 192 levels (known only after the build:
+ * every listed mesh is built into scratch first, the scene is written once all have built; the message names the mesh and its
+ * depth, as scene creation's does); a mesh that is not listed whose vertex box is not finite; stats->struct_size below 8.
+ * A mesh the device build refuses, and every mesh under the environment variable YART_HOST_BVH, is built and derived on the host
+ * and uploaded: the same bytes.
+ * Not kept current: the default pipeline's lobe-share heuristic stays as at create (every pipeline renders the same frame).
+ * Out of scope — re-create the scene: changed faces or vertex counts, uvs, materials, the replicas of a YartMulti. Per-vertex motion
+ * for the temporal accumulator: a deformed node's pixels are reprojected as if the node were rigid. */
+typedef struct YartMeshUpdate {
+  uint32_t mesh;                     /* index into the scene's meshes */
+  uint32_t n_vertices;               /* the mesh's vertex count, as at create */
+  const float* positions;            /* HOST, 3 per vertex, required */
+  const float* normals;              /* HOST, 3 per vertex, or NULL: kept */
+  const float* tangents;             /* HOST, 4 per vertex, or NULL: kept */
+} YartMeshUpdate;
+typedef struct YartSceneMeshUpdate {
+  uint32_t struct_size;              /* sizeof(YartSceneMeshUpdate) */
+  uint32_t n_meshes;                 /* meshes listed: 1 .. the scene's mesh count */
+  const YartMeshUpdate* meshes;      /* each mesh at most once */
+  uint32_t flags;                    /* YART_UPDATE_REBUILD_TOP */
+} YartSceneMeshUpdate;
+int yart_hip_scene_update_meshes(YartScene* scene, const YartSceneMeshUpdate* update, void* stream, YartSceneUpdateStats* stats /* may be NULL */);
 
 /* glTF 2.0 / GLB import — what `gltf::load(path)` (src/gltf/gltf.cpp:319-358) followed
  * by the frontend's environment set-up (src/main.cpp:78-86) gives the renderer: materials with the KHR
@@ -504,6 +546,13 @@ int yart_hip_debug_counters(YartScene* scene, uint64_t* out32);
  * nodeWorld pairs (8 floats per node), the TlasNode records (32 bytes each; *n_tlas_out of them, 0 for a scene of fewer than 64
  * nodes; room for 2 * nodes - 1). Any output pointer may be NULL. */
 int yart_hip_probe_scene_graph(YartScene* scene, void* nodes_out, float* node_world_out, void* tlas_out, uint32_t* n_tlas_out);
+/* diagnostic read-back of one mesh as the kernels see it, from the device (not from the library's host copy): its MeshDev record
+ * (64 bytes: nodeOffset, leafOffset, triOffset, vertOffset, nTris, nVerts, nNodes, hasAlpha, 8 unused words), its nNodes BvhNode records
+ * (32 bytes; the link words with alpha and span bits), its nTris LeafTri (48 bytes) and ShadeTri (128 bytes) records, its nVerts
+ * vPos / vNormal / vTangent entries (4 floats each), and the scene's current traversal stack bound. Any output pointer may be NULL:
+ * a first call with mesh_dev_out alone gives the counts the arrays need. */
+int yart_hip_probe_mesh(YartScene* scene, uint32_t mesh, void* mesh_dev_out, void* nodes_out, void* leaf_out, void* shade_out, float* vpos_out,
+                        float* vnormal_out, float* vtangent_out, uint32_t* stack_bound_out);
 /* measurement builds (-DYART_SHADE_REGIONS=1, tools/shade_regions.py) only: wave cycles [0..15], visits [16..31] and
  * active lanes [32..47] per code region of the shade kernel since the last call; YART_E_INVALID in the product build */
 int yart_hip_debug_shade_regions(uint64_t* out48);

@@ -85,6 +85,18 @@ class DeviceScene {
     check(yart_hip_scene_update(h_, &u, stream, &st));
     return st;
   }
+  // yart_hip_scene_update_meshes: new vertices for the listed meshes (each at most once; vertex counts as at create; normals /
+  // tangents NULL: kept); rebuildTop: YART_UPDATE_REBUILD_TOP. Returns the update's statistics.
+  YartSceneUpdateStats updateMeshes(const std::vector<YartMeshUpdate>& meshes, bool rebuildTop = false, void* stream = nullptr) {
+    YartSceneMeshUpdate u{};
+    u.struct_size = uint32_t(sizeof(u));
+    u.n_meshes = uint32_t(meshes.size()); u.meshes = meshes.data();
+    u.flags = rebuildTop ? YART_UPDATE_REBUILD_TOP : 0u;
+    YartSceneUpdateStats st{};
+    st.struct_size = uint32_t(sizeof(st));
+    check(yart_hip_scene_update_meshes(h_, &u, stream, &st));
+    return st;
+  }
   // yart_hip_render_aovs: the frame plus the feature buffers of `mask` (YART_AOV_*), from the same camera samples. Several GPUs:
   // one call per device with params.rank / world_size, then add the buffers (ids: by max).
   AovFrame renderAovs(const YartCameraDesc& cam, const YartRenderParams& params, uint32_t mask = YART_AOV_ALL, YartStats* stats = nullptr) {

@@ -101,7 +101,26 @@ class SceneUpdateStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_double), ("ms_device", C.c_double)]
 
 
+class MeshUpdate(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("n_vertices", C.c_uint32), ("positions", C.c_void_p), ("normals", C.c_void_p),
+                ("tangents", C.c_void_p)]
+
+
+class SceneMeshUpdate(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_meshes", C.c_uint32), ("meshes", C.POINTER(MeshUpdate)), ("flags", C.c_uint32)]
+
+
 UPDATE_REBUILD_TOP = 1
+# the records of DeviceScene.mesh_records(): csrc/scene_types.hpp MeshDev, BvhNode (link: index | alpha bit 26 | span << 27),
+# LeafTri (mat_flags: MAT_* of the material; a leaf's first record: | span << 8) and ShadeTri
+MESH_DTYPE = np.dtype([("node_offset", np.uint32), ("leaf_offset", np.uint32), ("tri_offset", np.uint32), ("vert_offset", np.uint32),
+                       ("n_tris", np.uint32), ("n_verts", np.uint32), ("n_nodes", np.uint32), ("has_alpha", np.uint32),
+                       ("pad", np.uint32, 8)])
+BVH_NODE_DTYPE = np.dtype([("bmin", np.float32, 3), ("bmax", np.float32, 3), ("link", np.uint32), ("span", np.uint32)])
+LEAF_TRI_DTYPE = np.dtype([("p0", np.float32, 3), ("tri", np.uint32), ("e1", np.float32, 3), ("mat_flags", np.uint32),
+                           ("e2", np.float32, 3), ("material", np.uint32)])
+SHADE_TRI_DTYPE = np.dtype([("n", np.float32, (3, 3)), ("t", np.float32, (3, 4)), ("uv", np.float32, (3, 2)), ("material", np.uint32),
+                            ("light", np.int32), ("pad", np.uint32, 3)])
 # the records of DeviceScene.scene_graph(): csrc/scene_types.hpp NodeDev and TlasNode
 NODE_DTYPE = np.dtype([("fwd", np.float32, 16), ("inv", np.float32, 16), ("bmin", np.float32, 3), ("mesh", np.int32),
                        ("bmax", np.float32, 3), ("skip", np.uint32), ("parent", np.int32), ("depth", np.uint32),
@@ -335,7 +354,8 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_temporal_accumulate_device", "yart_hip_temporal_accumulate_host",
            "yart_hip_temporal_accumulate_moments_device", "yart_hip_temporal_accumulate_moments_host",
            "yart_hip_temporal_set_motion",
-           "yart_hip_scene_update", "yart_hip_probe_scene_graph"]
+           "yart_hip_scene_update", "yart_hip_probe_scene_graph",
+           "yart_hip_scene_update_meshes", "yart_hip_probe_mesh"]
 
 LIB_COUNT_PATH = os.path.join(_HERE, "libyart_hip_count.so")   # instrumented twin (exact test counters)
 _libs = {}
@@ -425,6 +445,9 @@ def lib(instrumented: bool = False):
                                                                 C.c_void_p, C.c_void_p]
         L.yart_hip_scene_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdate), C.c_void_p, C.POINTER(SceneUpdateStats)]
         L.yart_hip_probe_scene_graph.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+        L.yart_hip_scene_update_meshes.argtypes = [C.c_void_p, C.POINTER(SceneMeshUpdate), C.c_void_p, C.POINTER(SceneUpdateStats)]
+        L.yart_hip_probe_mesh.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.POINTER(C.c_uint32)]
         L.yart_hip_bvh_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.yart_hip_bvh_copy.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         _libs[path] = L
@@ -624,6 +647,49 @@ class DeviceScene:
             from . import temporal
             return temporal.node_motion(previous, self._nodes)
         return None
+
+    def update_meshes(self, meshes, rebuild_top=False, stream=None):
+        """yart_hip_scene_update_meshes: new vertices for meshes of the scene in place. ``meshes``: {mesh index: positions} or
+        {mesh index: (positions, normals, tangents)} with (n, 3) / (n, 3) / (n, 4) arrays for the mesh's n vertices; normals /
+        tangents may be None or left out: kept. Faces, uvs, materials and the node list stay. ``rebuild_top``: rebuild the top-level
+        hierarchy instead of refitting its boxes. The call's statistics are in ``self.last_update``."""
+        keep, md = [], (MeshUpdate * max(len(meshes), 1))()
+        for k, (mesh, arrays) in enumerate(meshes.items()):
+            if isinstance(arrays, np.ndarray) or not isinstance(arrays, (tuple, list)):
+                arrays = (arrays,)
+            arrays = tuple(arrays) + (None,) * (3 - len(arrays))
+            ptrs, n = [], None
+            for a, width in zip(arrays, (3, 3, 4)):
+                if a is None:
+                    ptrs.append(None)
+                    continue
+                a = np.ascontiguousarray(a, np.float32).reshape(-1, width)
+                if n is not None and len(a) != n:
+                    raise YartError(YART_E_INVALID, f"update_meshes: mesh {mesh}: the arrays differ in their vertex counts")
+                n = len(a)
+                keep.append(a)
+                ptrs.append(a.ctypes.data_as(C.c_void_p))
+            n = n or 0
+            md[k] = MeshUpdate(int(mesh), n, ptrs[0], ptrs[1], ptrs[2])
+        up = SceneMeshUpdate(C.sizeof(SceneMeshUpdate), len(meshes), md, UPDATE_REBUILD_TOP if rebuild_top else 0)
+        st = SceneUpdateStats(C.sizeof(SceneUpdateStats))
+        _check(self._L.yart_hip_scene_update_meshes(self._h, C.byref(up), stream, C.byref(st)), self._L)
+        self.last_update = dict(launches=st.launches, ms_total=st.ms_total, ms_device=st.ms_device)
+
+    def mesh_records(self, mesh):
+        """yart_hip_probe_mesh: one mesh as the kernels see it, read back from the device: dict(mesh: MESH_DTYPE record, nodes:
+        BVH_NODE_DTYPE, leaves: LEAF_TRI_DTYPE, shade: SHADE_TRI_DTYPE, positions / normals / tangents: (n_verts, 4) float32,
+        stack_bound: the scene's current traversal stack bound)."""
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        md, bound = np.zeros(1, MESH_DTYPE), C.c_uint32()
+        _check(self._L.yart_hip_probe_mesh(self._h, int(mesh), vp(md), None, None, None, None, None, None, C.byref(bound)), self._L)
+        nt, nv, nn = int(md["n_tris"][0]), int(md["n_verts"][0]), int(md["n_nodes"][0])
+        nodes, leaves, shade = np.zeros(nn, BVH_NODE_DTYPE), np.zeros(nt, LEAF_TRI_DTYPE), np.zeros(nt, SHADE_TRI_DTYPE)
+        pos, nrm, tan = (np.zeros((nv, 4), np.float32) for _ in range(3))
+        _check(self._L.yart_hip_probe_mesh(self._h, int(mesh), vp(md), vp(nodes), vp(leaves), vp(shade), vp(pos), vp(nrm), vp(tan),
+                                           C.byref(bound)), self._L)
+        return dict(mesh=md[0], nodes=nodes, leaves=leaves, shade=shade, positions=pos, normals=nrm, tangents=tan,
+                    stack_bound=int(bound.value))
 
     def scene_graph(self):
         """yart_hip_probe_scene_graph: what an update re-derives, read back from the device: (nodes, node_world, tlas) as

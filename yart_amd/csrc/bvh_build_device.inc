@@ -642,37 +642,55 @@ __global__ void k_emit(Args a, uint32_t base, uint32_t count) {
   a.out[at] = o;
 }
 
-// Builds the BVH of one mesh on `device`. Returns false (nothing written) if the input has NaN coordinates or the tree is
-// deeper than kMaxLevels: the caller then builds on the host. ms: device time of the build, upload and download excluded.
-inline bool build(int device, const float* positions, uint32_t nVerts, const uint32_t* tris, uint32_t stride, uint32_t nTris,
-                  std::vector<BvhNode>& nodesOut, std::vector<uint32_t>& indicesOut, double* ms) {
-  require(nTris >= 1 && nVerts >= 1 && stride >= 3, "bvh build: empty mesh");
-  HIP_CHECK(hipSetDevice(device));
-  DevBuf<float> pos, cent, tb;
-  DevBuf<uint32_t> tri, idx, idxTmp, code, tmpR, tmpL, counter, localRoots;
+// The build's working arrays, sized by the triangle count and grown on demand: a caller that builds again and again (a scene
+// whose meshes deform, mesh_update_kernels.inc) keeps one of these and allocates nothing per build.
+struct Scratch {
+  DevBuf<float> cent, tb;
+  DevBuf<uint32_t> idxTmp, code, tmpR, tmpL, counter, localRoots;
   DevBuf<BNode> nodes;
-  DevBuf<BvhNode> out;
-  pos.ensure(size_t(nVerts) * 3); tri.ensure(size_t(nTris) * stride);
-  HIP_CHECK(hipMemcpy(pos.p, positions, size_t(nVerts) * 12, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(tri.p, tris, size_t(nTris) * stride * 4, hipMemcpyHostToDevice));
-  cent.ensure(size_t(nTris) * 3); tb.ensure(size_t(nTris) * 6);
-  idx.ensure(nTris); idxTmp.ensure(nTris); code.ensure(nTris); tmpR.ensure(nTris); tmpL.ensure(nTris); counter.ensure(8);
-  nodes.ensure(size_t(nTris) * 4); out.ensure(size_t(nTris) * 2); localRoots.ensure(size_t(nTris) + 1);
-  HIP_CHECK(hipMemset(counter.p, 0, 32));
+  void ensure(uint32_t nTris) {
+    cent.ensure(size_t(nTris) * 3); tb.ensure(size_t(nTris) * 6);
+    idxTmp.ensure(nTris); code.ensure(nTris); tmpR.ensure(nTris); tmpL.ensure(nTris); counter.ensure(8);
+    nodes.ensure(size_t(nTris) * 4); localRoots.ensure(size_t(nTris) + 1);
+  }
+};
+// What a build leaves on the device besides the node array and the permutation: the build nodes (ids [0, created) from the level
+// kernels, [2 nTris, 2 nTris + createdLocal) from k_subtree) with their index ranges and parent links, for passes over the tree.
+struct Built {
+  Args args{};
+  uint32_t created = 0, createdLocal = 0;
+  uint32_t launches = 0;
+  uint32_t nNodes() const { return created + createdLocal; }
+};
+
+// The build proper, on device arrays and a stream: `positions` (3 floats per vertex) and `tris` (`stride` words per triangle, the
+// first three its vertices) are read; `out` (room for 2 nTris nodes) takes the reference's node array, `idx` (nTris) the index
+// permutation. Returns false (`out` / `idx` hold nothing of use) if the input has NaN coordinates or the tree is deeper than
+// kMaxLevels. The counters of every level are read back: `stream` is synchronised that often. ms: device time, if asked for.
+inline bool buildCore(Scratch& sc, const float* positions, const uint32_t* tris, uint32_t stride, uint32_t nTris, BvhNode* out, uint32_t* idx,
+                      hipStream_t stream, Built& built, double* ms) {
+  require(nTris >= 1 && stride >= 3, "bvh build: empty mesh");
+  sc.ensure(nTris);
+  HIP_CHECK(hipMemsetAsync(sc.counter.p, 0, 32, stream));
   Args a{};
-  a.pos = pos.p; a.tris = tri.p; a.stride = stride; a.n = nTris; a.cent = cent.p; a.tb = tb.p;
-  a.idx = idx.p; a.idxTmp = idxTmp.p; a.code = code.p; a.tmpR = tmpR.p; a.tmpL = tmpL.p;
-  a.nodes = nodes.p; a.counter = counter.p; a.out = out.p; a.localRoots = localRoots.p;
+  a.pos = positions; a.tris = tris; a.stride = stride; a.n = nTris; a.cent = sc.cent.p; a.tb = sc.tb.p;
+  a.idx = idx; a.idxTmp = sc.idxTmp.p; a.code = sc.code.p; a.tmpR = sc.tmpR.p; a.tmpL = sc.tmpL.p;
+  a.nodes = sc.nodes.p; a.counter = sc.counter.p; a.out = out; a.localRoots = sc.localRoots.p;
+  built = Built{};
+  built.args = a;
   struct Events {                           // (destroyed on every way out)
     hipEvent_t a = nullptr, b = nullptr;
     ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
   } ev;
-  HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
-  const hipEvent_t e0 = ev.a, e1 = ev.b;
-  HIP_CHECK(hipEventRecord(e0, 0));
-  hipLaunchKernelGGL(k_prepare, dim3((nTris + 255) / 256), dim3(256), 0, 0, a);
-  hipLaunchKernelGGL(k_root, dim3(1), dim3(1024), 0, 0, a);
+  if (ms) { HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b)); HIP_CHECK(hipEventRecord(ev.a, stream)); }
+  auto readCounters = [&](uint32_t* c, uint32_t words) {
+    HIP_CHECK(hipMemcpyAsync(c, sc.counter.p, size_t(words) * 4, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+  };
+  hipLaunchKernelGGL(k_prepare, dim3((nTris + 255) / 256), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(k_root, dim3(1), dim3(1024), 0, stream, a);
   HIP_CHECK(hipGetLastError());
+  built.launches += 2;
   const bool trace = std::getenv("YART_DEVBVH_TRACE") != nullptr;     // phase times on stderr (hipDeviceSynchronize between phases)
   auto lap = [&, last = std::chrono::steady_clock::now()](const char* what) mutable {
     if (!trace) return;
@@ -688,12 +706,13 @@ inline bool build(int device, const float* positions, uint32_t nVerts, const uin
   for (uint32_t start = 0; start < created;) {
     if (int(levelStart.size()) > kMaxLevels) { ok = false; break; }
     const uint32_t count = created - start;
-    HIP_CHECK(hipMemsetAsync(counter.p + 2, 0, 4, 0));
-    if (anyBig) hipLaunchKernelGGL(k_level<1024>, dim3(count), dim3(1024), 0, 0, a, start);
-    hipLaunchKernelGGL(k_level<64>, dim3(count), dim3(64), 0, 0, a, start);
+    HIP_CHECK(hipMemsetAsync(sc.counter.p + 2, 0, 4, stream));
+    if (anyBig) { hipLaunchKernelGGL(k_level<1024>, dim3(count), dim3(1024), 0, stream, a, start); built.launches++; }
+    hipLaunchKernelGGL(k_level<64>, dim3(count), dim3(64), 0, stream, a, start);
     HIP_CHECK(hipGetLastError());
+    built.launches++;
     uint32_t c[3];
-    HIP_CHECK(hipMemcpy(c, counter.p, 12, hipMemcpyDeviceToHost));
+    readCounters(c, 3);
     if (c[1]) { ok = false; break; }
     anyBig = c[2] != 0;
     if (trace) std::fprintf(stderr, "devbvh level %2zu: %u nodes (big: %d) ", levelStart.size() - 1, count, int(anyBig));
@@ -704,36 +723,62 @@ inline bool build(int device, const float* positions, uint32_t nVerts, const uin
   uint32_t createdLocal = 0;
   if (ok) {
     uint32_t c[5];
-    HIP_CHECK(hipMemcpy(c, counter.p, 20, hipMemcpyDeviceToHost));
-    if (c[4]) hipLaunchKernelGGL(k_subtree, dim3(c[4]), dim3(64), 0, 0, a);
+    readCounters(c, 5);
+    if (c[4]) { hipLaunchKernelGGL(k_subtree, dim3(c[4]), dim3(64), 0, stream, a); built.launches++; }
     if (trace) std::fprintf(stderr, "devbvh %u subtrees ", c[4]);
     lap("subtrees");
     for (size_t l = levelStart.size(); l-- > 0;) {
       const uint32_t s0 = levelStart[l], cnt = (l + 1 < levelStart.size() ? levelStart[l + 1] : created) - s0;
-      hipLaunchKernelGGL(k_count_inner, dim3((cnt + 255) / 256), dim3(256), 0, 0, a, s0, cnt);
+      hipLaunchKernelGGL(k_count_inner, dim3((cnt + 255) / 256), dim3(256), 0, stream, a, s0, cnt);
     }
     for (size_t l = 0; l < levelStart.size(); l++) {
       const uint32_t s0 = levelStart[l], cnt = (l + 1 < levelStart.size() ? levelStart[l + 1] : created) - s0;
-      hipLaunchKernelGGL(k_number, dim3((cnt + 255) / 256), dim3(256), 0, 0, a, s0, cnt);
+      hipLaunchKernelGGL(k_number, dim3((cnt + 255) / 256), dim3(256), 0, stream, a, s0, cnt);
     }
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpy(c, counter.p, 20, hipMemcpyDeviceToHost));
+    built.launches += 2u * uint32_t(levelStart.size());
+    readCounters(c, 5);
     if (c[1]) ok = false;
     createdLocal = c[3];
     if (ok) {
-      hipLaunchKernelGGL(k_emit, dim3((created + 255) / 256), dim3(256), 0, 0, a, 0u, created);
-      if (createdLocal) hipLaunchKernelGGL(k_emit, dim3((createdLocal + 255) / 256), dim3(256), 0, 0, a, nTris * 2u, createdLocal);
+      hipLaunchKernelGGL(k_emit, dim3((created + 255) / 256), dim3(256), 0, stream, a, 0u, created);
+      if (createdLocal) hipLaunchKernelGGL(k_emit, dim3((createdLocal + 255) / 256), dim3(256), 0, stream, a, nTris * 2u, createdLocal);
       HIP_CHECK(hipGetLastError());
+      built.launches += createdLocal ? 2u : 1u;
     }
   }
   lap("numbering + emit");
-  HIP_CHECK(hipEventRecord(e1, 0));
-  HIP_CHECK(hipEventSynchronize(e1));
-  float t = 0.0f;
-  HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
+  if (ms) {
+    HIP_CHECK(hipEventRecord(ev.b, stream));
+    HIP_CHECK(hipEventSynchronize(ev.b));
+    float t = 0.0f;
+    HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
+    *ms = t;
+  }
+  built.created = created; built.createdLocal = createdLocal;
+  return ok;
+}
+
+// Builds the BVH of one mesh on `device`. Returns false (nothing written) if the input has NaN coordinates or the tree is
+// deeper than kMaxLevels: the caller then builds on the host. ms: device time of the build, upload and download excluded.
+inline bool build(int device, const float* positions, uint32_t nVerts, const uint32_t* tris, uint32_t stride, uint32_t nTris,
+                  std::vector<BvhNode>& nodesOut, std::vector<uint32_t>& indicesOut, double* ms) {
+  require(nTris >= 1 && nVerts >= 1 && stride >= 3, "bvh build: empty mesh");
+  HIP_CHECK(hipSetDevice(device));
+  DevBuf<float> pos;
+  DevBuf<uint32_t> tri, idx;
+  DevBuf<BvhNode> out;
+  Scratch sc;
+  pos.ensure(size_t(nVerts) * 3); tri.ensure(size_t(nTris) * stride);
+  HIP_CHECK(hipMemcpy(pos.p, positions, size_t(nVerts) * 12, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(tri.p, tris, size_t(nTris) * stride * 4, hipMemcpyHostToDevice));
+  idx.ensure(nTris); out.ensure(size_t(nTris) * 2);
+  Built b;
+  double t = 0.0;
+  const bool ok = buildCore(sc, pos.p, tri.p, stride, nTris, out.p, idx.p, nullptr, b, &t);   // (the event pair also waits for the last launch)
   if (ms) *ms = t;
   if (!ok) return false;
-  nodesOut.resize(size_t(created) + createdLocal); indicesOut.resize(nTris);
+  nodesOut.resize(b.nNodes()); indicesOut.resize(nTris);
   HIP_CHECK(hipMemcpy(nodesOut.data(), out.p, nodesOut.size() * sizeof(BvhNode), hipMemcpyDeviceToHost));
   HIP_CHECK(hipMemcpy(indicesOut.data(), idx.p, size_t(nTris) * 4, hipMemcpyDeviceToHost));
   return true;

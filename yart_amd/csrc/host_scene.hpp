@@ -33,6 +33,9 @@ inline uint8_t lobeClass(const MaterialDev& mt) {
                  ((mt.clearcoat > 0.0f || mt.texClearcoat >= 0) ? 2u : 0u) | (mt.cMetallic > 0.0f ? 4u : 0u));
 }
 
+// After yart_hip_scene_update_meshes the per-mesh records that only the upload reads — shadeTris, bvhNodes, leafTris, vNormal,
+// vTangent — are the device's alone (re-derived there, not mirrored here); everything the library reads after create is kept
+// current: meshes, bvhIndices, vPos, meshBox, meshStackNeed, stackBound, nodes, nodeWorld, tlas, the lights.
 struct HostImage {
   std::vector<ShadeTri> shadeTris;
   std::vector<BvhNode> bvhNodes;
@@ -74,6 +77,8 @@ struct HostImage {
   // in) and the lights as they were described at create. (The nodes' parent / mesh are in `nodes`.)
   std::vector<SuBox> meshBox;
   std::vector<YartLightDesc> lightDesc;
+  // What yart_hip_scene_update_meshes re-derives stackBound from: every mesh's bvhStackNeed.
+  std::vector<uint32_t> meshStackNeed;
 
   SceneDev view() const {
     SceneDev s{};
@@ -414,6 +419,7 @@ inline HostImage buildHostImage(const YartSceneDesc& d, MeshBvhFn bvhFn = nullpt
       const uint32_t need = bvhStackNeed(b.nodes.data(), b.nodes.size());
       checkStackBound(need, uint32_t(im.meshes.size()));
       im.stackBound = std::max(im.stackBound, need);
+      im.meshStackNeed.push_back(need);
     }
     im.bvhNodes.insert(im.bvhNodes.end(), b.nodes.begin(), b.nodes.end());
     for (uint32_t k = 0; k < m.n_faces; k++) {

@@ -47,6 +47,7 @@
 #include "../../include/yart_hip.h"
 #include "estimator.hpp"
 #include "host_scene.hpp"
+#include "mesh_update.hpp"
 #include "integrator.hpp"
 #include "scene_file.hpp"
 #include "gltf_reader.hpp"
@@ -291,6 +292,23 @@ struct SceneUpdateTables {
   DevBuf<uint32_t> stageDesc, stageFlags;
 };
 
+// What yart_hip_scene_update_meshes keeps per scene (mesh_update_kernels.inc), all grown on demand so that an animation allocates
+// nothing per frame: the device build's working arrays, per listed mesh the staging arrays a rebuilt mesh waits in until every
+// listed mesh has built, and the second node array the meshes are repacked into when a node count changes.
+struct MeshStage {
+  DevBuf<float> pos, nrm, tan;                          // the caller's arrays, packed as given
+  DevBuf<BvhNode> nodes; DevBuf<uint32_t> idx; DevBuf<LeafTri> leaf;
+  std::vector<uint32_t> idxHost;
+  uint32_t nNodes = 0, hasAlpha = 0, need = 0;
+};
+struct MeshUpdateState {
+  devbvh::Scratch scratch;
+  std::vector<std::unique_ptr<MeshStage>> stages;
+  DevBuf<uint32_t> prefix, result;
+  DevBuf<BvhNode> nodesAlt;
+  std::vector<int8_t> meshAlpha;                        // per mesh: a face has an alpha-tested material (-1: not looked at yet)
+};
+
 struct YartScene {
   int device = 0;
   HostImage host;
@@ -330,6 +348,7 @@ struct YartScene {
   unsigned long long lastCounters[32] = {0};
   uint32_t pixW = 0, pixH = 0, pixTile = 0, pixRank = 0, pixWorld = 0;
   SceneUpdateTables su;
+  MeshUpdateState meshUp;
   std::mutex mu;
 };
 
@@ -1599,4 +1618,5 @@ int yart_hip_bvh_build_host(const float* positions, uint32_t n_verts, const uint
 
 #include "postprocess.inc"
 #include "scene_update_kernels.inc"
+#include "mesh_update_kernels.inc"
 #include "probes.inc"
