@@ -6,7 +6,8 @@
 //   k_wf_generate        camera rays of a batch;  k_wf_refill / k_wf_pool_init / k_wf_pool_advance  the path pool's rounds
 //   k_wf_reset_retry     after a retry pass;  k_wf_advance  swap queue counters between two bounces
 //   k_wf_compact / k_wf_compact_commit   dense copy of the survivors' state (late bounces)
-//   k_wf_roulette        from the second bounce on: Russian roulette of the `shadow` paths -> `next`
+//   k_wf_roulette        path pool only: Russian roulette of the `shadow` paths at depth >= 2 (the batch-synchronous pipeline
+//                        decides in k_wf_shade, wavefront.hpp: wfRouletteTentative)
 
 // SamplerTables of one render (sampler.hpp): entries for dims x this rank's pixels, hashDim
 // values, byte-wise XOR tables of the Sobol' dimension-1 matrix (LutDev::sobol columns 52..103)
@@ -159,16 +160,16 @@ __global__ void k_wf_compact_commit(WfArgs a) {
 __global__ void k_wf_advance(uint32_t* counters, unsigned long long* pathsLog) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     counters[0] = counters[1];
-    if (pathsLog) *pathsLog += counters[1];
+    if (pathsLog) *pathsLog += counters[1] - counters[WC_DUMMY];      // (entries of paths written out since they were queued: WF_DEAD)
     for (uint32_t k = 1; k < WC_COUNT; k++) if (k != WC_STARTED) counters[k] = 0;
   }
 }
 
 // ---------------------------------------------------------------------------------------
-//   k_wf_roulette       from the second bounce on (a.bounce >= 1: the paths leave the bounce at depth >= 2): Russian roulette
-//                       + next-bounce decision of the paths of the `shadow` queue, after their shadow rays
-//                       (mis-integrator.cpp:96-102) -> `next` queue. Not launched after the last bounce (every such path is
-//                       WF_FINAL and was written out by the shadow kernels).
+//   k_wf_roulette       Russian roulette + next-bounce decision of the paths of the `shadow` queue, after their shadow rays
+//                       (mis-integrator.cpp:96-102). Launched by the path pool only, whose k_wf_shade leaves the decision
+//                       to it (no draw is ever pending there); the batch-synchronous form below the pool's is kept for a
+//                       pipeline that cannot decide in shade (a.bounce >= 1: the paths leave the bounce at depth >= 2).
 // ---------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kBlock) k_wf_roulette(WfArgs a) {
   WF_EMPTY_BLOCK(a.counters[WC_SHADOW], kBlock);

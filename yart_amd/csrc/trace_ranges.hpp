@@ -4,7 +4,7 @@
 // (cpu/tile-renderer.hpp:111-113, 146-147, 169, 212-215); YartStats carries the same figures per stage from HIP events.
 // For a profiler's timeline the stages are also marked as roctx ranges: `rocprofv3 --marker-trace --kernel-trace` then
 // shows sampler tables / generate / bounce k { extend, shade, shadow, roulette, compact } / blend around the kernels
-// they launch. The roctx library is loaded with dlopen on first use (as RCCL is, multi_device.inc): without it — or with
+// they launch (`roulette` has been an empty range since k_wf_shade took the decision). The roctx library is loaded with dlopen on first use (as RCCL is, multi_device.inc): without it — or with
 // YART_ROCTX=0 — a range costs one predictable branch. Launches are asynchronous, so a range normally covers the
 // ENQUEUE of its stage; with YART_ROCTX_SYNC=1 a range ends with a synchronisation of the render stream and covers the
 // stage's execution (a measurement mode: it serialises host and device, never set by default).

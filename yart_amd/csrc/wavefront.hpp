@@ -3,13 +3,16 @@
 //
 //   generate  camera ray, path state                       (ray-integrator.cpp:11-18)
 //   extend    closest-hit traversal of every live path     (testNode, :20-54)
-//   shade     miss / emission / BSDF sample / NEE set-up / throughput update; Russian roulette of the paths that cast no
-//             shadow ray (mis-integrator.cpp:27-102, 111-124)
+//   shade     miss / emission / BSDF sample / NEE set-up / throughput update; Russian roulette + next-bounce decision
+//             (mis-integrator.cpp:27-102, 111-124) — final for a path without a shadow ray, TENTATIVE for one with a shadow
+//             ray: the reference draws after the shadow traversal, whose alpha tests may consume sampler dimensions first
 //   shadow    any-hit traversal of the shadow rays (:135-148); the NEE contribution (:125-133) is added to the path's
-//             radiance where the traversal result is committed (wfShadowCommit) — no pass of its own
-//   roulette  for the paths that cast a shadow ray: the Russian roulette + next-bounce decision (:96-102) AFTER the shadow
-//             traversal, which may consume sampler dimensions first. Needed from the second bounce on only (the roulette
-//             starts at depth 2): 16-48 bytes per path instead of the 120 a full post pass moved
+//             radiance where the traversal result is committed (wfShadowCommit) — no pass of its own. Only the general
+//             kernels have a sampler, so only they can move the dimension counter: they draw the roulette again at the
+//             walk's final dimension and repair a decision that flipped (wfShadowCommitGeneral). A ray the lean kernel
+//             commits drew nothing: shade's decision stands, and the lean kernels know nothing of it.
+// The roulette was a streaming stage of its own after the shadow stage (k_wf_roulette) until shade took the decision; the
+// path pool (YART_FLAG_PATH_POOL) still runs it.
 //
 // Path state lives in HBM as float4-packed SoA arrays indexed by path slot, so that a
 // wave's 64 lanes read 1 KiB contiguous per field group. Every arithmetic expression is
@@ -23,7 +26,7 @@ struct WfState {
   // ray0 = {o.xyz, d.x}  ray1 = {d.yz, lastPdf, accRoughness}
   // thr = {att.xyz, dim(u32)}   acc = {L.xyz, flags(u32)}
   // hit0 = {t, u, v, tri(u32)}  hit1 = {hit word (wfHitWord), morton.lo, morton.hi, sampler-table column (u32)}
-  // sh0 = {to.xyz, -}  sh1 = {attPre.xyz, denom}  sh2 = {Lif.xyz, cosTerm}   (read where a shadow ray's result is committed)
+  // sh0 = {to.xyz, dim(u32) at the start of the shadow walk}  sh1 = {attPre.xyz, denom}  sh2 = {Lif.xyz, cosTerm}   (read where a shadow ray's result is committed)
   f4 *ray0, *ray1, *thr, *acc, *hit0, *hit1, *sh0, *sh1, *sh2;
 };
 // exact test counters of the instrumented build (libyart_hip_count.so); empty otherwise
@@ -32,6 +35,7 @@ struct WfTally {
   uint32_t box = 0, tri = 0, trav = 0, shade = 0;
   uint32_t resumed = 0;        // handed-over rays the general kernels took up where the lean kernel stood
   uint32_t waste = 0;          // box tests the lean kernels spent on rays they then handed to the general kernels
+  uint32_t flipAlive = 0, flipDead = 0;   // tentative roulette decisions the general shadow kernels reversed: dead -> alive, alive -> dead
 #endif
 #if defined(YART_TRACE_STATS)
   // debug build: wave-iteration / active-lane counts per phase of the wave tracer
@@ -54,9 +58,11 @@ struct WfTally {
 #if defined(YART_COUNT_TRAVERSAL)
 #define WF_TALLY_TRAV(t, ac) ((t).box += (ac).nBox, (t).tri += (ac).nTri, (t).trav += (ac).nTrav)
 #define WF_TALLY_SHADE(t) ((t).shade++)
+#define WF_TALLY_FLIP(t, toAlive) ((toAlive) ? (t).flipAlive++ : (t).flipDead++)
 #else
 #define WF_TALLY_TRAV(t, ac) ((void)0)
 #define WF_TALLY_SHADE(t) ((void)0)
+#define WF_TALLY_FLIP(t, toAlive) ((void)0)
 #endif
 
 // Debug build -DYART_SHADE_REGIONS=1 (tools/shade_regions.py): where a wave of k_wf_shade spends its cycles. SR_MARK(k) at
@@ -91,7 +97,17 @@ enum : uint32_t { WF_SPECULAR = 1u << 8, WF_REGULARIZED = 1u << 9, WF_MISS = 1u 
                   // set by shade for a path with a shadow ray in flight: FINAL = the bounce budget is used up, whoever commits the
                   // shadow ray's result writes the path's radiance out; ATT_NAN = the throughput before the bounce is not finite,
                   // so that even an occluded light sample changes the radiance (L += attenuation * 0, mis-integrator.cpp:80)
-                  WF_FINAL = 1u << 11, WF_ATT_NAN = 1u << 12 };
+                  WF_FINAL = 1u << 11, WF_ATT_NAN = 1u << 12,
+                  // RR_PENDING, set by shade for a path with a shadow ray in flight that leaves the bounce at depth >= 2 with
+                  // a throughput below 1: the roulette draw of this bounce has been made at the dimension the shadow walk
+                  // starts with (sh0.w); thr holds the UNSCALED throughput and the dimension AFTER that draw. The path died in
+                  // the draw: RR_PENDING | FINAL — whoever commits the shadow ray writes the radiance out, as for a used-up
+                  // bounce budget (the record is the one k_wf_roulette wrote: same radiance, same ray count). It survived:
+                  // RR_PENDING alone, and the path is in `next`; the scaling att /= 1 - q is applied where the path is next
+                  // loaded (wfShade), which rebuilds the flag word and so clears the flag.
+                  // DEAD: a general shadow kernel reversed a survival after the path had been queued; its `next` entry is
+                  // traversed once more and skipped by shade (nothing counted, written or queued).
+                  WF_RR_PENDING = 1u << 13, WF_DEAD = 1u << 14 };
 
 // hit word of the path state: scene node (bits 0..19) | shade class = material index, or kWfClassMiss
 // (bits 20..30) | back side (bit 31). The class is what k_wf_shade buckets its waves by.
@@ -165,6 +181,23 @@ YART_HD bool wfRoulette(const RenderConst& rc, WfPath& p) {
   }
   return depth < rc.maxDepth;
 }
+// The same decision, tentatively, for a path whose shadow ray is still to be traced (shade; depth >= 2 and not WF_FINAL, so
+// depth < maxDepth): the draw is made at the dimension the shadow walk starts with — the reference's draw unless an alpha test
+// of that walk draws first, which only the general shadow kernels can see (wfShadowCommitGeneral). The throughput stays
+// unscaled (wfRouletteScale where the path is next loaded); the dimension moves past the draw. Returns true if the path goes
+// to `next`.
+YART_HD bool wfRouletteTentative(const RenderConst& rc, WfPath& p) {
+  if (!(maxComponent(p.att) < 1.0f)) return true;                // no draw whatever the dimension: nothing is pending
+  const float q = stdmax(0.0f, 1.0f - maxComponent(p.att));
+  p.flags |= WF_RR_PENDING;
+  if (get1D(p.smp, rc.sampler) < q) { p.flags |= WF_FINAL; return false; }
+  return true;
+}
+// the scaling of a path that survived a pending draw (wfRoulette's own expressions on the same bits)
+YART_HD void wfRouletteScale(f3& att) {
+  const float q = stdmax(0.0f, 1.0f - maxComponent(att));
+  att /= 1.0f - q;
+}
 
 // generate: RayIntegrator::sample up to the first trace
 YART_HD void wfGenerate(const RenderConst& rc, const uint32_t* sobol, const CameraDev& cam, uint32_t px,
@@ -215,13 +248,17 @@ YART_HD bool wfRouletteAfterShadow(const RenderConst& rc, const WfState& s, uint
 // unoccluded -> L += attPre * (Lif * attOcc * cos / denom), one more ray; occluded -> L += attPre * 0, which only a non-finite
 // throughput makes visible (WF_ATT_NAN); a path whose bounce budget is used up (WF_FINAL) is written out here.
 // Returns 1 if the ray counts (unoccluded).
-YART_HD uint32_t wfShadowCommit(const WfState& s, uint32_t slot, bool occluded, f3 attOcc, f4* out, uint32_t* slotMap, bool pool) {
-  f4 a = wfLd(s.acc + slot);
-  uint32_t flags = asU(a.w);
-  if (occluded && !(flags & (WF_FINAL | WF_ATT_NAN))) return 0u;
+// `a`: the path's acc record as loaded, `flags`: its flag word, which the caller may have changed — `flagsChanged`: it must
+// then reach memory even where nothing else does. `sh12`: the path's sh1 and sh2 records if the caller has loaded them.
+YART_HD uint32_t wfShadowCommitLoaded(const WfState& s, uint32_t slot, f4 a, uint32_t flags, bool flagsChanged, bool occluded, f3 attOcc,
+                                      f4* out, uint32_t* slotMap, bool pool, const f4* sh12 = nullptr) {
+  if (occluded && !(flags & (WF_FINAL | WF_ATT_NAN))) {
+    if (flagsChanged) wfSt1(&s.acc[slot].w, asF(flags));
+    return 0u;
+  }
   f3 L = mk3(a.x, a.y, a.z);
   if (!occluded) {
-    const f4 s1 = wfLd(s.sh1 + slot), s2 = wfLd(s.sh2 + slot);
+    const f4 s1 = sh12 ? sh12[0] : wfLd(s.sh1 + slot), s2 = sh12 ? sh12[1] : wfLd(s.sh2 + slot);
     L += mk3(s1.x, s1.y, s1.z) * (mk3(s2.x, s2.y, s2.z) * attOcc * s2.w / s1.w);
     flags += WF_NEE_ONE;
   } else if (flags & WF_ATT_NAN) {
@@ -231,6 +268,49 @@ YART_HD uint32_t wfShadowCommit(const WfState& s, uint32_t slot, bool occluded, 
   if (flags & WF_FINAL) wfRetire(out, slotMap, slot, mk4(L.x, L.y, L.z, asF(wfPathRays(flags))), pool);
   else wfSt(s.acc + slot, mk4(L.x, L.y, L.z, asF(flags)));
   return occluded ? 0u : 1u;
+}
+// the lean kernels' commit: no sampler, no dimension — a tentative roulette decision stands as shade took it
+YART_HD uint32_t wfShadowCommit(const WfState& s, uint32_t slot, bool occluded, f3 attOcc, f4* out, uint32_t* slotMap, bool pool) {
+  const f4 a = wfLd(s.acc + slot);
+  return wfShadowCommitLoaded(s, slot, a, asU(a.w), false, occluded, attOcc, out, slotMap, pool);
+}
+// The general kernels' commit. `dim0`, `dim`: the sampler dimension before and after the walk (its alpha tests may have drawn).
+// Equal: nothing to do beyond the lean kernels' commit. Else, no draw pending: the dimension is stored for the path's next
+// draw. A draw pending (WF_RR_PENDING): shade drew at dim0, the reference draws at `dim` — the roulette is drawn again there
+// from the stored, unscaled throughput, and the dimension after it stored. A decision that flips is repaired in place:
+//   dead -> alive: WF_FINAL is cleared before the commit, the path appended to `next` (repair.revived);
+//   alive -> dead: the radiance is written out here (WF_FINAL for the commit) and the path state marked WF_DEAD for the
+//                  shade kernel, which meets the path's `next` entry once more (repair.died counts these entries).
+// Neither in the path pool, whose paths keep their slots. `Repair`: wavefront_kernels.inc: WfRepair.
+template <class Repair>
+YART_HD uint32_t wfShadowCommitGeneral(const SamplerConfig& cfg, const WfState& s, uint32_t slot, bool occluded, f3 attOcc, uint32_t dim0,
+                                       uint32_t dim, f4* out, uint32_t* slotMap, bool pool, Repair& repair, WfTally& tally) {
+  // Everything the commit may read is requested before anything is used: these kernels wait on memory latency, and a second
+  // draw behind the flag word, with the NEE terms behind that, would put four round trips where the lean commit has two.
+  const f4 a = wfLd(s.acc + slot), t = wfLd(s.thr + slot), h1 = wfLd(s.hit1 + slot);
+  f4 sh12[2] = {a, a};
+  if (!occluded) { sh12[0] = wfLd(s.sh1 + slot); sh12[1] = wfLd(s.sh2 + slot); }
+  uint32_t flags = asU(a.w);
+  bool flagsChanged = false;
+  if (dim != dim0 && !(flags & WF_RR_PENDING)) wfSt1(&s.thr[slot].w, asF(dim));
+  else if (dim != dim0) {
+    Sampler smp;
+    smp.dim = dim; smp.morton = uint64_t(asU(h1.y)) | (uint64_t(asU(h1.z)) << 32); smp.pix = asU(h1.w);
+    const float q = stdmax(0.0f, 1.0f - maxComponent(mk3(t.x, t.y, t.z)));
+    const bool dies = get1D(smp, cfg) < q, wasDead = (flags & WF_FINAL) != 0u;
+    if (!dies) wfSt1(&s.thr[slot].w, asF(smp.dim));
+    if (wasDead && !dies) {
+      flags &= ~uint32_t(WF_FINAL); flagsChanged = true;
+      if (!pool) repair.revived(slot);
+      WF_TALLY_FLIP(tally, true);
+    } else if (!wasDead && dies) {
+      flags |= WF_FINAL;
+      wfSt1(&s.acc[slot].w, asF(flags | WF_DEAD));             // (the commit below retires the path and stores nothing else)
+      if (!pool) repair.died();
+      WF_TALLY_FLIP(tally, false);
+    }
+  }
+  return wfShadowCommitLoaded(s, slot, a, flags, flagsChanged, occluded, attOcc, out, slotMap, pool, occluded ? nullptr : sh12);
 }
 
 // extend, general variant (one ray per lane): every triangle kind, any node transforms; only the sampler dimension can
@@ -275,9 +355,10 @@ YART_HD bool wfExtendFast(const SceneDev& sc, const TravStack& stk, const WfStat
 
 // shadow ray of the path in slot i, one ray per lane (mis-integrator.cpp:137-146); the result is committed here
 // (wfShadowCommit). Fast variant: same contract as wfExtendFast. `rays` counts the unoccluded ones.
-template <int MODE>
+struct WfNoRepair { YART_HD void revived(uint32_t) {} YART_HD void died() {} };     // (the fast variant never repairs)
+template <int MODE, class Repair>
 YART_HD bool wfShadow(const SceneDev& sc, const RenderConst& rc, const TravStack& stk, const WfState& s,
-                      uint32_t i, WfTally& tally, f4* out, uint32_t* slotMap, bool pool, uint32_t& rays) {
+                      uint32_t i, WfTally& tally, f4* out, uint32_t* slotMap, bool pool, uint32_t& rays, Repair& repair) {
   const f4 r0 = s.ray0[i], s0 = s.sh0[i];
   const f3 from = mk3(r0.x, r0.y, r0.z), to = mk3(s0.x, s0.y, s0.z);
   const f3 dir = normalized(to - from);                     // :140
@@ -286,27 +367,29 @@ YART_HD bool wfShadow(const SceneDev& sc, const RenderConst& rc, const TravStack
   hr.u = hr.v = 0; hr.tri = 0; hr.node = 0; hr.backSide = 0;
   f3 attOcc = mk3(1.0f);
   Sampler smp; smp.dim = 0; smp.morton = 0;
-  uint32_t dim0 = 0;
   AlphaCtx ac; ac.sampler = &smp; ac.cfg = rc.sampler;
   if (!(MODE & TRAV_FAST)) {
     const f4 h1 = s.hit1[i];
-    smp.dim = dim0 = asU(s.thr[i].w);
+    smp.dim = asU(s0.w);                                    // (thr.w may stand past a pending roulette draw already)
     smp.morton = uint64_t(asU(h1.y)) | (uint64_t(asU(h1.z)) << 32); smp.pix = asU(h1.w);
   }
   const bool occluded = traverseScene<true, MODE>(sc, from, dir, 0.001f, hr, attOcc, stk, ac);
   WF_TALLY_TRAV(tally, ac);
   if ((MODE & TRAV_FAST) && ac.deferred) return false;
-  if (!(MODE & TRAV_FAST) && smp.dim != dim0) s.thr[i].w = asF(smp.dim);
-  rays += wfShadowCommit(s, i, occluded, attOcc, out, slotMap, pool);
+  if (MODE & TRAV_FAST) rays += wfShadowCommit(s, i, occluded, attOcc, out, slotMap, pool);
+  else rays += wfShadowCommitGeneral(rc.sampler, s, i, occluded, attOcc, asU(s0.w), smp.dim, out, slotMap, pool, repair, tally);
   return true;
 }
 
-enum WfShadeResult { WF_TERMINATED = 0, WF_CONTINUE = 1, WF_SHADOW = 2 };
+// (WF_SKIPPED: the entry of a path that has been written out already, WF_DEAD — nothing was counted or written)
+enum WfShadeResult { WF_TERMINATED = 0, WF_CONTINUE = 1, WF_SHADOW = 2, WF_SKIPPED = 3 };
 
 // shade: everything between the two trace calls of one bounce. `rays` counts path segments.
 YART_HD WfShadeResult wfShade(const SceneDev& sc, const RenderConst& rc, const uint32_t* sobol, const WfState& s,
                               uint32_t i, WfPath& p, uint32_t& rays, WfTally& tally) {
   p = wfLoad(s, i);
+  if (p.flags & WF_DEAD) return WF_SKIPPED;
+  if (p.flags & WF_RR_PENDING) wfRouletteScale(p.att);          // survived the last bounce's roulette: thr holds the unscaled throughput
   const f4 h0 = wfLd(s.hit0 + i);
   const uint32_t nodeBack = asU(s.hit1[i].x);
   const uint32_t depth = p.flags & WF_DEPTH_MASK;
@@ -412,7 +495,7 @@ YART_HD WfShadeResult wfShade(const SceneDev& sc, const RenderConst& rc, const u
         float pdfLight = pl * ls.pdf / absDot(ls.n, ls.wi);
         if (l.type == LIGHT_AREA) pdfLight *= length2(hit.p - ls.p);
         const f3 Lif = ls.Li * f;
-        wfSt(s.sh0 + i, mk4(ls.p.x, ls.p.y, ls.p.z, 0.0f));
+        wfSt(s.sh0 + i, mk4(ls.p.x, ls.p.y, ls.p.z, asF(p.smp.dim)));       // .w: the dimension the shadow walk's alpha tests draw from
         wfSt(s.sh1 + i, mk4(p.att.x, p.att.y, p.att.z, pdfBSDF + pdfLight));
         wfSt(s.sh2 + i, mk4(Lif.x, Lif.y, Lif.z, absDot(ls.wi, hit.n)));
         shadow = true;

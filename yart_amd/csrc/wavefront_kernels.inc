@@ -11,20 +11,22 @@
 //                      kernel): no alpha / transparency code, identity-only if the scene allows;
 //                      paths that meet such a triangle go to the `retry` queue
 //   k_wf_extend_retry_lean  general closest-hit traversal of the `retry` queue
-//   k_wf_shade         miss / BSDF / NEE set-up / roulette of the paths without a shadow ray; survivors -> `next`,
-//                      shadow rays -> `shadow` (at the first bounce, where no roulette can apply yet, also -> `next`)
+//   k_wf_shade         miss / BSDF / NEE set-up / roulette — tentative for a path with a shadow ray (wavefront.hpp:
+//                      WF_RR_PENDING) —; survivors -> `next`, shadow rays -> `shadow`
 //   k_wf_shadow_lean   any-hit traversal of the `shadow` queue, lean variant; the NEE contribution is added to the
 //                      path's radiance where the result is committed (wfShadowCommit)
-//   k_wf_shadow_retry_lean  general any-hit traversal of the shadow `retry` queue
+//   k_wf_shadow_retry_lean  general any-hit traversal of the shadow `retry` queue; draws a pending roulette again at the
+//                      walk's final sampler dimension and repairs a decision that flipped (wfShadowCommitGeneral)
 // (k_wf_extend_fast / k_wf_extend / k_wf_shadow_fast / k_wf_shadow: the one-ray-per-lane forms of the same stages.)
 // and, between these, the streaming passes of stream_kernels.inc (unit 0): k_wf_generate before the first bounce,
-// k_wf_reset_retry after a retry pass, k_wf_roulette, k_wf_advance and k_wf_compact / k_wf_compact_commit after the shadow stage;
-// k_wf_refill, k_wf_pool_init and k_wf_pool_advance in the path pool; k_sampler_tables once per render.
+// k_wf_reset_retry after a retry pass, k_wf_advance and k_wf_compact / k_wf_compact_commit after the shadow stage;
+// k_wf_refill, k_wf_roulette, k_wf_pool_init and k_wf_pool_advance in the path pool; k_sampler_tables once per render.
 //
 // Round 2 had a pass (k_wf_post) between the shadow traversal and the next bounce for the NEE contribution and the
 // roulette: 46 ms and 205 GB per C3 frame. The contribution is now added by the lanes of the shadow kernels — VALU-bound
 // kernels that leave the memory system idle — when they commit a ray's result, together for all lanes that finished since
-// the last refill; what is left for a pass is the roulette, from depth 2 on, on a third of the bytes.
+// the last refill. What was left for a pass, the roulette from depth 2 on (k_wf_roulette: 22.7 ms of a 795 ms step in 12 launches),
+// is decided in k_wf_shade since; only the path pool still runs the pass.
 //
 // The traversal kernels are persistent grids: a wave takes its first 64 queue entries by wave
 // index and further ones from an atomic cursor, and exits when the cursor passes the queue
@@ -93,7 +95,8 @@ enum WfCounter : uint32_t {   // words of WfArgs::counters
   WC_RETRY = 6, WC_CUR_RETRY = 7,
   WC_RESUME = 8,               // resume records handed out (in ranges of 64)
   WC_STARTED = 9,              // path pool: paths of the batch started so far (may overshoot WfArgs::nPaths; kept across rounds)
-  WC_COUNT = 10
+  WC_DUMMY = 10,               // entries of `next` whose path a general shadow kernel has written out since (WF_DEAD): not paths of the next bounce
+  WC_COUNT = 11
 };
 
 // A workgroup whose waves would find nothing in their first round of the queue — entries are dealt by wave index first, `per` per
@@ -173,6 +176,40 @@ __device__ __forceinline__ void leanSceneToLds(SceneDev& sc, LeanSceneLds& l, ui
   sc.nodes = reinterpret_cast<const NodeDev*>(l.node); sc.nodeWorld = reinterpret_cast<const f4*>(l.world);
   sc.meshes = reinterpret_cast<const MeshDev*>(l.mesh);
 }
+// What the general shadow kernels do when they reverse a roulette decision of k_wf_shade (wavefront.hpp: wfShadowCommitGeneral):
+// rare — a few per thousand shadow rays —, and from divergent code, one lane at a time, so neither a queue append per event (a word
+// takes ~90 atomics per microsecond; a 1080p x 256 spp frame has about a million events) nor WaveStageT's ballots fit. A wave
+// collects the paths it revives in LDS (count: an LDS atomic) and appends them to `next` when it is done; what does not fit goes
+// to the queue directly; the paths it retires are counted per lane and added up once.
+constexpr uint32_t kRepairCap = 32;       // (528 B per workgroup: the general kernels keep their 4 workgroups per CU)
+struct WfRepairLds { uint32_t slots[kBlock / 64][kRepairCap]; uint32_t n[kBlock / 64]; };
+struct WfRepair {
+  uint32_t* slots; uint32_t* n;       // this wave's row and count in LDS
+  uint32_t* qNext; uint32_t* counters;
+  uint32_t dummies;
+  __device__ __forceinline__ WfRepair(WfRepairLds& l, uint32_t* q, uint32_t* c) : slots(l.slots[threadIdx.x >> 6]), n(&l.n[threadIdx.x >> 6]), qNext(q), counters(c), dummies(0) {
+    if ((threadIdx.x & 63u) == 0) *n = 0;                  // (same wave, program order: no barrier needed before the first use)
+  }
+  __device__ __forceinline__ void revived(uint32_t slot) {
+    const uint32_t i = atomicAdd(n, 1u);
+    if (i < kRepairCap) slots[i] = slot;
+    else qNext[atomicAdd(&counters[WC_NEXT], 1u)] = slot;
+  }
+  __device__ __forceinline__ void died() { dummies++; }
+  __device__ __forceinline__ void flush() {                // (convergent: at the end of the kernel)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t count = *n < kRepairCap ? *n : kRepairCap;
+    if (count != 0u) {
+      uint32_t base = 0;
+      if (lane == 0) base = atomicAdd(&counters[WC_NEXT], count);
+      base = __shfl(base, 0);
+      for (uint32_t i = lane; i < count; i += 64u) qNext[base + i] = slots[i];
+    }
+    uint32_t d = dummies;
+    for (int o = 32; o > 0; o >>= 1) d += __shfl_down(d, o);
+    if (lane == 0 && d) atomicAdd(&counters[WC_DUMMY], d);
+  }
+};
 constexpr uint32_t kRetryStageCap = 128;     // retries are rare: a small stage keeps the lean kernels at 6 blocks / CU
 
 // a finished path's radiance and its ray count (path segments + unoccluded NEE rays): one 16-byte record per (pixel, sample)
@@ -233,6 +270,7 @@ __device__ __forceinline__ void wfTraverseQueue(const WfArgs& a, const uint32_t*
 #if defined(YART_COUNT_TRAVERSAL)
   // the roofline kernel's own share of the exact counters (bench.py): stats[5..7]
   if (LEAN_EXTEND) { wfAddStat(a.stats + 5, tally.trav); wfAddStat(a.stats + 6, tally.box); wfAddStat(a.stats + 7, tally.tri); }
+  wfAddStat(a.stats + 10, tally.flipAlive); wfAddStat(a.stats + 11, tally.flipDead);     // (k_wf_shadow: roulette decisions of shade reversed)
 #endif
 }
 
@@ -259,7 +297,7 @@ __global__ void __launch_bounds__(kBlock, 6) k_wf_shadow_fast(WfArgs a) {
   __shared__ uint64_t ldsStack[kWfLdsStackFast * kBlock];
   uint32_t rays = 0;
   wfTraverseQueue<kWfLdsStackFast, false, false>(a, a.qS, a.counters[WC_SHADOW], &a.counters[WC_CUR_SHADOW], ldsStack,
-      [&](const TravStack& stk, uint32_t slot, WfTally& tally) { return !wfShadow<MODE>(a.sc, a.rc, stk, a.st, slot, tally, a.L, a.slotMap, a.poolSlots != 0u, rays); });
+      [&](const TravStack& stk, uint32_t slot, WfTally& tally) { WfNoRepair none; return !wfShadow<MODE>(a.sc, a.rc, stk, a.st, slot, tally, a.L, a.slotMap, a.poolSlots != 0u, rays, none); });
   wfAddStat(a.stats, rays);
 }
 template <bool RETRY>
@@ -267,12 +305,15 @@ __global__ void __launch_bounds__(kBlock, 4) k_wf_shadow(WfArgs a) {
   WF_DYN(a);
   __shared__ uint64_t ldsStack[kWfLdsStack * kBlock];
   uint32_t rays = 0;
+  __shared__ WfRepairLds repairLds;
+  WfRepair repair(repairLds, a.qB, a.counters);
   wfTraverseQueue<kWfLdsStack, true, false>(a, RETRY ? a.qR : a.qS, a.counters[RETRY ? WC_RETRY : WC_SHADOW],
       &a.counters[RETRY ? WC_CUR_RETRY : WC_CUR_SHADOW], ldsStack,
       [&](const TravStack& stk, uint32_t slot, WfTally& tally) {
-        wfShadow<TRAV_GENERAL>(a.sc, a.rc, stk, a.st, slot, tally, a.L, a.slotMap, a.poolSlots != 0u, rays);
+        wfShadow<TRAV_GENERAL>(a.sc, a.rc, stk, a.st, slot, tally, a.L, a.slotMap, a.poolSlots != 0u, rays, repair);
         return false;
       });
+  repair.flush();
   wfAddStat(a.stats, rays);
 }
 // Lean kernels with in-wave ray replacement (trace_lean.hpp); same queues, counters and results as
@@ -414,24 +455,29 @@ __global__ void __launch_bounds__(kBlock, YART_RETRY_WAVES) k_wf_shadow_retry_le
     __syncthreads();
     a.rc.sampler.tab.hash = sHash;
   }
+  __shared__ WfRepairLds repairLds;
+  WfRepair repair(repairLds, a.qB, a.counters);
   traceLeanAny<true, TRAV_GENERAL, NODES>(a.sc, a.rc.sampler, stk, a.qR, a.counters[WC_RETRY], &a.counters[WC_CUR_RETRY],
       [&](uint32_t slot) {
         const f4 r0 = wfLd(st.ray0 + slot), s0 = wfLd(st.sh0 + slot), h1 = wfLd(st.hit1 + slot);
         const f3 from = mk3(r0.x, r0.y, r0.z), to = mk3(s0.x, s0.y, s0.z);
         LeanRay r; r.o = from; r.d = normalized(to - from); r.tMax = length(to - from) - 0.001f;
-        r.smp.dim = asU(wfLd1(&st.thr[slot].w)); r.smp.morton = uint64_t(asU(h1.y)) | (uint64_t(asU(h1.z)) << 32); r.smp.pix = asU(h1.w);
+        r.smp.dim = asU(s0.w); r.smp.morton = uint64_t(asU(h1.y)) | (uint64_t(asU(h1.z)) << 32); r.smp.pix = asU(h1.w);   // (thr.w may stand past a pending roulette draw)
         return r;
       },
       [&](uint32_t slot, const HitRec&, bool occluded, f3 att, uint32_t dim) {
-        wfSt1(&st.thr[slot].w, asF(dim));                       // (alpha tests of the shadow walk draw before the roulette does)
-        nRays += wfShadowCommit(st, slot, occluded, att, a.L, a.slotMap, a.poolSlots != 0u);
+        // (alpha tests of the shadow walk draw before the roulette does: the dimension is stored, a pending roulette drawn again)
+        nRays += wfShadowCommitGeneral(a.rc.sampler, st, slot, occluded, att, asU(wfLd1(&st.sh0[slot].w)), dim, a.L, a.slotMap, a.poolSlots != 0u,
+                                       repair, tally);
       },
       [&](bool, uint32_t) {}, tally);
+  repair.flush();
   wfAddStat(a.stats, nRays);
   wfFlushTally(a.stats, tally);
 #if defined(YART_COUNT_TRAVERSAL)
   wfAddStat(a.stats + 30, tally.trav);       // shadow rays the lean kernel handed over
   wfAddStat(a.stats + 9, tally.resumed);
+  wfAddStat(a.stats + 10, tally.flipAlive); wfAddStat(a.stats + 11, tally.flipDead);     // roulette decisions of shade reversed
 #endif
 }
 
@@ -576,16 +622,21 @@ __global__ void __launch_bounds__(kShadeBlock, kShadeBlocksPerCU) k_wf_shade(WfA
       WfPath p;
       WfShadeResult r = wfShade(a.sc, a.rc, sobol, a.st, slot, p, rays, tally);
       if (r == WF_SHADOW) {
-        // The roulette of a path with a shadow ray comes after the shadow traversal (which may draw sampler dimensions):
-        // k_wf_roulette. At depth 1 it cannot apply yet (wfRoulette: depth > 1), the path simply continues; a path whose
-        // bounce budget is used up (WF_FINAL, set by wfShade) is written out by whoever commits its shadow ray.
-        wfStoreThr(a.st, slot, p);              // (wfShade has stored the new ray)
+        // The roulette of a path with a shadow ray comes after the shadow traversal, which may draw sampler dimensions — but
+        // only in the general kernels: the decision is taken here, tentatively, and a general shadow kernel whose walk drew
+        // takes it again (wfRouletteTentative, wfShadowCommitGeneral). At depth 1 none applies yet (wfRoulette: depth > 1),
+        // the path simply continues; a path whose bounce budget is used up (WF_FINAL, set by wfShade) — or that dies in the
+        // tentative draw — is written out by whoever commits its shadow ray. (Path pool: k_wf_roulette decides, after the
+        // shadow stage.)
         toShadow = true;
-        toNext = (p.flags & WF_DEPTH_MASK) <= 1u && !(p.flags & WF_FINAL);
+        if (p.flags & WF_FINAL) toNext = false;
+        else if ((p.flags & WF_DEPTH_MASK) <= 1u) toNext = true;
+        else toNext = !a.poolSlots && wfRouletteTentative(a.rc, p);
+        wfStoreThr(a.st, slot, p);              // (wfShade has stored the new ray)
       } else if (r == WF_CONTINUE && wfRoulette(a.rc, p)) {
         wfStoreThr(a.st, slot, p);
         toNext = true;
-      } else {
+      } else if (r != WF_SKIPPED) {
         // segments traced: a path that ends inside wfShade (miss / absorbed) still carries the depth it entered with
         const uint32_t segs = (p.flags & WF_DEPTH_MASK) + (r == WF_TERMINATED ? 1u : 0u);
         wfRetire(a.L, a.slotMap, p.slot, mk4(p.L.x, p.L.y, p.L.z, asF(segs + ((p.flags & WF_NEE_MASK) >> WF_NEE_SHIFT))), a.poolSlots != 0u);

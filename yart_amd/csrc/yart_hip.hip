@@ -973,13 +973,12 @@ void runWavefrontBatch(YartScene& s, const RenderPlan& pl, const Batch& b, Stage
       TraceRange rgShadow("yart:shadow", stream);
       shadowStage(pl, a, t, stream);
     }
-    // Russian roulette of the paths that cast a shadow ray: from the second bounce on (at depth 1 none applies: k_wf_shade
-    // queued them itself), not after the last one (their radiance has been written out by the shadow kernels)
+    // Russian roulette thins the paths from the second bounce on (at depth 1 none applies), not after the last one (every
+    // path is written out then). It is no stage: k_wf_shade decides, the general shadow kernels repair what an alpha test's
+    // draw reverses (wavefront.hpp: wfRouletteTentative, wfShadowCommitGeneral). The range stays, empty, where the pass
+    // ran until then: tools that read the trace by name find the bounce's layout unchanged.
     const bool thinning = bounce >= 1 && bounce + 1 < maxDepth;
-    if (thinning) {
-      TraceRange rgR("yart:roulette", stream);
-      streamingPass(s, k_wf_roulette, a, t, stream);
-    }
+    if (thinning) { TraceRange rgR("yart:roulette"); }
     hipLaunchKernelGGL(k_wf_advance, dim3(1), dim3(64), 0, stream, s.wfCounters.p, bounce + 1 < 16u ? s.pathsLog.p + bounce + 1 : nullptr);
     HIP_CHECK(hipGetLastError());
     std::swap(a.qA, a.qB);
