@@ -290,8 +290,9 @@ int yart_hip_scene_update(YartScene* scene, const YartSceneUpdate* update, void*
  * A mesh the device build refuses, and every mesh under the environment variable YART_HOST_BVH, is built and derived on the host
  * and uploaded: the same bytes.
  * Not kept current: the default pipeline's lobe-share heuristic stays as at create (every pipeline renders the same frame).
- * Out of scope — re-create the scene: changed faces or vertex counts, uvs, materials, the replicas of a YartMulti. Per-vertex motion
- * for the temporal accumulator: a deformed node's pixels are reprojected as if the node were rigid. */
+ * Out of scope — re-create the scene: changed faces or vertex counts, uvs, materials, the replicas of a YartMulti.
+ * Motion for the temporal accumulator: yart_hip_scene_keep_previous before the frame's updates and yart_hip_scene_pixel_motion_device
+ * after its render (below) say per pixel where a deformed — or rigidly moved — surface point was in the previous frame. */
 typedef struct YartMeshUpdate {
   uint32_t mesh;                     /* index into the scene's meshes */
   uint32_t n_vertices;               /* the mesh's vertex count, as at create */
@@ -306,6 +307,56 @@ typedef struct YartSceneMeshUpdate {
   uint32_t flags;                    /* YART_UPDATE_REBUILD_TOP */
 } YartSceneMeshUpdate;
 int yart_hip_scene_update_meshes(YartScene* scene, const YartSceneMeshUpdate* update, void* stream, YartSceneUpdateStats* stats /* may be NULL */);
+
+/* The scene remembers the frame it holds as its PREVIOUS frame: its node array and its vertex positions are copied into scene-owned
+ * arrays — two device-to-device copies on `stream`; the call returns after they have completed. The arrays are allocated by the
+ * first call: a scene that never calls it pays nothing. Called once per frame, BEFORE that frame's yart_hip_scene_update /
+ * yart_hip_scene_update_meshes (which run in either order and do not change). Locking as for the update entries. The replicas of a
+ * YartMulti are out of scope. YART_E_INVALID: a NULL scene; YART_E_HIP: the allocation or a copy failed. */
+int yart_hip_scene_keep_previous(YartScene* scene, void* stream);
+
+/* PER-PIXEL MOTION between the previous frame (yart_hip_scene_keep_previous) and the scene as it is now, from the feature buffers of
+ * a frame rendered from the scene as it is now: per pixel where the surface point it shows was in the previous frame, P', and what
+ * its normal was, n' — for nodes that moved rigidly and for meshes deformed by yart_hip_scene_update_meshes alike. The records are
+ * what yart_hip_temporal_set_pixel_motion takes. d_aovs: position, normal, coverage and ids are required; buffers of other mask bits
+ * are not touched. d_records: 8 floats per pixel, 16-byte aligned, read as two 16-byte words {P'.xyz, kind} and {n'.xyz, 0}; kind is
+ * a uint32 stored as bits: 0 static (the record is all zero), 1 moved. DEVICE pointers on `stream`; returns after completion on it.
+ * DEFINITION. Two kernels; csrc/scene_motion.hpp states them, yart_amd/scene_motion.py scene_motion_reference is the NumPy statement
+ * the tests compare with, on bits.
+ *   Per scene node, in binary64 (every operation individually rounded, no FMA contraction), by a walk from the node to the root over
+ *   `parent`, for the current and for the previous node array, with the top three rows of fwd / inv as 3 x 4 matrices whose last
+ *   row is (0, 0, 0, 1):   Wc = fwd_root · … · fwd_node,  Ac = inv_node · … · inv_root;  Wp, Ap the same of the previous array.
+ *   The walk starts from the node's own matrix and multiplies a parent's on (W = fwd_parent · W, A = A · inv_parent); an element of a
+ *   product is (x0 * y0 + x1 * y1) + x2 * y2, and + x3 (the word times 1) in the last column. The four matrices are rounded to
+ *   binary32 at the end. changed = some fwd or inv word (all 16 of each) of a node on the chain differs between the two arrays.
+ *   Per pixel p, in binary32 under the rules of the temporal definition below (dot, cross, individually rounded operations in the
+ *   order written; sqrtf correctly rounded), with (node, ·, ·, tri) = ids(p), P = position(p), n = normal(p):
+ *   STATIC — an all-zero record — if any of: coverage(p) != 1.0f; a component of P or n is not finite; uint32(node) >= the scene's
+ *     node count; the node has no mesh; uint32(tri) >= the triangle count of the node's mesh (the scene's, not ids(p)[1]); the node
+ *     is not changed and the x, y, z words of the triangle's three current vertex positions equal its three previous ones.
+ *   Otherwise, with a, b, c the current and a', b', c' the previous positions of the triangle's vertices, M · x = (dot(M row i .xyz,
+ *   x) + M row i .w) and M_lin^T · x = (dot(M column j of the 3 x 3 part, x)):
+ *     po = Ac · P;   e1 = b - a;   e2 = c - a;   r = po - a
+ *     d11 = dot(e1, e1);  d12 = dot(e1, e2);  d22 = dot(e2, e2);  r1 = dot(r, e1);  r2 = dot(r, e2);  det = d11 * d22 - d12 * d12
+ *     u = (d22 * r1 - d12 * r2) / det;   v = (d11 * r2 - d12 * r1) / det
+ *     f1 = b' - a';   f2 = c' - a';   p' = (a' + u * f1) + v * f2;   P' = Wp · p'
+ *   — the affine map from the current triangle to the previous one, extended to the triangle's plane (position is an average over
+ *   the samples and may lie beyond sample 0's triangle); the offset along the normal is dropped. The normal goes by the inverse
+ *   transpose of the same map:
+ *     no = Wc_lin^T · n;   g11, g12, g22, gdet from f1, f2 as d11, d12, d22, det from e1, e2
+ *     D1 = (g22 * f1 - g12 * f2) / gdet;   D2 = (g11 * f2 - g12 * f1) / gdet;   N = cross(e1, e2);   N' = cross(f1, f2)
+ *     gamma = dot(no, N) / sqrtf(dot(N, N) * dot(N', N'))
+ *     n'o = (dot(no, e1) * D1 + dot(no, e2) * D2) + gamma * N';   n' = Ap_lin^T · n'o     (no renormalisation)
+ *   — exact for per-triangle rigid motion; a strain changes |n'| only through the tangential part of a shading normal.
+ *   kind = 1 with P' and n' as computed, finite or not: the accumulator refuses a non-finite record per pixel.
+ * YART_E_INVALID, with a message and before any device work: a NULL scene, d_aovs or d_records; a required buffer missing from
+ * d_aovs->mask (or NULL, or beyond its struct_size); 0 pixels or more than 2^28; a d_records that is not 16-byte aligned; a scene on
+ * which yart_hip_scene_keep_previous was never called. Locking as for the update entries. */
+struct YartAovBuffers;           /* (defined with the feature buffers below) */
+int yart_hip_scene_pixel_motion_device(YartScene* scene, const struct YartAovBuffers* d_aovs, uint32_t width, uint32_t height,
+                                       float* d_records, void* stream);
+/* Same, HOST pointers (records needs no alignment): the buffers are copied to the scene's device and the records copied back. */
+int yart_hip_scene_pixel_motion_host(YartScene* scene, const struct YartAovBuffers* aovs, uint32_t width, uint32_t height, float* records);
 
 /* glTF 2.0 / GLB import — what `gltf::load(path)` (src/gltf/gltf.cpp:319-358) followed
  * by the frontend's environment set-up (src/main.cpp:78-86) gives the renderer: materials with the KHR
@@ -734,7 +785,14 @@ int yart_hip_denoise_atrous_var_host(const float* rgba, const float* variance, c
  *     a tap q counts iff ... dot(n', n_hist(q)) >= normal_cos_min; fabsf(dot(n', P_hist(q) - P')) <= plane_tolerance * depth(p) ...
  *   Node equality, the weights, the blend, N, a, the moments and the new history record — {P, N}, {n(p), node}, the CURRENT values —
  *   are unchanged, and so is pass 2 of the moments form, which works on the new records only.
- * Out of scope: deforming meshes, a wider search when all four taps fail, colour clamps against ghosting, yart_hip_multi_*. */
+ * PER-PIXEL MOTION (yart_hip_temporal_set_pixel_motion): one record of 8 floats per pixel, two 16-byte words {P'.xyz, kind} and
+ * {n'.xyz, 0}, as yart_hip_scene_pixel_motion_* writes them — for deforming meshes, which no per-node record describes. The
+ * definition changes for a pixel whose record has kind == 1 and for no other, exactly as for a MOVING pixel above with P' and n'
+ * taken from the record: reprojectable(p) additionally needs them finite, the projection and the tap tests use them; node
+ * equality, the weights, the blend, N, the moments, the new record with the CURRENT P and n, and pass 2 are untouched. A pixel
+ * whose kind is not 1 runs the operations it ran before.
+ * Out of scope: screen-space motion-vector output, a wider search when all four taps fail, colour clamps against ghosting,
+ * yart_hip_multi_*. */
 #define YART_TEMPORAL_DEMODULATE 1u         /* accumulate rgb / d, return acc * d (needs YART_AOV_ALBEDO) */
 #define YART_TEMPORAL_DEFAULT_ALPHA_MIN 0.1f
 #define YART_TEMPORAL_DEFAULT_MAX_HISTORY 8u
@@ -752,7 +810,7 @@ typedef struct YartTemporal YartTemporal;
 /* width, height > 0 (at most 2^28 pixels); device < 0: the device current at the first accumulate call. No device is touched. */
 int yart_hip_temporal_create(uint32_t width, uint32_t height, int device, YartTemporal** out);
 void yart_hip_temporal_destroy(YartTemporal* temporal);
-/* Forget the history: the next frame is a first frame. A pending motion is forgotten too. */
+/* Forget the history: the next frame is a first frame. A pending motion (per node or per pixel) is forgotten too. */
 int yart_hip_temporal_reset(YartTemporal* temporal);
 /* Per-node motion for the NEXT accumulate call on the handle (PER-NODE MOTION above). The records are copied into the handle and no
  * device is touched. The motion applies to the next accumulate call — either form, device or host entry — that passes its own
@@ -766,6 +824,20 @@ typedef struct YartTemporalMotion {
   const float* records;        /* HOST, n_nodes * 24 floats */
 } YartTemporalMotion;
 int yart_hip_temporal_set_motion(YartTemporal* temporal, const YartTemporalMotion* motion);
+/* Per-pixel motion for the NEXT accumulate call on the handle (PER-PIXEL MOTION above). records: width * height * 8 floats in the
+ * address space of the accumulate call that consumes them — a DEVICE pointer (16-byte aligned; written on that call's stream or
+ * complete before it) for the _device entries, a HOST pointer for the _host entries. They are NOT copied: they must stay valid until
+ * that call returns. Pending and consumed exactly as yart_hip_temporal_set_motion's: the records apply to the next accumulate call
+ * of either form that passes its checks (a _device call refuses misaligned records with YART_E_INVALID and leaves them pending);
+ * motion == NULL clears; yart_hip_temporal_reset clears. ONE motion is pending at a time: each of the two setters replaces whatever
+ * the other left. No device is touched.
+ * YART_E_INVALID, with a message and nothing left pending: a NULL temporal; a struct_size smaller than YartTemporalPixelMotion; NULL
+ * records. */
+typedef struct YartTemporalPixelMotion {
+  uint32_t struct_size;        /* sizeof(YartTemporalPixelMotion) */
+  const float* records;        /* width * height * 8 floats, in the consuming call's address space */
+} YartTemporalPixelMotion;
+int yart_hip_temporal_set_pixel_motion(YartTemporal* temporal, const YartTemporalPixelMotion* motion);
 /* One frame. DEVICE pointers on `stream` (hipStream_t, may be NULL); returns after completion on that stream. d_rgba: width * height
  * * 4 floats; d_variance: width * height; d_aovs: position, normal, depth, coverage and ids are required (and albedo with
  * YART_TEMPORAL_DEMODULATE), as yart_hip_render_moments_device fills them; buffers of other mask bits are not touched.

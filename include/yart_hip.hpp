@@ -97,6 +97,15 @@ class DeviceScene {
     check(yart_hip_scene_update_meshes(h_, &u, stream, &st));
     return st;
   }
+  // yart_hip_scene_keep_previous: the scene remembers the frame it holds as its previous frame; once per frame, before its updates
+  void keepPrevious(void* stream = nullptr) { check(yart_hip_scene_keep_previous(h_, stream)); }
+  // yart_hip_scene_pixel_motion_host: the per-pixel motion records (8 floats per pixel) between the kept frame and the scene as it
+  // is now, from the host feature buffers (position, normal, coverage, ids) of a frame rendered from the scene as it is now
+  std::vector<float> pixelMotion(const YartAovBuffers& aovs, uint32_t width, uint32_t height) {
+    std::vector<float> records(size_t(width) * height * 8);
+    check(yart_hip_scene_pixel_motion_host(h_, &aovs, width, height, records.data()));
+    return records;
+  }
   // yart_hip_render_aovs: the frame plus the feature buffers of `mask` (YART_AOV_*), from the same camera samples. Several GPUs:
   // one call per device with params.rank / world_size, then add the buffers (ids: by max).
   AovFrame renderAovs(const YartCameraDesc& cam, const YartRenderParams& params, uint32_t mask = YART_AOV_ALL, YartStats* stats = nullptr) {
@@ -248,6 +257,14 @@ class Temporal {
     YartTemporalMotion m{};
     m.struct_size = uint32_t(sizeof(m)); m.n_nodes = uint32_t(records.size() / 24); m.records = records.data();
     check(yart_hip_temporal_set_motion(m_handle, &m));
+  }
+  // per-pixel motion for the next accumulate call (yart_hip_temporal_set_pixel_motion): 8 floats per pixel, in the address space
+  // of the call that consumes them (host for accumulate / accumulateMoments), NOT copied: valid until that call returns; null: clear
+  void setPixelMotion(const float* records) {
+    if (!records) { check(yart_hip_temporal_set_pixel_motion(m_handle, nullptr)); return; }
+    YartTemporalPixelMotion m{};
+    m.struct_size = uint32_t(sizeof(m)); m.records = records;
+    check(yart_hip_temporal_set_pixel_motion(m_handle, &m));
   }
   // one frame, host buffers: the accumulated frame, its variance and the history length per pixel
   TemporalFrame accumulate(const YartCameraDesc& camera, const std::vector<float>& rgba, const std::vector<float>& variance,

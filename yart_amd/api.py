@@ -279,6 +279,12 @@ class TemporalMotion(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_nodes", C.c_uint32), ("records", C.c_void_p)]
 
 
+class TemporalPixelMotion(C.Structure):
+    """YartTemporalPixelMotion (include/yart_hip.h): the per-pixel motion records for the next accumulate call."""
+    _fields_ = [("struct_size", C.c_uint32), ("records", C.c_void_p)]
+
+
+PIXEL_MOTION_AOVS = ("position", "normal", "coverage", "ids")      # what yart_hip_scene_pixel_motion_* reads
 FLAG_TEMPORAL_DEMODULATE = 1
 TEMPORAL_AOVS = ("position", "normal", "depth", "coverage", "ids")     # + "albedo" when demodulating
 
@@ -355,7 +361,9 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_temporal_accumulate_moments_device", "yart_hip_temporal_accumulate_moments_host",
            "yart_hip_temporal_set_motion",
            "yart_hip_scene_update", "yart_hip_probe_scene_graph",
-           "yart_hip_scene_update_meshes", "yart_hip_probe_mesh"]
+           "yart_hip_scene_update_meshes", "yart_hip_probe_mesh",
+           "yart_hip_scene_keep_previous", "yart_hip_scene_pixel_motion_device", "yart_hip_scene_pixel_motion_host",
+           "yart_hip_temporal_set_pixel_motion"]
 
 LIB_COUNT_PATH = os.path.join(_HERE, "libyart_hip_count.so")   # instrumented twin (exact test counters)
 _libs = {}
@@ -448,6 +456,10 @@ def lib(instrumented: bool = False):
         L.yart_hip_scene_update_meshes.argtypes = [C.c_void_p, C.POINTER(SceneMeshUpdate), C.c_void_p, C.POINTER(SceneUpdateStats)]
         L.yart_hip_probe_mesh.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.POINTER(C.c_uint32)]
+        L.yart_hip_scene_keep_previous.argtypes = [C.c_void_p, C.c_void_p]
+        L.yart_hip_scene_pixel_motion_device.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.yart_hip_scene_pixel_motion_host.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.c_uint32, C.c_uint32, C.c_void_p]
+        L.yart_hip_temporal_set_pixel_motion.argtypes = [C.c_void_p, C.POINTER(TemporalPixelMotion)]
         L.yart_hip_bvh_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.yart_hip_bvh_copy.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         _libs[path] = L
@@ -676,6 +688,52 @@ class DeviceScene:
         _check(self._L.yart_hip_scene_update_meshes(self._h, C.byref(up), stream, C.byref(st)), self._L)
         self.last_update = dict(launches=st.launches, ms_total=st.ms_total, ms_device=st.ms_device)
 
+    def keep_previous(self, stream=None):
+        """yart_hip_scene_keep_previous: the scene remembers the frame it holds (node transforms and vertex positions) as its
+        previous frame. Once per frame, before that frame's ``update`` / ``update_meshes``."""
+        _check(self._L.yart_hip_scene_keep_previous(self._h, stream), self._L)
+
+    def pixel_motion(self, aovs: dict):
+        """yart_hip_scene_pixel_motion_host: the per-pixel motion records between the frame ``keep_previous`` kept and the scene
+        as it is now, from the feature buffers (``render_aovs``: position, normal, coverage, ids) of a frame rendered from the
+        scene as it is now -> (H, W, 8) float32, what ``TemporalAccumulator.accumulate(pixel_motion=)`` takes.
+        yart_amd.scene_motion.scene_motion_reference states the arithmetic in NumPy."""
+        h, w = np.asarray(aovs["coverage"]).shape[:2]
+        ab, keep = AovBuffers(), []
+        ab.struct_size = C.sizeof(AovBuffers)
+        for name in PIXEL_MOTION_AOVS:
+            bit, ch, dt = AOVS[name]
+            a = np.ascontiguousarray(aovs[name], dt)
+            assert a.size == h * w * ch, name
+            keep.append(a)
+            ab.mask |= bit
+            setattr(ab, name, a.ctypes.data_as(C.c_void_p))
+        rec = np.empty((h, w, 8), np.float32)
+        _check(self._L.yart_hip_scene_pixel_motion_host(self._h, C.byref(ab), w, h, rec.ctypes.data_as(C.c_void_p)), self._L)
+        return rec
+
+    def pixel_motion_into(self, records_tensor, aov_tensors: dict, stream=None):
+        """``pixel_motion`` on CUDA/HIP torch tensors (yart_hip_scene_pixel_motion_device) on ``stream`` (an integer handle; None:
+        torch's current stream): ``records_tensor`` is a contiguous float32 device tensor of H*W*8 elements, (H, W, ...) its first
+        two dimensions; what ``TemporalAccumulator.accumulate_into(pixel_motion=)`` takes."""
+        import torch
+        h, w = int(records_tensor.shape[0]), int(records_tensor.shape[1])
+        assert records_tensor.is_cuda and records_tensor.is_contiguous() and records_tensor.dtype == torch.float32
+        assert records_tensor.numel() == h * w * 8
+        ab = AovBuffers()
+        ab.struct_size = C.sizeof(AovBuffers)
+        for name in PIXEL_MOTION_AOVS:
+            t = aov_tensors[name]
+            bit, ch, _ = AOVS[name]
+            assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() == h * w * ch, name
+            ab.mask |= bit
+            setattr(ab, name, C.c_void_p(t.data_ptr()))
+        if stream is None:
+            stream = torch.cuda.current_stream(records_tensor.device).cuda_stream
+        _check(self._L.yart_hip_scene_pixel_motion_device(self._h, C.byref(ab), w, h, C.c_void_p(records_tensor.data_ptr()),
+                                                          C.c_void_p(stream) if stream else None), self._L)
+        return records_tensor
+
     def mesh_records(self, mesh):
         """yart_hip_probe_mesh: one mesh as the kernels see it, read back from the device: dict(mesh: MESH_DTYPE record, nodes:
         BVH_NODE_DTYPE, leaves: LEAF_TRI_DTYPE, shade: SHADE_TRI_DTYPE, positions / normals / tangents: (n_verts, 4) float32,
@@ -888,7 +946,7 @@ class DeviceScene:
 
     def render_denoised(self, p: dict, iterations=None, sigma_color=DEFAULT_SIGMA_COLOR, sigma_normal=None, sigma_depth=None,
                         demodulate=True, rank=0, world_size=1, flags=0, device="cuda", variance_guided=False,
-                        sigma_luma=DEFAULT_VAR_SIGMA_LUMA, temporal=None, motion=None):
+                        sigma_luma=DEFAULT_VAR_SIGMA_LUMA, temporal=None, motion=None, pixel_motion=False):
         """``render_aovs_into`` for albedo, normal and depth, then the à-trous filter (``denoise_into``) on the same device
         buffers, on torch's current stream: no host round trip. Returns (noisy frame, denoised frame, {name: guide}) as torch
         tensors of ``device`` ((H, W, 4); guides (H, W, 3) / (H, W)).
@@ -902,9 +960,14 @@ class DeviceScene:
         filter on the accumulated frame and variance (``variance_guided`` is implied). Returns (noisy frame, denoised frame, guides) with "accumulated" (H, W, 4),
         "accumulated_variance" (H, W) and "length" (H, W, int32 holding the uint32) among the guides. None: as before.
         ``motion`` (with ``temporal``): how this scene's nodes moved since the previous frame's scene — the records of
-        yart_amd.temporal.node_motion(previous nodes, these nodes) —, handed to ``temporal.accumulate_into``."""
+        yart_amd.temporal.node_motion(previous nodes, these nodes) —, handed to ``temporal.accumulate_into``.
+        ``pixel_motion=True`` (with ``temporal``, not with ``motion``): the scene was updated in place since ``keep_previous``:
+        the per-pixel records are computed from the frame's own feature buffers (``pixel_motion_into``, on the same stream) and
+        handed to ``temporal.accumulate_into``; they are returned among the guides as "pixel_motion" (H, W, 8)."""
         import torch
         assert motion is None or temporal is not None, "render_denoised: motion needs a temporal accumulator"
+        assert not pixel_motion or temporal is not None, "render_denoised: pixel_motion needs a temporal accumulator"
+        assert not pixel_motion or motion is None, "render_denoised: one motion at a time, motion= or pixel_motion=True"
         if temporal is not None:
             variance_guided = True
         dflt = ((DEFAULT_VAR_ITERATIONS, DEFAULT_VAR_SIGMA_NORMAL, DEFAULT_VAR_SIGMA_DEPTH) if variance_guided else
@@ -926,11 +989,16 @@ class DeviceScene:
             self.render_moments_into(noisy, feats, {"variance": variance}, p, rank, world_size, flags, stream=stream)
             acc, acc_var = torch.empty_like(noisy), torch.empty_like(variance)
             length = torch.empty((h, w), dtype=torch.int32, device=device)
+            extra, records = {}, None
+            if pixel_motion:
+                records = torch.empty((h, w, 8), dtype=torch.float32, device=device)
+                self.pixel_motion_into(records, feats, stream=stream)
+                extra["pixel_motion"] = records
             temporal.accumulate_into(acc, acc_var, length, p, noisy, variance, feats, demodulate=demodulate, stream=stream,
-                                     motion=motion)
+                                     motion=motion, pixel_motion=records)
             clean = torch.empty_like(noisy)
             denoise_var_into(clean, acc, acc_var, guides, iterations, sigma_luma, sigma_normal, sigma_depth, demodulate)
-            return noisy, clean, dict(feats, variance=variance, accumulated=acc, accumulated_variance=acc_var, length=length)
+            return noisy, clean, dict(feats, variance=variance, accumulated=acc, accumulated_variance=acc_var, length=length, **extra)
         if variance_guided:
             variance = torch.empty((h, w), dtype=torch.float32, device=device)
             self.render_moments_into(noisy, guides, {"variance": variance}, p, rank, world_size, flags, stream=stream)
@@ -1341,6 +1409,25 @@ class TemporalAccumulator:
         tm = TemporalMotion(C.sizeof(TemporalMotion), rec.size // MOTION_WORDS, rec.ctypes.data_as(C.c_void_p))
         _check(self._L.yart_hip_temporal_set_motion(self._h, C.byref(tm)), self._L)
 
+    def set_pixel_motion(self, records):
+        """Per-pixel motion for the next ``accumulate`` / ``accumulate_into`` (yart_hip_temporal_set_pixel_motion), which consumes
+        it: ``DeviceScene.pixel_motion``'s (H, W, 8) float32 NumPy array for ``accumulate``, ``pixel_motion_into``'s device tensor
+        for ``accumulate_into``. The records are NOT copied: the caller keeps them alive until that call has returned. None clears
+        a pending motion; a motion set by ``set_motion`` is replaced."""
+        if records is None:
+            _check(self._L.yart_hip_temporal_set_pixel_motion(self._h, None), self._L)
+            return
+        if isinstance(records, np.ndarray):
+            assert records.dtype == np.float32 and records.flags.c_contiguous, "pixel motion: a contiguous float32 array"
+            ptr = records.ctypes.data
+        else:
+            assert records.is_cuda and records.is_contiguous() and records.element_size() == 4, "pixel motion: a contiguous float32 device tensor"
+            ptr = records.data_ptr()
+        n = records.size if isinstance(records, np.ndarray) else records.numel()
+        assert n == self.width * self.height * 8, "pixel motion: (H, W, 8) records"
+        pm = TemporalPixelMotion(C.sizeof(TemporalPixelMotion), C.c_void_p(ptr))
+        _check(self._L.yart_hip_temporal_set_pixel_motion(self._h, C.byref(pm)), self._L)
+
     def _camera(self, cam):
         return cam if isinstance(cam, CameraDesc) else make_camera(cam)
 
@@ -1350,13 +1437,15 @@ class TemporalAccumulator:
         make = make_temporal_moment_params if self.moments else make_temporal_params
         return make(demodulate=demodulate, **dict(self.params, **over))
 
-    def accumulate(self, cam, frame, variance, aovs: dict, demodulate=None, out=None, out_variance=None, motion=None, **over):
+    def accumulate(self, cam, frame, variance, aovs: dict, demodulate=None, out=None, out_variance=None, motion=None,
+                   pixel_motion=None, **over):
         """One frame on NumPy arrays (yart_hip_temporal_accumulate_host, or _moments_host in the moments form). ``cam``: the frame's camera (a params dict as
         ``render`` takes it, or a CameraDesc); ``frame`` (H, W, 4); ``variance`` (H, W); ``aovs``: the feature buffers by name —
         position, normal, depth, coverage, ids, and albedo when demodulating (``demodulate`` None: whenever albedo is given).
         ``out`` / ``out_variance`` may be ``frame`` / ``variance``. ``motion``: this frame's per-node motion records
-        (``set_motion`` is called first); None: whatever is pending. Returns (accumulated frame, its variance, history length
-        (H, W) uint32)."""
+        (``set_motion`` is called first); None: whatever is pending. ``pixel_motion``: this frame's per-pixel records, an
+        (H, W, 8) float32 array (``set_pixel_motion`` is called first; not together with ``motion``). Returns (accumulated frame,
+        its variance, history length (H, W) uint32)."""
         h, w = self.height, self.width
         frame = np.ascontiguousarray(frame, np.float32)
         variance = np.ascontiguousarray(variance, np.float32)
@@ -1383,8 +1472,13 @@ class TemporalAccumulator:
             assert o.dtype == np.float32 and o.flags.c_contiguous and o.size == size
         length = np.empty((h, w), np.uint32)
         tp = self._params(demodulate, over)
+        assert motion is None or pixel_motion is None, "one motion at a time: motion= or pixel_motion="
         if motion is not None:
             self.set_motion(motion)
+        if pixel_motion is not None:
+            assert isinstance(pixel_motion, np.ndarray), "accumulate: pixel_motion is host data (accumulate_into takes a device tensor)"
+            pixel_motion = np.ascontiguousarray(pixel_motion)
+            self.set_pixel_motion(pixel_motion)
         fn = self._L.yart_hip_temporal_accumulate_moments_host if self.moments else self._L.yart_hip_temporal_accumulate_host
         _check(fn(self._h, C.byref(self._camera(cam)), frame.ctypes.data_as(C.c_void_p), variance.ctypes.data_as(C.c_void_p),
                   C.byref(ab), C.byref(tp), out.ctypes.data_as(C.c_void_p), out_variance.ctypes.data_as(C.c_void_p),
@@ -1392,12 +1486,13 @@ class TemporalAccumulator:
         return out, out_variance, length
 
     def accumulate_into(self, out_tensor, out_variance_tensor, out_length_tensor, cam, frame_tensor, variance_tensor,
-                        aov_tensors: dict, demodulate=None, stream=None, motion=None, **over):
+                        aov_tensors: dict, demodulate=None, stream=None, motion=None, pixel_motion=None, **over):
         """``accumulate`` on CUDA/HIP torch tensors through ``data_ptr()`` (yart_hip_temporal_accumulate[_moments]_device), on ``stream``
         (an integer handle; None: torch's current stream): no host round trip. ``out_variance_tensor`` and
         ``out_length_tensor`` (H*W 4-byte elements: int32 holding the uint32) may be None; ``out_tensor`` may be
         ``frame_tensor`` and ``out_variance_tensor`` may be ``variance_tensor``. ``motion``: as ``accumulate`` takes it (a
-        NumPy array: the records are host data)."""
+        NumPy array: the records are host data). ``pixel_motion``: this frame's per-pixel records as a device tensor
+        (``DeviceScene.pixel_motion_into``), written on ``stream`` or complete; not together with ``motion``."""
         import torch
         h, w = self.height, self.width
         if demodulate is None:
@@ -1420,8 +1515,12 @@ class TemporalAccumulator:
             stream = torch.cuda.current_stream(frame_tensor.device).cuda_stream
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         tp = self._params(demodulate, over)
+        assert motion is None or pixel_motion is None, "one motion at a time: motion= or pixel_motion="
         if motion is not None:
             self.set_motion(motion)
+        if pixel_motion is not None:
+            assert not isinstance(pixel_motion, np.ndarray), "accumulate_into: pixel_motion is a device tensor"
+            self.set_pixel_motion(pixel_motion)
         with torch.cuda.device(frame_tensor.device):
             fn = self._L.yart_hip_temporal_accumulate_moments_device if self.moments else self._L.yart_hip_temporal_accumulate_device
             _check(fn(self._h, C.byref(self._camera(cam)), ptr(frame_tensor), ptr(variance_tensor), C.byref(ab), C.byref(tp),

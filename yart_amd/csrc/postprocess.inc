@@ -228,6 +228,8 @@ struct YartTemporal {
   std::vector<float> motion;                        // yart_hip_temporal_set_motion: the pending records, 24 floats per node; empty: none
   std::vector<float> motionTaken;                   // what the running call consumed: the source of its upload
   DevBuf<f4> motionDev;
+  const float* pixelMotion = nullptr;               // yart_hip_temporal_set_pixel_motion: the caller's pending records, 8 floats per pixel
+  const float* pixelMotionTaken = nullptr;          // what the running call consumed (only one of the two motions is ever pending)
 };
 namespace {
 struct TpCall { TpConst k; bool demodulate; YartAovBuffers aovs; };
@@ -288,6 +290,8 @@ void temporalCheckForm(const YartTemporal& t) {
 void temporalTakeMotion(YartTemporal& t) {
   t.motionTaken.clear();
   t.motionTaken.swap(t.motion);
+  t.pixelMotionTaken = t.pixelMotion;
+  t.pixelMotion = nullptr;
 }
 
 // device pointers (c.aovs included); the handle's device is current and its mutex held; returns after completion on `st`
@@ -308,7 +312,10 @@ void temporalRun(YartTemporal& t, TpCall c, const YartCameraDesc& cam, const flo
   a.k = c.k;
   if (t.haveHistory) a.cam = tpCamera(makeCamera(t.camera));
   const dim3 grid(a.tilesX * ((t.height + 15u) / 16u));
-  if (!t.motionTaken.empty()) {                     // on `st`, before the kernel that reads it
+  if (t.pixelMotionTaken) {                         // device records, written on `st` or complete before the call
+    const TpDevicePixelRecords motion{reinterpret_cast<const f4*>(t.pixelMotionTaken)};
+    hipLaunchKernelGGL((k_tp_accumulate<MOMENTS, true, true>), grid, dim3(kBlock), 0, st, a, motion);
+  } else if (!t.motionTaken.empty()) {              // on `st`, before the kernel that reads it
     const size_t words = t.motionTaken.size() / 4;
     t.motionDev.ensure(words);
     HIP_CHECK(hipMemcpyAsync(t.motionDev.p, t.motionTaken.data(), words * sizeof(f4), hipMemcpyHostToDevice, st));
@@ -358,6 +365,7 @@ int yart_hip_temporal_reset(YartTemporal* temporal) {
     std::lock_guard<std::mutex> lock(temporal->mu);
     temporal->haveHistory = false;
     temporal->motion.clear();
+    temporal->pixelMotion = nullptr;
   });
 }
 
@@ -366,6 +374,7 @@ int yart_hip_temporal_set_motion(YartTemporal* temporal, const YartTemporalMotio
     require(temporal != nullptr, "temporal: handle pointer is null");
     std::lock_guard<std::mutex> lock(temporal->mu);
     temporal->motion.clear();                       // a refused motion leaves nothing pending
+    temporal->pixelMotion = nullptr;                // (one motion is pending at a time: a setter replaces what the other left)
     if (!motion) return;
     require(motion->struct_size >= sizeof(YartTemporalMotion), "temporal: struct_size is smaller than YartTemporalMotion");
     require(motion->n_nodes >= 1u && motion->n_nodes < kTpMotionMaxNodes, "temporal: motion: n_nodes is 0 or not below 2^20");
@@ -383,6 +392,19 @@ int yart_hip_temporal_set_motion(YartTemporal* temporal, const YartTemporalMotio
   });
 }
 
+int yart_hip_temporal_set_pixel_motion(YartTemporal* temporal, const YartTemporalPixelMotion* motion) {
+  return guarded([&] {
+    require(temporal != nullptr, "temporal: handle pointer is null");
+    std::lock_guard<std::mutex> lock(temporal->mu);
+    temporal->motion.clear();                       // a refused motion leaves nothing pending
+    temporal->pixelMotion = nullptr;
+    if (!motion) return;
+    require(motion->struct_size >= sizeof(YartTemporalPixelMotion), "temporal: struct_size is smaller than YartTemporalPixelMotion");
+    require(motion->records != nullptr, "temporal: pixel motion: records pointer is null");
+    temporal->pixelMotion = motion->records;
+  });
+}
+
 }  // extern "C"
 namespace {
 template <bool MOMENTS, class Params>
@@ -393,6 +415,7 @@ int temporalAccumulateDevice(YartTemporal* temporal, const YartCameraDesc* cam, 
     const TpCall c = temporalCheck(temporal, cam, d_rgba, d_variance, d_aovs, params, d_out_rgba);
     std::lock_guard<std::mutex> lock(temporal->mu);
     temporalCheckForm<MOMENTS>(*temporal);
+    require((reinterpret_cast<uintptr_t>(temporal->pixelMotion) & 15u) == 0u, "temporal: the pending per-pixel motion records are not 16-byte aligned");
     temporalTakeMotion(*temporal);
     temporalSelectDevice(*temporal);
     temporalRun<MOMENTS>(*temporal, c, *cam, d_rgba, d_variance, d_out_rgba, d_out_variance, d_out_length, static_cast<hipStream_t>(stream));
@@ -409,11 +432,17 @@ int temporalAccumulateHost(YartTemporal* temporal, const YartCameraDesc* cam, co
     temporalTakeMotion(*temporal);
     temporalSelectDevice(*temporal);
     const size_t n = size_t(temporal->width) * temporal->height;
-    // frame (4) | variance (1) | position (3) | normal (3) | depth (1) | coverage (1) | ids (4) | albedo (3) | length (1) words per pixel;
-    // frame and variance are accumulated in place
+    // per-pixel motion records (8, when pending) | frame (4) | variance (1) | position (3) | normal (3) | depth (1) | coverage (1) |
+    // ids (4) | albedo (3) | length (1) words per pixel; frame and variance are accumulated in place
     DevBuf<float> buf;
-    buf.ensure(n * 21);
+    const float* hostRecords = temporal->pixelMotionTaken;
+    buf.ensure(n * (hostRecords ? 29 : 21));
     float* w = buf.p;
+    if (hostRecords) {
+      HIP_CHECK(hipMemcpy(w, hostRecords, n * 8 * 4, hipMemcpyHostToDevice));
+      temporal->pixelMotionTaken = w;
+      w += n * 8;
+    }
     auto put = [&](const void* src, size_t words) {
       float* dst = w; w += n * words;
       if (src) HIP_CHECK(hipMemcpy(dst, src, n * words * 4, hipMemcpyHostToDevice));

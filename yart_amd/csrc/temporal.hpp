@@ -16,6 +16,7 @@
 // and runs a second pass, tpSpatialVariance, over the image the first one wrote: a pixel whose history is too short for the
 // temporal estimate takes the variance of m1 over its 7 x 7 neighbourhood on the same surface.
 #pragma once
+#include <type_traits>
 #include "denoise.hpp"
 #include "scene_types.hpp"
 
@@ -83,11 +84,27 @@ struct TpNoMotion {                              // no motion is pending: compil
   YART_HD f4 word(uint32_t, uint32_t) const { return dnF4(0.0f, 0.0f, 0.0f, 0.0f); }
 };
 
+// Per-pixel motion (yart_hip_temporal_set_pixel_motion): one record of two 16-byte words per pixel, {P'.xyz, kind} and {n'.xyz, 0},
+// as yart_hip_scene_pixel_motion_* writes them (scene_motion.hpp). A Motion of this kind has kPixel and is made for ONE pixel:
+// motion.word(i) fetches word i of that pixel's record. The pixel is MOVING when kind is 1.
+template <class Motion, class = void> struct TpIsPixelMotion : std::false_type {};
+template <class Motion> struct TpIsPixelMotion<Motion, std::void_t<decltype(Motion::kPixel)>> : std::true_type {};
+
 // What a pixel is projected with and what its taps are tested with: P' and n' of a moving pixel, P and n of any other.
 struct TpMoved { f3 P, n; bool finite; };
 template <class Motion>
 YART_HD TpMoved tpMoved(const Motion& motion, const TpIn& in) {
-  if constexpr (!Motion::kNone) {
+  if constexpr (TpIsPixelMotion<Motion>::value) {
+    const f4 w0 = motion.word(0u);               // first: it carries kind
+    if (dnBits(w0.w) == 1u) {
+      const f4 w1 = motion.word(1u);
+      TpMoved mv;
+      mv.P = mk3(w0.x, w0.y, w0.z);
+      mv.n = mk3(w1.x, w1.y, w1.z);
+      mv.finite = tpFinite3(mv.P) && tpFinite3(mv.n);
+      return mv;
+    }
+  } else if constexpr (!Motion::kNone) {
     if (in.node < motion.nodes()) {
       const f4 n0 = motion.word(in.node, 3u);    // first: it carries kind
       if (dnBits(n0.w) == 1u) {

@@ -15,6 +15,10 @@
 //                     aligned loads; a tile's lanes mostly share a node, so all but the first are line hits. Launched only for
 //                     the call that consumes a motion: the <·, false> kernels are the code from before there was one.
 //
+//   k_tp_accumulate<·, true, true>   with pending per-pixel records (yart_hip_temporal_set_pixel_motion): a lane loads the first
+//                     word of its pixel's record, which carries kind, and the second only when the pixel moved — two aligned,
+//                     coalesced 16-byte loads (32 bytes per pixel). Launched only for the call that consumes the records.
+//
 //   k_tp_accumulate<true>   the moments form, pass 1: the same, with rec3 — one more aligned 16-byte load per counting tap and
 //                     one more 16-byte store.
 //   k_tp_spatial_variance   the moments form, pass 2, launched after pass 1 on the image it wrote, same tile: a lane whose pixel
@@ -54,11 +58,27 @@ struct TpArgs {
   TpConst k;
   TpCamera cam;
 };
-// MOTION: the launch has a per-node motion, `motion`; else the second argument is empty and the code is that of a kernel without it
-template <bool MOTION>
-using TpMotionArg = typename std::conditional<MOTION, TpDeviceMotion, TpNoMotion>::type;
-template <bool MOMENTS, bool MOTION>
-__global__ void __launch_bounds__(kBlock) k_tp_accumulate(TpArgs a, TpMotionArg<MOTION> motion) {
+// per-pixel records (yart_hip_temporal_set_pixel_motion): the launch's argument, and what a lane makes of it for its pixel
+struct TpDevicePixelMotion {
+  static constexpr bool kNone = false, kPixel = true;
+  const f4* rec;                                   // the pixel's two words
+  __device__ __forceinline__ f4 word(uint32_t i) const { return dnLd(rec + i); }
+};
+struct TpDevicePixelRecords { const f4* rec; };    // two words per pixel
+
+// MOTION: the launch has a motion, `motion` — per-node records, or with PIXEL per-pixel ones; else the second argument is empty and
+// the code is that of a kernel without a motion
+template <bool MOTION, bool PIXEL>
+using TpMotionArg = typename std::conditional<PIXEL, TpDevicePixelRecords,
+                                              typename std::conditional<MOTION, TpDeviceMotion, TpNoMotion>::type>::type;
+template <bool MOTION, bool PIXEL>
+__device__ __forceinline__ auto tpMotionOf(const TpMotionArg<MOTION, PIXEL>& motion, size_t p) {
+  if constexpr (PIXEL) return TpDevicePixelMotion{motion.rec + p * 2u};
+  else return motion;
+}
+template <bool MOMENTS, bool MOTION, bool PIXEL = false>
+__global__ void __launch_bounds__(kBlock) k_tp_accumulate(TpArgs a, TpMotionArg<MOTION, PIXEL> motion) {
+  static_assert(MOTION || !PIXEL, "per-pixel records are a motion");
   const uint32_t ty = blockIdx.x / a.tilesX, tx = blockIdx.x - ty * a.tilesX;
   const uint32_t x = tx * 16u + (threadIdx.x % 16u), y = ty * 16u + (threadIdx.x / 16u);
   if (x >= a.k.width || y >= a.k.height) return;
@@ -76,7 +96,7 @@ __global__ void __launch_bounds__(kBlock) k_tp_accumulate(TpArgs a, TpMotionArg<
   TpDeviceHist hist;
   hist.r0 = a.histIn; hist.r1 = a.histIn + a.n; hist.r2 = a.histIn + size_t(a.n) * 2;
   hist.r3 = MOMENTS ? a.histIn + size_t(a.n) * 3 : nullptr;
-  const TpOut o = tpAccumulatePixel<MOMENTS>(hist, motion, a.k, a.cam, in, a.albedo != nullptr, alb);
+  const TpOut o = tpAccumulatePixel<MOMENTS>(hist, tpMotionOf<MOTION, PIXEL>(motion, p), a.k, a.cam, in, a.albedo != nullptr, alb);
   dnSt(a.histOut + p, o.rec0);
   dnSt(a.histOut + a.n + p, o.rec1);
   dnSt(a.histOut + size_t(a.n) * 2 + p, o.rec2);

@@ -24,6 +24,8 @@
 //                multi_device.inc       several GPUs behind one handle, with its pixel pack / unpack / copy kernels
 //                postprocess.inc        tonemap / encode, the a-trous denoiser (denoise_kernels.inc) and temporal accumulation
 //                                       (temporal_kernels.inc): kernels, drivers and entries
+//                scene_update_kernels.inc, mesh_update_kernels.inc, scene_motion_kernels.inc      a scene's next frame in place: new
+//                                       transforms, new vertices, and the per-pixel motion between the two frames
 //                probes.inc             the diagnostic kernels k_probe_* and the yart_hip_probe_* entries
 //   units 1-4  wavefront_units.hip under -DYART_TU=1..4: the path kernels, which are templates and are emitted where they are
 //              instantiated — 1 the lean closest-hit kernels k_wf_extend_lean<MODE, NODES>, 2 the lean any-hit kernels
@@ -349,6 +351,10 @@ struct YartScene {
   uint32_t pixW = 0, pixH = 0, pixTile = 0, pixRank = 0, pixWorld = 0;
   SceneUpdateTables su;
   MeshUpdateState meshUp;
+  // yart_hip_scene_keep_previous (scene_motion_kernels.inc): the node and vertex arrays of the previous frame, allocated by the first
+  // call; the nodes' composed transforms and the host entry's staging buffer of yart_hip_scene_pixel_motion_*
+  DevBuf<NodeDev> nodesPrev; DevBuf<f4> vPosPrev, smChains; DevBuf<float> smStage;
+  bool havePrevious = false;
   std::mutex mu;
 };
 
@@ -1618,4 +1624,5 @@ int yart_hip_bvh_build_host(const float* positions, uint32_t n_verts, const uint
 #include "postprocess.inc"
 #include "scene_update_kernels.inc"
 #include "mesh_update_kernels.inc"
+#include "scene_motion_kernels.inc"
 #include "probes.inc"

@@ -12,7 +12,9 @@ luminance moments and the sum of squared frame weights accumulated next to the c
 and the second pass that estimates the variance of the short pixels from their 7 x 7 neighbourhood.
 
 Both take ``motion``: the per-node motion records of ``yart_hip_temporal_set_motion`` — how each scene node moved since the
-previous frame — which :func:`node_motion` builds from the node lists of the two frames' scenes.
+previous frame — which :func:`node_motion` builds from the node lists of the two frames' scenes; and ``pixel_motion``: the
+per-pixel records of ``yart_hip_temporal_set_pixel_motion`` — where each pixel's surface point was, and what its normal was, in
+the previous frame —, which ``yart_amd.scene_motion.scene_motion_reference`` states: the motion of deforming meshes.
 """
 from __future__ import annotations
 
@@ -33,6 +35,9 @@ MOTION_WORDS = 24
 MOTION_KIND_WORD = 15
 MOTION_STATIC, MOTION_MOVING = 0, 1
 MOTION_MAX_NODES = 1 << 20
+# include/yart_hip.h: YartTemporalPixelMotion — floats per record and the word that holds kind
+PIXEL_MOTION_WORDS = 8
+PIXEL_MOTION_KIND_WORD = 3
 
 _F = np.float32
 _FLT_MAX = np.float32(3.4028235e38)
@@ -103,6 +108,14 @@ def motion_records(motion):
     return rec
 
 
+def pixel_motion_records(pixel_motion, width, height):
+    """``pixel_motion`` as the (H, W, 8) float32 array of records"""
+    rec = np.ascontiguousarray(pixel_motion)
+    assert rec.dtype == np.float32, "pixel motion records are float32 (kind is a uint32 stored as bits)"
+    assert rec.size == width * height * PIXEL_MOTION_WORDS, "pixel motion: 8 floats per pixel"
+    return rec.reshape(height, width, PIXEL_MOTION_WORDS)
+
+
 def _node_field(node, name, index):
     if isinstance(node, dict):
         return node[name]
@@ -160,31 +173,34 @@ class TemporalHistory:
 
 def temporal_reference(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo=None,
                        alpha_min=DEFAULT_ALPHA_MIN, max_history=DEFAULT_MAX_HISTORY, normal_cos_min=DEFAULT_NORMAL_COS_MIN,
-                       plane_tolerance=DEFAULT_PLANE_TOLERANCE, demodulate=None, motion=None):
+                       plane_tolerance=DEFAULT_PLANE_TOLERANCE, demodulate=None, motion=None, pixel_motion=None):
     """One frame: ``history`` (a :class:`TemporalHistory`, updated in place), ``cam`` the frame's camera (see
     :func:`camera_fields`), ``rgba`` (H, W, 4), ``variance`` (H, W), ``position`` / ``normal`` (H, W, 3), ``depth`` / ``coverage``
     (H, W), ``ids`` (H, W, 4) int32, ``albedo`` (H, W, 3) or None. ``demodulate``: None = whenever an albedo buffer is given.
     ``motion``: None, or the (n_nodes, 24) float32 per-node motion records of this frame (``kind`` as bits in column 15; see
     :func:`node_motion`): a pixel whose ``ids[0]`` is below n_nodes and whose record's kind is 1 is projected, and its taps are
     validated, with P' = M P and n' = Nm n; every other pixel is untouched by it.
+    ``pixel_motion`` (not together with ``motion``): None, or the (H, W, 8) float32 per-pixel records of
+    ``yart_hip_temporal_set_pixel_motion`` (``yart_amd.scene_motion.scene_motion_reference``): a pixel whose record's kind (the
+    bits of word 3) is 1 takes P' from words 0 .. 2 and n' from words 4 .. 6; every other pixel is untouched by it.
     Returns (accumulated frame (H, W, 4) float32, its variance (H, W) float32, history length (H, W) uint32)."""
     return _accumulate(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo, alpha_min, max_history,
-                       normal_cos_min, plane_tolerance, demodulate, None, motion)
+                       normal_cos_min, plane_tolerance, demodulate, None, motion, pixel_motion)
 
 
 def temporal_moments_reference(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo=None,
                                alpha_min=DEFAULT_ALPHA_MIN, max_history=DEFAULT_MAX_HISTORY,
                                normal_cos_min=DEFAULT_NORMAL_COS_MIN, plane_tolerance=DEFAULT_PLANE_TOLERANCE,
-                               min_moment_history=DEFAULT_MIN_MOMENT_HISTORY, demodulate=None, motion=None):
+                               min_moment_history=DEFAULT_MIN_MOMENT_HISTORY, demodulate=None, motion=None, pixel_motion=None):
     """One frame of the moments form; arguments and results as :func:`temporal_reference`, and ``min_moment_history`` (>= 2).
     The history additionally carries ``moments``; a history is in one form from its first frame to the next ``reset``."""
     assert int(min_moment_history) >= 2
     return _accumulate(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo, alpha_min, max_history,
-                       normal_cos_min, plane_tolerance, demodulate, int(min_moment_history), motion)
+                       normal_cos_min, plane_tolerance, demodulate, int(min_moment_history), motion, pixel_motion)
 
 
 def _accumulate(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo, alpha_min, max_history,
-                normal_cos_min, plane_tolerance, demodulate, min_moment_history, motion=None):
+                normal_cos_min, plane_tolerance, demodulate, min_moment_history, motion=None, pixel_motion=None):
     """Pass 1 of both forms (``min_moment_history`` None: the plain form), then pass 2 of the moments form."""
     moments = min_moment_history is not None
     form = "moments" if moments else "plain"
@@ -228,6 +244,14 @@ def _accumulate(history, cam, rgba, variance, position, normal, depth, coverage,
             moving = in_range & (r[..., MOTION_KIND_WORD].view(np.uint32) == np.uint32(MOTION_MOVING))
             Pm = np.stack([_dot(r[..., 4 * i:4 * i + 3], P) + r[..., 4 * i + 3] for i in range(3)], -1).astype(_F)
             nm = np.stack([_dot(r[..., 12 + 4 * i:15 + 4 * i], n) for i in range(3)], -1).astype(_F)
+            reproj &= ~moving | (np.isfinite(Pm).all(-1) & np.isfinite(nm).all(-1))
+            Pq = np.where(moving[..., None], Pm, P).astype(_F)
+            nq = np.where(moving[..., None], nm, n).astype(_F)
+        if pixel_motion is not None:
+            assert motion is None, "one motion at a time: per node or per pixel"
+            r = pixel_motion_records(pixel_motion, w, h)
+            moving = r[..., PIXEL_MOTION_KIND_WORD].view(np.uint32) == np.uint32(MOTION_MOVING)
+            Pm, nm = r[..., 0:3], r[..., 4:7]
             reproj &= ~moving | (np.isfinite(Pm).all(-1) & np.isfinite(nm).all(-1))
             Pq = np.where(moving[..., None], Pm, P).astype(_F)
             nq = np.where(moving[..., None], nm, n).astype(_F)
