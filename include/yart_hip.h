@@ -584,6 +584,20 @@ int yart_hip_probe_math_pairs(int fn, uint64_t n, const float* a, const float* b
 /* closest hit of n world rays (ox,oy,oz,dx,dy,dz) -> 16 floats each:
  * hit, t, u, v, px,py,pz, nx,ny,nz, tx,ty,tz, triIdx, lightIdx, backSide */
 int yart_hip_probe_hits(YartScene* scene, uint32_t n, const float* rays, float* out);
+/* Diagnostic: one walk of the scene (csrc/traverse.hpp traverseScene, then finalizeHit) per caller-supplied ray, in the
+ * instantiation `walk` selects: 0 TRAV_GENERAL, 1 TRAV_FAST, 2 TRAV_FAST | TRAV_IDENTITY (YART_E_INVALID unless every node
+ * chain of the scene is the identity). The sampler is the one a render with `params` constructs (samples, tile_size).
+ * rays: n records of 12 words: origin[3], direction[3], tMax (f32; +inf for a closest-hit ray), kind (0 closest hit, 1
+ *   occlusion: the walk of MISIntegrator::unoccluded), x, y, s (the sampler is started on pixel (x, y), sample s before the
+ *   walk, so stochastic alpha tests draw what a path's would; x, y < 65536, s < params->samples), one unused word. Every ray
+ *   enters the walk with tMin = 0.001 and hit.t = tMax.
+ * out: n records of 20 words: 0 hit / occluded, 1 mesh-local triangle, 2 light index (-1: none), 3 back side, 4 t, 5..7 p,
+ *   8..10 n, 11..13 tangent (world space; closest-hit rays with a hit, otherwise 0), 14..16 the attenuation the walk
+ *   accumulated (1, 1, 1 unless an occlusion ray passed transparent surfaces), 17 one get1D() drawn after the walk (pins the
+ *   number of dimensions the walk consumed), 18 deferred, 19 zero. The fast walks set `deferred` and zero every other word for
+ *   a ray they hand over to the general walk; for an occlusion ray they report words 0, 14..16 (unoccluded rays) and 17 only,
+ *   which is all the shadow kernels take from them. */
+int yart_hip_probe_rays(YartScene* scene, const YartRenderParams* params, uint32_t n, const uint32_t* rays, int walk, uint32_t* out);
 /* Diagnostic: the camera ray of n (x, y, sample) triples -> 6 floats each (origin, direction), drawn exactly as bounce 0 of that
  * sample draws it: startPixelSample, the film and the lens draw (core/sampler.hpp), Camera::getRay (core/camera.hpp:138-164) */
 int yart_hip_probe_camera_rays(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, uint32_t n,

@@ -1,5 +1,8 @@
 // oracle_main.cpp — TEST INFRASTRUCTURE: command-line front end of the CPU restatement.
 //   yart_oracle kat    <scene.yscn> <params.txt> <out.json>   same KAT program as ref_driver.cpp
+//   yart_oracle hits   <scene.yscn> <params.txt> <rays.bin> <out.bin>   one record per ray through testNode(root) (rayrec.hpp);
+//                      <out.bin>.events gets the ray's event mask (u16, Integrator::RayEvent) and stdout the number of rays
+//                      that met each event, as JSON
 //   yart_oracle render <scene.yscn> <params.txt> <out.f32>    tile-threaded render (the reference's
 //                      scheme: 64x64 tiles popped from a shared queue, tile-renderer.hpp:118-309)
 // LUT tables are read from tests/golden/ref_tables.bin (dumped from the compiled reference;
@@ -14,6 +17,7 @@
 
 #include "kat_common.hpp"
 #include "params.hpp"
+#include "rayrec.hpp"
 #include "yart_oracle.hpp"
 
 using namespace orc;
@@ -203,6 +207,48 @@ static int doKat(const Scene& sc, const yscn::SceneFile& sf, const params::Param
   return 0;
 }
 
+static int doHits(const Scene& sc, const params::Params& p, const std::string& raysPath, const std::string& outPath) {
+  Camera cam = makeCamera(p);
+  SobolSampler sampler(p.spp, p.tile);
+  Integrator integ;
+  integ.scene = &sc; integ.cam = &cam; integ.sampler = &sampler; integ.maxDepth = p.depth;
+  static const char* names[Integrator::EV_COUNT] = {"nan_slab", "u_eq_0", "u_eq_1", "v_eq_0", "uv_eq_1", "t_eq_hit_t", "t_eq_tmin", "t_eq_tmax",
+                                                    "det_near_eps", "d1_eq_d2", "pop_eq", "node_eq", "alpha_candidate", "transparent_candidate"};
+  uint64_t counts[Integrator::EV_COUNT] = {0};
+  std::vector<rayrec::Rec> out;
+  std::vector<uint16_t> masks;
+  const auto rays = rayrec::load(raysPath);
+  for (const rayrec::Ray& q : rays) {
+    sampler.startPixelSample(q.x, q.y, q.s);
+    Ray r(V3(q.o[0], q.o[1], q.o[2]), V3(q.d[0], q.d[1], q.d[2]));
+    r.nee = q.kind != 0;
+    Hit h;
+    h.t = q.tMax;
+    Integrator::RayEvents ev;
+    ev.tMax = q.tMax;
+    integ.ev = &ev;
+    const bool hit = integ.testNode(r, 0.001f, h, *sc.root);
+    integ.ev = nullptr;
+    rayrec::Rec o = rayrec::miss();
+    o.hit = hit;
+    if (hit) {
+      o.tri = h.idx; o.light = h.lightIdx; o.backSide = h.backSide; o.t = h.t;
+      if (!q.kind) { o.p[0] = h.p.x; o.p[1] = h.p.y; o.p[2] = h.p.z; o.n[0] = h.n.x; o.n[1] = h.n.y; o.n[2] = h.n.z; o.tg[0] = h.tg.x; o.tg[1] = h.tg.y; o.tg[2] = h.tg.z; }
+    }
+    o.att[0] = h.attenuation.x; o.att[1] = h.attenuation.y; o.att[2] = h.attenuation.z;
+    o.draw = sampler.get1D();
+    out.push_back(o);
+    masks.push_back(uint16_t(ev.mask));
+    for (uint32_t k = 0; k < Integrator::EV_COUNT; k++) counts[k] += (ev.mask >> k) & 1u;
+  }
+  rayrec::save(outPath, out);
+  rayrec::save(outPath + ".events", masks);
+  std::printf("{\"rays\": %zu", rays.size());
+  for (uint32_t k = 0; k < Integrator::EV_COUNT; k++) std::printf(", \"%s\": %llu", names[k], (unsigned long long) counts[k]);
+  std::printf("}\n");
+  return 0;
+}
+
 static int doRender(const Scene& sc, const params::Params& p, const std::string& outPath) {
   const uint32_t W = p.width, H = p.height, T = p.tile;
   Camera cam = makeCamera(p);
@@ -354,8 +400,9 @@ int main(int argc, char** argv) {
     try { return doTonemap(argv[2], unsigned(std::atoi(argv[3])), unsigned(std::atoi(argv[4])), argv[5], argv[6], argv[7]); }
     catch (const std::exception& e) { std::fprintf(stderr, "yart_oracle: %s\n", e.what()); return 2; }
   }
-  if (argc != 5) {
-    std::fprintf(stderr, "usage: yart_oracle kat|render <scene.yscn> <params.txt> <out>\n");
+  const bool hits = argc == 6 && std::string(argv[1]) == "hits";
+  if (argc != 5 && !hits) {
+    std::fprintf(stderr, "usage: yart_oracle kat|render <scene.yscn> <params.txt> <out> | hits <scene.yscn> <params.txt> <rays.bin> <out.bin>\n");
     return 1;
   }
   try {
@@ -365,6 +412,7 @@ int main(int argc, char** argv) {
     Scene sc = buildScene(sf, luts.data());
     for (auto& m : sc.materials) m.lut = &sc.luts;     // the Scene object may have moved
     std::string mode = argv[1];
+    if (hits) return doHits(sc, p, argv[4], argv[5]);
     if (mode == "kat") return doKat(sc, sf, p, argv[4]);
     if (mode == "render") return doRender(sc, p, argv[4]);
   } catch (const std::exception& e) {

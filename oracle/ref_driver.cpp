@@ -12,6 +12,7 @@
 // Modes:
 //   yart_ref render <scene.yscn> <params.txt> <out.f32>     raw RGBA32F, W*H*4 floats
 //   yart_ref kat    <scene.yscn> <params.txt> <out.json>    known-answer vectors
+//   yart_ref hits   <scene.yscn> <params.txt> <rays.bin> <out.bin>   one record per ray through testNode(root) (rayrec.hpp)
 //   yart_ref luts   <out.bin>                               raw dump of the 8 LUT tables
 //   yart_ref bvh    <scene.yscn> <mesh> <out.bin>           node array + index array
 //   yart_ref tonemap <in.f32> <w> <h> <look|-> <out.f32> <out.ppm>   AgX (none|golden|punchy, "-": no
@@ -46,6 +47,7 @@
 #include "yscn.hpp"
 #include "params.hpp"
 #include "kat_common.hpp"
+#include "rayrec.hpp"
 
 using namespace yart;
 using namespace yart::math;
@@ -65,6 +67,25 @@ struct MISDepth : cpu::MISIntegrator {
     return sample(p.x(), p.y());
   }
   bool probeHit(const Ray& r, cpu::Hit& h) { return testNode(r, 0.001f, h, scene->root()); }
+  // `hits` mode (rayrec.hpp): one ray through testNode(root) after startPixelSample, as Li (kind 0: mis-integrator.cpp:24-27)
+  // or unoccluded (kind 1: :140-145, Ray::nee set and Hit::t = tMax) enter it, then one get1D()
+  rayrec::Rec probeRay(const rayrec::Ray& q) {
+    m_sampler.startPixelSample({q.x, q.y}, q.s);
+    Ray r(float3(q.o[0], q.o[1], q.o[2]), float3(q.d[0], q.d[1], q.d[2]));
+    cpu::Hit h;
+    r.nee = q.kind != 0;
+    h.t = q.tMax;
+    const bool hit = testNode(r, 0.001f, h, scene->root());
+    rayrec::Rec o = rayrec::miss();
+    o.hit = hit;
+    if (hit) {
+      o.tri = h.idx; o.light = h.lightIdx; o.backSide = h.backSide; o.t = h.t;
+      if (!q.kind) for (int c = 0; c < 3; c++) { o.p[c] = h.p[c]; o.n[c] = h.n[c]; o.tg[c] = h.tg[c]; }
+    }
+    for (int c = 0; c < 3; c++) o.att[c] = h.attenuation[c];
+    o.draw = m_sampler.get1D();
+    return o;
+  }
   // setup() is private in MISIntegrator; Integrator::render() (public) calls it and
   // then loops over an empty default samplingBounds.
   void probeSetup() { render(); }
@@ -526,6 +547,22 @@ static int doKat(const std::string& scenePath, const std::string& paramPath,
   return 0;
 }
 
+static int doHits(const std::string& scenePath, const std::string& paramPath, const std::string& raysPath, const std::string& outPath) {
+  auto sf = yscn::load(scenePath);
+  auto p = params::load(paramPath);
+  auto built = build(sf);
+  Camera cam = makeCamera(p);
+  Buffer tb(p.tile, p.tile);
+  SobolSampler<FastOwenScrambler> sampler(p.spp, {p.tile, p.tile});
+  MISDepth integ(tb, cam, sampler);
+  integ.scene = built.scene.get();
+  integ.probeSetup();
+  std::vector<rayrec::Rec> out;
+  for (const rayrec::Ray& q : rayrec::load(raysPath)) out.push_back(integ.probeRay(q));
+  rayrec::save(outPath, out);
+  return 0;
+}
+
 static int doTonemap(const char* in, unsigned w, unsigned h, const std::string& look, const char* outF32, const char* outPpm) {
   std::ifstream f(in, std::ios::binary);
   std::vector<float> hdr(size_t(w) * h * 4);
@@ -675,6 +712,7 @@ int main(int argc, char** argv) {
   try {
     if (mode == "render" && argc == 5) return doRender(argv[2], argv[3], argv[4]);
     if (mode == "kat" && argc == 5) return doKat(argv[2], argv[3], argv[4]);
+    if (mode == "hits" && argc == 6) return doHits(argv[2], argv[3], argv[4], argv[5]);
     if (mode == "luts" && argc == 3) return doLuts(argv[2]);
     if (mode == "bvh" && argc == 5) return doBvh(argv[2], size_t(std::atoi(argv[3])), argv[4]);
     if (mode == "texture" && argc == 7) return doTexture(argv[2], std::atoi(argv[3]), std::atoi(argv[4]), argv[5], argv[6]);
@@ -688,6 +726,6 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "yart_ref: %s\n", e.what());
     return 2;
   }
-  std::fprintf(stderr, "usage: yart_ref render|kat <scene.yscn> <params.txt> <out> | luts <out> | bvh <scene> <mesh> <out>\n");
+  std::fprintf(stderr, "usage: yart_ref render|kat <scene.yscn> <params.txt> <out> | hits <scene.yscn> <params.txt> <rays.bin> <out.bin> | luts <out> | bvh <scene> <mesh> <out>\n");
   return 1;
 }

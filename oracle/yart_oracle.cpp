@@ -101,12 +101,14 @@ Scene buildScene(const yscn::SceneFile& sf, const float* lutTables) {
   return s;
 }
 
-bool Integrator::testBox(const Ray& ray, float t0, float t1, const Bounds& b, float* d) {   // ray-integrator.cpp:231-261
+bool Integrator::testBox(const Ray& ray, float t0, float t1, const Bounds& b, float* d, RayEvents* e) {   // ray-integrator.cpp:231-261
   auto pick = [&](int which, int axis) { return which == 0 ? b.mn[axis] : b.mx[axis]; };
   V3 bmin(pick(ray.sign[0], 0), pick(ray.sign[1], 1), pick(ray.sign[2], 2));
   V3 bmax(pick(1 - ray.sign[0], 0), pick(1 - ray.sign[1], 1), pick(1 - ray.sign[2], 2));
   V3 tmin = bmin * ray.idir + ray.odir;                       // vec.hpp:325-334: a*b + c, unfused
   V3 tmax = bmax * ray.idir + ray.odir;
+  if (e && (tmin.x != tmin.x || tmin.y != tmin.y || tmin.z != tmin.z || tmax.x != tmax.x || tmax.y != tmax.y || tmax.z != tmax.z))
+    e->mask |= EV_NAN_SLAB;
   t0 = mmax(tmin.x, t0); t0 = mmax(tmin.y, t0); t0 = mmax(tmin.z, t0);
   t1 = mmin(tmax.x, t1); t1 = mmin(tmax.y, t1); t1 = mmin(tmax.z, t1);
   *d = t0;
@@ -121,17 +123,22 @@ bool Integrator::testTriangle(const Ray& ray, float tMin, Hit& hit, const Mesh& 
   const V3 re2 = cross(ray.d, e2);
   const float det = dot(e1, re2);
   bool back = det < 0;
+  if (ev && double(std::abs(det)) >= 0.25e-12 && double(std::abs(det)) <= 4e-12) ev->mask |= EV_DET;
   if (std::abs(det) < 1e-12) return false;                    // double epsilon, math_base.hpp:11
   const float inv = 1.0f / det;
   const V3 b = ray.o - p0;
   const float u = dot(b, re2) * inv;
+  if (ev) ev->mask |= (u == 0.0f ? EV_U0 : 0u) | (u == 1.0f ? EV_U1 : 0u);
   if (u < 0.0f || u > 1.0f) return false;
   const V3 be1 = cross(b, e1);
   const float v = dot(ray.d, be1) * inv;
+  if (ev) ev->mask |= (v == 0.0f ? EV_V0 : 0u) | (v >= 0.0f && u + v == 1.0f ? EV_UV1 : 0u);
   if (v < 0.0f || u + v > 1.0f) return false;
   const float t = dot(e2, be1) * inv;
+  if (ev) ev->mask |= (t == hit.t ? EV_TIE : 0u) | (t == tMin ? EV_TMIN : 0u) | (ray.nee && t == ev->tMax ? EV_TMAX : 0u);
   if (t <= tMin || hit.t <= t) return false;
   const Material& bsdf = scene->materials[mesh.mat[idx]];
+  if (ev) ev->mask |= (bsdf.hasAlpha ? EV_ALPHA : 0u) | (bsdf.transparent() ? EV_TRANSPARENT : 0u);
   const float w = 1.0f - u - v;
   V2 uv = w * mesh.uv[i0] + u * mesh.uv[i1] + v * mesh.uv[i2];
   float alpha = bsdf.alpha(uv);
@@ -155,8 +162,9 @@ bool Integrator::testBVH(const Ray& ray, float tMin, Hit& hit, const Mesh& mesh)
   uint32_t sp = 0;
   bool didHit = false;
   nBox++; nBoxNee += ray.nee;
-  if (!testBox(ray, tMin, hit.t, node->b, &d)) return false;
+  if (!testBox(ray, tMin, hit.t, node->b, &d, ev)) return false;
   while (true) {
+    if (ev && d == hit.t) ev->mask |= EV_POP;
     if (d < hit.t) {
       if (node->span > 0) {
         for (size_t i = 0; i < node->span; i++) {
@@ -171,8 +179,9 @@ bool Integrator::testBVH(const Ray& ray, float tMin, Hit& hit, const Mesh& mesh)
         const BVHNode* c2 = &mesh.nodes[node->leftFirst + 1];
         float d1, d2;
         nBox += 2; nBoxNee += 2 * ray.nee;
-        bool h1 = testBox(ray, tMin, hit.t, c1->b, &d1);
-        bool h2 = testBox(ray, tMin, hit.t, c2->b, &d2);
+        bool h1 = testBox(ray, tMin, hit.t, c1->b, &d1, ev);
+        bool h2 = testBox(ray, tMin, hit.t, c2->b, &d2, ev);
+        if (ev && h1 && h2 && d1 == d2) ev->mask |= EV_D1D2;
         if (h1) {
           if (h2) {
             if (d1 > d2) { std::swap(d1, d2); std::swap(c1, c2); }
@@ -217,7 +226,9 @@ bool Integrator::testNode(const Ray& ray, float tMin, Hit& hit, const Node& node
   r.nee = ray.nee;
   float d;
   nBox++; nBoxNee += ray.nee;
-  if (!testBox(r, tMin, hit.t, node.bounds, &d) || hit.t < d) return false;
+  const bool inBox = testBox(r, tMin, hit.t, node.bounds, &d, ev);
+  if (ev && inBox && hit.t == d) ev->mask |= EV_NODE;
+  if (!inBox || hit.t < d) return false;
   bool didHit = false;
   if (node.mesh) didHit = testMesh(r, tMin, hit, *node.mesh);
   for (const auto& c : node.children) didHit |= testNode(r, tMin, hit, *c);

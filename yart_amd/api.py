@@ -363,7 +363,8 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_scene_update", "yart_hip_probe_scene_graph",
            "yart_hip_scene_update_meshes", "yart_hip_probe_mesh",
            "yart_hip_scene_keep_previous", "yart_hip_scene_pixel_motion_device", "yart_hip_scene_pixel_motion_host",
-           "yart_hip_temporal_set_pixel_motion"]
+           "yart_hip_temporal_set_pixel_motion",
+           "yart_hip_probe_rays"]
 
 LIB_COUNT_PATH = os.path.join(_HERE, "libyart_hip_count.so")   # instrumented twin (exact test counters)
 _libs = {}
@@ -400,6 +401,7 @@ def lib(instrumented: bool = False):
         L.yart_hip_probe_samples.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams),
                                              C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
         L.yart_hip_probe_hits.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.yart_hip_probe_rays.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
         L.yart_hip_probe_sampler.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
         L.yart_hip_tonemap_agx.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
         L.yart_hip_encode_rgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -1035,6 +1037,17 @@ class DeviceScene:
         out = np.empty((len(a), 16), np.float32)
         _check(self._L.yart_hip_probe_hits(self._h, len(a), a.ctypes.data_as(C.c_void_p),
                                          out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def probe_rays(self, p: dict, rays, walk: int = 0):
+        """One walk of the scene per ray record (include/yart_hip.h yart_hip_probe_rays): `rays` holds 12 32-bit words per ray
+        (origin, direction, tMax, kind, x, y, s, pad — any dtype of that size), `walk` selects TRAV_GENERAL (0), TRAV_FAST (1) or
+        TRAV_FAST | TRAV_IDENTITY (2); the sampler is the one a render with `p` constructs. Returns uint32 [n, 20] result words."""
+        a = np.ascontiguousarray(rays).view(np.uint32).reshape(-1, 12)
+        out = np.empty((len(a), 20), np.uint32)
+        rp = make_params(p)
+        _check(self._L.yart_hip_probe_rays(self._h, C.byref(rp), len(a), a.ctypes.data_as(C.c_void_p), int(walk),
+                                           out.ctypes.data_as(C.c_void_p)), self._L)
         return out
 
     def probe_sampler(self, spp, tile, cases, pattern, use_tables=False):

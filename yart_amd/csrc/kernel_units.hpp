@@ -15,6 +15,8 @@ AnyKernel shadowFast(bool ident);
 AnyKernel extendGeneral(bool retry);
 AnyKernel shadowGeneral(bool retry);
 AnyKernel shade(bool sort, bool fit, bool env1);      // unit 4: k_wf_shade<SORT, FIT, ENV1>
+// (unit 0 alone holds the diagnostics of probes.inc, k_probe_rays<MODE> among them: the three walks of traverseScene it
+// instantiates are copies of its own, so no path kernel's code or unit changes with it)
 #if defined(YART_SHADE_REGIONS)
 void shadeRegionsTake(unsigned long long* v48);       // (measurement builds: the shade kernel's region counters live in unit 4)
 #endif

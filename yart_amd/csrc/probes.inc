@@ -2,6 +2,7 @@
 // which runs one piece of the device code on caller-supplied input (included by yart_hip.hip, unit 0, last: the entries use
 // YartScene, guarded, validate and the kernels of stream_kernels.inc, aov_kernels.inc and moment_kernels.inc).
 #include "tonemap.hpp"         // (ypowf, for k_probe_math)
+#include "probe_record.hpp"
 
 namespace {
 
@@ -66,6 +67,20 @@ __global__ void __launch_bounds__(kBlock) k_probe_hits(ProbeHitArgs a) {
     q[10] = h.tg.x; q[11] = h.tg.y; q[12] = h.tg.z;
     q[13] = float(localTri(a.sc, hr)); q[14] = float(h.lightIdx); q[15] = h.backSide ? 1.0f : 0.0f;
   }
+}
+
+// one walk of traverseScene per caller-supplied ray record (yart_hip_probe_rays, include/yart_hip.h; probe_record.hpp): MODE is
+// the instantiation, the ray's kind word picks the <false> / <true> form, the sampler is the render's
+struct ProbeRayArgs { SceneDev sc; SamplerConfig cfg; const uint32_t* rays; uint32_t n; uint32_t* out; uint64_t* spill; };
+template <int MODE>
+__global__ void __launch_bounds__(kBlock) k_probe_rays(ProbeRayArgs a) {
+  __shared__ uint64_t ldsStack[kLdsStack * kBlock];
+  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
+  TravStack stk;
+  stk.lds = (lds_u64*)(ldsStack + threadIdx.x); stk.ldsStride = kBlock; stk.ldsDepth = kLdsStack;
+  stk.spill = a.spill + gtid; stk.spillStride = gridDim.x * blockDim.x;
+  if (gtid >= a.n) return;
+  probeRayRecord<MODE>(a.sc, a.cfg, stk, a.rays + size_t(gtid) * 12, a.out + size_t(gtid) * 20);
 }
 
 // the math the frames rest on, one function at a time (diagnostic, yart_hip_probe_math[_pairs]): the very inline functions the
@@ -160,6 +175,37 @@ int yart_hip_probe_hits(YartScene* scene, uint32_t n, const float* rays, float* 
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(out, res.p, size_t(n) * 16 * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int yart_hip_probe_rays(YartScene* scene, const YartRenderParams* params, uint32_t n, const uint32_t* rays, int walk, uint32_t* out) {
+  return guarded([&] {
+    require(scene && params && rays && out, "probe_rays: null pointer");
+    require(walk >= 0 && walk <= 2, "probe_rays: walk must be 0 (general), 1 (fast) or 2 (fast, identity)");
+    require(params->samples > 0 && params->tile_size > 0 && params->tile_size <= 4096, "probe_rays: samples / tile_size out of range");
+    for (uint32_t i = 0; i < n; i++) {
+      const uint32_t* q = rays + size_t(i) * 12;
+      require(q[7] <= 1u, "probe_rays: kind must be 0 (closest hit) or 1 (occlusion)");
+      require(q[8] < 65536u && q[9] < 65536u && q[10] < params->samples, "probe_rays: pixel / sample out of range");
+    }
+    std::lock_guard<std::mutex> lock(scene->mu);
+    YartScene& s = *scene;
+    require(walk != 2 || s.host.allIdentity, "probe_rays: walk 2 (TRAV_IDENTITY) needs a scene whose node chains are all the identity");
+    if (n == 0) return;
+    HIP_CHECK(hipSetDevice(s.device));
+    const int grid = int((n + kBlock - 1) / kBlock);
+    s.spill.ensure(size_t(grid) * kBlock * spillDepthFor(s.host, false));
+    DevBuf<uint32_t> in, res;
+    in.ensure(size_t(n) * 12); res.ensure(size_t(n) * 20);
+    HIP_CHECK(hipMemcpy(in.p, rays, size_t(n) * 12 * 4, hipMemcpyHostToDevice));
+    ProbeRayArgs a{};
+    a.sc = s.dev; a.cfg = makeRenderConst(*params).sampler; a.rays = in.p; a.n = n; a.out = res.p; a.spill = s.spill.p;
+    if (walk == 0) hipLaunchKernelGGL(k_probe_rays<TRAV_GENERAL>, dim3(grid), dim3(kBlock), 0, nullptr, a);
+    else if (walk == 1) hipLaunchKernelGGL(k_probe_rays<TRAV_FAST>, dim3(grid), dim3(kBlock), 0, nullptr, a);
+    else hipLaunchKernelGGL((k_probe_rays<TRAV_FAST | TRAV_IDENTITY>), dim3(grid), dim3(kBlock), 0, nullptr, a);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out, res.p, size_t(n) * 20 * 4, hipMemcpyDeviceToHost));
   });
 }
 
