@@ -755,7 +755,7 @@ int yart_hip_denoise_atrous_var_host(const float* rgba, const float* variance, c
  * by the first accumulate call (yart_hip_temporal_create touches no device), and the YartCameraDesc of the last accumulated frame.
  * DEFINITION. Every operation is an individually rounded binary32 operation in the order written (no FMA contraction); dot(a, b) is
  * (a.x * b.x + a.y * b.y) + a.z * b.z, cross(a, b) = (a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); only
- * + - * /, floorf and comparisons occur. csrc/temporal.hpp states it; yart_amd/temporal.py temporal_reference is the NumPy
+ * + - * /, floorf and comparisons occur (and sqrtf, with a CLIP). csrc/temporal.hpp states it; yart_amd/temporal.py temporal_reference is the NumPy
  * statement the tests compare with, on bits.
  *   Current pixel p:
  *     d = alb > 1e-3f ? alb : 1.0f per channel with YART_TEMPORAL_DEMODULATE (the filters' rule), else (1, 1, 1) (albedo is not read)
@@ -805,8 +805,33 @@ int yart_hip_denoise_atrous_var_host(const float* rgba, const float* variance, c
  * taken from the record: reprojectable(p) additionally needs them finite, the projection and the tap tests use them; node
  * equality, the weights, the blend, N, the moments, the new record with the CURRENT P and n, and pass 2 are untouched. A pixel
  * whose kind is not 1 runs the operations it ran before.
- * Out of scope: screen-space motion-vector output, a wider search when all four taps fail, colour clamps against ghosting,
- * yart_hip_multi_*. */
+ * CLIP (yart_hip_temporal_set_clip): variance clipping of the history against ghosting. Geometry alone validates a tap, so a light
+ * that moves or dims, or a shadow that crosses a static wall, leaves every tap valid and the stale colour in the blend. With a clip
+ * set, the fetched history colour is clipped, per channel, to mean +- gamma * standard deviation of the current frame's
+ * demodulated colour over the (2 radius + 1)^2 window around p: history the frame supports passes untouched, the rest is pulled to
+ * the edge of what the frame supports. Under the rules above; sqrtf is the correctly rounded binary32 square root (the only
+ * operation the clip adds to + - * /, floorf and comparisons). The definition changes for a usable pixel p WITH A COUNTING TAP SET,
+ * after h (and h1, h2 in the moments form) is formed and before the blend; a pixel without a counting tap, a first frame and an
+ * unusable pixel produce the bits they produce without a clip:
+ *     window: dy = -radius .. radius outer, dx = -radius .. radius inner. A neighbour q COUNTS iff it is inside the image, every
+ *     component of c(q) = rgb(q) / d(q) is finite, and, when demodulating, every component of albedo(q) is finite. (variance(q)
+ *     plays no part; p itself is a neighbour like any other.)
+ *     over the counting neighbours, from 0.0f and 0, per channel: s1 = s1 + c(q);  s2 = s2 + c(q) * c(q);  k = k + 1
+ *     k < 2: nothing is clipped. Otherwise, per channel:
+ *       mu = s1 / float(k);  e2 = s2 / float(k);  var = e2 - mu * mu;  var = var > 0.0f ? var : 0.0f;  sd = sqrtf(var)
+ *       lo = mu - gamma * sd;  hi = mu + gamma * sd
+ *       mu, e2 and sd all finite: h = h < lo ? lo : (h > hi ? hi : h);  otherwise the channel is left alone (an overflowing c * c
+ *       would clip to infinity — or, where mu * mu overflows with it, var is NaN, sd 0, and it would clip to a huge mu)
+ *     N, a, v_h, hw2, the history length and the tap tests are unchanged.
+ *   The moments form, additionally: the same sums for y(q) = luma(c(q)) give mu_y, e2_y and sd_y; with all three finite, h1' = h1 clipped the
+ *     same way, and if h1' != h1: h2 = h2 + (h1' * h1' - h1 * h1), then h1 = h1' — the history's luminance distribution is translated,
+ *     so its temporal variance h2 - h1 * h1 is kept. Pass 2 is untouched.
+ *   The defaults minimise, over radius 1 .. 3 x gamma {0.5, 1, 1.5, 2, 3}, the worst case over the 6-frame orbits of the two golden
+ *   scenes, unchanged and with every emitter dimmed to a quarter from frame 4 on, of the last frame's error against 1024 spp relative
+ *   to the better of unclipped accumulation and not accumulating (tools/temporal_clip_sweep.py, profiles/temporal_clip_sweep.txt:
+ *   radius 1, gamma 0.5; 0.93 / 0.98 of the unclipped RMSE on the unchanged orbits of cornell / material, and after the dimming 1.08
+ *   of the last frame's alone on cornell, where unclipped accumulation is at 4.4, and 0.75 on material).
+ * Out of scope: screen-space motion-vector output, a wider search when all four taps fail, yart_hip_multi_*. */
 #define YART_TEMPORAL_DEMODULATE 1u         /* accumulate rgb / d, return acc * d (needs YART_AOV_ALBEDO) */
 #define YART_TEMPORAL_DEFAULT_ALPHA_MIN 0.1f
 #define YART_TEMPORAL_DEFAULT_MAX_HISTORY 8u
@@ -852,6 +877,21 @@ typedef struct YartTemporalPixelMotion {
   const float* records;        /* width * height * 8 floats, in the consuming call's address space */
 } YartTemporalPixelMotion;
 int yart_hip_temporal_set_pixel_motion(YartTemporal* temporal, const YartTemporalPixelMotion* motion);
+/* The clip of the history to the frame's neighbourhood (CLIP above): a SETTING of the handle. It touches no device; it stays set
+ * across accumulate calls — both forms, every motion, device and host entries — and across yart_hip_temporal_reset until it is set
+ * again; clip == NULL turns it off. A new handle has no clip, and without one every call runs the code and produces the bits it
+ * did before there was a clip. With a clip the kernel reads the neighbours' d_rgba, so a _device call whose d_out_rgba is d_rgba
+ * first copies the frame, on the call's stream, into a staging buffer the handle owns (16 bytes per pixel, allocated on first need).
+ * YART_E_INVALID, with a message and the previous setting kept: a NULL temporal; a struct_size smaller than YartTemporalClip; a
+ * radius outside 1 .. 3; a gamma that is not finite or is negative. */
+#define YART_TEMPORAL_DEFAULT_CLIP_RADIUS 1u
+#define YART_TEMPORAL_DEFAULT_CLIP_GAMMA 0.5f
+typedef struct YartTemporalClip {
+  uint32_t struct_size;        /* sizeof(YartTemporalClip) */
+  uint32_t radius;             /* 1 .. 3: the window is (2 radius + 1)^2 */
+  float gamma;                 /* finite, >= 0 */
+} YartTemporalClip;
+int yart_hip_temporal_set_clip(YartTemporal* temporal, const YartTemporalClip* clip);
 /* One frame. DEVICE pointers on `stream` (hipStream_t, may be NULL); returns after completion on that stream. d_rgba: width * height
  * * 4 floats; d_variance: width * height; d_aovs: position, normal, depth, coverage and ids are required (and albedo with
  * YART_TEMPORAL_DEMODULATE), as yart_hip_render_moments_device fills them; buffers of other mask bits are not touched.

@@ -233,6 +233,11 @@ inline YartTemporalMomentParams temporalMomentDefaults(bool demodulate = false) 
   p.flags = demodulate ? YART_TEMPORAL_DEMODULATE : 0u;
   return p;
 }
+inline YartTemporalClip temporalClipDefaults() {
+  YartTemporalClip c{};
+  c.struct_size = uint32_t(sizeof(c)); c.radius = YART_TEMPORAL_DEFAULT_CLIP_RADIUS; c.gamma = YART_TEMPORAL_DEFAULT_CLIP_GAMMA;
+  return c;
+}
 struct TemporalFeatures {                   // the frame's feature buffers: 3 / 3 / 1 / 1 / 4 (/ 3) values per pixel
   std::vector<float> position, normal, depth, coverage;
   std::vector<int32_t> ids;
@@ -266,6 +271,10 @@ class Temporal {
     m.struct_size = uint32_t(sizeof(m)); m.records = records;
     check(yart_hip_temporal_set_pixel_motion(m_handle, &m));
   }
+  // the clip of the history to the frame's neighbourhood (yart_hip_temporal_set_clip): it stays set, across reset too, until it is
+  // set again; null: off
+  void setClip(const YartTemporalClip* clip) { check(yart_hip_temporal_set_clip(m_handle, clip)); }
+  void setClip(const YartTemporalClip& clip) { setClip(&clip); }
   // one frame, host buffers: the accumulated frame, its variance and the history length per pixel
   TemporalFrame accumulate(const YartCameraDesc& camera, const std::vector<float>& rgba, const std::vector<float>& variance,
                            const TemporalFeatures& f, const YartTemporalParams& params) {

@@ -29,8 +29,8 @@ from .denoise import (DEFAULT_ITERATIONS, DEFAULT_SIGMA_COLOR, DEFAULT_SIGMA_DEP
 from .denoise import (DEFAULT_VAR_ITERATIONS, DEFAULT_VAR_SIGMA_DEPTH, DEFAULT_VAR_SIGMA_LUMA, DEFAULT_VAR_SIGMA_NORMAL,
                       atrous_var_reference)  # noqa: F401 (the NumPy statement of denoise_var / denoise_var_into)
 from .moments import moments_reference  # noqa: F401 (the NumPy statement of render_moments / probe_moments)
-from .temporal import (DEFAULT_ALPHA_MIN, DEFAULT_MAX_HISTORY, DEFAULT_MIN_MOMENT_HISTORY, DEFAULT_NORMAL_COS_MIN,
-                       DEFAULT_PLANE_TOLERANCE, MOTION_WORDS, node_motion, temporal_moments_reference,
+from .temporal import (DEFAULT_ALPHA_MIN, DEFAULT_CLIP_GAMMA, DEFAULT_CLIP_RADIUS, DEFAULT_MAX_HISTORY, DEFAULT_MIN_MOMENT_HISTORY, DEFAULT_NORMAL_COS_MIN,
+                       DEFAULT_PLANE_TOLERANCE, MOTION_WORDS, clip_of, node_motion, temporal_moments_reference,
                        temporal_reference)  # noqa: F401 (the NumPy statement of TemporalAccumulator.accumulate / accumulate_into)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -284,6 +284,11 @@ class TemporalPixelMotion(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("records", C.c_void_p)]
 
 
+class TemporalClip(C.Structure):
+    """YartTemporalClip (include/yart_hip.h): the clip of the history to the frame's neighbourhood, a setting of the handle."""
+    _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_uint32), ("gamma", C.c_float)]
+
+
 PIXEL_MOTION_AOVS = ("position", "normal", "coverage", "ids")      # what yart_hip_scene_pixel_motion_* reads
 FLAG_TEMPORAL_DEMODULATE = 1
 TEMPORAL_AOVS = ("position", "normal", "depth", "coverage", "ids")     # + "albedo" when demodulating
@@ -364,7 +369,8 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_scene_update_meshes", "yart_hip_probe_mesh",
            "yart_hip_scene_keep_previous", "yart_hip_scene_pixel_motion_device", "yart_hip_scene_pixel_motion_host",
            "yart_hip_temporal_set_pixel_motion",
-           "yart_hip_probe_rays"]
+           "yart_hip_probe_rays",
+           "yart_hip_temporal_set_clip"]
 
 LIB_COUNT_PATH = os.path.join(_HERE, "libyart_hip_count.so")   # instrumented twin (exact test counters)
 _libs = {}
@@ -462,6 +468,7 @@ def lib(instrumented: bool = False):
         L.yart_hip_scene_pixel_motion_device.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.yart_hip_scene_pixel_motion_host.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.c_uint32, C.c_uint32, C.c_void_p]
         L.yart_hip_temporal_set_pixel_motion.argtypes = [C.c_void_p, C.POINTER(TemporalPixelMotion)]
+        L.yart_hip_temporal_set_clip.argtypes = [C.c_void_p, C.POINTER(TemporalClip)]
         L.yart_hip_bvh_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.yart_hip_bvh_copy.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         _libs[path] = L
@@ -1376,11 +1383,13 @@ class TemporalAccumulator:
     ``moments=True``: the moments form (yart_hip_temporal_accumulate_moments_*; 128 bytes per pixel): the returned variance is
     estimated from the accumulated luminance moments, and from the 7 x 7 neighbourhood where the history is shorter than
     ``min_moment_history`` — the form for low sample counts, where the rendered variance is 0 or nearly so.
-    yart_amd.temporal.temporal_moments_reference states it. A handle is in one form between resets."""
+    yart_amd.temporal.temporal_moments_reference states it. A handle is in one form between resets.
+    ``clip``: the clip of the history to the frame's neighbourhood, against ghosting when the lighting changes
+    (yart_hip_temporal_set_clip): None (off), True (the defaults) or (radius, gamma); see ``set_clip``."""
 
     def __init__(self, width: int, height: int, device: int = 0, alpha_min=DEFAULT_ALPHA_MIN, max_history=DEFAULT_MAX_HISTORY,
                  normal_cos_min=DEFAULT_NORMAL_COS_MIN, plane_tolerance=DEFAULT_PLANE_TOLERANCE, moments=False,
-                 min_moment_history=DEFAULT_MIN_MOMENT_HISTORY):
+                 min_moment_history=DEFAULT_MIN_MOMENT_HISTORY, clip=None):
         self._L = lib()
         self.width, self.height, self.device = int(width), int(height), int(device)
         self.moments = bool(moments)
@@ -1391,6 +1400,9 @@ class TemporalAccumulator:
         h = C.c_void_p()
         _check(self._L.yart_hip_temporal_create(self.width, self.height, self.device, C.byref(h)), self._L)
         self._h = h
+        self.clip = None
+        if clip is not None and clip is not False:
+            self.set_clip(clip)
 
     @property
     def handle(self):
@@ -1408,8 +1420,23 @@ class TemporalAccumulator:
             pass
 
     def reset(self):
-        """Forget the history (and a pending motion): the next frame is a first frame."""
+        """Forget the history (and a pending motion; not the clip): the next frame is a first frame."""
         _check(self._L.yart_hip_temporal_reset(self._h), self._L)
+
+    def set_clip(self, clip):
+        """The clip of every following frame (yart_hip_temporal_set_clip): None turns it off, True sets the defaults
+        (DEFAULT_CLIP_RADIUS, DEFAULT_CLIP_GAMMA), (radius, gamma) sets radius 1 .. 3 and a finite gamma >= 0. The setting stays,
+        across ``reset`` too, until it is set again; a refused one keeps the previous setting. ``self.clip`` is the setting as
+        the references' ``clip=`` takes it."""
+        if clip is None or clip is False:
+            _check(self._L.yart_hip_temporal_set_clip(self._h, None), self._L)
+            self.clip = None
+            return
+        radius, gamma = (DEFAULT_CLIP_RADIUS, DEFAULT_CLIP_GAMMA) if clip is True else clip
+        assert int(radius) == radius and 0 <= int(radius) < 1 << 32, "clip: radius is an unsigned integer"
+        tc = TemporalClip(C.sizeof(TemporalClip), int(radius), float(gamma))
+        _check(self._L.yart_hip_temporal_set_clip(self._h, C.byref(tc)), self._L)
+        self.clip = (int(radius), float(gamma))
 
     def set_motion(self, motion):
         """Per-node motion for the next ``accumulate`` / ``accumulate_into`` (yart_hip_temporal_set_motion), which consumes it:

@@ -214,7 +214,8 @@ int yart_hip_denoise_atrous_var_host(const float* rgba, const float* variance, c
 
 // Temporal accumulation (temporal_kernels.inc: k_tp_accumulate). The arguments are judged before any device is touched; the handle's
 // history — two images of three record planes, 96 bytes per pixel; four planes, 128 bytes, in the moments form — is allocated by
-// the first call that gets that far. A handle is in one form from its first accumulate to the next reset.
+// the first call that gets that far. A handle is in one form from its first accumulate to the next reset. The clip
+// (yart_hip_temporal_set_clip) is a setting that stays; with one, a call whose output aliases its frame stages the frame first.
 }  // extern "C"
 struct YartTemporal {
   uint32_t width = 0, height = 0;
@@ -230,6 +231,10 @@ struct YartTemporal {
   DevBuf<f4> motionDev;
   const float* pixelMotion = nullptr;               // yart_hip_temporal_set_pixel_motion: the caller's pending records, 8 floats per pixel
   const float* pixelMotionTaken = nullptr;          // what the running call consumed (only one of the two motions is ever pending)
+  bool clip = false;                                // yart_hip_temporal_set_clip: the setting; it stays until it is set again
+  uint32_t clipRadius = 0;
+  float clipGamma = 0.0f;
+  DevBuf<f4> staging;                               // with a clip, the frame of a call whose d_out_rgba is d_rgba: 16 bytes per pixel
 };
 namespace {
 struct TpCall { TpConst k; bool demodulate; YartAovBuffers aovs; };
@@ -294,6 +299,13 @@ void temporalTakeMotion(YartTemporal& t) {
   t.pixelMotion = nullptr;
 }
 
+// MOTION / PIXEL as k_tp_accumulate takes them; clip: the CLIP instantiation, which is launched only while a clip is set
+template <bool MOMENTS, bool MOTION, bool PIXEL, class Motion>
+void temporalLaunch(bool clip, dim3 grid, hipStream_t st, const TpArgs& a, const Motion& motion) {
+  if (clip) hipLaunchKernelGGL((k_tp_accumulate<MOMENTS, MOTION, PIXEL, true>), grid, dim3(kBlock), 0, st, a, motion);
+  else hipLaunchKernelGGL((k_tp_accumulate<MOMENTS, MOTION, PIXEL>), grid, dim3(kBlock), 0, st, a, motion);
+}
+
 // device pointers (c.aovs included); the handle's device is current and its mutex held; returns after completion on `st`
 template <bool MOMENTS>
 void temporalRun(YartTemporal& t, TpCall c, const YartCameraDesc& cam, const float* rgba, const float* variance, float* out,
@@ -311,18 +323,26 @@ void temporalRun(YartTemporal& t, TpCall c, const YartCameraDesc& cam, const flo
   a.n = n; a.tilesX = (t.width + 15u) / 16u;
   a.k = c.k;
   if (t.haveHistory) a.cam = tpCamera(makeCamera(t.camera));
+  if (t.clip) {
+    a.clipRadius = t.clipRadius; a.clipGamma = t.clipGamma;
+    if (out == rgba) {                              // the kernel reads neighbours' rgba: a copy, on `st`, before the kernel overwrites it
+      t.staging.ensure(n);
+      HIP_CHECK(hipMemcpyAsync(t.staging.p, rgba, size_t(n) * sizeof(f4), hipMemcpyDeviceToDevice, st));
+      a.rgba = reinterpret_cast<const float*>(t.staging.p);
+    }
+  }
   const dim3 grid(a.tilesX * ((t.height + 15u) / 16u));
   if (t.pixelMotionTaken) {                         // device records, written on `st` or complete before the call
     const TpDevicePixelRecords motion{reinterpret_cast<const f4*>(t.pixelMotionTaken)};
-    hipLaunchKernelGGL((k_tp_accumulate<MOMENTS, true, true>), grid, dim3(kBlock), 0, st, a, motion);
+    temporalLaunch<MOMENTS, true, true>(t.clip, grid, st, a, motion);
   } else if (!t.motionTaken.empty()) {              // on `st`, before the kernel that reads it
     const size_t words = t.motionTaken.size() / 4;
     t.motionDev.ensure(words);
     HIP_CHECK(hipMemcpyAsync(t.motionDev.p, t.motionTaken.data(), words * sizeof(f4), hipMemcpyHostToDevice, st));
     const TpDeviceMotion motion{t.motionDev.p, uint32_t(words / kTpMotionWords)};
-    hipLaunchKernelGGL((k_tp_accumulate<MOMENTS, true>), grid, dim3(kBlock), 0, st, a, motion);
+    temporalLaunch<MOMENTS, true, false>(t.clip, grid, st, a, motion);
   } else {
-    hipLaunchKernelGGL((k_tp_accumulate<MOMENTS, false>), grid, dim3(kBlock), 0, st, a, TpNoMotion{});
+    temporalLaunch<MOMENTS, false, false>(t.clip, grid, st, a, TpNoMotion{});
   }
   HIP_CHECK(hipGetLastError());
   if (MOMENTS) {                                    // pass 2 on the image pass 1 wrote
@@ -355,7 +375,7 @@ int yart_hip_temporal_create(uint32_t width, uint32_t height, int device, YartTe
 
 void yart_hip_temporal_destroy(YartTemporal* temporal) {
   if (!temporal) return;
-  if (temporal->hist.p && temporal->device >= 0) (void)hipSetDevice(temporal->device);
+  if ((temporal->hist.p || temporal->staging.p) && temporal->device >= 0) (void)hipSetDevice(temporal->device);
   delete temporal;
 }
 
@@ -366,6 +386,18 @@ int yart_hip_temporal_reset(YartTemporal* temporal) {
     temporal->haveHistory = false;
     temporal->motion.clear();
     temporal->pixelMotion = nullptr;
+  });
+}
+
+int yart_hip_temporal_set_clip(YartTemporal* temporal, const YartTemporalClip* clip) {
+  return guarded([&] {
+    require(temporal != nullptr, "temporal: handle pointer is null");
+    std::lock_guard<std::mutex> lock(temporal->mu);
+    if (!clip) { temporal->clip = false; return; }  // (a refused clip keeps the previous setting: nothing is written before the checks)
+    require(clip->struct_size >= sizeof(YartTemporalClip), "temporal: struct_size is smaller than YartTemporalClip");
+    require(clip->radius >= 1u && clip->radius <= kTpClipMaxRadius, "temporal: clip: radius is outside 1 .. 3");
+    require(std::isfinite(clip->gamma) && clip->gamma >= 0.0f, "temporal: clip: gamma is not finite or is negative");
+    temporal->clip = true; temporal->clipRadius = clip->radius; temporal->clipGamma = clip->gamma;
   });
 }
 

@@ -3,7 +3,7 @@
 //
 // The definition is the comment above yart_hip_temporal_accumulate_device in include/yart_hip.h; this file states it operation by
 // operation: every operation an individually rounded binary32 operation in the order written (the build has no FMA contraction).
-// Only + - * /, floorf, comparisons and integer min / max: no libm.
+// Only + - * /, floorf, sqrtf (correctly rounded; the clip alone), comparisons and integer min / max: no other libm.
 //
 // Per pixel the handle keeps three 16-byte records in each of two history images (96 bytes; the pass reads the neighbours of one
 // image while it writes the other), each record kind in a plane of its own so that neighbouring lanes load neighbouring words:
@@ -122,12 +122,78 @@ YART_HD TpMoved tpMoved(const Motion& motion, const TpIn& in) {
   return TpMoved{in.P, in.n, true};
 }
 
+// The clip of the history to the frame's neighbourhood (yart_hip_temporal_set_clip; CLIP in the header's definition). A Frame
+// decides how a neighbour of the pixel is fetched, and like a per-pixel Motion it is made for ONE pixel: frame.texel(dx, dy) is
+// the texel of the pixel (x + dx, y + dy) — {c.r, c.g, c.b, counts}, c = rgb / d the neighbour's demodulated colour and counts
+// (u32 bits) 1 when the neighbour counts, 0 when it does not or lies outside the image —; frame.radius() and frame.gamma() are
+// the handle's setting. tpTexel forms a texel from a pixel's frame and albedo: the kernel forms each pixel's once per tile
+// (temporal_kernels.inc), the host statement on every fetch; the operations, and so the bits, are the same.
+struct TpNoFrame {                               // no clip is set: compiles to the code without one
+  static constexpr bool kNone = true;
+  YART_HD uint32_t radius() const { return 0u; }
+  YART_HD float gamma() const { return 0.0f; }
+  YART_HD f4 texel(int, int) const { return dnF4(0.0f, 0.0f, 0.0f, 0.0f); }
+};
+constexpr uint32_t kTpClipMaxRadius = 3;
+YART_HD f4 tpTexel(bool demodulate, float r, float g, float b, f3 alb) {
+  const f3 d = tpDivisor(demodulate, alb);
+  const float cr = r / d.x, cg = g / d.y, cb = b / d.z;
+  bool counts = dnFinite(cr) && dnFinite(cg) && dnFinite(cb);
+  if (demodulate) counts = counts && tpFinite3(alb);
+  return dnF4(cr, cg, cb, __builtin_bit_cast(float, counts ? 1u : 0u));
+}
+// value clipped to mu +- gamma * sd of the sums s1, s2 over kf neighbours; applied: mu, e2 and sd are finite (else value is returned)
+YART_HD float tpClipTo(float value, float s1, float s2, float kf, float gamma, bool& applied) {
+  const float mu = s1 / kf, e2 = s2 / kf;
+  float var = e2 - mu * mu;
+  var = var > 0.0f ? var : 0.0f;
+  const float sd = sqrtf(var);
+  const float lo = mu - gamma * sd, hi = mu + gamma * sd;
+  applied = dnFinite(mu) && dnFinite(e2) && dnFinite(sd);
+  if (!applied) return value;
+  return value < lo ? lo : (value > hi ? hi : value);
+}
+// h (and h1, h2 with MOMENTS) of a pixel with a counting tap set, clipped
+template <bool MOMENTS, class Frame>
+YART_HD void tpClipHistory(const Frame& frame, float& hr, float& hg, float& hb, float& h1, float& h2) {
+  const int r = int(frame.radius());
+  const float gamma = frame.gamma();
+  float s1r = 0.0f, s1g = 0.0f, s1b = 0.0f, s2r = 0.0f, s2g = 0.0f, s2b = 0.0f, sy1 = 0.0f, sy2 = 0.0f;
+  uint32_t cnt = 0u;
+  for (int dy = -r; dy <= r; dy++)
+    for (int dx = -r; dx <= r; dx++) {
+      const f4 t = frame.texel(dx, dy);
+      if (dnBits(t.w) == 0u) continue;
+      s1r = s1r + t.x; s1g = s1g + t.y; s1b = s1b + t.z;
+      s2r = s2r + t.x * t.x; s2g = s2g + t.y * t.y; s2b = s2b + t.z * t.z;
+      if constexpr (MOMENTS) {
+        const float yq = dnLuma(t.x, t.y, t.z);
+        sy1 = sy1 + yq; sy2 = sy2 + yq * yq;
+      }
+      cnt++;
+    }
+  if (cnt < 2u) return;
+  const float kf = float(cnt);
+  bool applied;
+  hr = tpClipTo(hr, s1r, s2r, kf, gamma, applied);
+  hg = tpClipTo(hg, s1g, s2g, kf, gamma, applied);
+  hb = tpClipTo(hb, s1b, s2b, kf, gamma, applied);
+  if constexpr (MOMENTS) {
+    const float to = tpClipTo(h1, sy1, sy2, kf, gamma, applied);
+    if (applied && to != h1) {                   // the history's luminance distribution is translated: h2 - h1^2 is kept
+      h2 = h2 + (to * to - h1 * h1);
+      h1 = to;
+    }
+  }
+}
+
 // One pixel. Hist decides how a 16-byte record of the previous history image is fetched: hist.rec0(q) / rec1(q) / rec2(q) (and
 // rec3(q) with MOMENTS), q = y * width + x. demodulate: the call demodulates, and alb is the pixel's albedo (by value: no array
 // for the kernel to keep). MOMENTS: the moments form — pass 1 of it; a short pixel's o.variance / rec0.w are provisional.
-template <bool MOMENTS, class Hist, class Motion>
-YART_HD TpOut tpAccumulatePixel(const Hist& hist, const Motion& motion, const TpConst& k, const TpCamera& cam, const TpIn& in,
-                                bool demodulate, f3 alb) {
+// Frame: TpNoFrame, or the pixel's neighbourhood in the frame when a clip is set.
+template <bool MOMENTS, class Hist, class Motion, class Frame>
+YART_HD TpOut tpAccumulatePixel(const Hist& hist, const Motion& motion, const Frame& frame, const TpConst& k, const TpCamera& cam,
+                                const TpIn& in, bool demodulate, f3 alb) {
   TpOut o;
   const f3 d = tpDivisor(demodulate, alb);
   const float cr = in.rgba.x / d.x, cg = in.rgba.y / d.y, cb = in.rgba.z / d.z;
@@ -193,7 +259,13 @@ YART_HD TpOut tpAccumulatePixel(const Hist& hist, const Motion& motion, const Tp
   const float y = MOMENTS ? dnLuma(cr, cg, cb) : 0.0f;
   float m1 = y, m2 = y * y, w2 = 1.0f;
   if (any) {
-    const float hr = accR / wsum, hg = accG / wsum, hb = accB / wsum, hv = accV / wsum;
+    float hr = accR / wsum, hg = accG / wsum, hb = accB / wsum;
+    const float hv = accV / wsum;
+    float h1 = 0.0f, h2 = 0.0f;
+    if constexpr (!Frame::kNone) {             // the clip: after h (and h1, h2) is formed, before the blend
+      if (MOMENTS) { h1 = acc1 / wsum; h2 = acc2 / wsum; }
+      tpClipHistory<MOMENTS>(frame, hr, hg, hb, h1, h2);
+    }
     N = minLen >= k.maxHistory ? k.maxHistory : minLen + 1u;
     const float inv = 1.0f / float(N);
     const float a = inv > k.alphaMin ? inv : k.alphaMin;
@@ -201,7 +273,8 @@ YART_HD TpOut tpAccumulatePixel(const Hist& hist, const Motion& motion, const Tp
     outR = hr + a * (cr - hr); outG = hg + a * (cg - hg); outB = hb + a * (cb - hb);
     outV = (a * a) * v + (b * b) * hv;
     if (MOMENTS) {
-      const float h1 = acc1 / wsum, h2 = acc2 / wsum, hw2 = accW2 / wsum;
+      if constexpr (Frame::kNone) { h1 = acc1 / wsum; h2 = acc2 / wsum; }
+      const float hw2 = accW2 / wsum;
       m1 = h1 + a * (y - h1);
       m2 = h2 + a * (y * y - h2);
       w2 = (a * a) * 1.0f + (b * b) * hw2;
@@ -222,15 +295,21 @@ YART_HD TpOut tpAccumulatePixel(const Hist& hist, const Motion& motion, const Tp
   return o;
 }
 
+// without a clip, as the callers from before there was one name it
+template <bool MOMENTS, class Hist, class Motion>
+YART_HD TpOut tpAccumulatePixel(const Hist& hist, const Motion& motion, const TpConst& k, const TpCamera& cam, const TpIn& in,
+                                bool demodulate, f3 alb) {
+  return tpAccumulatePixel<MOMENTS, Hist, Motion, TpNoFrame>(hist, motion, TpNoFrame{}, k, cam, in, demodulate, alb);
+}
 // without a motion, as the callers from before there was one name it
 template <bool MOMENTS, class Hist>
 YART_HD TpOut tpAccumulatePixel(const Hist& hist, const TpConst& k, const TpCamera& cam, const TpIn& in, bool demodulate, f3 alb) {
-  return tpAccumulatePixel<MOMENTS, Hist, TpNoMotion>(hist, TpNoMotion{}, k, cam, in, demodulate, alb);
+  return tpAccumulatePixel<MOMENTS, Hist, TpNoMotion, TpNoFrame>(hist, TpNoMotion{}, TpNoFrame{}, k, cam, in, demodulate, alb);
 }
 // the plain form, as its callers have always named it
 template <class Hist>
 YART_HD TpOut tpAccumulatePixel(const Hist& hist, const TpConst& k, const TpCamera& cam, const TpIn& in, bool demodulate, f3 alb) {
-  return tpAccumulatePixel<false, Hist, TpNoMotion>(hist, TpNoMotion{}, k, cam, in, demodulate, alb);
+  return tpAccumulatePixel<false, Hist, TpNoMotion, TpNoFrame>(hist, TpNoMotion{}, TpNoFrame{}, k, cam, in, demodulate, alb);
 }
 
 // Pass 2 of the moments form, one pixel (x, y) of the image pass 1 just wrote (hist: rec1 / rec2 / rec3 of that image); depth is

@@ -27,8 +27,20 @@
 //                     rec3 only for a tap that counts; a tile's taps fall into 22 x 22 pixels, 1.9 times the tile, the regime
 //                     of k_dn_atrous<·, 0>: no LDS tile — and writes its own rec0.w and out_variance, nothing a neighbour reads.
 //
+//   k_tp_accumulate<·, ·, ·, true>   with a clip set on the handle (yart_hip_temporal_set_clip): the workgroup first forms the texel
+//                     {c.rgb, counts} of every pixel of its tile and a halo of `radius` around it — at most 22 x 22 — ONCE, into
+//                     LDS: all 256 lanes take part, those outside the image included, before any returns; image edges are bounds
+//                     checked and a texel outside the image does not count. After the barrier a lane with a counting tap set sums
+//                     its (2 radius + 1)^2 window from LDS in the defined order, one 16-byte LDS read per neighbour, where it
+//                     would otherwise issue 3 IEEE divides and load 28 bytes per neighbour. Chosen over a pre-pass that writes
+//                     mu and sd per pixel, which was not built: a second launch and 24 - 32 bytes per pixel written and read
+//                     back, where the tile adds no memory traffic beyond the halo (profiles/temporal_clip.txt has the times).
+//                     Launched only while a clip is set: the <·, ·, ·, false> kernels are the code from before there was one
+//                     (profiles/temporal_clip_resources.txt).
+//
 // History: two images of three (the moments form: four) planes of 16-byte records (temporal.hpp), 96 (128) bytes per pixel, owned
-// by the YartTemporal handle. The kernels use neither LDS nor scratch memory; none of the existing kernels changes.
+// by the YartTemporal handle. The CLIP kernels use 11 KB of LDS (below); no other kernel here uses LDS, and none uses scratch
+// memory; none of the existing kernels changes.
 
 struct TpDeviceHist {
   const f4 *r0, *r1, *r2, *r3;                     // r3: the moments form only
@@ -57,6 +69,8 @@ struct TpArgs {
   uint32_t n, tilesX;
   TpConst k;
   TpCamera cam;
+  uint32_t clipRadius;                             // the CLIP kernels only: the handle's setting
+  float clipGamma;
 };
 // per-pixel records (yart_hip_temporal_set_pixel_motion): the launch's argument, and what a lane makes of it for its pixel
 struct TpDevicePixelMotion {
@@ -76,11 +90,55 @@ __device__ __forceinline__ auto tpMotionOf(const TpMotionArg<MOTION, PIXEL>& mot
   if constexpr (PIXEL) return TpDevicePixelMotion{motion.rec + p * 2u};
   else return motion;
 }
-template <bool MOMENTS, bool MOTION, bool PIXEL = false>
+// The clip's tile: the texels (temporal.hpp tpTexel) of the workgroup's 16 x 16 pixels and a halo of `radius` around them, at most
+// 22 rows, in LDS. A row is kTpTilePitch = 32 texels = 512 bytes, two bank rows: the lanes of a wave read 4 rows x 16 consecutive
+// texels with one 16-byte LDS read, whose four 16-lane groups each take 8 lanes of one row and 4 + 4 of the next — at a pitch that
+// is a multiple of 16 texels the 16 lanes of a group fall on 16 different 16-byte slots, whatever the window offset (a pitch of 22
+// puts 8 of them on slots another 8 use: measured at 1920 x 1080 and radius 3, + 0.016 ms on a call of 0.164 ms, a third again
+// of the clip's cost; profiles/temporal_clip.txt).
+constexpr uint32_t kTpTilePitch = 32u;
+constexpr uint32_t kTpTileRows = 16u + 2u * kTpClipMaxRadius;
+struct TpDeviceFrame {
+  static constexpr bool kNone = false;
+  const f4* at;                                    // the pixel's own texel in the tile
+  uint32_t r;
+  float g;
+  __device__ __forceinline__ uint32_t radius() const { return r; }
+  __device__ __forceinline__ float gamma() const { return g; }
+  __device__ __forceinline__ f4 texel(int dx, int dy) const { return at[dy * int(kTpTilePitch) + dx]; }
+};
+
+template <bool CLIP>
+__device__ __forceinline__ auto tpFrameOf(const f4* own, const TpArgs& a) {
+  if constexpr (CLIP) return TpDeviceFrame{own, a.clipRadius, a.clipGamma};
+  else return TpNoFrame{};
+}
+
+template <bool MOMENTS, bool MOTION, bool PIXEL = false, bool CLIP = false>
 __global__ void __launch_bounds__(kBlock) k_tp_accumulate(TpArgs a, TpMotionArg<MOTION, PIXEL> motion) {
   static_assert(MOTION || !PIXEL, "per-pixel records are a motion");
   const uint32_t ty = blockIdx.x / a.tilesX, tx = blockIdx.x - ty * a.tilesX;
   const uint32_t x = tx * 16u + (threadIdx.x % 16u), y = ty * 16u + (threadIdx.x / 16u);
+  [[maybe_unused]] const f4* own = nullptr;
+  if constexpr (CLIP) {                            // every lane of the workgroup, those outside the image included, before any returns
+    __shared__ f4 tile[kTpTileRows * kTpTilePitch];
+    const int r = int(a.clipRadius), side = 16 + 2 * r;
+    const int x0 = int(tx * 16u) - r, y0 = int(ty * 16u) - r;
+    for (int i = int(threadIdx.x); i < side * side; i += int(kBlock)) {
+      const int ly = i / side, lx = i - ly * side;
+      const int qx = x0 + lx, qy = y0 + ly;
+      f4 t = dnF4(0.0f, 0.0f, 0.0f, 0.0f);         // outside the image: does not count
+      if (qx >= 0 && qx < int(a.k.width) && qy >= 0 && qy < int(a.k.height)) {
+        const size_t q = size_t(qy) * a.k.width + size_t(qx);
+        f3 alb = mk3(1.0f);
+        if (a.albedo) alb = mk3(a.albedo[q * 3], a.albedo[q * 3 + 1], a.albedo[q * 3 + 2]);
+        t = tpTexel(a.albedo != nullptr, a.rgba[q * 4], a.rgba[q * 4 + 1], a.rgba[q * 4 + 2], alb);
+      }
+      tile[uint32_t(ly) * kTpTilePitch + uint32_t(lx)] = t;
+    }
+    __syncthreads();
+    own = tile + (threadIdx.x / 16u + uint32_t(r)) * kTpTilePitch + (threadIdx.x % 16u + uint32_t(r));
+  }
   if (x >= a.k.width || y >= a.k.height) return;
   const size_t p = size_t(y) * a.k.width + x;
   TpIn in;
@@ -96,7 +154,8 @@ __global__ void __launch_bounds__(kBlock) k_tp_accumulate(TpArgs a, TpMotionArg<
   TpDeviceHist hist;
   hist.r0 = a.histIn; hist.r1 = a.histIn + a.n; hist.r2 = a.histIn + size_t(a.n) * 2;
   hist.r3 = MOMENTS ? a.histIn + size_t(a.n) * 3 : nullptr;
-  const TpOut o = tpAccumulatePixel<MOMENTS>(hist, tpMotionOf<MOTION, PIXEL>(motion, p), a.k, a.cam, in, a.albedo != nullptr, alb);
+  const TpOut o = tpAccumulatePixel<MOMENTS>(hist, tpMotionOf<MOTION, PIXEL>(motion, p), tpFrameOf<CLIP>(own, a), a.k, a.cam, in,
+                                             a.albedo != nullptr, alb);
   dnSt(a.histOut + p, o.rec0);
   dnSt(a.histOut + a.n + p, o.rec1);
   dnSt(a.histOut + size_t(a.n) * 2 + p, o.rec2);

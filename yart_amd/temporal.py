@@ -15,6 +15,10 @@ Both take ``motion``: the per-node motion records of ``yart_hip_temporal_set_mot
 previous frame — which :func:`node_motion` builds from the node lists of the two frames' scenes; and ``pixel_motion``: the
 per-pixel records of ``yart_hip_temporal_set_pixel_motion`` — where each pixel's surface point was, and what its normal was, in
 the previous frame —, which ``yart_amd.scene_motion.scene_motion_reference`` states: the motion of deforming meshes.
+
+And ``clip``: the setting of ``yart_hip_temporal_set_clip`` — the fetched history is clipped to the statistics of the frame's
+demodulated colour over a small window before the blend (:func:`_clip_history`), against the ghosting a change of the lighting
+leaves in a history whose taps are all geometrically valid.
 """
 from __future__ import annotations
 
@@ -38,6 +42,10 @@ MOTION_MAX_NODES = 1 << 20
 # include/yart_hip.h: YartTemporalPixelMotion — floats per record and the word that holds kind
 PIXEL_MOTION_WORDS = 8
 PIXEL_MOTION_KIND_WORD = 3
+# include/yart_hip.h: YART_TEMPORAL_DEFAULT_CLIP_* (chosen by profiles/temporal_clip_sweep.txt) and the limits of YartTemporalClip
+DEFAULT_CLIP_RADIUS = 1
+DEFAULT_CLIP_GAMMA = 0.5
+CLIP_MAX_RADIUS = 3
 
 _F = np.float32
 _FLT_MAX = np.float32(3.4028235e38)
@@ -155,6 +163,19 @@ def node_motion(nodes_prev, nodes_cur):
     return rec
 
 
+def clip_of(clip):
+    """``clip`` as ``yart_hip_temporal_set_clip`` takes it: None (off), or (radius, gamma) checked as the entry checks them;
+    True: the defaults."""
+    if clip is None or clip is False:
+        return None
+    if clip is True:
+        return DEFAULT_CLIP_RADIUS, DEFAULT_CLIP_GAMMA
+    radius, gamma = clip
+    assert int(radius) == radius and 1 <= int(radius) <= CLIP_MAX_RADIUS, "clip: radius is outside 1 .. 3"
+    assert np.isfinite(_F(gamma)) and _F(gamma) >= 0, "clip: gamma is not finite or is negative"
+    return int(radius), float(gamma)
+
+
 class TemporalHistory:
     """The state of a ``YartTemporal`` handle: the history records of the last accumulated frame — ``colour`` (H, W, 3),
     ``variance`` (H, W), ``position`` (H, W, 3), ``length`` (H, W) uint32, ``normal`` (H, W, 3), ``node`` (H, W) uint32 — and
@@ -173,7 +194,7 @@ class TemporalHistory:
 
 def temporal_reference(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo=None,
                        alpha_min=DEFAULT_ALPHA_MIN, max_history=DEFAULT_MAX_HISTORY, normal_cos_min=DEFAULT_NORMAL_COS_MIN,
-                       plane_tolerance=DEFAULT_PLANE_TOLERANCE, demodulate=None, motion=None, pixel_motion=None):
+                       plane_tolerance=DEFAULT_PLANE_TOLERANCE, demodulate=None, motion=None, pixel_motion=None, clip=None):
     """One frame: ``history`` (a :class:`TemporalHistory`, updated in place), ``cam`` the frame's camera (see
     :func:`camera_fields`), ``rgba`` (H, W, 4), ``variance`` (H, W), ``position`` / ``normal`` (H, W, 3), ``depth`` / ``coverage``
     (H, W), ``ids`` (H, W, 4) int32, ``albedo`` (H, W, 3) or None. ``demodulate``: None = whenever an albedo buffer is given.
@@ -183,26 +204,75 @@ def temporal_reference(history, cam, rgba, variance, position, normal, depth, co
     ``pixel_motion`` (not together with ``motion``): None, or the (H, W, 8) float32 per-pixel records of
     ``yart_hip_temporal_set_pixel_motion`` (``yart_amd.scene_motion.scene_motion_reference``): a pixel whose record's kind (the
     bits of word 3) is 1 takes P' from words 0 .. 2 and n' from words 4 .. 6; every other pixel is untouched by it.
+    ``clip``: None, True (the defaults) or (radius, gamma), the setting of ``yart_hip_temporal_set_clip``: the fetched history is
+    clipped to mean +- gamma * standard deviation of the frame's demodulated colour over the (2 radius + 1)^2 window.
     Returns (accumulated frame (H, W, 4) float32, its variance (H, W) float32, history length (H, W) uint32)."""
     return _accumulate(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo, alpha_min, max_history,
-                       normal_cos_min, plane_tolerance, demodulate, None, motion, pixel_motion)
+                       normal_cos_min, plane_tolerance, demodulate, None, motion, pixel_motion, clip)
 
 
 def temporal_moments_reference(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo=None,
                                alpha_min=DEFAULT_ALPHA_MIN, max_history=DEFAULT_MAX_HISTORY,
                                normal_cos_min=DEFAULT_NORMAL_COS_MIN, plane_tolerance=DEFAULT_PLANE_TOLERANCE,
-                               min_moment_history=DEFAULT_MIN_MOMENT_HISTORY, demodulate=None, motion=None, pixel_motion=None):
+                               min_moment_history=DEFAULT_MIN_MOMENT_HISTORY, demodulate=None, motion=None, pixel_motion=None,
+                               clip=None):
     """One frame of the moments form; arguments and results as :func:`temporal_reference`, and ``min_moment_history`` (>= 2).
     The history additionally carries ``moments``; a history is in one form from its first frame to the next ``reset``."""
     assert int(min_moment_history) >= 2
     return _accumulate(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo, alpha_min, max_history,
-                       normal_cos_min, plane_tolerance, demodulate, int(min_moment_history), motion, pixel_motion)
+                       normal_cos_min, plane_tolerance, demodulate, int(min_moment_history), motion, pixel_motion, clip)
+
+
+def _clip_history(clip, c, alb, any_tap, hc, hm, moments):
+    """The clip of the definition: the history colour ``hc`` (and h1, h2 of ``hm`` in the moments form) of the pixels with a
+    counting tap set, clipped to the statistics of the frame's demodulated colour ``c`` over the window -> (hc, hm)."""
+    radius, gamma = clip[0], _F(clip[1])
+    h, w = c.shape[:2]
+    counting = np.isfinite(c).all(-1)
+    if alb is not None:
+        counting &= np.isfinite(alb).all(-1)
+    y = _luma(c)
+    s1, s2 = np.zeros((h, w, 3), _F), np.zeros((h, w, 3), _F)
+    sy1, sy2 = np.zeros((h, w), _F), np.zeros((h, w), _F)
+    cnt = np.zeros((h, w), np.uint32)
+    ys, xs = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    for dy in range(-radius, radius + 1):
+        for dx in range(-radius, radius + 1):
+            qy, qx = ys + dy, xs + dx
+            cy, cx = np.clip(qy, 0, h - 1), np.clip(qx, 0, w - 1)
+            counts = (qx >= 0) & (qx < w) & (qy >= 0) & (qy < h) & counting[cy, cx]
+            cq, yq = c[cy, cx], y[cy, cx]
+            s1 = np.where(counts[..., None], s1 + cq, s1).astype(_F)
+            s2 = np.where(counts[..., None], s2 + cq * cq, s2).astype(_F)
+            sy1 = np.where(counts, sy1 + yq, sy1).astype(_F)
+            sy2 = np.where(counts, sy2 + yq * yq, sy2).astype(_F)
+            cnt = np.where(counts, cnt + np.uint32(1), cnt).astype(np.uint32)
+    kf = cnt.astype(_F)
+    applies = any_tap & (cnt >= 2)
+
+    def clipped(value, t1, t2, k, applies):
+        mu, e2 = t1 / k, t2 / k
+        var = e2 - mu * mu
+        var = np.where(var > _F(0.0), var, _F(0.0)).astype(_F)
+        sd = np.sqrt(var)
+        lo, hi = mu - gamma * sd, mu + gamma * sd
+        to = np.where(value < lo, lo, np.where(value > hi, hi, value)).astype(_F)
+        applies = applies & np.isfinite(mu) & np.isfinite(e2) & np.isfinite(sd)
+        return np.where(applies, to, value).astype(_F), applies
+    hc, _ = clipped(hc, s1, s2, kf[..., None], applies[..., None])
+    if moments:
+        h1, applied = clipped(hm[..., 0], sy1, sy2, kf, applies)
+        moved = applied & (h1 != hm[..., 0])
+        h2 = np.where(moved, hm[..., 1] + (h1 * h1 - hm[..., 0] * hm[..., 0]), hm[..., 1]).astype(_F)
+        hm = np.stack([h1, h2, hm[..., 2]], -1).astype(_F)
+    return hc, hm
 
 
 def _accumulate(history, cam, rgba, variance, position, normal, depth, coverage, ids, albedo, alpha_min, max_history,
-                normal_cos_min, plane_tolerance, demodulate, min_moment_history, motion=None, pixel_motion=None):
+                normal_cos_min, plane_tolerance, demodulate, min_moment_history, motion=None, pixel_motion=None, clip=None):
     """Pass 1 of both forms (``min_moment_history`` None: the plain form), then pass 2 of the moments form."""
     moments = min_moment_history is not None
+    clip = clip_of(clip)
     form = "moments" if moments else "plain"
     assert history.camera is None or history.form == form, "the history is in the other form: reset it first"
     if demodulate is None:
@@ -300,6 +370,9 @@ def _accumulate(history, cam, rgba, variance, position, normal, depth, coverage,
         # -- blend ------------------------------------------------------------------------------------------------------------
         hc = acc / wsum[..., None]
         hv = acc_v / wsum
+        hm = acc_m / wsum[..., None]
+        if clip is not None:
+            hc, hm = _clip_history(clip, c, alb, any_tap, hc, hm, moments)
         N = np.where(min_len >= max_history, max_history, min_len + np.uint32(1)).astype(np.uint32)
         N = np.where(any_tap, N, np.uint32(1)).astype(np.uint32)
         inv = _F(1.0) / N.astype(_F)
@@ -311,7 +384,6 @@ def _accumulate(history, cam, rgba, variance, position, normal, depth, coverage,
             # -- the luminance moments, the sum of squared frame weights, and the temporal estimate ---------------------------
             y = _luma(c)
             yy = y * y
-            hm = acc_m / wsum[..., None]
             m1 = np.where(any_tap, hm[..., 0] + a * (y - hm[..., 0]), y).astype(_F)
             m2 = np.where(any_tap, hm[..., 1] + a * (yy - hm[..., 1]), yy).astype(_F)
             w2 = np.where(any_tap, (a * a) * _F(1.0) + (b * b) * hm[..., 2], _F(1.0)).astype(_F)
