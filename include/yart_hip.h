@@ -250,8 +250,9 @@ void yart_hip_scene_destroy(YartScene* scene);
  * Stream order: the copies and kernels of the update are enqueued on `stream`; the caller orders them against renders of this
  * scene that are still running on OTHER streams (yart_hip_render*_device). A scene's first update (and the first refit after a
  * YART_UPDATE_REBUILD_TOP) also uploads its topology tables with blocking copies on the null stream.
- * Out of scope — re-create the scene: a changed topology (nodes added, removed, re-parented or re-meshed), materials / emission,
- * and the replicas of a YartMulti. Deforming meshes: yart_hip_scene_update_meshes below. */
+ * Out of scope — re-create the scene: a changed topology (nodes added, removed, re-parented or re-meshed) and the replicas of a
+ * YartMulti. Deforming meshes: yart_hip_scene_update_meshes below; materials, light emission and environment images:
+ * yart_hip_scene_update_lighting below. */
 #define YART_UPDATE_REBUILD_TOP 1u   /* rebuild the top-level hierarchy (host, create's own code) instead of refitting its boxes */
 typedef struct YartSceneUpdate {
   uint32_t struct_size;              /* sizeof(YartSceneUpdate) */
@@ -290,7 +291,8 @@ int yart_hip_scene_update(YartScene* scene, const YartSceneUpdate* update, void*
  * A mesh the device build refuses, and every mesh under the environment variable YART_HOST_BVH, is built and derived on the host
  * and uploaded: the same bytes.
  * Not kept current: the default pipeline's lobe-share heuristic stays as at create (every pipeline renders the same frame).
- * Out of scope — re-create the scene: changed faces or vertex counts, uvs, materials, the replicas of a YartMulti.
+ * Out of scope — re-create the scene: changed faces or vertex counts, uvs, a face's material index, the replicas of a YartMulti
+ * (the materials' values, light emission and environment images: yart_hip_scene_update_lighting below).
  * Motion for the temporal accumulator: yart_hip_scene_keep_previous before the frame's updates and yart_hip_scene_pixel_motion_device
  * after its render (below) say per pixel where a deformed — or rigidly moved — surface point was in the previous frame. */
 typedef struct YartMeshUpdate {
@@ -307,6 +309,56 @@ typedef struct YartSceneMeshUpdate {
   uint32_t flags;                    /* YART_UPDATE_REBUILD_TOP */
 } YartSceneMeshUpdate;
 int yart_hip_scene_update_meshes(YartScene* scene, const YartSceneMeshUpdate* update, void* stream, YartSceneUpdateStats* stats /* may be NULL */);
+
+/* New materials, new light emission and new environment images for a scene that is on the device — a lamp that dims, a material
+ * whose colour or roughness is keyed, a sky whose sun moves — without yart_hip_scene_destroy + yart_hip_scene_create: meshes, BVHs,
+ * the scene graph, material textures and their footprint records stay where they are. Afterwards the scene holds, and renders in every
+ * pipeline, the bits of a scene freshly created from the same description. The three update entries combine in any order.
+ * materials (n_materials = 0: untouched; else the scene's material count, every record): every numeric field may change — base,
+ * emission, metallic, roughness, transmission, ior, anisotropic, aniso_rotation, clearcoat, clearcoat_roughness, normal_scale,
+ * volume_color, volume_density. The device records are re-derived on the host by scene creation's arithmetic and uploaded, with the
+ * per-material lobe classes. The six texture slots stay where creation left them, the alpha-test flag stays (it depends on the texels),
+ * the emission flag is re-derived.
+ * lights (n_lights = 0: untouched; else the scene's light count, every record): emission, radius, fwd and inv may change. Re-derived on
+ * the host by the functions creation uses: the area lights' area and power, the power CDF and the total power; a uniform infinite
+ * light's power; an image light's power from its radius and its image's average radiance. The library does not couple a light's
+ * emission to its material's: as at create the caller describes both.
+ * images (n_images = 0: untouched; each texture at most once): new texels for the float RGB map of image lights, of the same size.
+ * They are uploaded into the texture's place, its footprint records are rewritten where the scene has them, and for every image light
+ * that uses the texture the sampling tables — function, conditional CDFs, row integrals, marginal CDF and integral, guide tables,
+ * interleaved records — are rebuilt in place ON THE DEVICE; the image's average radiance (a sequential binary32 sum in row-major
+ * order) is taken on the host meanwhile, and the lights' power follows it.
+ * Locking, `stream`, `stats` and "returns after the work has completed on `stream`" as for yart_hip_scene_update.
+ * YART_E_INVALID, with the scene and the device exactly as they were (everything is checked before the first write): scene or update
+ * NULL; struct_size too small; flags other than 0; all three counts 0; a count that is neither 0 nor the scene's, or its pointer NULL;
+ * a material's tex_* or thin_transmission changed; a change that would make a thin material's transmission positive or zero (the
+ * transparency bit lives in the meshes' leaf records); a light's type, mesh, tri, two_sided or texture changed; a word of a material,
+ * of a light's radius or emission or of a matrix that is not finite; a texture index that is out of range, listed twice, not float RGB
+ * or not used by an image light; width or height not the texture's; pixels NULL; a texel word that is not finite or whose magnitude
+ * exceeds 2^64 (stricter than creation, on purpose: no row sum, marginal sum or average can then overflow, and every CDF is finite
+ * and nondecreasing); stats->struct_size below 8.
+ * Any other failure (YART_E_HIP) leaves the scene unusable, as for the other update entries.
+ * Not kept current: the default pipeline's lobe-share heuristic stays as at create (every pipeline renders the same frame), as for
+ * yart_hip_scene_update_meshes.
+ * Out of scope — re-create the scene: changed texture assignments or texels of material textures, changes that flip a material's
+ * transparency or thin_transmission, lights added or removed, face_light changes, a resized environment image, and the replicas of a
+ * YartMulti. */
+typedef struct YartEnvImageUpdate {
+  uint32_t texture;                  /* index into the scene's textures: a float RGB texture that at least one image light uses */
+  uint32_t width, height;            /* the texture's, as at create */
+  const float* pixels;               /* HOST, 3 floats per texel, row-major, required */
+} YartEnvImageUpdate;
+typedef struct YartSceneLightingUpdate {
+  uint32_t struct_size;              /* sizeof(YartSceneLightingUpdate) */
+  uint32_t n_materials;              /* 0: materials untouched; else the scene's material count */
+  const YartMaterialDesc* materials; /* every record; tex_* and thin_transmission as at create */
+  uint32_t n_lights;                 /* 0: lights untouched; else the scene's light count */
+  const YartLightDesc* lights;       /* every record; type, mesh, tri, two_sided and texture as at create */
+  uint32_t n_images;                 /* 0: environment images untouched */
+  const YartEnvImageUpdate* images;  /* each texture at most once */
+  uint32_t flags;                    /* none defined: must be 0 */
+} YartSceneLightingUpdate;
+int yart_hip_scene_update_lighting(YartScene* scene, const YartSceneLightingUpdate* update, void* stream, YartSceneUpdateStats* stats /* may be NULL */);
 
 /* The scene remembers the frame it holds as its PREVIOUS frame: its node array and its vertex positions are copied into scene-owned
  * arrays — two device-to-device copies on `stream`; the call returns after they have completed. The arrays are allocated by the
@@ -618,6 +670,26 @@ int yart_hip_probe_scene_graph(YartScene* scene, void* nodes_out, float* node_wo
  * a first call with mesh_dev_out alone gives the counts the arrays need. */
 int yart_hip_probe_mesh(YartScene* scene, uint32_t mesh, void* mesh_dev_out, void* nodes_out, void* leaf_out, void* shade_out, float* vpos_out,
                         float* vnormal_out, float* vtangent_out, uint32_t* stack_bound_out);
+/* diagnostic read-back of what yart_hip_scene_update_lighting re-derives, from the device (not from the library's host copy). The
+ * caller sets struct_size; the call fills in every count (elements of the arrays below, as the device holds them: padded to at least
+ * one) and total_power, and copies into every array pointer that is not NULL — a first call with all of them NULL gives the sizes.
+ * materials: MaterialDev records (176 bytes); mat_class: the lobe-class bytes (padded to a multiple of 4); lights: LightDev records
+ * (176 bytes); envs: EnvDev records (48 bytes: w, h, funcOffset, cdfOffset, rowIntOffset, margCdfOffset, margIntegral, surfaceArea,
+ * guideOffset, guideKw, guideKh, pairOffset); env_data / env_guide: the image lights' tables; area_power_cdf; tex_f32: the float
+ * texels; tex_quads: the footprint-record array in bytes (n_tex_quad_bytes = 0 where the scene has none; bytes that belong to no
+ * record are unspecified); textures: TexDev records (32 bytes: offset, width, height, channels, type, isFloat, quadOffset in 16-byte
+ * units or 0xffffffff, quadStride), which say where a texture's texels and records lie. */
+typedef struct YartLightingProbe {
+  uint32_t struct_size;              /* sizeof(YartLightingProbe) */
+  float total_power;
+  uint64_t n_materials, n_mat_class, n_lights, n_envs, n_env_data, n_env_guide, n_area_power_cdf, n_tex_f32, n_tex_quad_bytes, n_textures;
+  void* materials; uint8_t* mat_class; void* lights; void* envs; float* env_data; uint32_t* env_guide; float* area_power_cdf;
+  float* tex_f32; uint8_t* tex_quads; void* textures;
+} YartLightingProbe;
+int yart_hip_probe_lighting(YartScene* scene, YartLightingProbe* probe);
+/* the host part of an image replacement on its own (measurements): the three sequential binary32 sums over n_texels RGB texels in
+ * row-major order, as scene creation and yart_hip_scene_update_lighting take them for an image light's average radiance */
+int yart_hip_probe_texel_sum(const float* pixels, uint64_t n_texels, float* sum3_out);
 /* measurement builds (-DYART_SHADE_REGIONS=1, tools/shade_regions.py) only: wave cycles [0..15], visits [16..31] and
  * active lanes [32..47] per code region of the shade kernel since the last call; YART_E_INVALID in the product build */
 int yart_hip_debug_shade_regions(uint64_t* out48);

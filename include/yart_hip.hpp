@@ -97,6 +97,21 @@ class DeviceScene {
     check(yart_hip_scene_update_meshes(h_, &u, stream, &st));
     return st;
   }
+  // yart_hip_scene_update_lighting: new material values (empty: untouched; else every material of the scene), new light emission /
+  // radius / transforms (empty: untouched; else every light) and new texels for the maps of image lights (each texture at most
+  // once; the size as at create). Returns the update's statistics.
+  YartSceneUpdateStats updateLighting(const std::vector<YartMaterialDesc>& materials, const std::vector<YartLightDesc>& lights,
+                                      const std::vector<YartEnvImageUpdate>& images, void* stream = nullptr) {
+    YartSceneLightingUpdate u{};
+    u.struct_size = uint32_t(sizeof(u));
+    u.n_materials = uint32_t(materials.size()); u.materials = materials.empty() ? nullptr : materials.data();
+    u.n_lights = uint32_t(lights.size()); u.lights = lights.empty() ? nullptr : lights.data();
+    u.n_images = uint32_t(images.size()); u.images = images.empty() ? nullptr : images.data();
+    YartSceneUpdateStats st{};
+    st.struct_size = uint32_t(sizeof(st));
+    check(yart_hip_scene_update_lighting(h_, &u, stream, &st));
+    return st;
+  }
   // yart_hip_scene_keep_previous: the scene remembers the frame it holds as its previous frame; once per frame, before its updates
   void keepPrevious(void* stream = nullptr) { check(yart_hip_scene_keep_previous(h_, stream)); }
   // yart_hip_scene_pixel_motion_host: the per-pixel motion records (8 floats per pixel) between the kept frame and the scene as it

@@ -110,7 +110,46 @@ class SceneMeshUpdate(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_meshes", C.c_uint32), ("meshes", C.POINTER(MeshUpdate)), ("flags", C.c_uint32)]
 
 
+class EnvImageUpdate(C.Structure):
+    _fields_ = [("texture", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("pixels", C.c_void_p)]
+
+
+class SceneLightingUpdate(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_materials", C.c_uint32), ("materials", C.POINTER(MaterialDesc)),
+                ("n_lights", C.c_uint32), ("lights", C.POINTER(LightDesc)), ("n_images", C.c_uint32),
+                ("images", C.POINTER(EnvImageUpdate)), ("flags", C.c_uint32)]
+
+
+LIGHTING_PROBE_ARRAYS = ("materials", "mat_class", "lights", "envs", "env_data", "env_guide", "area_power_cdf", "tex_f32", "tex_quads",
+                         "textures")
+
+
+class LightingProbe(C.Structure):
+    _fields_ = ([("struct_size", C.c_uint32), ("total_power", C.c_float)] +
+                [(n, C.c_uint64) for n in ("n_materials", "n_mat_class", "n_lights", "n_envs", "n_env_data", "n_env_guide",
+                                           "n_area_power_cdf", "n_tex_f32", "n_tex_quad_bytes", "n_textures")] +
+                [(n, C.c_void_p) for n in LIGHTING_PROBE_ARRAYS])
+
+
 UPDATE_REBUILD_TOP = 1
+# the records of DeviceScene.lighting_records(): csrc/scene_types.hpp MaterialDev (flags: 1 thin, 2 alpha-tested, 4 emissive,
+# 8 transparent), LightDev, EnvDev and TexDev (quad_offset in 16-byte units, 0xffffffff: no footprint records of its own)
+MATERIAL_DEV_DTYPE = np.dtype([("base", np.float32, 3), ("transmission", np.float32), ("emission", np.float32, 3), ("metallic", np.float32),
+                               ("ior", np.float32), ("roughness", np.float32), ("anisotropic", np.float32), ("clearcoat", np.float32),
+                               ("clearcoat_roughness", np.float32), ("flags", np.uint32), ("volume_density", np.float32),
+                               ("tex_base", np.int32), ("volume_color", np.float32, 3), ("tex_mr", np.int32),
+                               ("tex_transmission", np.int32), ("tex_normal", np.int32), ("tex_clearcoat", np.int32),
+                               ("tex_emission", np.int32), ("local_rot", np.float32, 9), ("inv_rot", np.float32, 9), ("pad", np.uint32, 2)])
+LIGHT_DEV_DTYPE = np.dtype([("type", np.uint32), ("mesh", np.int32), ("tri", np.uint32), ("two_sided", np.uint32),
+                            ("emission", np.float32, 3), ("area", np.float32), ("power", np.float32), ("radius", np.float32),
+                            ("texture", np.int32), ("env", np.uint32), ("fwd", np.float32, 16), ("inv", np.float32, 16)])
+ENV_DEV_DTYPE = np.dtype([("w", np.uint32), ("h", np.uint32), ("func_offset", np.uint32), ("cdf_offset", np.uint32),
+                          ("row_int_offset", np.uint32), ("marg_cdf_offset", np.uint32), ("marg_integral", np.float32),
+                          ("surface_area", np.float32), ("guide_offset", np.uint32), ("guide_kw", np.uint32), ("guide_kh", np.uint32),
+                          ("pair_offset", np.uint32)])
+TEX_DEV_DTYPE = np.dtype([("offset", np.uint32), ("width", np.uint32), ("height", np.uint32), ("channels", np.uint32), ("type", np.uint32),
+                          ("is_float", np.uint32), ("quad_offset", np.uint32), ("quad_stride", np.uint32)])
+assert (MATERIAL_DEV_DTYPE.itemsize, LIGHT_DEV_DTYPE.itemsize, ENV_DEV_DTYPE.itemsize, TEX_DEV_DTYPE.itemsize) == (176, 176, 48, 32)
 # the records of DeviceScene.mesh_records(): csrc/scene_types.hpp MeshDev, BvhNode (link: index | alpha bit 26 | span << 27),
 # LeafTri (mat_flags: MAT_* of the material; a leaf's first record: | span << 8) and ShadeTri
 MESH_DTYPE = np.dtype([("node_offset", np.uint32), ("leaf_offset", np.uint32), ("tri_offset", np.uint32), ("vert_offset", np.uint32),
@@ -367,6 +406,7 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_temporal_set_motion",
            "yart_hip_scene_update", "yart_hip_probe_scene_graph",
            "yart_hip_scene_update_meshes", "yart_hip_probe_mesh",
+           "yart_hip_scene_update_lighting", "yart_hip_probe_lighting", "yart_hip_probe_texel_sum",
            "yart_hip_scene_keep_previous", "yart_hip_scene_pixel_motion_device", "yart_hip_scene_pixel_motion_host",
            "yart_hip_temporal_set_pixel_motion",
            "yart_hip_probe_rays",
@@ -464,6 +504,9 @@ def lib(instrumented: bool = False):
         L.yart_hip_scene_update_meshes.argtypes = [C.c_void_p, C.POINTER(SceneMeshUpdate), C.c_void_p, C.POINTER(SceneUpdateStats)]
         L.yart_hip_probe_mesh.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.POINTER(C.c_uint32)]
+        L.yart_hip_scene_update_lighting.argtypes = [C.c_void_p, C.POINTER(SceneLightingUpdate), C.c_void_p, C.POINTER(SceneUpdateStats)]
+        L.yart_hip_probe_lighting.argtypes = [C.c_void_p, C.POINTER(LightingProbe)]
+        L.yart_hip_probe_texel_sum.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
         L.yart_hip_scene_keep_previous.argtypes = [C.c_void_p, C.c_void_p]
         L.yart_hip_scene_pixel_motion_device.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.yart_hip_scene_pixel_motion_host.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.c_uint32, C.c_uint32, C.c_void_p]
@@ -696,6 +739,53 @@ class DeviceScene:
         st = SceneUpdateStats(C.sizeof(SceneUpdateStats))
         _check(self._L.yart_hip_scene_update_meshes(self._h, C.byref(up), stream, C.byref(st)), self._L)
         self.last_update = dict(launches=st.launches, ms_total=st.ms_total, ms_device=st.ms_device)
+
+    def update_lighting(self, materials=None, lights=None, images=None, stream=None):
+        """yart_hip_scene_update_lighting: new material values, new light emission / radius / transforms and new environment images
+        for the scene in place. ``materials`` / ``lights``: the material / light lists of a :class:`yscn.Scene` (all of them; texture
+        slots, thin_transmission and the lights' type / mesh / tri / two_sided / texture as at create), None: untouched. ``images``:
+        {texture index: (H, W, 3) float32 array} — new texels, of the same size, for the maps of image lights; their sampling tables
+        are rebuilt on the device. The call's statistics are in ``self.last_update``."""
+        keep = []
+        materials = list(materials) if materials is not None else []
+        md = (MaterialDesc * max(len(materials), 1))()
+        for i, m in enumerate(materials):
+            C.memmove(C.byref(md[i]), m.pack(), C.sizeof(MaterialDesc))
+        lights = list(lights) if lights is not None else []
+        ld = (LightDesc * max(len(lights), 1))()
+        for i, l in enumerate(lights):
+            ld[i] = LightDesc(l.type, l.mesh, l.tri, int(l.two_sided), l.texture, l.radius, _f(l.emission, 3), _f(l.fwd, 16), _f(l.inv, 16))
+        images = dict(images) if images is not None else {}
+        im = (EnvImageUpdate * max(len(images), 1))()
+        for k, (tex, px) in enumerate(images.items()):
+            px = np.ascontiguousarray(px, np.float32)
+            if px.ndim != 3 or px.shape[2] != 3:
+                raise YartError(YART_E_INVALID, f"update_lighting: image {tex}: not an (H, W, 3) array")
+            keep.append(px)
+            im[k] = EnvImageUpdate(int(tex), px.shape[1], px.shape[0], px.ctypes.data_as(C.c_void_p))
+        up = SceneLightingUpdate(C.sizeof(SceneLightingUpdate), len(materials), md if materials else None, len(lights),
+                                 ld if lights else None, len(images), im if images else None, 0)
+        st = SceneUpdateStats(C.sizeof(SceneUpdateStats))
+        _check(self._L.yart_hip_scene_update_lighting(self._h, C.byref(up), stream, C.byref(st)), self._L)
+        self.last_update = dict(launches=st.launches, ms_total=st.ms_total, ms_device=st.ms_device)
+
+    def lighting_records(self):
+        """yart_hip_probe_lighting: what ``update_lighting`` re-derives, read back from the device: dict(materials:
+        MATERIAL_DEV_DTYPE, mat_class: uint8 lobe classes, lights: LIGHT_DEV_DTYPE, envs: ENV_DEV_DTYPE, env_data: float32, env_guide:
+        uint32, area_power_cdf: float32, total_power: float, tex_f32: float32, tex_quads: uint8 (the footprint-record array, empty
+        where the scene has none; bytes outside the records are unspecified), textures: TEX_DEV_DTYPE)."""
+        pr = LightingProbe(C.sizeof(LightingProbe))
+        _check(self._L.yart_hip_probe_lighting(self._h, C.byref(pr)), self._L)
+        shape = dict(materials=(pr.n_materials, MATERIAL_DEV_DTYPE), mat_class=(pr.n_mat_class, np.uint8), lights=(pr.n_lights, LIGHT_DEV_DTYPE),
+                     envs=(pr.n_envs, ENV_DEV_DTYPE), env_data=(pr.n_env_data, np.float32), env_guide=(pr.n_env_guide, np.uint32),
+                     area_power_cdf=(pr.n_area_power_cdf, np.float32), tex_f32=(pr.n_tex_f32, np.float32),
+                     tex_quads=(pr.n_tex_quad_bytes, np.uint8), textures=(pr.n_textures, TEX_DEV_DTYPE))
+        out = {name: np.zeros(int(n), dt) for name, (n, dt) in shape.items()}
+        for name, a in out.items():
+            setattr(pr, name, a.ctypes.data_as(C.c_void_p) if len(a) else None)
+        _check(self._L.yart_hip_probe_lighting(self._h, C.byref(pr)), self._L)
+        out["total_power"] = float(pr.total_power)
+        return out
 
     def keep_previous(self, stream=None):
         """yart_hip_scene_keep_previous: the scene remembers the frame it holds (node transforms and vertex positions) as its

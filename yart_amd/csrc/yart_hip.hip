@@ -24,8 +24,9 @@
 //                multi_device.inc       several GPUs behind one handle, with its pixel pack / unpack / copy kernels
 //                postprocess.inc        tonemap / encode, the a-trous denoiser (denoise_kernels.inc) and temporal accumulation
 //                                       (temporal_kernels.inc): kernels, drivers and entries
-//                scene_update_kernels.inc, mesh_update_kernels.inc, scene_motion_kernels.inc      a scene's next frame in place: new
-//                                       transforms, new vertices, and the per-pixel motion between the two frames
+//                scene_update_kernels.inc, mesh_update_kernels.inc, lighting_update_kernels.inc, scene_motion_kernels.inc      a scene's
+//                                       next frame in place: new transforms, new vertices, new materials / light emission /
+//                                       environment images, and the per-pixel motion between the two frames
 //                probes.inc             the diagnostic kernels k_probe_* and the yart_hip_probe_* entries
 //   units 1-4  wavefront_units.hip under -DYART_TU=1..4: the path kernels, which are templates and are emitted where they are
 //              instantiated — 1 the lean closest-hit kernels k_wf_extend_lean<MODE, NODES>, 2 the lean any-hit kernels
@@ -50,6 +51,7 @@
 #include "estimator.hpp"
 #include "host_scene.hpp"
 #include "mesh_update.hpp"
+#include "lighting_update.hpp"
 #include "integrator.hpp"
 #include "scene_file.hpp"
 #include "gltf_reader.hpp"
@@ -311,6 +313,14 @@ struct MeshUpdateState {
   std::vector<int8_t> meshAlpha;                        // per mesh: a face has an alpha-tested material (-1: not looked at yet)
 };
 
+// What yart_hip_scene_update_lighting keeps per scene (lighting_update_kernels.inc): the material descriptors as the scene was last
+// given them (create's, then an update's: what an update's tex_* / thin_transmission are compared with), and per EnvDev record the
+// sequential texel sum of its map (Lavg's numerator), taken when an update first needs it.
+struct LightingUpdateState {
+  std::vector<YartMaterialDesc> materialDesc;
+  std::vector<LuSum> envSum; std::vector<uint8_t> envSumKnown;
+};
+
 struct YartScene {
   int device = 0;
   HostImage host;
@@ -351,6 +361,7 @@ struct YartScene {
   uint32_t pixW = 0, pixH = 0, pixTile = 0, pixRank = 0, pixWorld = 0;
   SceneUpdateTables su;
   MeshUpdateState meshUp;
+  LightingUpdateState lightUp;
   // yart_hip_scene_keep_previous (scene_motion_kernels.inc): the node and vertex arrays of the previous frame, allocated by the first
   // call; the nodes' composed transforms and the host entry's staging buffer of yart_hip_scene_pixel_motion_*
   DevBuf<NodeDev> nodesPrev; DevBuf<f4> vPosPrev, smChains; DevBuf<float> smStage;
@@ -442,6 +453,7 @@ YartScene* createScene(const YartSceneDesc& desc, int device, uint32_t sceneFlag
   // for the host builder; the two give the same bytes, and every GPU test that compares a frame with the reference's checks it
   if ((sceneFlags & YART_SCENE_HOST_BVH) || std::getenv("YART_HOST_BVH")) s->host = buildHostImage(desc);
   else s->host = buildHostImage(desc, deviceMeshBvh, &dev);
+  if (desc.n_materials) s->lightUp.materialDesc.assign(desc.materials, desc.materials + desc.n_materials);
   hipDeviceProp_t prop;
   HIP_CHECK(hipGetDeviceProperties(&prop, dev));
   s->numCUs = prop.multiProcessorCount;
@@ -1624,5 +1636,6 @@ int yart_hip_bvh_build_host(const float* positions, uint32_t n_verts, const uint
 #include "postprocess.inc"
 #include "scene_update_kernels.inc"
 #include "mesh_update_kernels.inc"
+#include "lighting_update_kernels.inc"
 #include "scene_motion_kernels.inc"
 #include "probes.inc"
