@@ -650,6 +650,22 @@ int yart_hip_probe_hits(YartScene* scene, uint32_t n, const float* rays, float* 
  *   a ray they hand over to the general walk; for an occlusion ray they report words 0, 14..16 (unoccluded rays) and 17 only,
  *   which is all the shadow kernels take from them. */
 int yart_hip_probe_rays(YartScene* scene, const YartRenderParams* params, uint32_t n, const uint32_t* rays, int walk, uint32_t* out);
+/* Diagnostic: the shading code (csrc/bsdf.hpp, csrc/lights.hpp) one call at a time on caller-supplied operands, in the forms
+ * only the device runs. cases: n records of 32 words, out: n records of 32 words; oracle/shaderec.hpp spells both out: word 0
+ * the kind (0 the five GGX table lookups, 1 a texture fetch, 2 a material's alpha / base colour / shading normal /
+ * attenuation, 3 a BSDF's f, pdf and sample, 4 a light's sample, pdf, Le and selection probability, 5 the light sampler's
+ * choice), word 1 the texture / material / light index, word 2 bit 0 `regularized`, words 4..31 the float operands.
+ * form is a bit set: 1 the functions receive the LDS copy of the glossy lobes' GGX tables that the shade kernel builds (the
+ * first LutDev::glassE floats and, behind them, the tables' address for the glass lookups); 2 the material, texture, light,
+ * environment and infinite-light tables are LDS copies where they fit the shade kernel's slots (kShade*Slots); 4 a BSDF case
+ * goes through one matEvaluate and bsdfSampleImplE / bsdfFImplE / bsdfPdfImplE in the local frame, as the wavefront shade
+ * stage calls them, instead of bsdfSample / bsdfF / bsdfPdf. Whether textures are read through 2x2 footprint records is a
+ * property of the scene (YART_TEX_QUADS_MAX_MB at creation).
+ * Everything is checked before a device is touched — YART_E_INVALID for a null pointer, an unknown kind or form bit, an index
+ * at or above the scene's count, an operand that is not finite, a PICK case in a scene without lights or whose u lies outside [0, 1), a TEX case on a texture
+ * that has no footprint records of its own in a scene that uses them, n above 2^20 — so that no case makes a lane read outside
+ * the scene. */
+int yart_hip_probe_shading(YartScene* scene, uint32_t n, const uint32_t* cases, uint32_t form, uint32_t* out);
 /* Diagnostic: the camera ray of n (x, y, sample) triples -> 6 floats each (origin, direction), drawn exactly as bounce 0 of that
  * sample draws it: startPixelSample, the film and the lens draw (core/sampler.hpp), Camera::getRay (core/camera.hpp:138-164) */
 int yart_hip_probe_camera_rays(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, uint32_t n,

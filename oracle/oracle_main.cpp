@@ -3,6 +3,9 @@
 //   yart_oracle hits   <scene.yscn> <params.txt> <rays.bin> <out.bin>   one record per ray through testNode(root) (rayrec.hpp);
 //                      <out.bin>.events gets the ray's event mask (u16, Integrator::RayEvent) and stdout the number of rays
 //                      that met each event, as JSON
+//   yart_oracle shade  <scene.yscn> <params.txt> <cases.bin> <out.bin>   one record per case (shaderec.hpp); <out.bin>.events gets
+//                      the case's event mask (u32, ShadeEvent below), <out.bin>.probs the three lobe thresholds of every BSDF
+//                      case, and stdout the number of cases that met each event, as JSON
 //   yart_oracle render <scene.yscn> <params.txt> <out.f32>    tile-threaded render (the reference's
 //                      scheme: 64x64 tiles popped from a shared queue, tile-renderer.hpp:118-309)
 // LUT tables are read from tests/golden/ref_tables.bin (dumped from the compiled reference;
@@ -18,6 +21,7 @@
 #include "kat_common.hpp"
 #include "params.hpp"
 #include "rayrec.hpp"
+#include "shaderec.hpp"
 #include "yart_oracle.hpp"
 
 using namespace orc;
@@ -249,6 +253,180 @@ static int doHits(const Scene& sc, const params::Params& p, const std::string& r
   return 0;
 }
 
+// ---- shade mode: one record per case (shaderec.hpp) and the events each case met ---------------------------
+// The event bits, in bit order (tests/shadesuite.py EVENTS holds the same list): properties of the case's operands and of the
+// path the restatement took, recomputed here with the restatement's own arithmetic.
+enum ShadeEvent : uint32_t {
+  SE_TEX_INTEGER_UV, SE_TEX_NEGATIVE_UV, SE_TEX_FRAC_ONE, SE_TEX_LAST_CELL, SE_TEX_WEIGHT_ZERO,
+  SE_LUT_ON_GRID, SE_LUT_INDEX_CAP, SE_LUT_NEGATIVE_COS, SE_LUT_IOR_BELOW_1, SE_LUT_IOR_EQ_1,
+  SE_LOBE_CLEARCOAT, SE_LOBE_METALLIC, SE_LOBE_DIELECTRIC, SE_LOBE_GLOSSY, SE_ABSORBED, SE_SPECULAR, SE_SHORTCUT, SE_UC2_AT_THRESHOLD,
+  SE_ENV_U_ON_GUIDE, SE_ENV_U_ON_CDF, SE_ENV_ZERO_PDF, SE_OCTA_SEAM, SE_AREA_SAMPLE,
+  SE_PICK_INFINITE, SE_PICK_AREA, SE_PICK_ON_CDF, SE_PICK_NEAR_PINF, SE_COUNT
+};
+static const char* kShadeEventNames[SE_COUNT] = {
+  "tex_integer_uv", "tex_negative_uv", "tex_frac_one", "tex_last_cell", "tex_weight_zero",
+  "lut_on_grid", "lut_index_cap", "lut_negative_cos", "lut_ior_below_1", "lut_ior_eq_1",
+  "lobe_clearcoat", "lobe_metallic", "lobe_dielectric", "lobe_glossy", "absorbed", "specular", "shortcut", "uc2_at_threshold",
+  "env_u_on_guide", "env_u_on_cdf", "env_zero_pdf", "octa_seam", "area_sample",
+  "pick_infinite", "pick_area", "pick_on_cdf", "pick_near_pinf"};
+
+static uint32_t texEvents(const Texture& t, V2 uv) {            // Texture::sample's index arithmetic (texture.cpp:21-35)
+  uint32_t ev = 0;
+  const float in[2] = {uv.x, uv.y};
+  const uint32_t dim[2] = {t.w, t.h};
+  for (int a = 0; a < 2; a++) {
+    if (in[a] == std::floor(in[a])) ev |= 1u << SE_TEX_INTEGER_UV;
+    if (in[a] < 0.0f) ev |= 1u << SE_TEX_NEGATIVE_UV;
+    float x = in[a] - std::floor(in[a]);
+    if (x == 1.0f) ev |= 1u << SE_TEX_FRAC_ONE;             // just below an integer: the only way past the clamp
+    x *= float(dim[a] - 1);
+    const uint32_t i = mmin(dim[a] - 2, x);
+    if (i == dim[a] - 2) ev |= 1u << SE_TEX_LAST_CELL;
+    if (x - float(i) == 0.0f) ev |= 1u << SE_TEX_WEIGHT_ZERO;
+  }
+  return ev;
+}
+static uint32_t lutEvents(float c, float r, float f0, float ior) {
+  uint32_t ev = 0;
+  auto axis = [&](float x, float scale, uint64_t cap) {
+    const float s = x * scale;
+    const uint64_t i = toSizeT(s);
+    if (i >= cap) ev |= 1u << SE_LUT_INDEX_CAP;
+    if (s >= 0.0f && s == std::floor(s)) ev |= 1u << SE_LUT_ON_GRID;
+  };
+  axis(r, 31.0f, 30); axis(c, 31.0f, 30); axis(f0, 15.0f, 14); axis(r, 15.0f, 14); axis(c, 15.0f, 14);
+  if (c < 0.0f) ev |= 1u << SE_LUT_NEGATIVE_COS;
+  if (ior < 1.0f) ev |= 1u << SE_LUT_IOR_BELOW_1;
+  if (ior == 1.0f) ev |= 1u << SE_LUT_IOR_EQ_1;
+  return ev;
+}
+static uint32_t pow2ge(uint32_t n) { uint32_t k = 1; while (k < n) k <<= 1; return k; }
+static bool onCdf(const PC1D& d, float u) {
+  for (size_t k = 1; k + 1 < d.cdf.size(); k++) if (d.cdf[k] == u) return true;
+  return false;
+}
+static bool nearF(float a, float b) {                     // within two representable steps, a threshold that can decide
+  if (!(b > 0.0f) || !(b < 1.0f)) return false;
+  const int32_t ia = int32_t(__builtin_bit_cast(uint32_t, a)), ib = int32_t(__builtin_bit_cast(uint32_t, b));
+  return a >= 0.0f && std::abs(ia - ib) <= 2;
+}
+
+static int doShade(const Scene& sc, const std::string& casesPath, const std::string& outPath) {
+  using namespace shaderec;
+  uint64_t counts[SE_COUNT] = {0};
+  std::vector<Rec> out;
+  std::vector<uint32_t> masks;
+  std::vector<float> probs;                               // per case pClearcoat, pMetallic, pDielectric of a BSDF case, else 0
+  const auto cases = load(casesPath);
+  auto put3 = [](Rec& r, int k, V3 v) { put(r, k, v.x); put(r, k + 1, v.y); put(r, k + 2, v.z); };
+  for (const Case& q : cases) {
+    Rec r{};
+    uint32_t ev = 0;
+    float pr[3] = {0, 0, 0};
+    const float* f = q.f;
+    if (q.kind == SHADE_LUT) {
+      put(r, 0, sc.luts.ggxE(f[0], f[1])); put(r, 1, sc.luts.ggxEavg(f[1]));
+      put(r, 2, sc.luts.ggxBaseE(f[2], f[1], f[0])); put(r, 3, sc.luts.ggxBaseEavg(f[2], f[1]));
+      put(r, 4, sc.luts.ggxGlassE(f[3], f[1], std::abs(f[0])));
+      ev = lutEvents(f[0], f[1], f[2], f[3]);
+    } else if (q.kind == SHADE_TEX) {
+      const Texture& t = sc.textures.at(q.index);
+      float v[4] = {0, 0, 0, 0};
+      t.sample(V2{f[0], f[1]}, v);
+      for (uint32_t c = 0; c < t.c; c++) put(r, int(c), v[c]);
+      ev = texEvents(t, V2{f[0], f[1]});
+    } else if (q.kind == SHADE_MAT) {
+      const Material& b = sc.materials.at(q.index);
+      const V2 uv{f[0], f[1]};
+      put(r, 0, b.alpha(uv)); put3(r, 1, b.baseAt(uv));
+      put3(r, 4, b.normal(V3(f[2], f[3], f[4]), V4{f[5], f[6], f[7], f[8]}, uv));
+      put3(r, 7, b.attenuation(f[9]));
+    } else if (q.kind == SHADE_BSDF) {
+      const Material& b = sc.materials.at(q.index);
+      const V3 wo(f[0], f[1], f[2]), wi(f[3], f[4], f[5]), n(f[6], f[7], f[8]), t(f[9], f[10], f[11]);
+      const V2 uv{f[12], f[13]}, u{f[14], f[15]};
+      const V3 fv = b.f(wo, wi, n, t, uv);
+      const float pdf = b.pdf(wo, wi, n, t, uv);
+      Material::SampleTrace tr;
+      Material::sampleTrace() = &tr;
+      const BSDFSample s = b.sample(wo, n, t, uv, u, f[16], f[17], (q.flags & 1u) != 0);
+      Material::sampleTrace() = nullptr;
+      r.w[0] = uint32_t(s.scatter);
+      put3(r, 1, fv); put(r, 4, pdf); put3(r, 5, s.f); put3(r, 8, s.Le); put3(r, 11, s.wi); put(r, 14, s.pdf); put(r, 15, s.roughness);
+      ev |= 1u << (SE_LOBE_CLEARCOAT + uint32_t(tr.lobe));
+      if (s.scatter == 0) ev |= 1u << SE_ABSORBED;
+      if (s.scatter & 32) ev |= 1u << SE_SPECULAR;
+      if (tr.c == 0.0f && tr.m == 0.0f && tr.t == 0.0f) ev |= 1u << SE_SHORTCUT;
+      if (nearF(f[17], tr.pC) || nearF(f[17], tr.pM) || nearF(f[17], tr.pD)) ev |= 1u << SE_UC2_AT_THRESHOLD;
+      pr[0] = tr.pC; pr[1] = tr.pM; pr[2] = tr.pD;
+    } else if (q.kind == SHADE_LIGHT) {
+      const Light& l = *sc.lights.at(q.index);
+      const LightSample s = l.sample(V3(f[0], f[1], f[2]), V2{f[3], f[4]});
+      put3(r, 0, s.Li); put3(r, 3, s.wi); put3(r, 6, s.p); put3(r, 9, s.n); put(r, 12, s.pdf);
+      const V3 wi(f[5], f[6], f[7]);
+      put(r, 13, l.pdf(wi)); put3(r, 14, l.Le(octahedralUV(wi))); put(r, 17, sc.lightP(q.index));
+      if (l.kind() == Light::Area) ev |= 1u << SE_AREA_SAMPLE;
+      if (const auto* im = dynamic_cast<const ImageInfiniteLight*>(&l)) {
+        const uint32_t h = uint32_t(im->marg.func.size()), w = uint32_t(im->cond[0].func.size());
+        const float ky = f[4] * float(4u * pow2ge(h)), kx = f[3] * float(4u * pow2ge(w));
+        if (ky == std::floor(ky) || kx == std::floor(kx)) ev |= 1u << SE_ENV_U_ON_GUIDE;
+        uint32_t ov = 0;
+        im->marg.sample(f[4], nullptr, &ov);
+        if (onCdf(im->marg, f[4]) || onCdf(im->cond[ov], f[3])) ev |= 1u << SE_ENV_U_ON_CDF;
+        if (s.pdf == 0.0f) ev |= 1u << SE_ENV_ZERO_PDF;
+        if (wi.x == 0.0f || wi.y == 0.0f || wi.z == 0.0f) ev |= 1u << SE_OCTA_SEAM;
+      }
+    } else if (q.kind == SHADE_PICK) {
+      if (sc.lights.empty()) throw std::runtime_error("shade: a PICK case needs lights");
+      float pl = 0;
+      const Light* l = sc.sampleLight(f[0], pl);
+      for (size_t i = 0; i < sc.lights.size(); i++) if (sc.lights[i].get() == l) r.w[0] = uint32_t(i);
+      put(r, 1, pl);
+      const float pInf = sc.pInfinite();
+      ev |= 1u << (f[0] < pInf ? SE_PICK_INFINITE : SE_PICK_AREA);
+      if (std::abs(int64_t(__builtin_bit_cast(uint32_t, f[0])) - int64_t(__builtin_bit_cast(uint32_t, pInf))) <= 32) ev |= 1u << SE_PICK_NEAR_PINF;   // u >= 0: within 32 floats of the boundary
+      if (!(f[0] < pInf)) {
+        const float us = (f[0] - pInf) / (1.0f - pInf) * sc.totalPower;
+        for (float c : sc.powers) if (c == us) ev |= 1u << SE_PICK_ON_CDF;
+      }
+    } else throw std::runtime_error("shade: unknown kind");
+    out.push_back(r);
+    masks.push_back(ev);
+    probs.insert(probs.end(), pr, pr + 3);
+    for (uint32_t k = 0; k < SE_COUNT; k++) counts[k] += (ev >> k) & 1u;
+  }
+  save(outPath, out);
+  save(outPath + ".events", masks);
+  save(outPath + ".probs", probs);
+  {
+    // the tables a generator needs to aim at their entries (floats as bit patterns): the light sampler's, and per image light the
+    // marginal and conditional CDFs
+    FILE* tf = std::fopen((outPath + ".tables.json").c_str(), "w");
+    if (!tf) throw std::runtime_error("cannot write " + outPath + ".tables.json");
+    auto bits = [](float v) { return __builtin_bit_cast(uint32_t, v); };
+    auto list = [&](const std::vector<float>& v) { std::fputs("[", tf); for (size_t k = 0; k < v.size(); k++) std::fprintf(tf, "%s%u", k ? "," : "", bits(v[k])); std::fputs("]", tf); };
+    std::fprintf(tf, "{\"p_inf\": %u, \"total_power\": %u, \"powers\": ", bits(sc.pInfinite()), bits(sc.totalPower));
+    list(sc.powers);
+    std::fputs(", \"envs\": {", tf);
+    bool first = true;
+    for (size_t i = 0; i < sc.lights.size(); i++)
+      if (const auto* im = dynamic_cast<const ImageInfiniteLight*>(sc.lights[i].get())) {
+        std::fprintf(tf, "%s\"%zu\": {\"marg\": ", first ? "" : ", ", i);
+        first = false;
+        list(im->marg.cdf);
+        std::fputs(", \"cond\": [", tf);
+        for (size_t v = 0; v < im->cond.size(); v++) { if (v) std::fputs(",", tf); list(im->cond[v].cdf); }
+        std::fputs("]}", tf);
+      }
+    std::fputs("}}\n", tf);
+    std::fclose(tf);
+  }
+  std::printf("{\"cases\": %zu", cases.size());
+  for (uint32_t k = 0; k < SE_COUNT; k++) std::printf(", \"%s\": %llu", kShadeEventNames[k], (unsigned long long) counts[k]);
+  std::printf("}\n");
+  return 0;
+}
+
 static int doRender(const Scene& sc, const params::Params& p, const std::string& outPath) {
   const uint32_t W = p.width, H = p.height, T = p.tile;
   Camera cam = makeCamera(p);
@@ -401,8 +579,9 @@ int main(int argc, char** argv) {
     catch (const std::exception& e) { std::fprintf(stderr, "yart_oracle: %s\n", e.what()); return 2; }
   }
   const bool hits = argc == 6 && std::string(argv[1]) == "hits";
-  if (argc != 5 && !hits) {
-    std::fprintf(stderr, "usage: yart_oracle kat|render <scene.yscn> <params.txt> <out> | hits <scene.yscn> <params.txt> <rays.bin> <out.bin>\n");
+  const bool shade = argc == 6 && std::string(argv[1]) == "shade";
+  if (argc != 5 && !hits && !shade) {
+    std::fprintf(stderr, "usage: yart_oracle kat|render <scene.yscn> <params.txt> <out> | hits <scene.yscn> <params.txt> <rays.bin> <out.bin> | shade <scene.yscn> <params.txt> <cases.bin> <out.bin>\n");
     return 1;
   }
   try {
@@ -413,6 +592,7 @@ int main(int argc, char** argv) {
     for (auto& m : sc.materials) m.lut = &sc.luts;     // the Scene object may have moved
     std::string mode = argv[1];
     if (hits) return doHits(sc, p, argv[4], argv[5]);
+    if (shade) return doShade(sc, argv[4], argv[5]);
     if (mode == "kat") return doKat(sc, sf, p, argv[4]);
     if (mode == "render") return doRender(sc, p, argv[4]);
   } catch (const std::exception& e) {

@@ -13,6 +13,8 @@
 //   yart_ref render <scene.yscn> <params.txt> <out.f32>     raw RGBA32F, W*H*4 floats
 //   yart_ref kat    <scene.yscn> <params.txt> <out.json>    known-answer vectors
 //   yart_ref hits   <scene.yscn> <params.txt> <rays.bin> <out.bin>   one record per ray through testNode(root) (rayrec.hpp)
+//   yart_ref shade  <scene.yscn> <params.txt> <cases.bin> <out.bin>  one record per case (shaderec.hpp): the reference's own Texture,
+//                   LUT functions, BSDF, Light and PowerLightSampler per call, as the kat mode calls them for its fixed inputs
 //   yart_ref luts   <out.bin>                               raw dump of the 8 LUT tables
 //   yart_ref bvh    <scene.yscn> <mesh> <out.bin>           node array + index array
 //   yart_ref tonemap <in.f32> <w> <h> <look|-> <out.f32> <out.ppm>   AgX (none|golden|punchy, "-": no
@@ -48,6 +50,7 @@
 #include "params.hpp"
 #include "kat_common.hpp"
 #include "rayrec.hpp"
+#include "shaderec.hpp"
 
 using namespace yart;
 using namespace yart::math;
@@ -101,6 +104,8 @@ struct BuiltScene {
   std::unique_ptr<Scene> scene;
   std::vector<std::unique_ptr<HDRTexture>> hdr;   // env maps are owned by the caller (main.cpp:81)
   std::vector<const BSDF*> materials;
+  std::vector<const void*> tex;                   // SDR textures by scene index (the class is chosen by the channel count), nullptr for HDR
+  std::vector<const HDRTexture*> texHdr;
 };
 
 static Node buildNode(const yscn::SceneFile& sf, Scene& scene, size_t idx) {
@@ -205,6 +210,7 @@ static BuiltScene build(const yscn::SceneFile& sf) {
       scene.addLight(std::move(light));
     }
   }
+  out.tex = tex; out.texHdr = texHdr;
   return out;
 }
 
@@ -563,6 +569,75 @@ static int doHits(const std::string& scenePath, const std::string& paramPath, co
   return 0;
 }
 
+static int doShade(const std::string& scenePath, const std::string& casesPath, const std::string& outPath) {
+  using namespace shaderec;
+  auto sf = yscn::load(scenePath);
+  auto built = build(sf);
+  Scene& scene = *built.scene;
+  PowerLightSampler ls;
+  ls.init(&scene);
+  const size_t nl = scene.nLights();
+  auto put3 = [](Rec& r, int k, const float3& v) { for (int c = 0; c < 3; c++) put(r, k + c, v[c]); };
+  std::vector<Rec> out;
+  for (const Case& q : load(casesPath)) {
+    Rec r{};
+    const float* f = q.f;
+    if (q.kind == SHADE_LUT) {
+      put(r, 0, lut::ggxE(f[0], f[1]));
+      put(r, 1, lut::ggxEavg(f[1]));
+      put(r, 2, lut::ggxBaseE(f[2], f[1], f[0]));
+      put(r, 3, lut::ggxBaseEavg(f[2], f[1]));
+      put(r, 4, lut::ggxGlassE(f[3], f[1], std::abs(f[0])));
+    } else if (q.kind == SHADE_TEX) {
+      if (q.index >= sf.textures.size()) throw std::runtime_error("shade: texture index out of range");
+      const auto& t = sf.textures[q.index];
+      const float2 uv(f[0], f[1]);
+      if (t.dtype == 1) put3(r, 0, built.texHdr[q.index]->sample(uv));
+      else if (t.channels == 1) put(r, 0, static_cast<const MonoTexture*>(built.tex[q.index])->sample(uv));
+      else if (t.channels == 2) { auto v = static_cast<const SDRTexture<2>*>(built.tex[q.index])->sample(uv); put(r, 0, v[0]); put(r, 1, v[1]); }
+      else if (t.channels == 3) put3(r, 0, static_cast<const RGBTexture*>(built.tex[q.index])->sample(uv));
+      else { auto v = static_cast<const RGBATexture*>(built.tex[q.index])->sample(uv); for (int c = 0; c < 4; c++) put(r, c, v[c]); }
+    } else if (q.kind == SHADE_MAT) {
+      const BSDF& b = *built.materials.at(q.index);
+      const float2 uv(f[0], f[1]);
+      put(r, 0, b.alpha(uv));
+      put3(r, 1, b.base(uv));
+      put3(r, 4, b.normal(float3(f[2], f[3], f[4]), float4(f[5], f[6], f[7], f[8]), uv));
+      put3(r, 7, b.attenuation(f[9]));
+    } else if (q.kind == SHADE_BSDF) {
+      const BSDF& b = *built.materials.at(q.index);
+      const float3 wo(f[0], f[1], f[2]), wi(f[3], f[4], f[5]), n(f[6], f[7], f[8]), t(f[9], f[10], f[11]);
+      const float2 uv(f[12], f[13]), u(f[14], f[15]);
+      const float3 fv = b.f(wo, wi, n, t, uv);
+      const float pdf = b.pdf(wo, wi, n, t, uv);
+      const BSDFSample s = b.sample(wo, n, t, uv, u, f[16], f[17], (q.flags & 1u) != 0);
+      r.w[0] = uint32_t(s.scatter);
+      put3(r, 1, fv); put(r, 4, pdf);
+      put3(r, 5, s.f); put3(r, 8, s.Le); put3(r, 11, s.wi);
+      put(r, 14, s.pdf); put(r, 15, s.roughness);
+    } else if (q.kind == SHADE_LIGHT) {
+      if (q.index >= nl) throw std::runtime_error("shade: light index out of range");
+      const Light& l = scene.light(q.index);
+      const LightSample s = l.sample(float3(f[0], f[1], f[2]), float3(0, 1, 0), float2(f[3], f[4]), 0.0f);
+      put3(r, 0, s.Li); put3(r, 3, s.wi); put3(r, 6, s.p); put3(r, 9, s.n); put(r, 12, s.pdf);
+      const float3 wi(f[5], f[6], f[7]);
+      put(r, 13, l.pdf(wi));
+      put3(r, 14, l.Le(octahedralUV(wi)));
+      put(r, 17, ls.p(float3(), float3(), q.index));
+    } else if (q.kind == SHADE_PICK) {
+      if (nl == 0) throw std::runtime_error("shade: a PICK case needs lights");
+      const SampledLight s = ls.sample(float3(), float3(), f[0]);
+      uint32_t which = 0xffffffffu;
+      for (size_t i = 0; i < nl; i++) if (&scene.light(i) == &s.light) which = uint32_t(i);
+      r.w[0] = which;
+      put(r, 1, s.p);
+    } else throw std::runtime_error("shade: unknown kind");
+    out.push_back(r);
+  }
+  save(outPath, out);
+  return 0;
+}
+
 static int doTonemap(const char* in, unsigned w, unsigned h, const std::string& look, const char* outF32, const char* outPpm) {
   std::ifstream f(in, std::ios::binary);
   std::vector<float> hdr(size_t(w) * h * 4);
@@ -713,6 +788,7 @@ int main(int argc, char** argv) {
     if (mode == "render" && argc == 5) return doRender(argv[2], argv[3], argv[4]);
     if (mode == "kat" && argc == 5) return doKat(argv[2], argv[3], argv[4]);
     if (mode == "hits" && argc == 6) return doHits(argv[2], argv[3], argv[4], argv[5]);
+    if (mode == "shade" && argc == 6) return doShade(argv[2], argv[4], argv[5]);
     if (mode == "luts" && argc == 3) return doLuts(argv[2]);
     if (mode == "bvh" && argc == 5) return doBvh(argv[2], size_t(std::atoi(argv[3])), argv[4]);
     if (mode == "texture" && argc == 7) return doTexture(argv[2], std::atoi(argv[3]), std::atoi(argv[4]), argv[5], argv[6]);
@@ -726,6 +802,6 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "yart_ref: %s\n", e.what());
     return 2;
   }
-  std::fprintf(stderr, "usage: yart_ref render|kat <scene.yscn> <params.txt> <out> | hits <scene.yscn> <params.txt> <rays.bin> <out.bin> | luts <out> | bvh <scene> <mesh> <out>\n");
+  std::fprintf(stderr, "usage: yart_ref render|kat <scene.yscn> <params.txt> <out> | hits <scene.yscn> <params.txt> <rays.bin> <out.bin> | shade <scene.yscn> <params.txt> <cases.bin> <out.bin> | luts <out> | bvh <scene> <mesh> <out>\n");
   return 1;
 }

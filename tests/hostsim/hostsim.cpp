@@ -36,11 +36,13 @@ static thread_local StackProbe* t_stackProbe = nullptr;
 #include "../../oracle/kat_common.hpp"
 #include "../../oracle/params.hpp"
 #include "../../oracle/rayrec.hpp"
+#include "../../oracle/shaderec.hpp"
 #include "../../yart_amd/csrc/estimator.hpp"
 #include "../../yart_amd/csrc/host_scene.hpp"
 #include "../../yart_amd/csrc/tonemap.hpp"
 #include "../../yart_amd/csrc/integrator.hpp"
 #include "../../yart_amd/csrc/probe_record.hpp"
+#include "../../yart_amd/csrc/shade_record.hpp"
 #include "../../yart_amd/csrc/scene_file.hpp"
 
 using namespace yart_hip;
@@ -91,8 +93,63 @@ static PathCtx pathCtx(const Ctx& c, const StackMem& m, unsigned lane) {
   return px;
 }
 
+// The shading inputs of the KAT program (oracle/kat_common.hpp) as case records (oracle/shaderec.hpp): the LUT grid, per material
+// bsdfCasesPerMaterial x (one BSDF case, one MAT case), per light of kat::lightSubset four LIGHT cases, then 32 PICK cases where
+// the scene has lights. `kat` below evaluates exactly these records and `shade-kat-cases` writes them out (the device probe is fed
+// them and compared with the committed .kat.json), so the two cannot drift.
+static shaderec::Case shadeCase(uint32_t kind, uint32_t index, uint32_t flags = 0) {
+  shaderec::Case c{};
+  c.kind = kind; c.index = index; c.flags = flags;
+  return c;
+}
+static std::vector<shaderec::Case> katShadeCases(size_t nMaterials, size_t nLights) {
+  std::vector<shaderec::Case> v;
+  for (const auto& q : kat::lutInputs()) {
+    shaderec::Case c = shadeCase(SHADE_LUT, 0);
+    c.f[0] = q.c; c.f[1] = q.r; c.f[2] = q.f0; c.f[3] = q.ior;
+    v.push_back(c);
+  }
+  for (size_t m = 0; m < nMaterials; m++) {
+    kat::Lcg rng(1000 + uint32_t(m));
+    for (int k = 0; k < kat::bsdfCasesPerMaterial; k++) {
+      float r[12];
+      for (int q = 0; q < 6; q++) r[q] = rng.sym();
+      for (int q = 6; q < 12; q++) r[q] = rng.next();
+      const f3 wo = normalized(mk3(r[0], r[1], r[2])), wi = normalized(mk3(r[3], r[4], r[5]));
+      const f2 uv = mk2(r[6] * 3.0f - 1.0f, r[7] * 3.0f - 1.0f);
+      shaderec::Case b = shadeCase(SHADE_BSDF, uint32_t(m), uint32_t(k & 1));
+      const float fb[18] = {wo.x, wo.y, wo.z, wi.x, wi.y, wi.z, 0, 0, 1, 1, 0, 0, uv.x, uv.y, r[8], r[9], r[10], r[11]};
+      for (int q = 0; q < 18; q++) b.f[q] = fb[q];
+      v.push_back(b);
+      shaderec::Case a = shadeCase(SHADE_MAT, uint32_t(m));
+      const float fa[10] = {uv.x, uv.y, 0, 0, 1, 1, 0, 0, 1, r[10] * 4.0f};
+      for (int q = 0; q < 10; q++) a.f[q] = fa[q];
+      v.push_back(a);
+    }
+  }
+  kat::Lcg rng(4242);
+  for (size_t li : kat::lightSubset(nLights))
+    for (int k = 0; k < 4; k++) {
+      float r0 = rng.sym(), r1 = rng.next(), r2 = rng.sym(), r3 = rng.next(), r4 = rng.next();
+      float w0 = rng.sym(), w1 = rng.sym(), w2 = rng.sym();
+      const f3 wi = normalized(mk3(w0, w1, w2));
+      shaderec::Case c = shadeCase(SHADE_LIGHT, uint32_t(li));
+      const float fl[8] = {r0 * 4.0f, r1 * 8.0f, r2 * 4.0f, r3, r4, wi.x, wi.y, wi.z};
+      for (int q = 0; q < 8; q++) c.f[q] = fl[q];
+      v.push_back(c);
+    }
+  if (nLights > 0)
+    for (int k = 0; k < 32; k++) {
+      shaderec::Case c = shadeCase(SHADE_PICK, 0);
+      c.f[0] = rng.next();
+      v.push_back(c);
+    }
+  return v;
+}
+
 static int doKat(Ctx& c, const params::Params& p, const std::string& outPath) {
   kat::Writer w(outPath);
+  const std::vector<shaderec::Case> shadeCases = katShadeCases(c.im.nMaterials, c.sc.nLights);
   {
     std::vector<uint64_t> h, mb, mo;
     std::vector<int64_t> l2;
@@ -119,12 +176,14 @@ static int doKat(Ctx& c, const params::Params& p, const std::string& outPath) {
   {
     std::vector<float> e, ea, be, bea, ge, gea;
     const float* lut = c.sc.lut;
-    for (const auto& q : kat::lutInputs()) {
-      e.push_back(ggxE(lut, q.c, q.r));
-      ea.push_back(ggxEavg(lut, q.r));
-      be.push_back(ggxBaseE(lut, q.f0, q.r, q.c));
-      bea.push_back(ggxBaseEavg(lut, q.f0, q.r));
-      ge.push_back(ggxGlassE(lut, q.ior, q.r, std::fabs(q.c)));
+    for (const shaderec::Case& q : shadeCases) {
+      if (q.kind != SHADE_LUT) continue;
+      const float c = q.f[0], r = q.f[1], f0 = q.f[2], ior = q.f[3];
+      e.push_back(ggxE(lut, c, r));
+      ea.push_back(ggxEavg(lut, r));
+      be.push_back(ggxBaseE(lut, f0, r, c));
+      bea.push_back(ggxBaseEavg(lut, f0, r));
+      ge.push_back(ggxGlassE(lut, ior, r, std::fabs(c)));
       gea.push_back(0.0f);   // ggxGlassEavg is not on the path (unused by parametric.cpp)
     }
     w.f32("ggxE", e); w.f32("ggxEavg", ea); w.f32("ggxBaseE", be);
@@ -187,75 +246,62 @@ static int doKat(Ctx& c, const params::Params& p, const std::string& outPath) {
   {
     std::vector<float> fo;
     std::vector<int64_t> io;
-    const f3 n = mk3(0, 0, 1), t = mk3(1, 0, 0);
-    size_t nm = c.im.nMaterials;
-    for (size_t m = 0; m < nm; m++) {
-      const MaterialDev& mt = c.im.materials[m];
-      kat::Lcg rng(1000 + uint32_t(m));
-      for (int k = 0; k < kat::bsdfCasesPerMaterial; k++) {
-        float r[12];
-        for (int q = 0; q < 6; q++) r[q] = rng.sym();
-        for (int q = 6; q < 12; q++) r[q] = rng.next();
-        f3 wo = normalized(mk3(r[0], r[1], r[2]));
-        f3 wi = normalized(mk3(r[3], r[4], r[5]));
-        f2 uv = mk2(r[6] * 3.0f - 1.0f, r[7] * 3.0f - 1.0f);
-        f2 u = mk2(r[8], r[9]);
-        float uc = r[10], uc2 = r[11];
-        bool reg = k & 1;
-        f3 f = bsdfF(c.sc, mt, wo, wi, n, t, uv);
-        float pdf = bsdfPdf(c.sc, mt, wo, wi, n, t, uv);
-        BsdfSample s = bsdfSample(c.sc, mt, wo, n, t, uv, u, uc, uc2, reg);
-        fo.push_back(f.x); fo.push_back(f.y); fo.push_back(f.z);
-        fo.push_back(pdf);
-        io.push_back(s.scatter);
-        fo.push_back(s.f.x); fo.push_back(s.f.y); fo.push_back(s.f.z);
-        fo.push_back(s.Le.x); fo.push_back(s.Le.y); fo.push_back(s.Le.z);
-        fo.push_back(s.wi.x); fo.push_back(s.wi.y); fo.push_back(s.wi.z);
-        fo.push_back(s.pdf); fo.push_back(s.roughness);
-        fo.push_back(matAlpha(c.sc, mt, uv));
-        f3 base = matBase(c.sc, mt, uv);
-        fo.push_back(base.x); fo.push_back(base.y); fo.push_back(base.z);
-        f4 t4; t4.x = 1; t4.y = 0; t4.z = 0; t4.w = 1;
-        f3 sn = bsdfNormal(c.sc, mt, n, t4, uv);
-        fo.push_back(sn.x); fo.push_back(sn.y); fo.push_back(sn.z);
-        f3 att = matAttenuation(mt, uc * 4.0f);
-        fo.push_back(att.x); fo.push_back(att.y); fo.push_back(att.z);
-      }
-      io.push_back((mt.flags & MAT_TRANSPARENT) ? 1 : 0);
+    for (size_t k = 0; k < shadeCases.size(); k++) {
+      const shaderec::Case& q = shadeCases[k];
+      if (q.kind != SHADE_BSDF) continue;
+      const shaderec::Case& a = shadeCases[k + 1];          // the MAT case of the same draw
+      const MaterialDev& mt = c.im.materials[q.index];
+      const f3 wo = mk3(q.f[0], q.f[1], q.f[2]), wi = mk3(q.f[3], q.f[4], q.f[5]), n = mk3(q.f[6], q.f[7], q.f[8]), t = mk3(q.f[9], q.f[10], q.f[11]);
+      const f2 uv = mk2(q.f[12], q.f[13]), u = mk2(q.f[14], q.f[15]);
+      const float uc = q.f[16], uc2 = q.f[17];
+      const bool reg = q.flags & 1u;
+      f3 f = bsdfF(c.sc, mt, wo, wi, n, t, uv);
+      float pdf = bsdfPdf(c.sc, mt, wo, wi, n, t, uv);
+      BsdfSample s = bsdfSample(c.sc, mt, wo, n, t, uv, u, uc, uc2, reg);
+      fo.push_back(f.x); fo.push_back(f.y); fo.push_back(f.z);
+      fo.push_back(pdf);
+      io.push_back(s.scatter);
+      fo.push_back(s.f.x); fo.push_back(s.f.y); fo.push_back(s.f.z);
+      fo.push_back(s.Le.x); fo.push_back(s.Le.y); fo.push_back(s.Le.z);
+      fo.push_back(s.wi.x); fo.push_back(s.wi.y); fo.push_back(s.wi.z);
+      fo.push_back(s.pdf); fo.push_back(s.roughness);
+      const f2 auv = mk2(a.f[0], a.f[1]);
+      fo.push_back(matAlpha(c.sc, mt, auv));
+      f3 base = matBase(c.sc, mt, auv);
+      fo.push_back(base.x); fo.push_back(base.y); fo.push_back(base.z);
+      f4 t4; t4.x = a.f[5]; t4.y = a.f[6]; t4.z = a.f[7]; t4.w = a.f[8];
+      f3 sn = bsdfNormal(c.sc, mt, mk3(a.f[2], a.f[3], a.f[4]), t4, auv);
+      fo.push_back(sn.x); fo.push_back(sn.y); fo.push_back(sn.z);
+      f3 att = matAttenuation(mt, a.f[9]);
+      fo.push_back(att.x); fo.push_back(att.y); fo.push_back(att.z);
+      const bool lastOfMaterial = k + 2 >= shadeCases.size() || shadeCases[k + 2].kind != SHADE_BSDF || shadeCases[k + 2].index != q.index;
+      if (lastOfMaterial) io.push_back((mt.flags & MAT_TRANSPARENT) ? 1 : 0);
     }
     w.i64("bsdf_i", io); w.f32("bsdf_f", fo);
   }
   {
     std::vector<float> fo;
     std::vector<int64_t> io;
-    size_t nl = c.sc.nLights;
-    kat::Lcg rng(4242);
-    for (size_t li : kat::lightSubset(nl)) {
-      const LightDev& l = c.sc.lights[li];
-      fo.push_back(l.power);
-      for (int k = 0; k < 4; k++) {
-        float r0 = rng.sym(), r1 = rng.next(), r2 = rng.sym(), r3 = rng.next(), r4 = rng.next();
-        f3 pp = mk3(r0 * 4.0f, r1 * 8.0f, r2 * 4.0f);
-        f2 u = mk2(r3, r4);
-        LightSample s = lightSample(c.sc, l, pp, u);
+    for (size_t k = 0; k < shadeCases.size(); k++) {
+      const shaderec::Case& q = shadeCases[k];
+      if (q.kind == SHADE_LIGHT) {
+        const LightDev& l = c.sc.lights[q.index];
+        if (shadeCases[k - 1].kind != SHADE_LIGHT || shadeCases[k - 1].index != q.index) fo.push_back(l.power);
+        LightSample s = lightSample(c.sc, l, mk3(q.f[0], q.f[1], q.f[2]), mk2(q.f[3], q.f[4]));
         fo.push_back(s.Li.x); fo.push_back(s.Li.y); fo.push_back(s.Li.z);
         fo.push_back(s.wi.x); fo.push_back(s.wi.y); fo.push_back(s.wi.z);
         fo.push_back(s.p.x); fo.push_back(s.p.y); fo.push_back(s.p.z);
         fo.push_back(s.n.x); fo.push_back(s.n.y); fo.push_back(s.n.z);
         fo.push_back(s.pdf);
-        float w0 = rng.sym(), w1 = rng.sym(), w2 = rng.sym();
-        f3 wi = normalized(mk3(w0, w1, w2));
+        const f3 wi = mk3(q.f[5], q.f[6], q.f[7]);
         fo.push_back(lightPdf(c.sc, l, wi));
         f3 le = lightLe(c.sc, l, octahedralUV(wi));
         fo.push_back(le.x); fo.push_back(le.y); fo.push_back(le.z);
-      }
-      fo.push_back(lightSamplerP(c.sc, uint32_t(li)));
-    }
-    if (nl > 0) {
-      for (int k = 0; k < 32; k++) {
-        float u = rng.next();
+        if (k + 1 >= shadeCases.size() || shadeCases[k + 1].kind != SHADE_LIGHT || shadeCases[k + 1].index != q.index)
+          fo.push_back(lightSamplerP(c.sc, q.index));
+      } else if (q.kind == SHADE_PICK) {
         float pl;
-        uint32_t which = lightSamplerSample(c.sc, u, pl);
+        uint32_t which = lightSamplerSample(c.sc, q.f[0], pl);
         io.push_back(which);
         fo.push_back(pl);
       }
@@ -328,6 +374,30 @@ static int doHits(Ctx& c, const std::string& raysPath, const std::string& outPat
   }
   rayrec::save(outPath, out);
   std::printf("{\"hits\": \"ok\", \"rays\": %zu, \"walk\": %d, \"kept_rays_that_differ\": %zu}\n", k, walk, differ);
+  return 0;
+}
+
+// shade: one record per case of a case file (oracle/shaderec.hpp) through csrc/shade_record.hpp — the function k_probe_shading
+// runs. entries: 0 the plain entries (bsdfF / bsdfPdf / bsdfSample, what the KAT goes through), 1 one matEvaluate and the *ImplE
+// entries in the local frame, as wfShade calls them.
+static int doShade(Ctx& c, const std::string& casesPath, const std::string& outPath, int entries) {
+  if (entries < 0 || entries > 1) { std::fprintf(stderr, "shade: entries must be 0 (plain) or 1 (matEvaluate + *ImplE)\n"); return 2; }
+  std::vector<uint32_t> dims;
+  for (uint32_t t = 0; t < c.sc.nTextures; t++) { dims.push_back(c.sc.textures[t].width); dims.push_back(c.sc.textures[t].height); }
+  std::vector<shaderec::Rec> out;
+  const auto cases = shaderec::load(casesPath);
+  for (size_t k = 0; k < cases.size(); k++) {
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(&cases[k]);
+    if (const char* why = shadeCaseProblem(q, uint32_t(c.im.nMaterials), c.sc.nTextures, c.sc.nLights, dims.data())) {
+      std::fprintf(stderr, "shade: case %zu: %s\n", k, why);
+      return 2;
+    }
+    shaderec::Rec r;
+    shadeCaseRecord(c.sc, q, entries == 1, r.w);
+    out.push_back(r);
+  }
+  shaderec::save(outPath, out);
+  std::printf("{\"shade\": \"ok\", \"cases\": %zu, \"entries\": %d}\n", cases.size(), entries);
   return 0;
 }
 
@@ -810,8 +880,10 @@ int main(int argc, char** argv) {
   if (argc == 8 && std::string(argv[1]) == "tonemap")
     return doTonemap(argv[2], unsigned(std::atoi(argv[3])), unsigned(std::atoi(argv[4])), argv[5], argv[6], argv[7]);
   const bool hits = (argc == 6 || argc == 7) && std::string(argv[1]) == "hits";
-  if (argc != 5 && !hits) {
-    std::fprintf(stderr, "usage: hostsim kat|render|stackcheck <scene.yscn> <params.txt> <out> | hits <scene.yscn> <params.txt> <rays.bin> <out.bin> [walk]\n");
+  const bool shade = (argc == 6 || argc == 7) && std::string(argv[1]) == "shade";
+  if (argc != 5 && !hits && !shade) {
+    std::fprintf(stderr, "usage: hostsim kat|render|stackcheck|shade-kat-cases <scene.yscn> <params.txt> <out> | hits <scene.yscn> <params.txt> <rays.bin> <out.bin> [walk]"
+                         " | shade <scene.yscn> <params.txt> <cases.bin> <out.bin> [entries]\n");
     return 1;
   }
   try {
@@ -826,6 +898,8 @@ int main(int argc, char** argv) {
     c.rc.background = mk3(p.background[0], p.background[1], p.background[2]);
     std::string mode = argv[1];
     if (hits) return doHits(c, argv[4], argv[5], argc == 7 ? std::atoi(argv[6]) : 0);
+    if (shade) return doShade(c, argv[4], argv[5], argc == 7 ? std::atoi(argv[6]) : 0);
+    if (mode == "shade-kat-cases") { shaderec::save(argv[4], katShadeCases(c.im.nMaterials, c.sc.nLights)); return 0; }
     if (mode == "kat") return doKat(c, p, argv[4]);
     if (mode == "render") return doRender(c, p, argv[4]);
     if (mode == "stackcheck") return doRender(c, p, argv[4], true);

@@ -19,7 +19,7 @@ def test_every_kernel_is_in_one_unit(built, name):
     blob = open(os.path.join(ROOT, "yart_amd", name), "rb").read()
     counts = collections.Counter(m.group(1).decode() for m in KD.finditer(blob))
     # an empty or compressed fat binary must fail, not pass: kernels of unit 0, of the streaming passes and of units 4 and 1
-    for needle in ("12k_gmon_blendE", "13k_wf_generateE", "13k_wf_rouletteE", "10k_wf_shadeIL", "16k_wf_extend_leanIL"):
+    for needle in ("12k_gmon_blendE", "13k_wf_generateE", "13k_wf_rouletteE", "10k_wf_shadeIL", "16k_wf_extend_leanIL", "15k_probe_shadingE"):
         assert any(needle in k for k in counts), f"{name}: no kernel descriptor matches {needle}"
     gmon = [k for k in counts if "12k_gmon_blendE" in k]
     assert len(gmon) == 1, gmon

@@ -410,7 +410,8 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_scene_keep_previous", "yart_hip_scene_pixel_motion_device", "yart_hip_scene_pixel_motion_host",
            "yart_hip_temporal_set_pixel_motion",
            "yart_hip_probe_rays",
-           "yart_hip_temporal_set_clip"]
+           "yart_hip_temporal_set_clip",
+           "yart_hip_probe_shading"]
 
 LIB_COUNT_PATH = os.path.join(_HERE, "libyart_hip_count.so")   # instrumented twin (exact test counters)
 _libs = {}
@@ -448,6 +449,7 @@ def lib(instrumented: bool = False):
                                              C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
         L.yart_hip_probe_hits.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.yart_hip_probe_rays.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
+        L.yart_hip_probe_shading.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
         L.yart_hip_probe_sampler.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
         L.yart_hip_tonemap_agx.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
         L.yart_hip_encode_rgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -1145,6 +1147,16 @@ class DeviceScene:
         rp = make_params(p)
         _check(self._L.yart_hip_probe_rays(self._h, C.byref(rp), len(a), a.ctypes.data_as(C.c_void_p), int(walk),
                                            out.ctypes.data_as(C.c_void_p)), self._L)
+        return out
+
+    def probe_shading(self, cases, form: int = 0):
+        """One call of the shading code per case record (include/yart_hip.h yart_hip_probe_shading, oracle/shaderec.hpp):
+        `cases` holds 32 32-bit words per case (any dtype of that size), `form` is the bit set 1 (GGX tables in LDS) | 2 (scene
+        records in LDS) | 4 (matEvaluate + *ImplE). Returns uint32 [n, 32] result words."""
+        a = np.ascontiguousarray(cases).view(np.uint32).reshape(-1, 32)
+        out = np.empty((len(a), 32), np.uint32)
+        _check(self._L.yart_hip_probe_shading(self._h, len(a), a.ctypes.data_as(C.c_void_p), int(form),
+                                              out.ctypes.data_as(C.c_void_p)), self._L)
         return out
 
     def probe_sampler(self, spp, tile, cases, pattern, use_tables=False):

@@ -16,7 +16,8 @@ AnyKernel extendGeneral(bool retry);
 AnyKernel shadowGeneral(bool retry);
 AnyKernel shade(bool sort, bool fit, bool env1);      // unit 4: k_wf_shade<SORT, FIT, ENV1>
 // (unit 0 alone holds the diagnostics of probes.inc, k_probe_rays<MODE> among them: the three walks of traverseScene it
-// instantiates are copies of its own, so no path kernel's code or unit changes with it)
+// instantiates are copies of its own, so no path kernel's code or unit changes with it; likewise k_probe_shading, whose copies
+// of bsdf.hpp / lights.hpp and of the shade kernel's LDS set-up are unit 0's own)
 #if defined(YART_SHADE_REGIONS)
 void shadeRegionsTake(unsigned long long* v48);       // (measurement builds: the shade kernel's region counters live in unit 4)
 #endif

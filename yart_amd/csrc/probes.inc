@@ -3,6 +3,7 @@
 // YartScene, guarded, validate and the kernels of stream_kernels.inc, aov_kernels.inc and moment_kernels.inc).
 #include "tonemap.hpp"         // (ypowf, for k_probe_math)
 #include "probe_record.hpp"
+#include "shade_record.hpp"
 
 namespace {
 
@@ -81,6 +82,46 @@ __global__ void __launch_bounds__(kBlock) k_probe_rays(ProbeRayArgs a) {
   stk.spill = a.spill + gtid; stk.spillStride = gridDim.x * blockDim.x;
   if (gtid >= a.n) return;
   probeRayRecord<MODE>(a.sc, a.cfg, stk, a.rays + size_t(gtid) * 12, a.out + size_t(gtid) * 20);
+}
+
+// one case of the shading code per thread (yart_hip_probe_shading, include/yart_hip.h; shade_record.hpp): bsdf.hpp / lights.hpp as
+// the render kernels include them, in the forms only the device runs. The LDS set-up repeats k_wf_shade's (wavefront_kernels.inc):
+// form bit 1 hands the functions the LDS copy of the glossy lobes' GGX tables with the tables' address behind it, bit 2 repoints the
+// scene's small record tables to LDS copies where they fit the shade kernel's slots (generic pointers, as its non-FIT form does),
+// bit 4 sends a BSDF case through matEvaluate and the *ImplE entries.
+struct ProbeShadeArgs { SceneDev sc; const uint32_t* cases; uint32_t n, form; uint32_t* out; };
+__global__ void __launch_bounds__(kBlock) k_probe_shading(ProbeShadeArgs a) {
+  __shared__ float sLut[LutDev::glassE + 2];
+  __shared__ __attribute__((aligned(16))) uint32_t sMat[kShadeMatSlots * sizeof(MaterialDev) / 4], sTex[kShadeTexSlots * sizeof(TexDev) / 4],
+      sLight[kShadeLightSlots * sizeof(LightDev) / 4], sEnv[kShadeEnvSlots * sizeof(EnvDev) / 4], sInf[kShadeLightSlots];
+  if (a.form & SHADE_FORM_LDS_LUT) {
+    const float* g = a.sc.lut;
+    for (uint32_t k = threadIdx.x; k < LutDev::glassE; k += blockDim.x) sLut[k] = g[k];
+    if (threadIdx.x == 0) {
+      const uint64_t p = reinterpret_cast<uint64_t>(g);
+      reinterpret_cast<uint32_t*>(sLut)[LutDev::glassE] = uint32_t(p); reinterpret_cast<uint32_t*>(sLut)[LutDev::glassE + 1] = uint32_t(p >> 32);
+    }
+    __syncthreads();
+    a.sc.lut = sLut;
+  }
+  if (a.form & SHADE_FORM_LDS_RECORDS) {
+    const bool mOk = a.sc.nMaterials <= kShadeMatSlots, tOk = a.sc.nTextures <= kShadeTexSlots, lOk = a.sc.nLights <= kShadeLightSlots && a.sc.nLights > 0u,
+               eOk = a.sc.nEnvs <= kShadeEnvSlots, iOk = a.sc.nInfinite <= kShadeLightSlots && a.sc.nInfinite > 0u;
+    if (mOk) ldsCopyWords(sMat, a.sc.materials, a.sc.nMaterials * uint32_t(sizeof(MaterialDev) / 4));
+    if (tOk) ldsCopyWords(sTex, a.sc.textures, a.sc.nTextures * uint32_t(sizeof(TexDev) / 4));
+    if (lOk) ldsCopyWords(sLight, a.sc.lights, a.sc.nLights * uint32_t(sizeof(LightDev) / 4));
+    if (eOk) ldsCopyWords(sEnv, a.sc.envs, a.sc.nEnvs * uint32_t(sizeof(EnvDev) / 4));
+    if (iOk) ldsCopyWords(sInf, a.sc.infiniteLights, a.sc.nInfinite);
+    __syncthreads();
+    if (mOk) a.sc.materials = reinterpret_cast<const MaterialDev*>(sMat);
+    if (tOk) a.sc.textures = reinterpret_cast<const TexDev*>(sTex);
+    if (lOk) a.sc.lights = reinterpret_cast<const LightDev*>(sLight);
+    if (eOk) a.sc.envs = reinterpret_cast<const EnvDev*>(sEnv);
+    if (iOk) a.sc.infiniteLights = sInf;
+  }
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  shadeCaseRecord(a.sc, a.cases + size_t(i) * 32, (a.form & SHADE_FORM_IMPL_E) != 0u, a.out + size_t(i) * 32);
 }
 
 // the math the frames rest on, one function at a time (diagnostic, yart_hip_probe_math[_pairs]): the very inline functions the
@@ -206,6 +247,38 @@ int yart_hip_probe_rays(YartScene* scene, const YartRenderParams* params, uint32
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(out, res.p, size_t(n) * 20 * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int yart_hip_probe_shading(YartScene* scene, uint32_t n, const uint32_t* cases, uint32_t form, uint32_t* out) {
+  return guarded([&] {
+    require(scene && cases && out, "probe_shading: null pointer");
+    require((form & ~SHADE_FORM_ALL) == 0u, "probe_shading: unknown form bits (1 LDS tables, 2 LDS records, 4 matEvaluate + *ImplE)");
+    require(n <= (1u << 20), "probe_shading: more than 2^20 cases");
+    std::lock_guard<std::mutex> lock(scene->mu);
+    YartScene& s = *scene;
+    // everything a case names is checked against the scene before a device is touched: no lane reads outside the scene
+    std::vector<uint32_t> dims;
+    for (const TexDev& t : s.host.textures) { dims.push_back(t.width); dims.push_back(t.height); }
+    for (uint32_t i = 0; i < n; i++) {
+      const uint32_t* q = cases + size_t(i) * 32;
+      if (const char* why = shadeCaseProblem(q, s.host.nMaterials, uint32_t(s.host.textures.size()), s.host.nLights, dims.data()))
+        throw std::invalid_argument(std::string("probe_shading: case ") + std::to_string(i) + ": " + why);
+      // (a texture that only material bundles sample has no footprint records of its own, host_scene.hpp)
+      require(q[0] != SHADE_TEX || s.dev.texQuads == nullptr || s.host.textures[q[1]].quadOffset != kNoTexQuads,
+              "probe_shading: a TEX case names a texture without footprint records of its own");
+    }
+    if (n == 0) return;
+    HIP_CHECK(hipSetDevice(s.device));
+    DevBuf<uint32_t> in, res;
+    in.ensure(size_t(n) * 32); res.ensure(size_t(n) * 32);
+    HIP_CHECK(hipMemcpy(in.p, cases, size_t(n) * 32 * 4, hipMemcpyHostToDevice));
+    ProbeShadeArgs a{};
+    a.sc = s.dev; a.cases = in.p; a.n = n; a.form = form; a.out = res.p;
+    hipLaunchKernelGGL(k_probe_shading, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, a);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out, res.p, size_t(n) * 32 * 4, hipMemcpyDeviceToHost));
   });
 }
 
