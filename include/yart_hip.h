@@ -340,9 +340,9 @@ int yart_hip_scene_update_meshes(YartScene* scene, const YartSceneMeshUpdate* up
  * Any other failure (YART_E_HIP) leaves the scene unusable, as for the other update entries.
  * Not kept current: the default pipeline's lobe-share heuristic stays as at create (every pipeline renders the same frame), as for
  * yart_hip_scene_update_meshes.
- * Out of scope — re-create the scene: changed texture assignments or texels of material textures, changes that flip a material's
- * transparency or thin_transmission, lights added or removed, face_light changes, a resized environment image, and the replicas of a
- * YartMulti. */
+ * Out of scope — re-create the scene: changed texture assignments, changes that flip a material's transparency or
+ * thin_transmission, lights added or removed, face_light changes, a resized environment image, and the replicas of a YartMulti
+ * (the texels of material textures: yart_hip_scene_update_textures below). */
 typedef struct YartEnvImageUpdate {
   uint32_t texture;                  /* index into the scene's textures: a float RGB texture that at least one image light uses */
   uint32_t width, height;            /* the texture's, as at create */
@@ -359,6 +359,46 @@ typedef struct YartSceneLightingUpdate {
   uint32_t flags;                    /* none defined: must be 0 */
 } YartSceneLightingUpdate;
 int yart_hip_scene_update_lighting(YartScene* scene, const YartSceneLightingUpdate* update, void* stream, YartSceneUpdateStats* stats /* may be NULL */);
+
+/* New texels for 8-bit material textures of a scene that is on the device — a video screen, a flip-book decal, an animated emission
+ * or roughness map, a cut-out that grows or dissolves — without yart_hip_scene_destroy + yart_hip_scene_create. Afterwards the scene
+ * holds, and renders in every pipeline, the bits of a scene freshly created from the same description. The four update entries combine
+ * in any order. Per listed texture:
+ * texels: the pixels are copied into the texture's place (from host memory, or with YART_TEXELS_ON_DEVICE from memory of the scene's
+ * device: a decoded video frame, a procedural map); the neighbouring textures and the pad bytes behind a texture whose byte count is
+ * no multiple of 4 are untouched. The library's host copy follows (one device-to-host copy for device pixels).
+ * footprint records: rewritten where the scene has them, once per place that holds the texture — its own array, and every bundle of a
+ * base-colour / normal / metal-rough triple it is a member of (several materials share a bundle).
+ * alpha test: for a 4-channel texture that is some material's tex_base, "an alpha byte below 255" is decided anew by one pass over the
+ * texels on the device. Only where a material's flag CHANGES, the chain that scene creation derives from it is re-derived on the
+ * device, in place, for the meshes that have a face of such a material: the leaf records' alpha bit, the alpha bit of every BVH node's
+ * link word and the mesh's alpha flag (the shadow rays' pruning reads them). New texels that leave every flag as it was launch nothing
+ * beyond the copy, the footprint records and that one pass.
+ * Locking, `stream`, `stats` and "returns after the work has completed on `stream`" as for yart_hip_scene_update_lighting (`stream` is
+ * synchronised once more where a flag changed: the flags are read back before the chain is launched).
+ * YART_E_INVALID, with the scene and the device exactly as they were (everything is checked before the first write): scene or update
+ * NULL; struct_size too small; flags other than the defined ones; n_textures 0, or its pointer NULL; a texture index that is out of
+ * range (the scene's textures as given at create: the entries behind them, which creation adds for bundles, count as out of range) or
+ * listed twice; a float texture (image lights' maps: yart_hip_scene_update_lighting); a width, height or channel count that is not
+ * the texture's; pixels NULL; stats->struct_size below 8.
+ * Any other failure (YART_E_HIP) leaves the scene unusable, as for the other update entries.
+ * Not kept current: the default pipeline's lobe-share heuristic, as for the other entries.
+ * Out of scope — re-create the scene: changed texture assignments, resized textures, thin_transmission / transparency flips, and the
+ * replicas of a YartMulti. */
+#define YART_TEXELS_ON_DEVICE 1u     /* YartTextureUpdate::flags: pixels is device memory of the scene's device */
+typedef struct YartTextureUpdate {
+  uint32_t texture;                  /* index into the scene's textures as given at create */
+  uint32_t width, height, channels;  /* the texture's, as at create */
+  const void* pixels;                /* 8-bit texels, row-major, channels bytes per texel, required */
+  uint32_t flags;                    /* YART_TEXELS_ON_DEVICE, else pixels is host memory */
+} YartTextureUpdate;
+typedef struct YartSceneTextureUpdate {
+  uint32_t struct_size;              /* sizeof(YartSceneTextureUpdate) */
+  uint32_t n_textures;               /* textures listed: at least 1 */
+  const YartTextureUpdate* textures; /* each texture at most once */
+  uint32_t flags;                    /* none defined: must be 0 */
+} YartSceneTextureUpdate;
+int yart_hip_scene_update_textures(YartScene* scene, const YartSceneTextureUpdate* update, void* stream, YartSceneUpdateStats* stats /* may be NULL */);
 
 /* The scene remembers the frame it holds as its PREVIOUS frame: its node array and its vertex positions are copied into scene-owned
  * arrays — two device-to-device copies on `stream`; the call returns after they have completed. The arrays are allocated by the
@@ -706,6 +746,16 @@ int yart_hip_probe_lighting(YartScene* scene, YartLightingProbe* probe);
 /* the host part of an image replacement on its own (measurements): the three sequential binary32 sums over n_texels RGB texels in
  * row-major order, as scene creation and yart_hip_scene_update_lighting take them for an image light's average radiance */
 int yart_hip_probe_texel_sum(const float* pixels, uint64_t n_texels, float* sum3_out);
+/* diagnostic read-back of the 8-bit texels, from the device (not from the library's host copy), for yart_hip_scene_update_textures.
+ * The caller sets struct_size; the call fills in both counts and copies into every array pointer that is not NULL — a first call with
+ * both NULL gives the sizes. tex_u8: the byte array of all 8-bit textures (each padded to a multiple of 4 bytes; at least one
+ * element); textures: TexDev records (32 bytes, as in YartLightingProbe), the entries creation adds for bundles included. */
+typedef struct YartTexturesProbe {
+  uint32_t struct_size;              /* sizeof(YartTexturesProbe) */
+  uint64_t n_tex_u8, n_textures;
+  uint8_t* tex_u8; void* textures;
+} YartTexturesProbe;
+int yart_hip_probe_textures(YartScene* scene, YartTexturesProbe* probe);
 /* measurement builds (-DYART_SHADE_REGIONS=1, tools/shade_regions.py) only: wave cycles [0..15], visits [16..31] and
  * active lanes [32..47] per code region of the shade kernel since the last call; YART_E_INVALID in the product build */
 int yart_hip_debug_shade_regions(uint64_t* out48);

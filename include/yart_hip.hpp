@@ -112,6 +112,17 @@ class DeviceScene {
     check(yart_hip_scene_update_lighting(h_, &u, stream, &st));
     return st;
   }
+  // yart_hip_scene_update_textures: new texels for 8-bit material textures (each texture at most once; size and channels as at create;
+  // YART_TEXELS_ON_DEVICE in an entry's flags: its pixels are memory of the scene's device). Returns the update's statistics.
+  YartSceneUpdateStats updateTextures(const std::vector<YartTextureUpdate>& textures, void* stream = nullptr) {
+    YartSceneTextureUpdate u{};
+    u.struct_size = uint32_t(sizeof(u));
+    u.n_textures = uint32_t(textures.size()); u.textures = textures.empty() ? nullptr : textures.data();
+    YartSceneUpdateStats st{};
+    st.struct_size = uint32_t(sizeof(st));
+    check(yart_hip_scene_update_textures(h_, &u, stream, &st));
+    return st;
+  }
   // yart_hip_scene_keep_previous: the scene remembers the frame it holds as its previous frame; once per frame, before its updates
   void keepPrevious(void* stream = nullptr) { check(yart_hip_scene_keep_previous(h_, stream)); }
   // yart_hip_scene_pixel_motion_host: the per-pixel motion records (8 floats per pixel) between the kept frame and the scene as it

@@ -131,7 +131,22 @@ class LightingProbe(C.Structure):
                 [(n, C.c_void_p) for n in LIGHTING_PROBE_ARRAYS])
 
 
+class TextureUpdate(C.Structure):
+    _fields_ = [("texture", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("channels", C.c_uint32), ("pixels", C.c_void_p),
+                ("flags", C.c_uint32)]
+
+
+class SceneTextureUpdate(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_textures", C.c_uint32), ("textures", C.POINTER(TextureUpdate)), ("flags", C.c_uint32)]
+
+
+class TexturesProbe(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_tex_u8", C.c_uint64), ("n_textures", C.c_uint64), ("tex_u8", C.c_void_p),
+                ("textures", C.c_void_p)]
+
+
 UPDATE_REBUILD_TOP = 1
+TEXELS_ON_DEVICE = 1
 # the records of DeviceScene.lighting_records(): csrc/scene_types.hpp MaterialDev (flags: 1 thin, 2 alpha-tested, 4 emissive,
 # 8 transparent), LightDev, EnvDev and TexDev (quad_offset in 16-byte units, 0xffffffff: no footprint records of its own)
 MATERIAL_DEV_DTYPE = np.dtype([("base", np.float32, 3), ("transmission", np.float32), ("emission", np.float32, 3), ("metallic", np.float32),
@@ -407,6 +422,7 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_scene_update", "yart_hip_probe_scene_graph",
            "yart_hip_scene_update_meshes", "yart_hip_probe_mesh",
            "yart_hip_scene_update_lighting", "yart_hip_probe_lighting", "yart_hip_probe_texel_sum",
+           "yart_hip_scene_update_textures", "yart_hip_probe_textures",
            "yart_hip_scene_keep_previous", "yart_hip_scene_pixel_motion_device", "yart_hip_scene_pixel_motion_host",
            "yart_hip_temporal_set_pixel_motion",
            "yart_hip_probe_rays",
@@ -509,6 +525,8 @@ def lib(instrumented: bool = False):
         L.yart_hip_scene_update_lighting.argtypes = [C.c_void_p, C.POINTER(SceneLightingUpdate), C.c_void_p, C.POINTER(SceneUpdateStats)]
         L.yart_hip_probe_lighting.argtypes = [C.c_void_p, C.POINTER(LightingProbe)]
         L.yart_hip_probe_texel_sum.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+        L.yart_hip_scene_update_textures.argtypes = [C.c_void_p, C.POINTER(SceneTextureUpdate), C.c_void_p, C.POINTER(SceneUpdateStats)]
+        L.yart_hip_probe_textures.argtypes = [C.c_void_p, C.POINTER(TexturesProbe)]
         L.yart_hip_scene_keep_previous.argtypes = [C.c_void_p, C.c_void_p]
         L.yart_hip_scene_pixel_motion_device.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.yart_hip_scene_pixel_motion_host.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.c_uint32, C.c_uint32, C.c_void_p]
@@ -787,6 +805,47 @@ class DeviceScene:
             setattr(pr, name, a.ctypes.data_as(C.c_void_p) if len(a) else None)
         _check(self._L.yart_hip_probe_lighting(self._h, C.byref(pr)), self._L)
         out["total_power"] = float(pr.total_power)
+        return out
+
+    def update_textures(self, textures, stream=None):
+        """yart_hip_scene_update_textures: new texels for 8-bit material textures of the scene in place. ``textures``: {texture index:
+        pixels} with the texture's size and channel count as at create — a NumPy uint8 array of shape (H, W, C), or (H, W) for one
+        channel, is taken from host memory; a torch uint8 tensor of that shape on the scene's device (contiguous) is taken from device
+        memory. Footprint records, the materials' alpha-test flag and what the meshes derive from it follow. The call's statistics
+        are in ``self.last_update``."""
+        keep, td = [], (TextureUpdate * max(len(textures), 1))()
+        for k, (tex, px) in enumerate(dict(textures).items()):
+            if hasattr(px, "data_ptr"):                       # a torch tensor: device pixels
+                import torch
+                if px.dtype != torch.uint8 or not px.is_cuda or not px.is_contiguous():
+                    raise YartError(YART_E_INVALID, f"update_textures: texture {tex}: a tensor has to be contiguous uint8 on the scene's device")
+                shape, ptr, flags = tuple(px.shape), px.data_ptr(), TEXELS_ON_DEVICE
+            else:
+                px = np.ascontiguousarray(px)
+                if px.dtype != np.uint8:
+                    raise YartError(YART_E_INVALID, f"update_textures: texture {tex}: not a uint8 array")
+                shape, ptr, flags = px.shape, px.ctypes.data, 0
+            if len(shape) == 2:
+                shape = shape + (1,)
+            if len(shape) != 3:
+                raise YartError(YART_E_INVALID, f"update_textures: texture {tex}: not an (H, W, C) or (H, W) array")
+            keep.append(px)
+            td[k] = TextureUpdate(int(tex), shape[1], shape[0], shape[2], ptr, flags)
+        up = SceneTextureUpdate(C.sizeof(SceneTextureUpdate), len(textures), td, 0)
+        st = SceneUpdateStats(C.sizeof(SceneUpdateStats))
+        _check(self._L.yart_hip_scene_update_textures(self._h, C.byref(up), stream, C.byref(st)), self._L)
+        self.last_update = dict(launches=st.launches, ms_total=st.ms_total, ms_device=st.ms_device)
+
+    def texture_records(self):
+        """yart_hip_probe_textures: the 8-bit texels and the texture records, read back from the device: dict(tex_u8: uint8 (every
+        texture padded to a multiple of 4 bytes), textures: TEX_DEV_DTYPE (offset: a texture's first byte of tex_u8; behind the
+        scene's textures the entries creation adds for bundles))."""
+        pr = TexturesProbe(C.sizeof(TexturesProbe))
+        _check(self._L.yart_hip_probe_textures(self._h, C.byref(pr)), self._L)
+        out = dict(tex_u8=np.zeros(int(pr.n_tex_u8), np.uint8), textures=np.zeros(int(pr.n_textures), TEX_DEV_DTYPE))
+        for name, a in out.items():
+            setattr(pr, name, a.ctypes.data_as(C.c_void_p) if len(a) else None)
+        _check(self._L.yart_hip_probe_textures(self._h, C.byref(pr)), self._L)
         return out
 
     def keep_previous(self, stream=None):

@@ -24,9 +24,10 @@
 //                multi_device.inc       several GPUs behind one handle, with its pixel pack / unpack / copy kernels
 //                postprocess.inc        tonemap / encode, the a-trous denoiser (denoise_kernels.inc) and temporal accumulation
 //                                       (temporal_kernels.inc): kernels, drivers and entries
-//                scene_update_kernels.inc, mesh_update_kernels.inc, lighting_update_kernels.inc, scene_motion_kernels.inc      a scene's
-//                                       next frame in place: new transforms, new vertices, new materials / light emission /
-//                                       environment images, and the per-pixel motion between the two frames
+//                scene_update_kernels.inc, mesh_update_kernels.inc, lighting_update_kernels.inc, texture_update_kernels.inc,
+//                scene_motion_kernels.inc      a scene's next frame in place: new transforms, new vertices, new materials / light
+//                                       emission / environment images, new texels of material textures, and the per-pixel motion
+//                                       between the two frames
 //                probes.inc             the diagnostic kernels k_probe_* and the yart_hip_probe_* entries
 //   units 1-4  wavefront_units.hip under -DYART_TU=1..4: the path kernels, which are templates and are emitted where they are
 //              instantiated — 1 the lean closest-hit kernels k_wf_extend_lean<MODE, NODES>, 2 the lean any-hit kernels
@@ -52,6 +53,7 @@
 #include "host_scene.hpp"
 #include "mesh_update.hpp"
 #include "lighting_update.hpp"
+#include "texture_update.hpp"
 #include "integrator.hpp"
 #include "scene_file.hpp"
 #include "gltf_reader.hpp"
@@ -321,6 +323,13 @@ struct LightingUpdateState {
   std::vector<LuSum> envSum; std::vector<uint8_t> envSumKnown;
 };
 
+// What yart_hip_scene_update_textures keeps per scene (texture_update_kernels.inc): the words its kernels report in, and per mesh
+// the materials of its faces, listed when a material's alpha flag first changes.
+struct TextureUpdateState {
+  DevBuf<uint32_t> result;
+  std::vector<std::vector<uint32_t>> meshMaterials;
+};
+
 struct YartScene {
   int device = 0;
   HostImage host;
@@ -362,6 +371,7 @@ struct YartScene {
   SceneUpdateTables su;
   MeshUpdateState meshUp;
   LightingUpdateState lightUp;
+  TextureUpdateState texUp;
   // yart_hip_scene_keep_previous (scene_motion_kernels.inc): the node and vertex arrays of the previous frame, allocated by the first
   // call; the nodes' composed transforms and the host entry's staging buffer of yart_hip_scene_pixel_motion_*
   DevBuf<NodeDev> nodesPrev; DevBuf<f4> vPosPrev, smChains; DevBuf<float> smStage;
@@ -1637,5 +1647,6 @@ int yart_hip_bvh_build_host(const float* positions, uint32_t n_verts, const uint
 #include "scene_update_kernels.inc"
 #include "mesh_update_kernels.inc"
 #include "lighting_update_kernels.inc"
+#include "texture_update_kernels.inc"
 #include "scene_motion_kernels.inc"
 #include "probes.inc"
