@@ -1108,6 +1108,101 @@ int yart_hip_temporal_accumulate_moments_host(YartTemporal* temporal, const Yart
                                               const YartAovBuffers* aovs, const YartTemporalMomentParams* params, float* out_rgba,
                                               float* out_variance, uint32_t* out_length);
 
+/* The last stage of a sequence, after the denoiser: auto-exposure. A handle meters a linear-HDR RGBA32F frame on the device with a
+ * log-luminance histogram, turns it into an exposure with eye-style temporal adaptation — the state stays on the device —, and
+ * one kernel applies the gain, the AgX tonemap and the 8-bit encoding (what scale + yart_hip_tonemap_agx + yart_hip_encode_rgb8
+ * do in three passes).
+ * DEFINITION. Every operation is one individually rounded binary32 operation in the order written (no FMA contraction) unless it
+ * says binary64; log2f and expf have glibc's values (csrc/tonemap.hpp ylog2f, csrc/ymath.hpp yexpf). csrc/exposure.hpp states
+ * it; yart_amd/exposure.py exposure_reference / apply_reference are the NumPy statement the tests compare with, on bits. The
+ * histogram has B = 256 bins, fixed.
+ *   Formed once per call on the host:
+ *     bins_per_ev = 256.0f / (ev_max - ev_min);   bin_width = (ev_max - ev_min) / 256.0f;   key_ev = log2f(key)
+ *     a_up = 1.0f - expf(-(dt * speed_up));   a_down = 1.0f - expf(-(dt * speed_down))      dt: seconds since the previous frame
+ *   Meter, for every pixel p of the metering window:
+ *     Y = (0.2126f * r + 0.7152f * g) + 0.0722f * b
+ *     p is ignored (and counted in n_ignored) if r, g or b is not finite or if !(Y > 0); alpha is not read. Otherwise
+ *     ev = log2f(Y);   t = (ev - ev_min) * bins_per_ev;   bin = t < 0 ? 0 : (t >= 256.0f ? 255 : uint32_t(t));   hist[bin] += 1
+ *   Resolve:
+ *     N = sum of hist;   lo = floor(double(trim_low) * N);   hi = N - floor(double(trim_high) * N)     (hi > lo whenever N >= 1)
+ *     the bins in ascending order with a running count c:   k_b = |[c, c + hist[b]) n [lo, hi)|
+ *       centre_b = ev_min + (float(b) + 0.5f) * bin_width;   S += double(k_b) * double(centre_b)      (binary64, ascending)
+ *     K = hi - lo;   mean_ev = float(S / double(K))
+ *     target = min(gain_ev_max, max(gain_ev_min, (key_ev - mean_ev) + compensation_ev))
+ *   State (cur_ev, valid):
+ *     N == 0:    cur_ev, target_ev, mean_ev, gain and frames stay as they are and YART_EXPOSURE_EMPTY is set in flags
+ *     !valid (a new handle, or one after reset):   cur_ev = target, valid = 1
+ *     otherwise: d = target - cur_ev;   cur_ev = cur_ev + d * (d > 0 ? a_up : a_down)
+ *     then:      gain = expf(cur_ev * 0.6931472f);   frames += 1;   flags = 0
+ *     n_counted = N and n_ignored are the last meter call's in every case.
+ *   Apply, per pixel:  c = (r * gain, g * gain, b * gain);   look 0 .. 2: ldr = (AgX(c, look), 1);   look -1: ldr = (c, a);
+ *     rgb8 = the 8-bit encoding (yart_hip_encode_rgb8's) of each ldr channel. gain is read from the handle's device record; a handle
+ *     that has never metered (or was reset) applies gain 1.
+ * The defaults below are conventions (a +-16 EV range, the middle 80 % of the counted pixels, the 18 % grey key, an eye that adapts
+ * faster to light than to dark); nothing here is tuned.
+ * Memory: per handle, on the device, the accumulating histogram and the last call's (1 KB each) and one 40-byte record, allocated by
+ * the first call that needs a device. */
+#define YART_EXPOSURE_EMPTY 1u              /* YartExposureState::flags: the last meter call counted no pixel */
+#define YART_EXPOSURE_BINS 256u
+#define YART_EXPOSURE_DEFAULT_EV_MIN (-16.0f)
+#define YART_EXPOSURE_DEFAULT_EV_MAX 16.0f
+#define YART_EXPOSURE_DEFAULT_TRIM_LOW 0.10f
+#define YART_EXPOSURE_DEFAULT_TRIM_HIGH 0.10f
+#define YART_EXPOSURE_DEFAULT_KEY 0.18f
+#define YART_EXPOSURE_DEFAULT_COMPENSATION_EV 0.0f
+#define YART_EXPOSURE_DEFAULT_GAIN_EV_MIN (-16.0f)
+#define YART_EXPOSURE_DEFAULT_GAIN_EV_MAX 16.0f
+#define YART_EXPOSURE_DEFAULT_SPEED_UP 3.0f
+#define YART_EXPOSURE_DEFAULT_SPEED_DOWN 1.0f
+typedef struct YartExposureParams {
+  uint32_t struct_size;        /* sizeof(YartExposureParams) */
+  float ev_min, ev_max;        /* the histogram's range: finite, ev_min < ev_max */
+  float trim_low, trim_high;   /* the fractions of the counted pixels left out at either end: each in [0, 1), sum < 1 */
+  float key;                   /* the luminance the mean is mapped to: finite, > 0 */
+  float compensation_ev;       /* finite */
+  float gain_ev_min, gain_ev_max;   /* the target's clamp: finite, min <= max */
+  float speed_up, speed_down;  /* adaptation rates in 1/s towards a larger / smaller exposure: finite, >= 0 */
+  uint32_t x0, y0, x1, y1;     /* the metering window, half open; all 0: the whole frame; else x0 < x1 <= width, y0 < y1 <= height */
+} YartExposureParams;
+typedef struct YartExposureState {
+  uint32_t struct_size;        /* sizeof(YartExposureState), set by the caller */
+  float cur_ev, target_ev, mean_ev, gain;
+  uint32_t n_counted, n_ignored, frames, flags;   /* frames: the meter calls that counted a pixel since create / reset */
+} YartExposureState;
+typedef struct YartExposure YartExposure;
+/* device < 0: the device current at the first call that needs one. No device is touched. */
+int yart_hip_exposure_create(int device, YartExposure** out);
+void yart_hip_exposure_destroy(YartExposure* exposure);
+/* Back to a new handle: the next meter call snaps to its target, and until then apply uses gain 1. */
+int yart_hip_exposure_reset(YartExposure* exposure);
+/* Meter one frame (DEVICE pointer, 16-byte aligned) on `stream` (hipStream_t, may be NULL) and step the state by dt seconds; returns
+ * after completion on that stream. YART_E_INVALID, with a message and before any device is touched: a NULL exposure, d_rgba or
+ * params; a struct_size smaller than YartExposureParams; a width or height of 0 (or more than 2^28 pixels); a parameter outside the
+ * limits given with the struct; a dt that is not finite or negative. YART_E_NO_DEVICE without a HIP device. */
+int yart_hip_exposure_meter_device(YartExposure* exposure, const float* d_rgba, uint32_t width, uint32_t height,
+                                   const YartExposureParams* params, float dt, void* stream);
+/* Same, HOST pointer: the frame is copied to the handle's device and metered there. */
+int yart_hip_exposure_meter_host(YartExposure* exposure, const float* rgba, uint32_t width, uint32_t height,
+                                 const YartExposureParams* params, float dt);
+/* Apply the handle's gain, the tonemap (look -1: none) and the encoding to a frame (DEVICE pointers; d_ldr_rgba, RGBA32F, or
+ * d_rgb8, 3 bytes per pixel, may be NULL, not both; d_ldr_rgba may be d_rgba). YART_E_INVALID, before any device is touched: a NULL
+ * exposure or d_rgba, both outputs NULL, a width or height of 0 (or more than 2^28 pixels), a look outside -1 .. 2. */
+int yart_hip_exposure_apply_device(YartExposure* exposure, const float* d_rgba, uint32_t width, uint32_t height, int look,
+                                   float* d_ldr_rgba /* may be NULL */, uint8_t* d_rgb8 /* may be NULL */, void* stream);
+/* Same, HOST pointers */
+int yart_hip_exposure_apply_host(YartExposure* exposure, const float* rgba, uint32_t width, uint32_t height, int look, float* ldr_rgba,
+                                 uint8_t* rgb8);
+/* The state record, and in hist256 (may be NULL) the 256 bins of the last meter call. */
+int yart_hip_exposure_get(YartExposure* exposure, YartExposureState* state, uint32_t* hist256);
+/* Diagnostics (tools/exposure_bench.py): the device time in ms per launch, over `repeats` launches between two events on the NULL
+ * stream, of what = 0 / 1: the histogram kernel's two forms (per-wave counting / interleaved replicas), 2: the resolve kernel,
+ * 3: the apply kernel with both outputs, 4: the kernels of yart_hip_tonemap_agx and yart_hip_encode_rgb8 one after the other.
+ * DEVICE pointers; d_ldr_rgba and d_rgb8 are needed for 3 and 4. The handle's state may change; after 0 / 1 yart_hip_exposure_get
+ * reports the sum of the `repeats` histograms (the tests compare both forms' counts with it). */
+int yart_hip_debug_exposure_time(YartExposure* exposure, const float* d_rgba, uint32_t width, uint32_t height,
+                                 const YartExposureParams* params, int what, uint32_t repeats, float* d_ldr_rgba, uint8_t* d_rgb8,
+                                 float* ms_out);
+
 const char* yart_hip_last_error(void);
 int yart_hip_abi_version(void);
 int yart_hip_device_count(void);

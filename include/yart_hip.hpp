@@ -335,6 +335,54 @@ class Temporal {
   uint32_t m_width, m_height;
 };
 
+// Auto-exposure for a sequence of frames (yart_hip_exposure_*), the stage after the denoiser: meter builds a log-luminance
+// histogram of a linear-HDR frame on the device and steps the exposure by dt seconds; apply multiplies by the gain, tonemaps
+// (AgX; look -1: none) and encodes to 8 bits in one kernel. The state stays on the device.
+inline YartExposureParams exposureDefaults() {
+  YartExposureParams p{};
+  p.struct_size = uint32_t(sizeof(p)); p.ev_min = YART_EXPOSURE_DEFAULT_EV_MIN; p.ev_max = YART_EXPOSURE_DEFAULT_EV_MAX;
+  p.trim_low = YART_EXPOSURE_DEFAULT_TRIM_LOW; p.trim_high = YART_EXPOSURE_DEFAULT_TRIM_HIGH; p.key = YART_EXPOSURE_DEFAULT_KEY;
+  p.compensation_ev = YART_EXPOSURE_DEFAULT_COMPENSATION_EV; p.gain_ev_min = YART_EXPOSURE_DEFAULT_GAIN_EV_MIN;
+  p.gain_ev_max = YART_EXPOSURE_DEFAULT_GAIN_EV_MAX; p.speed_up = YART_EXPOSURE_DEFAULT_SPEED_UP; p.speed_down = YART_EXPOSURE_DEFAULT_SPEED_DOWN;
+  return p;                                 // x0 = y0 = x1 = y1 = 0: the whole frame
+}
+struct ExposedFrame { std::vector<float> ldr; std::vector<uint8_t> rgb8; };
+class Exposure {
+ public:
+  explicit Exposure(int device = 0) { check(yart_hip_exposure_create(device, &m_handle)); }
+  ~Exposure() { yart_hip_exposure_destroy(m_handle); }
+  Exposure(const Exposure&) = delete;
+  Exposure& operator=(const Exposure&) = delete;
+  Exposure(Exposure&& o) noexcept : m_handle(o.m_handle) { o.m_handle = nullptr; }
+
+  void reset() { check(yart_hip_exposure_reset(m_handle)); }
+  // one frame, host buffer (width * height * 4 floats); dt: seconds since the previous frame
+  YartExposureState meter(const std::vector<float>& rgba, uint32_t width, uint32_t height, const YartExposureParams& params, float dt) {
+    if (rgba.size() != size_t(width) * height * 4) throw Error(YART_E_INVALID, "Exposure::meter: the frame does not have width * height * 4 values");
+    check(yart_hip_exposure_meter_host(m_handle, rgba.data(), width, height, &params, dt));
+    return state();
+  }
+  ExposedFrame apply(const std::vector<float>& rgba, uint32_t width, uint32_t height, int look) {
+    const size_t n = size_t(width) * height;
+    if (rgba.size() != n * 4) throw Error(YART_E_INVALID, "Exposure::apply: the frame does not have width * height * 4 values");
+    ExposedFrame out{std::vector<float>(n * 4), std::vector<uint8_t>(n * 3)};
+    check(yart_hip_exposure_apply_host(m_handle, rgba.data(), width, height, look, out.ldr.data(), out.rgb8.data()));
+    return out;
+  }
+  // the state record; histogram (may be null): the 256 bins of the last meter call
+  YartExposureState state(std::vector<uint32_t>* histogram = nullptr) {
+    YartExposureState s{};
+    s.struct_size = uint32_t(sizeof(s));
+    if (histogram) histogram->assign(YART_EXPOSURE_BINS, 0u);
+    check(yart_hip_exposure_get(m_handle, &s, histogram ? histogram->data() : nullptr));
+    return s;
+  }
+  YartExposure* handle() const { return m_handle; }
+
+ private:
+  YartExposure* m_handle = nullptr;
+};
+
 // The scene replicated on several GPUs of this node (yart_hip_multi_*): TileRenderer's worker pool with a GPU per worker.
 class MultiDeviceScene {
  public:

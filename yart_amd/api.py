@@ -32,6 +32,8 @@ from .moments import moments_reference  # noqa: F401 (the NumPy statement of ren
 from .temporal import (DEFAULT_ALPHA_MIN, DEFAULT_CLIP_GAMMA, DEFAULT_CLIP_RADIUS, DEFAULT_MAX_HISTORY, DEFAULT_MIN_MOMENT_HISTORY, DEFAULT_NORMAL_COS_MIN,
                        DEFAULT_PLANE_TOLERANCE, MOTION_WORDS, clip_of, node_motion, temporal_moments_reference,
                        temporal_reference)  # noqa: F401 (the NumPy statement of TemporalAccumulator.accumulate / accumulate_into)
+from .exposure import (ExposureState, apply_reference, exposure_reference, look_index,
+                       params_of as exposure_params_of)  # noqa: F401 (the NumPy statement of AutoExposure.meter / apply)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libyart_hip.so")
@@ -343,6 +345,30 @@ class TemporalClip(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_uint32), ("gamma", C.c_float)]
 
 
+class ExposureParams(C.Structure):
+    """YartExposureParams (include/yart_hip.h): the knobs of the auto-exposure's meter call."""
+    _fields_ = [("struct_size", C.c_uint32), ("ev_min", C.c_float), ("ev_max", C.c_float), ("trim_low", C.c_float),
+                ("trim_high", C.c_float), ("key", C.c_float), ("compensation_ev", C.c_float), ("gain_ev_min", C.c_float),
+                ("gain_ev_max", C.c_float), ("speed_up", C.c_float), ("speed_down", C.c_float),
+                ("x0", C.c_uint32), ("y0", C.c_uint32), ("x1", C.c_uint32), ("y1", C.c_uint32)]
+
+
+class ExposureStateRecord(C.Structure):
+    """YartExposureState (include/yart_hip.h): what yart_hip_exposure_get reports."""
+    _fields_ = [("struct_size", C.c_uint32), ("cur_ev", C.c_float), ("target_ev", C.c_float), ("mean_ev", C.c_float),
+                ("gain", C.c_float), ("n_counted", C.c_uint32), ("n_ignored", C.c_uint32), ("frames", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+def make_exposure_params(**params) -> ExposureParams:
+    """``yart_amd.exposure.params_of``'s names (``window``: (x0, y0, x1, y1) or None for the whole frame)."""
+    p = exposure_params_of(**params)
+    win = p["window"] or (0, 0, 0, 0)
+    return ExposureParams(C.sizeof(ExposureParams), *(float(p[k]) for k in ("ev_min", "ev_max", "trim_low", "trim_high", "key",
+                                                                            "compensation_ev", "gain_ev_min", "gain_ev_max",
+                                                                            "speed_up", "speed_down")), *(int(v) for v in win))
+
+
 PIXEL_MOTION_AOVS = ("position", "normal", "coverage", "ids")      # what yart_hip_scene_pixel_motion_* reads
 FLAG_TEMPORAL_DEMODULATE = 1
 TEMPORAL_AOVS = ("position", "normal", "depth", "coverage", "ids")     # + "albedo" when demodulating
@@ -427,7 +453,11 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_temporal_set_pixel_motion",
            "yart_hip_probe_rays",
            "yart_hip_temporal_set_clip",
-           "yart_hip_probe_shading"]
+           "yart_hip_probe_shading",
+           "yart_hip_exposure_create", "yart_hip_exposure_destroy", "yart_hip_exposure_reset",
+           "yart_hip_exposure_meter_device", "yart_hip_exposure_meter_host",
+           "yart_hip_exposure_apply_device", "yart_hip_exposure_apply_host", "yart_hip_exposure_get",
+           "yart_hip_debug_exposure_time"]
 
 LIB_COUNT_PATH = os.path.join(_HERE, "libyart_hip_count.so")   # instrumented twin (exact test counters)
 _libs = {}
@@ -532,6 +562,19 @@ def lib(instrumented: bool = False):
         L.yart_hip_scene_pixel_motion_host.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.c_uint32, C.c_uint32, C.c_void_p]
         L.yart_hip_temporal_set_pixel_motion.argtypes = [C.c_void_p, C.POINTER(TemporalPixelMotion)]
         L.yart_hip_temporal_set_clip.argtypes = [C.c_void_p, C.POINTER(TemporalClip)]
+        L.yart_hip_exposure_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        L.yart_hip_exposure_destroy.argtypes = [C.c_void_p]
+        L.yart_hip_exposure_destroy.restype = None
+        L.yart_hip_exposure_reset.argtypes = [C.c_void_p]
+        L.yart_hip_exposure_meter_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(ExposureParams), C.c_float,
+                                                     C.c_void_p]
+        L.yart_hip_exposure_meter_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(ExposureParams), C.c_float]
+        L.yart_hip_exposure_apply_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]
+        L.yart_hip_exposure_apply_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
+        L.yart_hip_exposure_get.argtypes = [C.c_void_p, C.POINTER(ExposureStateRecord), C.c_void_p]
+        L.yart_hip_debug_exposure_time.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(ExposureParams), C.c_int,
+                                                   C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         L.yart_hip_bvh_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.yart_hip_bvh_copy.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         _libs[path] = L
@@ -1106,7 +1149,8 @@ class DeviceScene:
 
     def render_denoised(self, p: dict, iterations=None, sigma_color=DEFAULT_SIGMA_COLOR, sigma_normal=None, sigma_depth=None,
                         demodulate=True, rank=0, world_size=1, flags=0, device="cuda", variance_guided=False,
-                        sigma_luma=DEFAULT_VAR_SIGMA_LUMA, temporal=None, motion=None, pixel_motion=False):
+                        sigma_luma=DEFAULT_VAR_SIGMA_LUMA, temporal=None, motion=None, pixel_motion=False, exposure=None, dt=0.0,
+                        look=None):
         """``render_aovs_into`` for albedo, normal and depth, then the à-trous filter (``denoise_into``) on the same device
         buffers, on torch's current stream: no host round trip. Returns (noisy frame, denoised frame, {name: guide}) as torch
         tensors of ``device`` ((H, W, 4); guides (H, W, 3) / (H, W)).
@@ -1123,7 +1167,25 @@ class DeviceScene:
         yart_amd.temporal.node_motion(previous nodes, these nodes) —, handed to ``temporal.accumulate_into``.
         ``pixel_motion=True`` (with ``temporal``, not with ``motion``): the scene was updated in place since ``keep_previous``:
         the per-pixel records are computed from the frame's own feature buffers (``pixel_motion_into``, on the same stream) and
-        handed to ``temporal.accumulate_into``; they are returned among the guides as "pixel_motion" (H, W, 8)."""
+        handed to ``temporal.accumulate_into``; they are returned among the guides as "pixel_motion" (H, W, 8).
+        ``exposure``: an :class:`AutoExposure` — the display stage: the denoised frame is metered (``exposure.meter_into``,
+        ``dt`` seconds after the previous frame) and applied (``exposure.apply_into`` with ``look``: None = no tonemapper, or an
+        AgX look's name) on the same stream; "display" (H, W, 4) and "display_rgb8" (H, W, 3 uint8) are added to the guides.
+        None: as before."""
+        noisy, clean, guides = self._render_denoised(p, iterations, sigma_color, sigma_normal, sigma_depth, demodulate, rank, world_size,
+                                                     flags, device, variance_guided, sigma_luma, temporal, motion, pixel_motion)
+        if exposure is None:
+            return noisy, clean, guides
+        import torch
+        display = torch.empty_like(clean)
+        rgb8 = torch.empty(tuple(clean.shape[:2]) + (3,), dtype=torch.uint8, device=clean.device)
+        stream = torch.cuda.current_stream(clean.device).cuda_stream
+        exposure.meter_into(clean, dt, stream=stream)
+        exposure.apply_into(display, rgb8, clean, look, stream=stream)
+        return noisy, clean, dict(guides, display=display, display_rgb8=rgb8)
+
+    def _render_denoised(self, p, iterations, sigma_color, sigma_normal, sigma_depth, demodulate, rank, world_size, flags, device,
+                         variance_guided, sigma_luma, temporal, motion, pixel_motion):
         import torch
         assert motion is None or temporal is not None, "render_denoised: motion needs a temporal accumulator"
         assert not pixel_motion or temporal is not None, "render_denoised: pixel_motion needs a temporal accumulator"
@@ -1728,6 +1790,111 @@ class TemporalAccumulator:
                       ptr(out_tensor), ptr(out_variance_tensor), ptr(out_length_tensor), C.c_void_p(stream) if stream else None),
                    self._L)
         return out_tensor
+
+
+class AutoExposure:
+    """Auto-exposure for a sequence of frames (include/yart_hip.h: yart_hip_exposure_*), the stage after the denoiser: ``meter``
+    builds a log-luminance histogram of a linear-HDR frame on the device and steps the exposure towards its target with eye-style
+    adaptation over ``dt`` seconds; ``apply`` multiplies a frame by the gain, tonemaps it (AgX) and encodes it to 8 bits in one
+    kernel. The state stays on the device (about 2 KB per handle). ``params``: yart_amd.exposure.DEFAULTS' names — ``ev_min``,
+    ``ev_max``, ``trim_low``, ``trim_high``, ``key``, ``compensation_ev``, ``gain_ev_min``, ``gain_ev_max``, ``speed_up``,
+    ``speed_down``, ``window`` (x0, y0, x1, y1) —, the parameters of every meter call. ``device`` < 0: the device current at the
+    first frame. yart_amd.exposure.exposure_reference / apply_reference state the same arithmetic in NumPy."""
+
+    def __init__(self, device: int = 0, **params):
+        self._L = lib()
+        self.device = int(device)
+        self.params = exposure_params_of(**params)
+        h = C.c_void_p()
+        _check(self._L.yart_hip_exposure_create(self.device, C.byref(h)), self._L)
+        self._h = h
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.yart_hip_exposure_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        """Back to a new handle: the next ``meter`` snaps to its target; until then ``apply`` uses gain 1."""
+        _check(self._L.yart_hip_exposure_reset(self._h), self._L)
+
+    def meter(self, frame, dt):
+        """Meter an (H, W, 4) float32 NumPy frame (yart_hip_exposure_meter_host) and step the state by ``dt`` seconds.
+        Returns ``state()``."""
+        frame = np.ascontiguousarray(frame, np.float32)
+        h, w = frame.shape[:2]
+        assert frame.shape == (h, w, 4)
+        ep = make_exposure_params(**self.params)
+        _check(self._L.yart_hip_exposure_meter_host(self._h, frame.ctypes.data_as(C.c_void_p), w, h, C.byref(ep), float(dt)), self._L)
+        return self.state()
+
+    def apply(self, frame, look="none"):
+        """Gain, tonemap (``look``: None = no tonemapper, "none" / "golden" / "punchy") and 8-bit encoding of an (H, W, 4) float32
+        NumPy frame (yart_hip_exposure_apply_host). Returns (ldr float32 (H, W, 4), rgb8 (H, W, 3))."""
+        frame = np.ascontiguousarray(frame, np.float32)
+        h, w = frame.shape[:2]
+        assert frame.shape == (h, w, 4)
+        ldr, rgb = np.empty_like(frame), np.empty((h, w, 3), np.uint8)
+        _check(self._L.yart_hip_exposure_apply_host(self._h, frame.ctypes.data_as(C.c_void_p), w, h, look_index(look),
+                                                    ldr.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p)), self._L)
+        return ldr, rgb
+
+    def meter_into(self, frame_tensor, dt, stream=None):
+        """``meter`` of an (H, W, 4) float32 CUDA/HIP torch tensor (yart_hip_exposure_meter_device) on ``stream`` (a raw
+        hipStream_t), by default torch's current stream of the frame's device; returns after completion there. Nothing is
+        copied to the host: read ``state()`` when it is wanted."""
+        import torch
+        t = frame_tensor
+        h, w = int(t.shape[0]), int(t.shape[1])
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4)
+        if stream is None:
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+        ep = make_exposure_params(**self.params)
+        with torch.cuda.device(t.device):
+            _check(self._L.yart_hip_exposure_meter_device(self._h, C.c_void_p(t.data_ptr()), w, h, C.byref(ep), float(dt),
+                                                          C.c_void_p(stream) if stream else None), self._L)
+
+    def apply_into(self, ldr_tensor, rgb8_tensor, frame_tensor, look="none", stream=None):
+        """``apply`` on torch tensors (yart_hip_exposure_apply_device): ``ldr_tensor`` (H, W, 4) float32 or None (it may be
+        ``frame_tensor``), ``rgb8_tensor`` (H, W, 3) uint8 or None; not both None."""
+        import torch
+        t = frame_tensor
+        h, w = int(t.shape[0]), int(t.shape[1])
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4)
+        if ldr_tensor is not None:
+            o = ldr_tensor
+            assert o.is_cuda and o.is_contiguous() and o.dtype == torch.float32 and tuple(o.shape) == (h, w, 4), "ldr"
+        if rgb8_tensor is not None:
+            o = rgb8_tensor
+            assert o.is_cuda and o.is_contiguous() and o.dtype == torch.uint8 and tuple(o.shape) == (h, w, 3), "rgb8"
+        if stream is None:
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        with torch.cuda.device(t.device):
+            _check(self._L.yart_hip_exposure_apply_device(self._h, C.c_void_p(t.data_ptr()), w, h, look_index(look), ptr(ldr_tensor),
+                                                          ptr(rgb8_tensor), C.c_void_p(stream) if stream else None), self._L)
+
+    def state(self, histogram=False):
+        """The state record as a dict (``cur_ev``, ``target_ev``, ``mean_ev``, ``gain`` as np.float32; ``n_counted``,
+        ``n_ignored``, ``frames``, ``flags``); with ``histogram=True`` also ``"histogram"``: the last meter call's 256 bins."""
+        rec = ExposureStateRecord(C.sizeof(ExposureStateRecord))
+        hist = np.zeros(256, np.uint32) if histogram else None
+        _check(self._L.yart_hip_exposure_get(self._h, C.byref(rec), None if hist is None else hist.ctypes.data_as(C.c_void_p)), self._L)
+        d = {k: np.float32(getattr(rec, k)) for k in ("cur_ev", "target_ev", "mean_ev", "gain")}
+        d.update({k: int(getattr(rec, k)) for k in ("n_counted", "n_ignored", "frames", "flags")})
+        if histogram:
+            d["histogram"] = hist
+        return d
 
 
 def probe_moments(L_samples, chunks=None, exposure_scale=1.0):

@@ -1,9 +1,10 @@
 // postprocess.inc — what happens to a frame after it has been rendered: the AgX tonemap and the 8-bit encoding, the edge-avoiding
-// a-trous denoiser and temporal accumulation; kernels, host drivers and the entries of the C ABI (included by yart_hip.hip,
+// a-trous denoiser, temporal accumulation and auto-exposure; kernels, host drivers and the entries of the C ABI (included by yart_hip.hip,
 // unit 0, after `guarded`; nothing here needs a scene).
 #include "tonemap.hpp"
 #include "denoise.hpp"
 #include "temporal.hpp"
+#include "exposure.hpp"
 
 namespace {
 
@@ -27,6 +28,7 @@ __global__ void __launch_bounds__(kBlock) k_encode_rgb8(const f4* in, uint8_t* o
 
 #include "denoise_kernels.inc"
 #include "temporal_kernels.inc"
+#include "exposure_kernels.inc"
 
 }  // namespace
 
@@ -519,6 +521,257 @@ int yart_hip_temporal_accumulate_moments_host(YartTemporal* temporal, const Yart
                                               const YartAovBuffers* aovs, const YartTemporalMomentParams* params, float* out_rgba,
                                               float* out_variance, uint32_t* out_length) {
   return temporalAccumulateHost<true>(temporal, cam, rgba, variance, aovs, params, out_rgba, out_variance, out_length);
+}
+
+}  // extern "C"
+
+// Auto-exposure (exposure_kernels.inc: k_ex_histogram, k_ex_resolve, k_ex_apply). The arguments are judged before any device is
+// touched; the handle's device memory — the accumulating histogram, the last call's histogram and the state record — is allocated
+// by the first call that gets that far. The state never leaves the device between a meter call and the apply calls that follow.
+struct YartExposure {
+  int device = -1;                                  // < 0 until the first call that needs one: the device current then
+  std::mutex mu;
+  DevBuf<uint32_t> words;                           // hist (256) | ignored (1) | pad | last (256) | record
+  uint32_t* hist() const { return words.p; }
+  uint32_t* last() const { return words.p + kExLastAt; }
+  ExRecord* record() const { return reinterpret_cast<ExRecord*>(words.p + kExRecordAt); }
+  static constexpr size_t kExLastAt = 260, kExRecordAt = 516, kExWords = kExRecordAt + sizeof(ExRecord) / 4;
+};
+namespace {
+constexpr uint32_t kExMaxBlocks = 512u;            // k_ex_histogram's grid: at most 2 workgroups per CU, each striding over the window
+#ifndef YART_EXPOSURE_HISTOGRAM
+#define YART_EXPOSURE_HISTOGRAM 1                  // the kept form of k_ex_histogram (exposure_kernels.inc; profiles/auto_exposure.txt)
+#endif
+struct ExCall { ExConst k; uint32_t x0, y0, ww, wh; };
+
+ExCall exposureCheckMeter(const YartExposure* e, const void* rgba, uint32_t width, uint32_t height, const YartExposureParams* p, float dt) {
+  require(e != nullptr, "exposure: handle pointer is null");
+  require(rgba != nullptr, "exposure: rgba pointer is null");
+  require(p != nullptr, "exposure: params pointer is null");
+  require(p->struct_size >= sizeof(YartExposureParams), "exposure: struct_size is smaller than YartExposureParams");
+  require(width > 0 && height > 0, "exposure: width or height is 0");
+  require(uint64_t(width) * height <= (1ull << 28), "exposure: more than 2^28 pixels");
+  require(std::isfinite(p->ev_min) && std::isfinite(p->ev_max) && p->ev_min < p->ev_max, "exposure: ev_min / ev_max are not finite or ev_min >= ev_max");
+  require(p->trim_low >= 0.0f && p->trim_low < 1.0f && p->trim_high >= 0.0f && p->trim_high < 1.0f && p->trim_low + p->trim_high < 1.0f,
+          "exposure: trim_low / trim_high are outside [0, 1) or their sum is not below 1");
+  require(std::isfinite(p->key) && p->key > 0.0f, "exposure: key is not finite or not positive");
+  require(std::isfinite(p->compensation_ev), "exposure: compensation_ev is not finite");
+  require(std::isfinite(p->gain_ev_min) && std::isfinite(p->gain_ev_max) && p->gain_ev_min <= p->gain_ev_max,
+          "exposure: gain_ev_min / gain_ev_max are not finite or gain_ev_min > gain_ev_max");
+  require(std::isfinite(p->speed_up) && std::isfinite(p->speed_down) && p->speed_up >= 0.0f && p->speed_down >= 0.0f,
+          "exposure: speed_up / speed_down are not finite or negative");
+  require(std::isfinite(dt) && dt >= 0.0f, "exposure: dt is not finite or negative");
+  ExCall c{};
+  if (p->x0 == 0u && p->y0 == 0u && p->x1 == 0u && p->y1 == 0u) {
+    c.ww = width; c.wh = height;
+  } else {
+    require(p->x0 < p->x1 && p->x1 <= width && p->y0 < p->y1 && p->y1 <= height, "exposure: the metering window is empty or outside the frame");
+    c.x0 = p->x0; c.y0 = p->y0; c.ww = p->x1 - p->x0; c.wh = p->y1 - p->y0;
+  }
+  c.k = exConstants(p->ev_min, p->ev_max, p->trim_low, p->trim_high, p->key, p->compensation_ev, p->gain_ev_min, p->gain_ev_max,
+                    p->speed_up, p->speed_down, dt);
+  return c;
+}
+
+void exposureCheckApply(const YartExposure* e, const void* rgba, uint32_t width, uint32_t height, int look, const void* ldr, const void* rgb8) {
+  require(e != nullptr, "exposure: handle pointer is null");
+  require(rgba != nullptr, "exposure: rgba pointer is null");
+  require(ldr != nullptr || rgb8 != nullptr, "exposure: both outputs (ldr_rgba and rgb8) are null");
+  require(width > 0 && height > 0, "exposure: width or height is 0");
+  require(uint64_t(width) * height <= (1ull << 28), "exposure: more than 2^28 pixels");
+  require(look >= -1 && look <= 2, "exposure: look is outside -1 .. 2");
+}
+
+void exposureAligned(const void* p, const char* what) { require((reinterpret_cast<uintptr_t>(p) & 15u) == 0u, what); }
+
+// the handle's mutex held: its device made current, its memory allocated and a new handle's record written
+void exposureSelect(YartExposure& e) {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw HipError("no HIP device");
+  if (e.device < 0) HIP_CHECK(hipGetDevice(&e.device));
+  HIP_CHECK(hipSetDevice(e.device));
+  if (e.words.p) return;
+  e.words.ensure(YartExposure::kExWords);
+  HIP_CHECK(hipMemset(e.words.p, 0, YartExposure::kExWords * 4));
+  const ExRecord fresh = exNewRecord();
+  HIP_CHECK(hipMemcpy(e.record(), &fresh, sizeof(fresh), hipMemcpyHostToDevice));
+}
+
+template <int V>
+void exposureLaunchHistogram(const YartExposure& e, const ExCall& c, const float* rgba, uint32_t width, hipStream_t st) {
+  ExHistArgs ha{reinterpret_cast<const f4*>(rgba), e.hist(), width, c.x0, c.y0, c.ww, c.ww * c.wh, c.k};
+  constexpr uint32_t perPass = kBlock * kExUnroll;
+  const uint32_t blocks = std::min<uint32_t>((ha.n + perPass - 1) / perPass, kExMaxBlocks);
+  hipLaunchKernelGGL(k_ex_histogram<V>, dim3(blocks), dim3(kBlock), 0, st, ha);
+  HIP_CHECK(hipGetLastError());
+}
+void exposureLaunchResolve(const YartExposure& e, const ExCall& c, hipStream_t st) {
+  ExResolveArgs ra{e.hist(), e.last(), e.record(), c.k};
+  hipLaunchKernelGGL(k_ex_resolve, dim3(1), dim3(kBlock), 0, st, ra);
+  HIP_CHECK(hipGetLastError());
+}
+void exposureLaunchApply(const YartExposure& e, const float* rgba, uint32_t n, int look, float* ldr, uint8_t* rgb8, hipStream_t st) {
+  ExApplyArgs aa{reinterpret_cast<const f4*>(rgba), e.record(), reinterpret_cast<f4*>(ldr), rgb8, n, look};
+  const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
+  if (ldr && rgb8) hipLaunchKernelGGL((k_ex_apply<true, true>), grid, block, 0, st, aa);
+  else if (ldr) hipLaunchKernelGGL((k_ex_apply<true, false>), grid, block, 0, st, aa);
+  else hipLaunchKernelGGL((k_ex_apply<false, true>), grid, block, 0, st, aa);
+  HIP_CHECK(hipGetLastError());
+}
+
+// device pointers; the handle's device is current and its mutex held; returns after completion on `st`
+void exposureMeter(YartExposure& e, const ExCall& c, const float* rgba, uint32_t width, hipStream_t st) {
+  exposureLaunchHistogram<YART_EXPOSURE_HISTOGRAM>(e, c, rgba, width, st);
+  exposureLaunchResolve(e, c, st);
+  HIP_CHECK(hipStreamSynchronize(st));
+}
+}  // namespace
+extern "C" {
+
+int yart_hip_exposure_create(int device, YartExposure** out) {
+  return guarded([&] {
+    require(out != nullptr, "exposure: out pointer is null");
+    auto* e = new YartExposure;
+    e->device = device;
+    *out = e;
+  });
+}
+
+void yart_hip_exposure_destroy(YartExposure* exposure) {
+  if (!exposure) return;
+  if (exposure->words.p && exposure->device >= 0) (void)hipSetDevice(exposure->device);
+  delete exposure;
+}
+
+int yart_hip_exposure_reset(YartExposure* exposure) {
+  return guarded([&] {
+    require(exposure != nullptr, "exposure: handle pointer is null");
+    std::lock_guard<std::mutex> lock(exposure->mu);
+    if (!exposure->words.p) return;                 // nothing metered yet: a new handle already
+    HIP_CHECK(hipSetDevice(exposure->device));
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemset(exposure->words.p, 0, YartExposure::kExWords * 4));
+    const ExRecord fresh = exNewRecord();
+    HIP_CHECK(hipMemcpy(exposure->record(), &fresh, sizeof(fresh), hipMemcpyHostToDevice));
+  });
+}
+
+int yart_hip_exposure_meter_device(YartExposure* exposure, const float* d_rgba, uint32_t width, uint32_t height,
+                                   const YartExposureParams* params, float dt, void* stream) {
+  return guarded([&] {
+    const ExCall c = exposureCheckMeter(exposure, d_rgba, width, height, params, dt);
+    exposureAligned(d_rgba, "exposure: d_rgba is not 16-byte aligned");
+    std::lock_guard<std::mutex> lock(exposure->mu);
+    exposureSelect(*exposure);
+    exposureMeter(*exposure, c, d_rgba, width, static_cast<hipStream_t>(stream));
+  });
+}
+
+int yart_hip_exposure_meter_host(YartExposure* exposure, const float* rgba, uint32_t width, uint32_t height,
+                                 const YartExposureParams* params, float dt) {
+  return guarded([&] {
+    const ExCall c = exposureCheckMeter(exposure, rgba, width, height, params, dt);
+    std::lock_guard<std::mutex> lock(exposure->mu);
+    exposureSelect(*exposure);
+    const size_t n = size_t(width) * height;
+    DevBuf<float> frame;
+    frame.ensure(n * 4);
+    HIP_CHECK(hipMemcpy(frame.p, rgba, n * 16, hipMemcpyHostToDevice));
+    exposureMeter(*exposure, c, frame.p, width, nullptr);
+  });
+}
+
+int yart_hip_exposure_apply_device(YartExposure* exposure, const float* d_rgba, uint32_t width, uint32_t height, int look,
+                                   float* d_ldr_rgba, uint8_t* d_rgb8, void* stream) {
+  return guarded([&] {
+    exposureCheckApply(exposure, d_rgba, width, height, look, d_ldr_rgba, d_rgb8);
+    exposureAligned(d_rgba, "exposure: d_rgba is not 16-byte aligned");
+    exposureAligned(d_ldr_rgba, "exposure: d_ldr_rgba is not 16-byte aligned");
+    std::lock_guard<std::mutex> lock(exposure->mu);
+    exposureSelect(*exposure);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    exposureLaunchApply(*exposure, d_rgba, width * height, look, d_ldr_rgba, d_rgb8, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+  });
+}
+
+int yart_hip_exposure_apply_host(YartExposure* exposure, const float* rgba, uint32_t width, uint32_t height, int look, float* ldr_rgba,
+                                 uint8_t* rgb8) {
+  return guarded([&] {
+    exposureCheckApply(exposure, rgba, width, height, look, ldr_rgba, rgb8);
+    std::lock_guard<std::mutex> lock(exposure->mu);
+    exposureSelect(*exposure);
+    const size_t n = size_t(width) * height;
+    DevBuf<float> frame; DevBuf<uint8_t> bytes;     // the frame is tonemapped in place
+    frame.ensure(n * 4);
+    if (rgb8) bytes.ensure(n * 3);
+    HIP_CHECK(hipMemcpy(frame.p, rgba, n * 16, hipMemcpyHostToDevice));
+    exposureLaunchApply(*exposure, frame.p, uint32_t(n), look, ldr_rgba ? frame.p : nullptr, bytes.p, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    if (ldr_rgba) HIP_CHECK(hipMemcpy(ldr_rgba, frame.p, n * 16, hipMemcpyDeviceToHost));
+    if (rgb8) HIP_CHECK(hipMemcpy(rgb8, bytes.p, n * 3, hipMemcpyDeviceToHost));
+  });
+}
+
+int yart_hip_exposure_get(YartExposure* exposure, YartExposureState* state, uint32_t* hist256) {
+  return guarded([&] {
+    require(exposure != nullptr, "exposure: handle pointer is null");
+    require(state != nullptr, "exposure: state pointer is null");
+    require(state->struct_size >= sizeof(YartExposureState), "exposure: struct_size is smaller than YartExposureState");
+    std::lock_guard<std::mutex> lock(exposure->mu);
+    ExRecord r = exNewRecord();
+    if (exposure->words.p) {                        // (a handle that has touched no device reports a new handle's state)
+      HIP_CHECK(hipSetDevice(exposure->device));
+      HIP_CHECK(hipMemcpy(&r, exposure->record(), sizeof(r), hipMemcpyDeviceToHost));
+      if (hist256) HIP_CHECK(hipMemcpy(hist256, exposure->last(), kExBins * 4, hipMemcpyDeviceToHost));
+    } else if (hist256) {
+      std::fill(hist256, hist256 + kExBins, 0u);
+    }
+    state->cur_ev = r.curEv; state->target_ev = r.targetEv; state->mean_ev = r.meanEv; state->gain = r.gain;
+    state->n_counted = r.nCounted; state->n_ignored = r.nIgnored; state->frames = r.frames; state->flags = r.flags;
+  });
+}
+
+// Not part of the interface (tools/exposure_bench.py): the device time of one of the exposure kernels — or of the pair
+// k_tonemap_agx + k_encode_rgb8 that k_ex_apply replaces — over `repeats` launches between two events, in ms per launch.
+// what: 0 / 1 k_ex_histogram<0 / 1>, 2 k_ex_resolve, 3 k_ex_apply<true, true>, 4 the pair. d_ldr_rgba and d_rgb8: for 3 and 4.
+int yart_hip_debug_exposure_time(YartExposure* exposure, const float* d_rgba, uint32_t width, uint32_t height,
+                                 const YartExposureParams* params, int what, uint32_t repeats, float* d_ldr_rgba, uint8_t* d_rgb8,
+                                 float* ms_out) {
+  return guarded([&] {
+    const ExCall c = exposureCheckMeter(exposure, d_rgba, width, height, params, 0.0f);
+    require(what >= 0 && what <= 4 && repeats >= 1u && ms_out, "exposure: debug: bad argument");
+    require(what < 3 || (d_ldr_rgba && d_rgb8), "exposure: debug: outputs are null");
+    exposureAligned(d_rgba, "exposure: d_rgba is not 16-byte aligned");
+    std::lock_guard<std::mutex> lock(exposure->mu);
+    exposureSelect(*exposure);
+    YartExposure& e = *exposure;
+    const uint32_t n = width * height;
+    hipEvent_t t0, t1;
+    HIP_CHECK(hipEventCreate(&t0)); HIP_CHECK(hipEventCreate(&t1));
+    HIP_CHECK(hipEventRecord(t0, nullptr));
+    for (uint32_t i = 0; i < repeats; i++) {
+      if (what == 0) exposureLaunchHistogram<0>(e, c, d_rgba, width, nullptr);
+      else if (what == 1) exposureLaunchHistogram<1>(e, c, d_rgba, width, nullptr);
+      else if (what == 2) exposureLaunchResolve(e, c, nullptr);
+      else if (what == 3) exposureLaunchApply(e, d_rgba, n, 0, d_ldr_rgba, d_rgb8, nullptr);
+      else {
+        hipLaunchKernelGGL(k_tonemap_agx, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, reinterpret_cast<const f4*>(d_rgba),
+                           reinterpret_cast<f4*>(d_ldr_rgba), n, 0);
+        hipLaunchKernelGGL(k_encode_rgb8, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, nullptr, reinterpret_cast<const f4*>(d_ldr_rgba), d_rgb8, n);
+        HIP_CHECK(hipGetLastError());
+      }
+    }
+    HIP_CHECK(hipEventRecord(t1, nullptr));
+    HIP_CHECK(hipEventSynchronize(t1));
+    float ms = 0.0f;
+    HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
+    (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
+    *ms_out = ms / float(repeats);
+    // what the timed histogram launches left behind: the sum of `repeats` histograms, which yart_hip_exposure_get then reports
+    if (what < 2) HIP_CHECK(hipMemcpy(e.last(), e.hist(), kExBins * 4, hipMemcpyDeviceToDevice));
+    HIP_CHECK(hipMemset(e.hist(), 0, (kExBins + 1u) * 4));
+  });
 }
 
 }  // extern "C"
