@@ -834,6 +834,26 @@ static int doBvhCheck(const char* scenePath, unsigned threads) {
   return 0;
 }
 
+// bvhsum: the "bvh" section of the kat files alone, from the host builder (csrc/bvh_build.hpp) on `threads` threads: per mesh of the
+// scene the node count, the FNV-1a of the node words and the FNV-1a of the index array — what the "bvh" section of `yart_ref kat` holds for the
+// reference's trees (tests/bvhsuite.py, tests/golden/bvh/README.md: the mutation table is made with this mode)
+static int doBvhSum(const char* scenePath, unsigned threads, const char* outPath) {
+  auto loaded = loadSceneFile(scenePath);
+  std::vector<uint64_t> out;
+  for (uint32_t m = 0; m < loaded->desc.n_meshes; m++) {
+    const YartMeshDesc& md = loaded->desc.meshes[m];
+    SahBvhBuilder b;
+    b.setThreads(threads);
+    b.build(md.positions, md.faces, 4, md.n_faces);
+    out.push_back(b.nodes.size());
+    out.push_back(kat::fnv1a(b.nodes.data(), b.nodes.size() * sizeof(BvhNode)));
+    out.push_back(kat::fnv1a(b.indices.data(), b.indices.size() * 4));
+  }
+  kat::Writer w(outPath);
+  w.u64("bvh", out);
+  return 0;
+}
+
 // loadstress: N concurrent host callers of the scene loader and the scene build (what N threads holding their own YartScene
 // handles do on the host before anything reaches a device): .yscn parse, flattening, the task-parallel SAH build with its own
 // worker pool inside every caller. Every caller must arrive at the same image (node array hashed). Run under
@@ -875,6 +895,7 @@ int main(int argc, char** argv) {
   }
   if (argc == 4 && std::string(argv[1]) == "loadstress") return doLoadStress(argv[2], unsigned(std::atoi(argv[3])));
   if (argc == 4 && std::string(argv[1]) == "bvhcheck") return doBvhCheck(argv[2], unsigned(std::atoi(argv[3])));
+  if (argc == 5 && std::string(argv[1]) == "bvhsum") return doBvhSum(argv[2], unsigned(std::atoi(argv[3])), argv[4]);
   if (argc == 6 && std::string(argv[1]) == "estimator")
     return doEstimator(std::atoi(argv[2]), unsigned(std::atoi(argv[3])), argv[4], argv[5]);
   if (argc == 8 && std::string(argv[1]) == "tonemap")
