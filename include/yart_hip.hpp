@@ -80,10 +80,7 @@ class DeviceScene {
     u.n_nodes = uint32_t(nodes.size()); u.nodes = nodes.data();
     u.n_lights = uint32_t(lights.size()); u.lights = lights.empty() ? nullptr : lights.data();
     u.flags = rebuildTop ? YART_UPDATE_REBUILD_TOP : 0u;
-    YartSceneUpdateStats st{};
-    st.struct_size = uint32_t(sizeof(st));
-    check(yart_hip_scene_update(h_, &u, stream, &st));
-    return st;
+    return updateWith(yart_hip_scene_update, u, stream);
   }
   // yart_hip_scene_update_meshes: new vertices for the listed meshes (each at most once; vertex counts as at create; normals /
   // tangents NULL: kept); rebuildTop: YART_UPDATE_REBUILD_TOP. Returns the update's statistics.
@@ -92,10 +89,7 @@ class DeviceScene {
     u.struct_size = uint32_t(sizeof(u));
     u.n_meshes = uint32_t(meshes.size()); u.meshes = meshes.data();
     u.flags = rebuildTop ? YART_UPDATE_REBUILD_TOP : 0u;
-    YartSceneUpdateStats st{};
-    st.struct_size = uint32_t(sizeof(st));
-    check(yart_hip_scene_update_meshes(h_, &u, stream, &st));
-    return st;
+    return updateWith(yart_hip_scene_update_meshes, u, stream);
   }
   // yart_hip_scene_update_lighting: new material values (empty: untouched; else every material of the scene), new light emission /
   // radius / transforms (empty: untouched; else every light) and new texels for the maps of image lights (each texture at most
@@ -107,10 +101,7 @@ class DeviceScene {
     u.n_materials = uint32_t(materials.size()); u.materials = materials.empty() ? nullptr : materials.data();
     u.n_lights = uint32_t(lights.size()); u.lights = lights.empty() ? nullptr : lights.data();
     u.n_images = uint32_t(images.size()); u.images = images.empty() ? nullptr : images.data();
-    YartSceneUpdateStats st{};
-    st.struct_size = uint32_t(sizeof(st));
-    check(yart_hip_scene_update_lighting(h_, &u, stream, &st));
-    return st;
+    return updateWith(yart_hip_scene_update_lighting, u, stream);
   }
   // yart_hip_scene_update_textures: new texels for 8-bit material textures (each texture at most once; size and channels as at create;
   // YART_TEXELS_ON_DEVICE in an entry's flags: its pixels are memory of the scene's device). Returns the update's statistics.
@@ -118,10 +109,7 @@ class DeviceScene {
     YartSceneTextureUpdate u{};
     u.struct_size = uint32_t(sizeof(u));
     u.n_textures = uint32_t(textures.size()); u.textures = textures.empty() ? nullptr : textures.data();
-    YartSceneUpdateStats st{};
-    st.struct_size = uint32_t(sizeof(st));
-    check(yart_hip_scene_update_textures(h_, &u, stream, &st));
-    return st;
+    return updateWith(yart_hip_scene_update_textures, u, stream);
   }
   // yart_hip_scene_keep_previous: the scene remembers the frame it holds as its previous frame; once per frame, before its updates
   void keepPrevious(void* stream = nullptr) { check(yart_hip_scene_keep_previous(h_, stream)); }
@@ -178,6 +166,14 @@ class DeviceScene {
 
  private:
   explicit DeviceScene(YartScene* h) : h_(h) {}
+  // one of the yart_hip_scene_update* entries on this scene -> the update's statistics
+  template <class Update>
+  YartSceneUpdateStats updateWith(int (*entry)(YartScene*, const Update*, void*, YartSceneUpdateStats*), const Update& u, void* stream) {
+    YartSceneUpdateStats st{};
+    st.struct_size = uint32_t(sizeof(st));
+    check(entry(h_, &u, stream, &st));
+    return st;
+  }
   YartScene* h_ = nullptr;
 };
 

@@ -29,6 +29,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import updatesim
 from tests.conftest import ROOT
 from tests.test_scene_update_host import SIZE, SPP
 
@@ -197,35 +198,24 @@ def steps_of(states):
     return list(zip(states[:-1], states[1:])) + [(states[-1], states[0])]
 
 
-SIM_SOURCES = [os.path.join(ROOT, "tests", "lightingsim", "lightingsim.cpp"), os.path.join(ROOT, "yart_amd", "csrc", "_gen", "lut_data.cpp")]
+SIM_SOURCES = ["lightingsim/lightingsim.cpp"]
 
 
 @pytest.fixture(scope="module")
 def sim(built, tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("lightingsim") / "lightingsim")
-    r = subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-o", exe] + SIM_SOURCES + ["-lz", "-lpthread"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+    return updatesim.build_sim(str(tmp_path_factory.mktemp("lightingsim") / "lightingsim"), SIM_SOURCES)
 
 
 TAGS = ("materials", "lobe classes", "texF32", "envs", "envData", "envGuide", "lights", "areaPowerCdf", "totalPower")
 
 
 def run_sim(exe, tmp_path, s0, s1):
-    a, b = os.path.join(tmp_path, "old.yscn"), os.path.join(tmp_path, "new.yscn")
-    s0.save(a)
-    s1.save(b)
-    r = subprocess.run([exe, a, b], capture_output=True, text=True)
-    print(r.stdout)
-    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout[-3000:] + r.stderr[-2000:]
-    assert "DIFFERENT" not in r.stdout
-    for tag in TAGS:
-        assert re.search(rf"^EQUAL {tag} ", r.stdout, re.M), tag
+    out = updatesim.run_sim(exe, tmp_path, s0, s1, TAGS)
     envs = [dict(changed=bool(int(m.group(1))), w=int(m.group(2)), h=int(m.group(3)), black=int(m.group(4)), integral=float(m.group(5)))
-            for m in re.finditer(r"^env \d+ texture \d+ changed (\d) w (\d+) h (\d+) blackRows (\d+) margIntegral (\S+)$", r.stdout, re.M)]
-    classes = int(re.search(r"^classes changed (\d+)$", r.stdout, re.M).group(1))
-    cdf = re.search(r"^power cdf: (\d+) entries, (\d+) equal to their predecessor, total (\S+)$", r.stdout, re.M)
-    return dict(out=r.stdout, envs=envs, classes=classes, cdf_equal=int(cdf.group(2)), total=float(cdf.group(3)))
+            for m in re.finditer(r"^env \d+ texture \d+ changed (\d) w (\d+) h (\d+) blackRows (\d+) margIntegral (\S+)$", out, re.M)]
+    classes = int(re.search(r"^classes changed (\d+)$", out, re.M).group(1))
+    cdf = re.search(r"^power cdf: (\d+) entries, (\d+) equal to their predecessor, total (\S+)$", out, re.M)
+    return dict(out=out, envs=envs, classes=classes, cdf_equal=int(cdf.group(2)), total=float(cdf.group(3)))
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -286,10 +276,7 @@ def test_the_cases_hold_what_they_claim(built):
 def test_sanitized_build_runs_clean(built, tmp_path):
     """The same program under -fsanitize=address,undefined (a stand-alone program: no preloading), on the combined case and on the
     odd-sized map."""
-    exe = os.path.join(tmp_path, "lightingsim_san")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                        "-o", exe] + SIM_SOURCES + ["-lz", "-lpthread"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = updatesim.build_sim(os.path.join(tmp_path, "lightingsim_san"), SIM_SOURCES, sanitized=True)
     for name in ("combined", "sky_65x63"):
         states, _ = build_case(name)
         run_sim(exe, str(tmp_path), states[0], states[1])

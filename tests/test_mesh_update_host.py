@@ -25,6 +25,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import updatesim
 from tests.conftest import ROOT
 from tests.test_scene_update_host import SIZE, SPP, _two_cubes
 
@@ -136,30 +137,22 @@ def update_arrays(s, meshes, normals=True):
 
 @pytest.fixture(scope="module")
 def sim(built, tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("meshupdatesim") / "meshupdatesim")
-    r = subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-o", exe, os.path.join(ROOT, "tests", "meshupdatesim", "meshupdatesim.cpp"),
-                        os.path.join(ROOT, "yart_amd", "csrc", "_gen", "lut_data.cpp"), "-lz", "-lpthread"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+    return updatesim.build_sim(str(tmp_path_factory.mktemp("meshupdatesim") / "meshupdatesim"), SIM_SOURCES)
+
+
+SIM_SOURCES = ["meshupdatesim/meshupdatesim.cpp"]
+TAGS = ("stack bound", "vPos", "lights", "areaPowerCdf", "totalPower", "nodes", "nodeWorld", "rebuilt tlas")
 
 
 def run_sim(exe, tmp_path, s0, s1):
-    a, b = os.path.join(tmp_path, "old.yscn"), os.path.join(tmp_path, "new.yscn")
-    s0.save(a)
-    s1.save(b)
-    r = subprocess.run([exe, a, b], capture_output=True, text=True)
-    print(r.stdout)
-    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout[-3000:] + r.stderr[-2000:]
-    assert "DIFFERENT" not in r.stdout
-    for tag in ("stack bound", "vPos", "lights", "areaPowerCdf", "totalPower", "nodes", "nodeWorld", "rebuilt tlas"):
-        assert re.search(rf"^EQUAL {tag} ", r.stdout, re.M), tag
+    out = updatesim.run_sim(exe, tmp_path, s0, s1, TAGS)
     meshes = {}
-    for m in re.finditer(r"^mesh (\d+) changed (\d) nodes (\d+) was (\d+) need (\d+) was (\d+) alpha (\d)$", r.stdout, re.M):
+    for m in re.finditer(r"^mesh (\d+) changed (\d) nodes (\d+) was (\d+) need (\d+) was (\d+) alpha (\d)$", out, re.M):
         i, changed, nodes, nodes_was, need, need_was, alpha = (int(v) for v in m.groups())
         meshes[i] = dict(changed=bool(changed), nodes=nodes, nodes_was=nodes_was, need=need, need_was=need_was, alpha=alpha)
         for tag in ("node count", "nodes", "leaves", "hasAlpha", "stack need", "vertex box", "indices"):
-            assert re.search(rf"^EQUAL mesh {i} {tag} ", r.stdout, re.M), (i, tag)
-    return r.stdout, meshes
+            assert re.search(rf"^EQUAL mesh {i} {tag} ", out, re.M), (i, tag)
+    return out, meshes
 
 
 def host_tree(s, mesh):
@@ -230,11 +223,7 @@ def test_node_counts_and_depths_the_cases_rely_on(built):
 
 def test_sanitized_build_runs_clean(built, tmp_path):
     """The same program under -fsanitize=address,undefined (a stand-alone program: no preloading), once, on the alpha case."""
-    exe = os.path.join(tmp_path, "meshupdatesim_san")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                        "-o", exe, os.path.join(ROOT, "tests", "meshupdatesim", "meshupdatesim.cpp"),
-                        os.path.join(ROOT, "yart_amd", "csrc", "_gen", "lut_data.cpp"), "-lz", "-lpthread"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = updatesim.build_sim(os.path.join(tmp_path, "meshupdatesim_san"), SIM_SOURCES, sanitized=True)
     states, _, _ = build_case("alpha")
     run_sim(exe, str(tmp_path), states[0], states[1])
 

@@ -19,6 +19,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import updatesim
 from tests.conftest import ROOT
 
 SIZE, SPP = (48, 32), 4
@@ -147,26 +148,16 @@ def signed_zero_scenes():
 
 @pytest.fixture(scope="module")
 def sim(built, tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("sceneupdatesim") / "sceneupdatesim")
-    r = subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-o", exe, os.path.join(ROOT, "tests", "sceneupdatesim", "sceneupdatesim.cpp"),
-                        os.path.join(ROOT, "yart_amd", "csrc", "_gen", "lut_data.cpp"), "-lz", "-lpthread"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+    return updatesim.build_sim(str(tmp_path_factory.mktemp("sceneupdatesim") / "sceneupdatesim"), SIM_SOURCES)
+
+
+SIM_SOURCES = ["sceneupdatesim/sceneupdatesim.cpp"]
+TAGS = [f"{order} {what}" for order in ("host-path", "ascending", "descending", "shuffled-7", "round-trip") for what in ("nodes", "nodeWorld")] + \
+       ["rebuilt tlas", "lights", "areaPowerCdf", "totalPower"]
 
 
 def run_sim(exe, tmp_path, s0, s1, seed=1):
-    a, b = os.path.join(tmp_path, "old.yscn"), os.path.join(tmp_path, "new.yscn")
-    s0.save(a)
-    s1.save(b)
-    r = subprocess.run([exe, a, b, str(seed)], capture_output=True, text=True)
-    print(r.stdout)
-    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout[-3000:] + r.stderr[-2000:]
-    assert "DIFFERENT" not in r.stdout
-    for tag in ("host-path", "ascending", "descending", "shuffled-7", "round-trip"):
-        assert f"EQUAL {tag} nodes" in r.stdout and f"EQUAL {tag} nodeWorld" in r.stdout, tag
-    for tag in ("rebuilt tlas", "lights", "areaPowerCdf", "totalPower"):
-        assert f"EQUAL {tag}" in r.stdout, tag
-    return r.stdout
+    return updatesim.run_sim(exe, tmp_path, s0, s1, TAGS, seed)
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -193,11 +184,7 @@ def test_signed_zero_tie(sim, tmp_path):
 
 def test_sanitized_build_runs_clean(built, tmp_path):
     """The same program under -fsanitize=address,undefined (a stand-alone program: no preloading), once, on the 70-instance case."""
-    exe = os.path.join(tmp_path, "sceneupdatesim_san")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                        "-o", exe, os.path.join(ROOT, "tests", "sceneupdatesim", "sceneupdatesim.cpp"),
-                        os.path.join(ROOT, "yart_amd", "csrc", "_gen", "lut_data.cpp"), "-lz", "-lpthread"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = updatesim.build_sim(os.path.join(tmp_path, "sceneupdatesim_san"), SIM_SOURCES, sanitized=True)
     s0, s1, _, _, _ = build_case("instances")
     run_sim(exe, str(tmp_path), s0, s1)
 

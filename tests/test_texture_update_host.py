@@ -32,6 +32,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import updatesim
 from tests.conftest import ROOT
 from tests.test_scene_update_host import SIZE, SPP
 
@@ -222,35 +223,24 @@ def flipped_materials(prev, new):
     return [m for m in range(len(new.materials)) if has_alpha(prev, m) != has_alpha(new, m)]
 
 
-SIM_SOURCES = [os.path.join(ROOT, "tests", "texturesim", "texturesim.cpp"), os.path.join(ROOT, "yart_amd", "csrc", "_gen", "lut_data.cpp")]
+SIM_SOURCES = ["texturesim/texturesim.cpp"]
 
 
 @pytest.fixture(scope="module")
 def sim(built, tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("texturesim") / "texturesim")
-    r = subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-o", exe] + SIM_SOURCES + ["-lz", "-lpthread"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+    return updatesim.build_sim(str(tmp_path_factory.mktemp("texturesim") / "texturesim"), SIM_SOURCES)
 
 
 TAGS = ("texU8", "materials", "leaf records", "bvh nodes", "meshes", "textures")
 
 
 def run_sim(exe, tmp_path, s0, s1):
-    a, b = os.path.join(tmp_path, "old.yscn"), os.path.join(tmp_path, "new.yscn")
-    s0.save(a)
-    s1.save(b)
-    r = subprocess.run([exe, a, b], capture_output=True, text=True)
-    print(r.stdout)
-    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout[-3000:] + r.stderr[-2000:]
-    assert "DIFFERENT" not in r.stdout
-    for tag in TAGS:
-        assert re.search(rf"^EQUAL {tag} ", r.stdout, re.M), tag
+    out = updatesim.run_sim(exe, tmp_path, s0, s1, TAGS)
     textures = {int(m.group(1)): dict(changed=bool(int(m.group(2))), places=int(m.group(3)))
-                for m in re.finditer(r"^texture (\d+) changed (\d) places (\d+)$", r.stdout, re.M)}
+                for m in re.finditer(r"^texture (\d+) changed (\d) places (\d+)$", out, re.M)}
     meshes = [dict(nodes=int(m.group(1)), with_bit=int(m.group(2)), without_bit=int(m.group(3)), chain=bool(int(m.group(4))), max_span=int(m.group(5)))
-              for m in re.finditer(r"^mesh \d+ nodes (\d+) withBit (\d+) withoutBit (\d+) chain (\d) maxSpan (\d+)$", r.stdout, re.M)]
-    return dict(out=r.stdout, textures=textures, meshes=meshes, flipped=int(re.search(r"^flipped (\d+)$", r.stdout, re.M).group(1)))
+              for m in re.finditer(r"^mesh \d+ nodes (\d+) withBit (\d+) withoutBit (\d+) chain (\d) maxSpan (\d+)$", out, re.M)]
+    return dict(out=out, textures=textures, meshes=meshes, flipped=int(re.search(r"^flipped (\d+)$", out, re.M).group(1)))
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -318,10 +308,7 @@ def test_the_cases_hold_what_they_claim(sim, tmp_path):
 def test_sanitized_build_runs_clean(built, tmp_path):
     """The same program under -fsanitize=address,undefined (a stand-alone program: no preloading), on a flip with a mixed tree, on
     the long leaves, on the forms and on an odd-sized map."""
-    exe = os.path.join(tmp_path, "texturesim_san")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                        "-o", exe] + SIM_SOURCES + ["-lz", "-lpthread"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = updatesim.build_sim(os.path.join(tmp_path, "texturesim_san"), SIM_SOURCES, sanitized=True)
     for name in ("mixed", "stacked", "forms", "size_5x3x3", "reduce_2x129"):
         states, _ = build_case(name)
         run_sim(exe, str(tmp_path), states[0], states[1])

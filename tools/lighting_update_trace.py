@@ -16,52 +16,26 @@ import ctypes as C
 import os
 import statistics
 import sys
-import time
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from yart_amd import api, scenes  # noqa: E402
-
-RUNS = 5
-
-
-def median_ms(fn):
-    t = []
-    for _ in range(RUNS + 1):
-        t0 = time.perf_counter()
-        fn()
-        t.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(t[1:])
-
+from update_trace_common import median_ms, recreate_ms, scene_over, update_stats  # noqa: E402
 
 def measure(name, s, updates, out):
     """updates: two argument sets (materials, lights, images) taken in turn"""
     L = api.lib()
-    desc, keep = api.describe_scene(s)
-    h = C.c_void_p()
-    api._check(L.yart_hip_scene_create(C.byref(desc), 0, C.byref(h)), L)
-
-    def recreate():
-        nonlocal h
-        L.yart_hip_scene_destroy(h)
-        h = C.c_void_p()
-        api._check(L.yart_hip_scene_create(C.byref(desc), 0, C.byref(h)), L)
-    create = median_ms(recreate)
-    scene = api.DeviceScene.__new__(api.DeviceScene)          # the binding's marshalling over the handle made above
-    scene._h, scene._L, scene._keep, scene.last_update = h, L, [], None
-    total, device, launches = [], [], 0
-    for k in range(RUNS + 1):
-        scene.update_lighting(**updates[k % 2])
-        st = scene.last_update
-        total.append(st["ms_total"]); device.append(st["ms_device"]); launches = st["launches"]
+    create, h = recreate_ms(s)
+    scene = scene_over(h)
+    total, device, launches = update_stats(lambda k: scene.update_lighting(**updates[k % 2]) or scene.last_update)
     L.yart_hip_scene_destroy(h)
     scene._h = C.c_void_p()
     tris = sum(len(x.faces) for x in s.meshes)
     texels = sum(t.width * t.height for t in s.textures)
     upd_total = statistics.median(total[1:])
     line = (f"{name:<34} {tris:>7} tris, {texels / 1e6:6.2f} M texels, passed: {'+'.join(sorted(updates[0]))} | destroy+create {create:>9.3f} ms | "
-            f"update_lighting: total {upd_total:.3f} ms, device {statistics.median(device[1:]):.3f} ms, {launches} launches (first call {total[0]:.3f} ms)"
+            f"update_lighting: total {upd_total:.3f} ms, device {statistics.median(device[1:]):.3f} ms, {launches[-1]} launches (first call {total[0]:.3f} ms)"
             f" | {'FASTER' if upd_total < create else 'NOT FASTER'} than re-creation ({create / upd_total:.1f}x)")
     images = updates[0].get("images")
     if images:

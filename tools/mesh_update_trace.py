@@ -13,28 +13,16 @@ import ctypes as C
 import os
 import statistics
 import sys
-import time
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from yart_amd import api, scenes  # noqa: E402
-
-RUNS = 5
-
+from update_trace_common import recreate_ms, update_stats  # noqa: E402
 
 def measure(name, s, mesh, out):
     L = api.lib()
-    desc, keep = api.describe_scene(s)
-    h = C.c_void_p()
-    create = []
-    api._check(L.yart_hip_scene_create(C.byref(desc), 0, C.byref(h)), L)
-    for k in range(RUNS + 1):
-        t0 = time.perf_counter()
-        L.yart_hip_scene_destroy(h)
-        h = C.c_void_p()
-        api._check(L.yart_hip_scene_create(C.byref(desc), 0, C.byref(h)), L)
-        create.append((time.perf_counter() - t0) * 1e3)
+    create, h = recreate_ms(s)
     m = s.meshes[mesh]
     base = np.ascontiguousarray(m.positions, np.float32)
     sets = [np.ascontiguousarray(base * np.float32(1.0 + 0.03 * (k + 1))) for k in range(2)]
@@ -44,21 +32,21 @@ def measure(name, s, mesh, out):
     for tag in ("device", "host"):                  # the builder: the device build, and the host builder the library takes under YART_HOST_BVH
         if tag == "host":
             os.environ["YART_HOST_BVH"] = "1"
-        total, device, launches = [], [], 0
-        for k in range(RUNS + 1):
+        def update(k):
             one = (api.MeshUpdate * 1)(api.MeshUpdate(mesh, len(base), vp(sets[k % 2]), vp(nrm), vp(tan)))
             up = api.SceneMeshUpdate(C.sizeof(api.SceneMeshUpdate), 1, one, 0)
             st = api.SceneUpdateStats(C.sizeof(api.SceneUpdateStats))
             api._check(L.yart_hip_scene_update_meshes(h, C.byref(up), None, C.byref(st)), L)
-            total.append(st.ms_total); device.append(st.ms_device); launches = st.launches
+            return st
+        total, device, launches = update_stats(update)
         os.environ.pop("YART_HOST_BVH", None)
-        rows[tag] = (statistics.median(total[1:]), statistics.median(device[1:]), launches, total[0])
+        rows[tag] = (statistics.median(total[1:]), statistics.median(device[1:]), launches[-1], total[0])
     total, device, launches = [rows["device"][3], rows["device"][0]], [0.0, rows["device"][1]], rows["device"][2]
     L.yart_hip_scene_destroy(h)
     tris = sum(len(x.faces) for x in s.meshes)
     texels = sum(t.width * t.height for t in s.textures)
     line = (f"{name:<24} {tris:>8} tris, {texels / 1e6:6.2f} M texels, mesh {mesh} deforms ({len(m.faces)} tris) | destroy+create "
-            f"{statistics.median(create[1:]):>9.3f} ms | update_meshes: total {statistics.median(total[1:]):.3f} ms, device "
+            f"{create:>9.3f} ms | update_meshes: total {statistics.median(total[1:]):.3f} ms, device "
             f"{statistics.median(device[1:]):.3f} ms, {launches} launches (first call {total[0]:.3f} ms) | with the host builder "
             f"(YART_HOST_BVH): total {rows['host'][0]:.3f} ms, {rows['host'][2]} launches")
     print(line, flush=True)

@@ -16,9 +16,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from yart_amd import api, scenes  # noqa: E402
-
-RUNS = 5
-
+from update_trace_common import recreate_ms, update_stats  # noqa: E402
 
 def node_array(nodes, shift):
     nd = (api.NodeDesc * len(nodes))()
@@ -33,31 +31,22 @@ def node_array(nodes, shift):
 
 def measure(name, s, out):
     L = api.lib()
-    desc, keep = api.describe_scene(s)
-    h = C.c_void_p()
-    create = []
-    api._check(L.yart_hip_scene_create(C.byref(desc), 0, C.byref(h)), L)
-    for k in range(RUNS + 1):
-        t0 = time.perf_counter()
-        L.yart_hip_scene_destroy(h)
-        h = C.c_void_p()
-        api._check(L.yart_hip_scene_create(C.byref(desc), 0, C.byref(h)), L)
-        create.append((time.perf_counter() - t0) * 1e3)
+    create, h = recreate_ms(s)
     arrays = [node_array(s.nodes, 0.01 * (k + 1)) for k in range(2)]
     rows = {}
     for tag, flags in (("refit", 0), ("rebuild", api.UPDATE_REBUILD_TOP)):
-        total, device, launches = [], [], 0
-        for k in range(RUNS + 1):
+        def update(k):
             up = api.SceneUpdate(C.sizeof(api.SceneUpdate), len(s.nodes), arrays[k % 2], 0, None, flags)
             st = api.SceneUpdateStats(C.sizeof(api.SceneUpdateStats))
             api._check(L.yart_hip_scene_update(h, C.byref(up), None, C.byref(st)), L)
-            total.append(st.ms_total); device.append(st.ms_device); launches = st.launches
-        rows[tag] = (statistics.median(total[1:]), statistics.median(device[1:]), launches, total[0])
+            return st
+        total, device, launches = update_stats(update)
+        rows[tag] = (statistics.median(total[1:]), statistics.median(device[1:]), launches[-1], total[0])
     L.yart_hip_scene_destroy(h)
     tris = sum(len(m.faces) for m in s.meshes)
     # (first call: the scene's first update, which builds its topology tables — the refit runs come first on a fresh handle; the
     # rebuild runs follow on the same handle, so their warm-up is no first call and is not reported)
-    line = (f"{name:<22} {len(s.nodes):>7} nodes {tris:>8} tris | destroy+create {statistics.median(create[1:]):>10.3f} ms | "
+    line = (f"{name:<22} {len(s.nodes):>7} nodes {tris:>8} tris | destroy+create {create:>10.3f} ms | "
             f"update refit: total {rows['refit'][0]:.3f} ms, device {rows['refit'][1]:.3f} ms, {rows['refit'][2]} launches "
             f"(first call {rows['refit'][3]:.3f} ms) | "
             f"update rebuild: total {rows['rebuild'][0]:.3f} ms, device {rows['rebuild'][1]:.3f} ms, {rows['rebuild'][2]} launches")

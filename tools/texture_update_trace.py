@@ -15,50 +15,24 @@ import ctypes as C
 import os
 import statistics
 import sys
-import time
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from yart_amd import api, scenes  # noqa: E402
-
-RUNS = 5
-
-
-def median_ms(fn):
-    t = []
-    for _ in range(RUNS + 1):
-        t0 = time.perf_counter()
-        fn()
-        t.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(t[1:])
-
+from update_trace_common import recreate_ms, scene_over, update_stats  # noqa: E402
 
 def measure(name, s, updates, out):
     """updates: two {texture: uint8 array} taken in turn"""
     import torch
     L = api.lib()
-    desc, keep = api.describe_scene(s)
-    h = C.c_void_p()
-    api._check(L.yart_hip_scene_create(C.byref(desc), 0, C.byref(h)), L)
-
-    def recreate():
-        nonlocal h
-        L.yart_hip_scene_destroy(h)
-        h = C.c_void_p()
-        api._check(L.yart_hip_scene_create(C.byref(desc), 0, C.byref(h)), L)
-    create = median_ms(recreate)
-    scene = api.DeviceScene.__new__(api.DeviceScene)          # the binding's marshalling over the handle made above
-    scene._h, scene._L, scene._keep, scene.last_update = h, L, [], None
+    create, h = recreate_ms(s)
+    scene = scene_over(h)
     rows = []
     on_device = [{t: torch.from_numpy(np.ascontiguousarray(px)).to("cuda:0") for t, px in u.items()} for u in updates]
     torch.cuda.synchronize()
     for tag, args in (("host pixels", updates), ("device pixels", on_device)):
-        total, device, launches = [], [], []
-        for k in range(RUNS + 1):
-            scene.update_textures(args[k % 2])
-            st = scene.last_update
-            total.append(st["ms_total"]); device.append(st["ms_device"]); launches.append(st["launches"])
+        total, device, launches = update_stats(lambda k: scene.update_textures(args[k % 2]) or scene.last_update)
         rows.append((tag, statistics.median(total[1:]), statistics.median(device[1:]), sorted(set(launches[1:])), total[0]))
     L.yart_hip_scene_destroy(h)
     scene._h = C.c_void_p()

@@ -647,6 +647,14 @@ def _f(arr, n):
     return (C.c_float * n)(*[float(v) for v in np.asarray(arr, np.float32).reshape(-1)[:n]])
 
 
+def _light_descs(lights):
+    """the LightDesc array of a :class:`yscn.Scene` light list (one unused element for an empty list)"""
+    ld = (LightDesc * max(len(lights), 1))()
+    for i, l in enumerate(lights):
+        ld[i] = LightDesc(l.type, l.mesh, l.tri, int(l.two_sided), l.texture, l.radius, _f(l.emission, 3), _f(l.fwd, 16), _f(l.inv, 16))
+    return ld
+
+
 def make_camera(p: dict) -> CameraDesc:
     """``p`` uses the vocabulary of oracle/params.hpp / yart_amd.scenes."""
     c = CameraDesc()
@@ -740,15 +748,27 @@ class DeviceScene:
         nodes = (NodeDesc * len(s.nodes))()
         for i, n in enumerate(s.nodes):
             nodes[i] = NodeDesc(n.parent, n.mesh, _f(n.fwd, 16), _f(n.inv, 16))
-        lights = (LightDesc * max(len(s.lights), 1))()
-        for i, l in enumerate(s.lights):
-            lights[i] = LightDesc(l.type, l.mesh, l.tri, int(l.two_sided), l.texture, l.radius,
-                                  _f(l.emission, 3), _f(l.fwd, 16), _f(l.inv, 16))
+        lights = _light_descs(s.lights)
         keep += [tex, mats, meshes, nodes, lights]
         return SceneDesc(len(s.textures), len(s.materials), len(s.meshes), len(s.nodes), len(s.lights),
                          tex, mats, meshes, nodes, lights)
 
     # -- animation ----------------------------------------------------------------
+    def _update(self, entry, up, stream):
+        """one of the yart_hip_scene_update* entries on this scene; its statistics into ``self.last_update``"""
+        st = SceneUpdateStats(C.sizeof(SceneUpdateStats))
+        _check(getattr(self._L, entry)(self._h, C.byref(up), stream, C.byref(st)), self._L)
+        self.last_update = dict(launches=st.launches, ms_total=st.ms_total, ms_device=st.ms_device)
+
+    def _probe(self, entry, pr, shape):
+        """a probe entry's two calls: the first fills ``pr``'s sizes, ``shape()`` -> {field: (size, dtype)}, the second fills the arrays"""
+        _check(getattr(self._L, entry)(self._h, C.byref(pr)), self._L)
+        out = {name: np.zeros(int(n), dt) for name, (n, dt) in shape().items()}
+        for name, a in out.items():
+            setattr(pr, name, a.ctypes.data_as(C.c_void_p) if len(a) else None)
+        _check(getattr(self._L, entry)(self._h, C.byref(pr)), self._L)
+        return out
+
     def update(self, nodes, lights=None, rebuild_top=False, motion=False, stream=None):
         """yart_hip_scene_update: new transforms for the scene in place. ``nodes`` / ``lights``: the node / light lists of a
         :class:`yscn.Scene` — parent and mesh, and every light field but fwd / inv, as at create; ``lights=None`` leaves the lights
@@ -760,15 +780,11 @@ class DeviceScene:
         for i, n in enumerate(nodes):
             nd[i] = NodeDesc(n.parent, n.mesh, _f(n.fwd, 16), _f(n.inv, 16))
         lights = list(lights) if lights is not None else []
-        ld = (LightDesc * max(len(lights), 1))()
-        for i, l in enumerate(lights):
-            ld[i] = LightDesc(l.type, l.mesh, l.tri, int(l.two_sided), l.texture, l.radius, _f(l.emission, 3), _f(l.fwd, 16), _f(l.inv, 16))
+        ld = _light_descs(lights)
         up = SceneUpdate(C.sizeof(SceneUpdate), len(nodes), nd, len(lights), ld if lights else None, UPDATE_REBUILD_TOP if rebuild_top else 0)
-        st = SceneUpdateStats(C.sizeof(SceneUpdateStats))
         if motion and self._nodes is None:
             raise YartError(YART_E_INVALID, "update(motion=True): the scene was loaded from a file, its previous node list is not known")
-        _check(self._L.yart_hip_scene_update(self._h, C.byref(up), stream, C.byref(st)), self._L)
-        self.last_update = dict(launches=st.launches, ms_total=st.ms_total, ms_device=st.ms_device)
+        self._update("yart_hip_scene_update", up, stream)
         previous, self._nodes, self._n_nodes = self._nodes, _motion_snapshot(nodes), len(nodes)
         if motion:
             from . import temporal
@@ -799,9 +815,7 @@ class DeviceScene:
             n = n or 0
             md[k] = MeshUpdate(int(mesh), n, ptrs[0], ptrs[1], ptrs[2])
         up = SceneMeshUpdate(C.sizeof(SceneMeshUpdate), len(meshes), md, UPDATE_REBUILD_TOP if rebuild_top else 0)
-        st = SceneUpdateStats(C.sizeof(SceneUpdateStats))
-        _check(self._L.yart_hip_scene_update_meshes(self._h, C.byref(up), stream, C.byref(st)), self._L)
-        self.last_update = dict(launches=st.launches, ms_total=st.ms_total, ms_device=st.ms_device)
+        self._update("yart_hip_scene_update_meshes", up, stream)
 
     def update_lighting(self, materials=None, lights=None, images=None, stream=None):
         """yart_hip_scene_update_lighting: new material values, new light emission / radius / transforms and new environment images
@@ -815,9 +829,7 @@ class DeviceScene:
         for i, m in enumerate(materials):
             C.memmove(C.byref(md[i]), m.pack(), C.sizeof(MaterialDesc))
         lights = list(lights) if lights is not None else []
-        ld = (LightDesc * max(len(lights), 1))()
-        for i, l in enumerate(lights):
-            ld[i] = LightDesc(l.type, l.mesh, l.tri, int(l.two_sided), l.texture, l.radius, _f(l.emission, 3), _f(l.fwd, 16), _f(l.inv, 16))
+        ld = _light_descs(lights)
         images = dict(images) if images is not None else {}
         im = (EnvImageUpdate * max(len(images), 1))()
         for k, (tex, px) in enumerate(images.items()):
@@ -828,9 +840,7 @@ class DeviceScene:
             im[k] = EnvImageUpdate(int(tex), px.shape[1], px.shape[0], px.ctypes.data_as(C.c_void_p))
         up = SceneLightingUpdate(C.sizeof(SceneLightingUpdate), len(materials), md if materials else None, len(lights),
                                  ld if lights else None, len(images), im if images else None, 0)
-        st = SceneUpdateStats(C.sizeof(SceneUpdateStats))
-        _check(self._L.yart_hip_scene_update_lighting(self._h, C.byref(up), stream, C.byref(st)), self._L)
-        self.last_update = dict(launches=st.launches, ms_total=st.ms_total, ms_device=st.ms_device)
+        self._update("yart_hip_scene_update_lighting", up, stream)
 
     def lighting_records(self):
         """yart_hip_probe_lighting: what ``update_lighting`` re-derives, read back from the device: dict(materials:
@@ -838,15 +848,11 @@ class DeviceScene:
         uint32, area_power_cdf: float32, total_power: float, tex_f32: float32, tex_quads: uint8 (the footprint-record array, empty
         where the scene has none; bytes outside the records are unspecified), textures: TEX_DEV_DTYPE)."""
         pr = LightingProbe(C.sizeof(LightingProbe))
-        _check(self._L.yart_hip_probe_lighting(self._h, C.byref(pr)), self._L)
-        shape = dict(materials=(pr.n_materials, MATERIAL_DEV_DTYPE), mat_class=(pr.n_mat_class, np.uint8), lights=(pr.n_lights, LIGHT_DEV_DTYPE),
-                     envs=(pr.n_envs, ENV_DEV_DTYPE), env_data=(pr.n_env_data, np.float32), env_guide=(pr.n_env_guide, np.uint32),
-                     area_power_cdf=(pr.n_area_power_cdf, np.float32), tex_f32=(pr.n_tex_f32, np.float32),
-                     tex_quads=(pr.n_tex_quad_bytes, np.uint8), textures=(pr.n_textures, TEX_DEV_DTYPE))
-        out = {name: np.zeros(int(n), dt) for name, (n, dt) in shape.items()}
-        for name, a in out.items():
-            setattr(pr, name, a.ctypes.data_as(C.c_void_p) if len(a) else None)
-        _check(self._L.yart_hip_probe_lighting(self._h, C.byref(pr)), self._L)
+        out = self._probe("yart_hip_probe_lighting", pr, lambda: dict(
+            materials=(pr.n_materials, MATERIAL_DEV_DTYPE), mat_class=(pr.n_mat_class, np.uint8), lights=(pr.n_lights, LIGHT_DEV_DTYPE),
+            envs=(pr.n_envs, ENV_DEV_DTYPE), env_data=(pr.n_env_data, np.float32), env_guide=(pr.n_env_guide, np.uint32),
+            area_power_cdf=(pr.n_area_power_cdf, np.float32), tex_f32=(pr.n_tex_f32, np.float32),
+            tex_quads=(pr.n_tex_quad_bytes, np.uint8), textures=(pr.n_textures, TEX_DEV_DTYPE)))
         out["total_power"] = float(pr.total_power)
         return out
 
@@ -875,21 +881,14 @@ class DeviceScene:
             keep.append(px)
             td[k] = TextureUpdate(int(tex), shape[1], shape[0], shape[2], ptr, flags)
         up = SceneTextureUpdate(C.sizeof(SceneTextureUpdate), len(textures), td, 0)
-        st = SceneUpdateStats(C.sizeof(SceneUpdateStats))
-        _check(self._L.yart_hip_scene_update_textures(self._h, C.byref(up), stream, C.byref(st)), self._L)
-        self.last_update = dict(launches=st.launches, ms_total=st.ms_total, ms_device=st.ms_device)
+        self._update("yart_hip_scene_update_textures", up, stream)
 
     def texture_records(self):
         """yart_hip_probe_textures: the 8-bit texels and the texture records, read back from the device: dict(tex_u8: uint8 (every
         texture padded to a multiple of 4 bytes), textures: TEX_DEV_DTYPE (offset: a texture's first byte of tex_u8; behind the
         scene's textures the entries creation adds for bundles))."""
         pr = TexturesProbe(C.sizeof(TexturesProbe))
-        _check(self._L.yart_hip_probe_textures(self._h, C.byref(pr)), self._L)
-        out = dict(tex_u8=np.zeros(int(pr.n_tex_u8), np.uint8), textures=np.zeros(int(pr.n_textures), TEX_DEV_DTYPE))
-        for name, a in out.items():
-            setattr(pr, name, a.ctypes.data_as(C.c_void_p) if len(a) else None)
-        _check(self._L.yart_hip_probe_textures(self._h, C.byref(pr)), self._L)
-        return out
+        return self._probe("yart_hip_probe_textures", pr, lambda: dict(tex_u8=(pr.n_tex_u8, np.uint8), textures=(pr.n_textures, TEX_DEV_DTYPE)))
 
     def keep_previous(self, stream=None):
         """yart_hip_scene_keep_previous: the scene remembers the frame it holds (node transforms and vertex positions) as its

@@ -103,27 +103,20 @@ __global__ void __launch_bounds__(kBlock) k_lu_guide(LuEnvArgs a) {
   }
 }
 
-void luCheck(bool ok, const std::string& what) {
-  if (!ok) throw std::invalid_argument("scene_update_lighting: " + what);
-}
+constexpr UpdateCheck luCheck{"scene_update_lighting: "};
 
-// Everything that can refuse an update before the scene is looked at. Returns the update copied into a struct of this build's size.
-YartSceneLightingUpdate luValidateArguments(const YartScene* scene, const YartSceneLightingUpdate* up) {
-  luCheck(scene != nullptr, "scene pointer is null");
-  luCheck(up != nullptr, "update pointer is null");
-  luCheck(up->struct_size >= sizeof(YartSceneLightingUpdate), "struct_size is smaller than YartSceneLightingUpdate");
-  YartSceneLightingUpdate u = *up;
+// Everything that can refuse an update before the scene is looked at (behind updateHead's checks)
+void luValidateArguments(const YartSceneLightingUpdate& u) {
   luCheck(u.flags == 0u, "unknown flags (none are defined)");
   luCheck(u.n_materials || u.n_lights || u.n_images, "n_materials, n_lights and n_images are all 0");
   luCheck(!u.n_materials || u.materials != nullptr, "materials pointer is null");
   luCheck(!u.n_lights || u.lights != nullptr, "lights pointer is null");
   luCheck(!u.n_images || u.images != nullptr, "images pointer is null");
-  return u;
 }
 // ... and what compares it with the scene
-void luValidateAgainstScene(const YartScene* scene, const YartSceneLightingUpdate& u) {
-  const HostImage& h = scene->host;
-  const LightingUpdateState& lu = scene->lightUp;
+void luValidateAgainstScene(const YartScene& scene, const YartSceneLightingUpdate& u) {
+  const HostImage& h = scene.host;
+  const LightingUpdateState& lu = scene.lightUp;
   if (u.n_materials) {
     luCheck(u.n_materials == h.nMaterials, "n_materials is neither 0 nor the scene's material count " + std::to_string(h.nMaterials));
     luCheck(lu.materialDesc.size() == h.nMaterials, "internal: the scene does not hold its material descriptors");
@@ -133,8 +126,8 @@ void luValidateAgainstScene(const YartScene* scene, const YartSceneLightingUpdat
       luCheck(a.tex_base == b.tex_base && a.tex_mr == b.tex_mr && a.tex_transmission == b.tex_transmission && a.tex_normal == b.tex_normal &&
               a.tex_clearcoat == b.tex_clearcoat && a.tex_emission == b.tex_emission, name + ": a texture slot differs from the scene's");
       luCheck((a.thin_transmission != 0u) == (b.thin_transmission != 0u), name + ": thin_transmission differs from the scene's");
-      luCheck(suFiniteWords(a.base, 3) && suFiniteWords(a.emission, 3) && suFiniteWords(&a.metallic, 9) && suFiniteWords(a.volume_color, 3) &&
-              suFiniteWords(&a.volume_density, 1), name + ": a word is not finite");
+      luCheck(finiteWords(a.base, 3) && finiteWords(a.emission, 3) && finiteWords(&a.metallic, 9) && finiteWords(a.volume_color, 3) &&
+              finiteWords(&a.volume_density, 1), name + ": a word is not finite");
       luCheck(luTransparent(a) == ((h.materials[i].flags & MAT_TRANSPARENT) != 0u),
               name + ": the change would make a thin material transparent or opaque (transmission > 0: the leaf records carry that bit; such a scene is re-created)");
     }
@@ -144,10 +137,9 @@ void luValidateAgainstScene(const YartScene* scene, const YartSceneLightingUpdat
     for (uint32_t i = 0; i < u.n_lights; i++) {
       const YartLightDesc& a = u.lights[i]; const YartLightDesc& b = h.lightDesc[i];
       const std::string name = "light " + std::to_string(i);
-      luCheck(a.type == b.type && a.mesh == b.mesh && a.tri == b.tri && a.two_sided == b.two_sided && a.texture == b.texture,
-              name + ": type, mesh, tri, two_sided or texture differ from the scene's");
-      luCheck(suFiniteWords(&a.radius, 1) && suFiniteWords(a.emission, 3), name + ": radius or an emission word is not finite");
-      luCheck(suFiniteWords(a.fwd, 16) && suFiniteWords(a.inv, 16), name + ": a matrix word is not finite");
+      luCheck(sameLightTopology(a, b), name + ": type, mesh, tri, two_sided or texture differ from the scene's");
+      luCheck(finiteWords(&a.radius, 1) && finiteWords(a.emission, 3), name + ": radius or an emission word is not finite");
+      luCheck(finiteWords(a.fwd, 16) && finiteWords(a.inv, 16), name + ": a matrix word is not finite");
     }
   }
   std::vector<uint8_t> listed(h.textures.size(), 0);
@@ -176,7 +168,8 @@ void luValidateAgainstScene(const YartScene* scene, const YartSceneLightingUpdat
 uint32_t luGrid(size_t n) { return uint32_t(std::min<size_t>((n + kBlock - 1u) / kBlock, 65535u)); }
 
 // the tables of one image light from the texels that are in texF32 (in stream order)
-void luRebuildEnv(YartScene& s, uint32_t env, const TexDev& t, hipStream_t stream, uint32_t& launches) {
+void luRebuildEnv(YartScene& s, uint32_t env, const TexDev& t, UpdateCall& call) {
+  const hipStream_t stream = call.stream;
   const EnvDev& e = s.host.envs[env];
   const uint32_t w = e.w, h = e.h;
   // (what the kernels index: the record is create's, checked all the same before anything is launched from it)
@@ -188,25 +181,25 @@ void luRebuildEnv(YartScene& s, uint32_t env, const TexDev& t, hipStream_t strea
     throw HipError("scene_update_lighting: the tables of image light table " + std::to_string(env) + " do not have create's layout");
   LuEnvArgs a{s.texF32.p + t.offset, s.envData.p, s.envGuide.p, s.envs.p + env, e};
   hipLaunchKernelGGL(k_lu_func, dim3(luGrid(size_t(w) * h)), dim3(kBlock), 0, stream, a);
+  call.launched();
   hipLaunchKernelGGL(k_lu_rows, dim3((h + kLuTile - 1u) / kLuTile), dim3(64), 0, stream, a);
+  call.launched();
   hipLaunchKernelGGL(k_lu_norm, dim3(luGrid(size_t(w + 1u) * h)), dim3(kBlock), 0, stream, a);
+  call.launched();
   hipLaunchKernelGGL(k_lu_marginal, dim3(1), dim3(kBlock), 0, stream, a);
+  call.launched();
   hipLaunchKernelGGL(k_lu_guide, dim3(luGrid(size_t(e.guideKh) + 1u + size_t(h) * (size_t(e.guideKw) + 1u))), dim3(kBlock), 0, stream, a);
-  HIP_CHECK(hipGetLastError());
-  launches += 5u;
+  call.launched();
 }
 
 void luUpdate(YartScene& s, const YartSceneLightingUpdate& u, hipStream_t stream, YartSceneUpdateStats* stats) {
-  const auto wall0 = std::chrono::high_resolution_clock::now();
-  HIP_CHECK(hipSetDevice(s.device));
+  std::vector<uint8_t> cls;                                  // the lobe classes, and the one word of an EnvDev record that the device
+  std::vector<float> margIntegral;                           // derives (copies read / write the two: before the frame)
+  UpdateCall call(WallClock::now(), s.device, stream);
   HostImage& h = s.host;
   LightingUpdateState& lu = s.lightUp;
-  uint32_t launches = 0;
-  Timer tm;
-  HIP_CHECK(hipEventRecord(tm.a, stream));
   if (lu.envSumKnown.size() != h.envs.size()) { lu.envSumKnown.assign(h.envs.size(), 0); lu.envSum.assign(h.envs.size(), LuSum{0.0f, 0.0f, 0.0f}); }
   std::vector<uint32_t> touched;                             // the EnvDev records whose margIntegral the device rewrites
-  std::vector<uint8_t> cls;                                  // (the lobe classes: alive until the stream has been synchronised)
   for (uint32_t k = 0; k < u.n_images; k++) {
     const YartEnvImageUpdate& im = u.images[k];
     const TexDev& t = h.textures[im.texture];
@@ -215,12 +208,11 @@ void luUpdate(YartScene& s, const YartSceneLightingUpdate& u, hipStream_t stream
     if (s.texQuadsOn && t.quadOffset != kNoTexQuads) {
       TexQuadArgs qa{s.texU8.p, s.texF32.p, t, s.texQuads.p + size_t(t.quadOffset) * 16u};
       hipLaunchKernelGGL(k_tex_quads, dim3(luGrid(n / 3u)), dim3(kBlock), 0, stream, qa);
-      HIP_CHECK(hipGetLastError());
-      launches++;
+      call.launched();
     }
     for (uint32_t i = 0; i < h.nLights; i++)
       if (h.lights[i].type == LIGHT_IMAGE_INF && h.lights[i].texture == int32_t(im.texture)) {
-        luRebuildEnv(s, h.lights[i].envOffset, t, stream, launches);
+        luRebuildEnv(s, h.lights[i].envOffset, t, call);
         touched.push_back(h.lights[i].envOffset);
       }
     // on the host while the device works: the host's copy of the texels and their sum (its order is part of the bits)
@@ -237,7 +229,7 @@ void luUpdate(YartScene& s, const YartSceneLightingUpdate& u, hipStream_t stream
     HIP_CHECK(hipMemcpyAsync(s.materials.p, h.materials.data(), h.materials.size() * sizeof(MaterialDev), hipMemcpyHostToDevice, stream));
     HIP_CHECK(hipMemcpyAsync(s.matClass.p, cls.data(), cls.size(), hipMemcpyHostToDevice, stream));
   }
-  std::vector<float> margIntegral(touched.size());           // the one word of an EnvDev record that the device derives
+  margIntegral.resize(touched.size());
   for (size_t k = 0; k < touched.size(); k++)
     HIP_CHECK(hipMemcpyAsync(&margIntegral[k], &s.envs.p[touched[k]].margIntegral, 4, hipMemcpyDeviceToHost, stream));
   if (u.n_lights || u.n_images) {                            // (an image light's power follows its map's Lavg)
@@ -250,23 +242,11 @@ void luUpdate(YartScene& s, const YartSceneLightingUpdate& u, hipStream_t stream
     }
     const std::vector<YartLightDesc> desc = u.n_lights ? std::vector<YartLightDesc>(u.lights, u.lights + u.n_lights) : h.lightDesc;
     luRederiveLights(h, desc.data(), h.nLights, lu.envSum.data());
-    s.dev.totalPower = h.totalPower;
-    HIP_CHECK(hipMemcpyAsync(s.lights.p, h.lights.data(), h.lights.size() * sizeof(LightDev), hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(s.areaPowerCdf.p, h.areaPowerCdf.data(), h.areaPowerCdf.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    uploadLights(s, stream);
   }
-  HIP_CHECK(hipEventRecord(tm.b, stream));
-  HIP_CHECK(hipStreamSynchronize(stream));
+  call.close();
   for (size_t k = 0; k < touched.size(); k++) h.envs[touched[k]].margIntegral = margIntegral[k];
-  if (stats) {
-    YartSceneUpdateStats out{};
-    out.struct_size = stats->struct_size;
-    out.launches = launches;
-    float ms = 0.0f;
-    HIP_CHECK(hipEventElapsedTime(&ms, tm.a, tm.b));
-    out.ms_device = ms;
-    out.ms_total = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - wall0).count();
-    std::memcpy(stats, &out, std::min<size_t>(stats->struct_size, sizeof(out)));
-  }
+  call.finish(stats);
 }
 
 }  // namespace
@@ -274,13 +254,7 @@ void luUpdate(YartScene& s, const YartSceneLightingUpdate& u, hipStream_t stream
 extern "C" {
 
 int yart_hip_scene_update_lighting(YartScene* scene, const YartSceneLightingUpdate* update, void* stream, YartSceneUpdateStats* stats) {
-  return guarded([&] {
-    const YartSceneLightingUpdate u = luValidateArguments(scene, update);
-    luCheck(!stats || stats->struct_size >= 8u, "stats: struct_size is smaller than its first two fields");
-    std::lock_guard<std::mutex> lock(scene->mu);
-    luValidateAgainstScene(scene, u);
-    luUpdate(*scene, u, static_cast<hipStream_t>(stream), stats);
-  });
+  return updateEntry(luCheck, "YartSceneLightingUpdate", scene, update, stream, stats, luValidateArguments, luValidateAgainstScene, luUpdate);
 }
 
 int yart_hip_probe_lighting(YartScene* scene, YartLightingProbe* p) {

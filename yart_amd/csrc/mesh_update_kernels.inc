@@ -1,6 +1,6 @@
 // mesh_update_kernels.inc — yart_hip_scene_update_meshes: new vertices for meshes of a scene that is on the device, and the kernels
 // that re-derive what buildHostImage derives from a mesh's vertices and its BVH (included by yart_hip.hip, unit 0, behind
-// scene_update_kernels.inc: the entry ends in suUpdate). The arithmetic is csrc/mesh_update.hpp's; per listed mesh:
+// scene_update_kernels.inc: the entry ends in suRun). The arithmetic is csrc/mesh_update.hpp's; per listed mesh:
 //
 //   (copies)         the caller's positions / normals / tangents into the mesh's staging arrays, packed as the caller has them
 //   devbvh::buildCore  the reference's binned-SAH build over the staged positions and the scene's own faces (triVerts + triOffset),
@@ -17,7 +17,7 @@
 //                    zero records behind the last mesh) into a second array when a node count changed, and the two arrays swapped
 //   k_mu_verts       vPos / vNormal / vTangent entries from the staged arrays
 //   k_mu_shade       (normals or tangents given) the ShadeTri normals / tangents of the mesh's faces
-//   suUpdate         the scene-update chain with the scene's current transforms over the new vertex boxes
+//   suRun            the scene-update chain with the scene's current transforms over the new vertex boxes
 //
 // A mesh the device build refuses (more than devbvh::kMaxLevels levels) — and every mesh under the environment variable
 // YART_HOST_BVH, as at scene creation — is built and derived on the host (muDeriveHost) and uploaded into the same staging arrays.
@@ -105,24 +105,17 @@ __global__ void __launch_bounds__(kBlock) k_mu_links(MuLinkArgs a, uint32_t base
   atomicMax(a.result, depth);
 }
 
-void muCheck(bool ok, const std::string& what) {
-  if (!ok) throw std::invalid_argument("scene_update_meshes: " + what);
-}
+constexpr UpdateCheck muCheck{"scene_update_meshes: "};
 
-// Everything that can refuse an update before a mesh is built. Returns the update copied into a struct of this build's size.
-YartSceneMeshUpdate muValidateArguments(const YartScene* scene, const YartSceneMeshUpdate* up) {
-  muCheck(scene != nullptr, "scene pointer is null");
-  muCheck(up != nullptr, "update pointer is null");
-  muCheck(up->struct_size >= sizeof(YartSceneMeshUpdate), "struct_size is smaller than YartSceneMeshUpdate");
-  YartSceneMeshUpdate u = *up;
+// Everything that can refuse an update before a mesh is built (behind updateHead's checks)
+void muValidateArguments(const YartSceneMeshUpdate& u) {
   muCheck(u.meshes != nullptr, "meshes pointer is null");
   muCheck((u.flags & ~YART_UPDATE_REBUILD_TOP) == 0u, "unknown flags");
   muCheck(u.n_meshes >= 1u, "n_meshes is 0");
-  return u;
 }
 // ... and what compares it with the scene; boxes: the new vertex box of every listed mesh
-void muValidateAgainstScene(const YartScene* scene, const YartSceneMeshUpdate& u, std::vector<SuBox>& boxes) {
-  const HostImage& h = scene->host;
+void muValidateAgainstScene(const YartScene& scene, const YartSceneMeshUpdate& u, std::vector<SuBox>& boxes) {
+  const HostImage& h = scene.host;
   muCheck(u.n_meshes <= h.meshes.size(), "n_meshes is " + std::to_string(u.n_meshes) + ", the scene has " + std::to_string(h.meshes.size()) + " meshes");
   std::vector<uint8_t> listed(h.meshes.size(), 0);
   boxes.resize(u.n_meshes);
@@ -136,19 +129,17 @@ void muValidateAgainstScene(const YartScene* scene, const YartSceneMeshUpdate& u
                                                          std::to_string(h.meshes[m.mesh].nVerts) + " (the vertex count cannot change)");
     muCheck(m.positions != nullptr, name + ": positions pointer is null");
     const size_t nv = m.n_vertices;
-    auto finite = [](const float* p, size_t n) { for (size_t i = 0; i < n; i++) if (!std::isfinite(p[i])) return false; return true; };
-    muCheck(finite(m.positions, nv * 3u), name + ": a position word is not finite");
-    muCheck(!m.normals || finite(m.normals, nv * 3u), name + ": a normal word is not finite");
-    muCheck(!m.tangents || finite(m.tangents, nv * 4u), name + ": a tangent word is not finite");
+    muCheck(finiteWords(m.positions, nv * 3u), name + ": a position word is not finite");
+    muCheck(!m.normals || finiteWords(m.normals, nv * 3u), name + ": a normal word is not finite");
+    muCheck(!m.tangents || finiteWords(m.tangents, nv * 4u), name + ": a tangent word is not finite");
     boxes[k] = muVertexBox(m.positions, m.n_vertices);
   }
-  for (size_t m = 0; m < h.meshBox.size(); m++)
-    muCheck(listed[m] || (suFiniteWords(h.meshBox[m].mn, 3) && suFiniteWords(h.meshBox[m].mx, 3)),
-            "mesh " + std::to_string(m) + ": its vertex box is not finite (such a scene is re-created, not updated)");
+  checkMeshBoxes(muCheck, h, listed.data());
 }
 
 // One listed mesh into its staging arrays: upload, build, derive. Nothing of the scene is written.
-void muStageMesh(YartScene& s, const YartMeshUpdate& m, MeshStage& st, hipStream_t stream, uint32_t& launches) {
+void muStageMesh(YartScene& s, const YartMeshUpdate& m, MeshStage& st, UpdateCall& call) {
+  const hipStream_t stream = call.stream;
   const HostImage& h = s.host;
   MeshUpdateState& mu = s.meshUp;
   const MeshDev& md = h.meshes[m.mesh];
@@ -171,26 +162,25 @@ void muStageMesh(YartScene& s, const YartMeshUpdate& m, MeshStage& st, hipStream
   st.idxHost.resize(nt);
   const bool hostBuild = std::getenv("YART_HOST_BVH") != nullptr;      // (as scene creation: the host builder on request)
   if (!hostBuild && devbvh::buildCore(mu.scratch, st.pos.p, faces, 4u, nt, st.nodes.p, st.idx.p, stream, built, nullptr)) {
-    launches += built.launches;
+    call.launchedBy(built.launches);
     st.nNodes = built.nNodes();
     HIP_CHECK(hipMemsetAsync(mu.result.p, 0, 16, stream));
     MuLeafArgs la{st.pos.p, s.triVerts.p + md.triOffset, s.materials.p, st.idx.p, st.leaf.p, md.triOffset, nt, nv, uint32_t(h.materials.size()), mu.result.p};
     hipLaunchKernelGGL(k_mu_leaves, dim3((nt + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, la);
-    launches++;
+    call.launched();
     const bool alpha = mu.meshAlpha[m.mesh] > 0;
     if (alpha) {
       mu.prefix.ensure(size_t(nt) + 1u);
       hipLaunchKernelGGL(k_mu_alpha_scan, dim3(1), dim3(kMuScanBlock), 0, stream, st.leaf.p, mu.prefix.p, nt);
-      launches++;
+      call.launched();
     }
     MuLinkArgs ka{built.args, alpha ? mu.prefix.p : nullptr, st.leaf.p, mu.result.p, st.nNodes};
     hipLaunchKernelGGL(k_mu_links, dim3((built.created + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, ka, 0u, built.created);
-    launches++;
+    call.launched();
     if (built.createdLocal) {
       hipLaunchKernelGGL(k_mu_links, dim3((built.createdLocal + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, ka, nt * 2u, built.createdLocal);
-      launches++;
+      call.launched();
     }
-    HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(res, mu.result.p, 12, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipMemcpyAsync(st.idxHost.data(), st.idx.p, size_t(nt) * 4u, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
@@ -199,7 +189,7 @@ void muStageMesh(YartScene& s, const YartMeshUpdate& m, MeshStage& st, hipStream
     st.need = res[0]; st.hasAlpha = res[2];
   } else {
     // more levels than the level kernels take, or YART_HOST_BVH: the host builder (the same bytes) and the host statement of the derivation
-    launches += built.launches;
+    call.launchedBy(built.launches);
     SahBvhBuilder hb;
     const char* e = std::getenv("YART_BVH_THREADS");
     hb.setThreads(e ? unsigned(std::atoi(e)) : 0u);
@@ -223,15 +213,13 @@ void muStageMesh(YartScene& s, const YartMeshUpdate& m, MeshStage& st, hipStream
 }
 
 void muUpdate(YartScene& s, const YartSceneMeshUpdate& u, const std::vector<SuBox>& boxes, hipStream_t stream, YartSceneUpdateStats* stats) {
-  const auto wall0 = std::chrono::high_resolution_clock::now();
-  HIP_CHECK(hipSetDevice(s.device));
+  std::vector<YartNodeDesc> nodes;                           // (copies read the two: before the frame)
+  std::vector<uint32_t> flags;
+  UpdateCall call(WallClock::now(), s.device, stream);
   HostImage& h = s.host;
   MeshUpdateState& mu = s.meshUp;
-  uint32_t launches = 0;
-  Timer tm;
-  HIP_CHECK(hipEventRecord(tm.a, stream));
   while (mu.stages.size() < u.n_meshes) mu.stages.push_back(std::make_unique<MeshStage>());
-  for (uint32_t k = 0; k < u.n_meshes; k++) muStageMesh(s, u.meshes[k], *mu.stages[k], stream, launches);
+  for (uint32_t k = 0; k < u.n_meshes; k++) muStageMesh(s, u.meshes[k], *mu.stages[k], call);
 
   // ---- every listed mesh has built: from here on the scene is written
   const uint32_t nm = uint32_t(h.meshes.size());
@@ -274,13 +262,12 @@ void muUpdate(YartScene& s, const YartSceneMeshUpdate& u, const std::vector<SuBo
     MuVertArgs va{st.pos.p, m.normals ? st.nrm.p : nullptr, m.tangents ? st.tan.p : nullptr, s.vPos.p + md.vertOffset, s.vNormal.p + md.vertOffset,
                   s.vTangent.p + md.vertOffset, md.nVerts};
     hipLaunchKernelGGL(k_mu_verts, dim3((md.nVerts + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, va);
-    launches++;
+    call.launched();
     if (m.normals || m.tangents) {
       MuShadeArgs sa{va.nrm, va.tan, s.triVerts.p + md.triOffset, s.shadeTris.p + md.triOffset, md.nTris, md.nVerts};
       hipLaunchKernelGGL(k_mu_shade, dim3((md.nTris + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, sa);
-      launches++;
+      call.launched();
     }
-    HIP_CHECK(hipGetLastError());
     // the host image: what the library reads after create (yart_hip_bvh_info / _copy, the lights' vertices, the next update's boxes)
     md.nNodes = st.nNodes; md.hasAlpha = st.hasAlpha;
     h.meshStackNeed[m.mesh] = st.need;
@@ -302,36 +289,24 @@ void muUpdate(YartScene& s, const YartSceneMeshUpdate& u, const std::vector<SuBo
   if (!s.su.ready) suBuildTables(s);                        // (uploads h.meshBox)
   else for (uint32_t k = 0; k < u.n_meshes; k++)
     HIP_CHECK(hipMemcpyAsync(s.su.meshBox.p + u.meshes[k].mesh, &h.meshBox[u.meshes[k].mesh], sizeof(SuBox), hipMemcpyHostToDevice, stream));
-  std::vector<YartNodeDesc> nodes(h.nodes.size());
+  // (the chain takes transforms as the caller of yart_hip_scene_update gives them — its scatter kernel reads YartNodeDesc records —, so
+  // the current ones go to it in that form)
+  nodes.resize(h.nodes.size());
   for (size_t i = 0; i < nodes.size(); i++) {
     nodes[i].parent = h.nodes[i].parent; nodes[i].mesh = h.nodes[i].mesh;
     std::memcpy(nodes[i].fwd, h.nodes[i].xf.fwd, 64); std::memcpy(nodes[i].inv, h.nodes[i].xf.inv, 64);
   }
   YartSceneUpdate su{};
   su.struct_size = sizeof(su); su.n_nodes = uint32_t(nodes.size()); su.nodes = nodes.data(); su.flags = u.flags;
-  YartSceneUpdateStats suStats{};
-  suStats.struct_size = sizeof(suStats);
-  suUpdate(s, su, stream, &suStats);
-  launches += suStats.launches;
+  flags.resize(nodes.size());
+  suRun(s, su, flags, suIdentityFlags(su.nodes, su.n_nodes, flags.data()), call);
   if (lightsChange) {                                        // area lights on an updated mesh: from the host's new vertices, as create derives them
     const std::vector<YartLightDesc> desc = h.lightDesc;
     rederiveLights(h, desc.data(), h.nLights);
-    s.dev.totalPower = h.totalPower;
-    HIP_CHECK(hipMemcpyAsync(s.lights.p, h.lights.data(), h.lights.size() * sizeof(LightDev), hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(s.areaPowerCdf.p, h.areaPowerCdf.data(), h.areaPowerCdf.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    uploadLights(s, stream);
+    call.close();                                            // (once more: suRun closed the frame before this upload)
   }
-  HIP_CHECK(hipEventRecord(tm.b, stream));
-  HIP_CHECK(hipStreamSynchronize(stream));
-  if (stats) {
-    YartSceneUpdateStats out{};
-    out.struct_size = stats->struct_size;
-    out.launches = launches;
-    float ms = 0.0f;
-    HIP_CHECK(hipEventElapsedTime(&ms, tm.a, tm.b));
-    out.ms_device = ms;
-    out.ms_total = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - wall0).count();
-    std::memcpy(stats, &out, std::min<size_t>(stats->struct_size, sizeof(out)));
-  }
+  call.finish(stats);
 }
 
 }  // namespace
@@ -339,14 +314,11 @@ void muUpdate(YartScene& s, const YartSceneMeshUpdate& u, const std::vector<SuBo
 extern "C" {
 
 int yart_hip_scene_update_meshes(YartScene* scene, const YartSceneMeshUpdate* update, void* stream, YartSceneUpdateStats* stats) {
-  return guarded([&] {
-    const YartSceneMeshUpdate u = muValidateArguments(scene, update);
-    muCheck(!stats || stats->struct_size >= 8u, "stats: struct_size is smaller than its first two fields");
-    std::lock_guard<std::mutex> lock(scene->mu);
-    std::vector<SuBox> boxes;
-    muValidateAgainstScene(scene, u, boxes);
-    muUpdate(*scene, u, boxes, static_cast<hipStream_t>(stream), stats);
-  });
+  std::vector<SuBox> boxes;                                  // (the listed meshes' new vertex boxes: from the checks to the run)
+  return updateEntry(
+      muCheck, "YartSceneMeshUpdate", scene, update, stream, stats, muValidateArguments,
+      [&](const YartScene& s, const YartSceneMeshUpdate& u) { muValidateAgainstScene(s, u, boxes); },
+      [&](YartScene& s, const YartSceneMeshUpdate& u, hipStream_t st, YartSceneUpdateStats* out) { muUpdate(s, u, boxes, st, out); });
 }
 
 int yart_hip_probe_mesh(YartScene* scene, uint32_t mesh, void* mesh_dev_out, void* nodes_out, void* leaf_out, void* shade_out, float* vpos_out,

@@ -153,60 +153,41 @@ void suBuildTlasOrder(YartScene& s) {
   u.tlasReady = true;
 }
 
-void suCheck(bool ok, const std::string& what) {
-  if (!ok) throw std::invalid_argument("scene_update: " + what);
-}
-bool suFiniteWords(const float* m, uint32_t n) {
-  for (uint32_t k = 0; k < n; k++) if (!std::isfinite(m[k])) return false;
-  return true;
-}
+constexpr UpdateCheck suCheck{"scene_update: "};
 
-// Everything that can refuse an update, before anything is written. Returns the update copied into a struct of this build's size.
-// (first what needs no look at the scene — before its lock is taken —, then what compares the update with the scene)
-YartSceneUpdate suValidateArguments(const YartScene* scene, const YartSceneUpdate* up) {
-  suCheck(scene != nullptr, "scene pointer is null");
-  suCheck(up != nullptr, "update pointer is null");
-  suCheck(up->struct_size >= sizeof(YartSceneUpdate), "struct_size is smaller than YartSceneUpdate");
-  YartSceneUpdate u = *up;
+// Everything that can refuse an update, before anything is written: behind updateHead's checks what needs no look at the scene —
+// before its lock is taken —, then what compares the update with the scene
+void suValidateArguments(const YartSceneUpdate& u) {
   suCheck(u.nodes != nullptr, "nodes pointer is null");
   suCheck((u.flags & ~YART_UPDATE_REBUILD_TOP) == 0u, "unknown flags");
-  return u;
 }
-void suValidateAgainstScene(const YartScene* scene, const YartSceneUpdate& u) {
-  const HostImage& h = scene->host;
+void suValidateAgainstScene(const YartScene& scene, const YartSceneUpdate& u) {
+  const HostImage& h = scene.host;
   suCheck(u.n_nodes == h.nodes.size(), "n_nodes is " + std::to_string(u.n_nodes) + ", the scene has " + std::to_string(h.nodes.size()) + " nodes");
   suCheck(u.n_lights == 0u || u.n_lights == h.nLights, "n_lights is neither 0 nor the scene's light count " + std::to_string(h.nLights));
   suCheck(u.n_lights == 0u || u.lights != nullptr, "lights pointer is null");
   for (uint32_t i = 0; i < u.n_nodes; i++) {
     suCheck(u.nodes[i].parent == h.nodes[i].parent && u.nodes[i].mesh == h.nodes[i].mesh,
             "node " + std::to_string(i) + ": parent / mesh differ from the scene's (the topology cannot change)");
-    suCheck(suFiniteWords(u.nodes[i].fwd, 16) && suFiniteWords(u.nodes[i].inv, 16), "node " + std::to_string(i) + ": a matrix word is not finite");
+    suCheck(finiteWords(u.nodes[i].fwd, 16) && finiteWords(u.nodes[i].inv, 16), "node " + std::to_string(i) + ": a matrix word is not finite");
   }
   for (uint32_t i = 0; i < u.n_lights; i++) {
     const YartLightDesc& a = u.lights[i]; const YartLightDesc& b = h.lightDesc[i];
-    suCheck(a.type == b.type && a.mesh == b.mesh && a.tri == b.tri && a.two_sided == b.two_sided && a.texture == b.texture &&
-            std::memcmp(&a.radius, &b.radius, 4) == 0 && std::memcmp(a.emission, b.emission, 12) == 0,
+    suCheck(sameLightTopology(a, b) && std::memcmp(&a.radius, &b.radius, 4) == 0 && std::memcmp(a.emission, b.emission, 12) == 0,
             "light " + std::to_string(i) + ": a field other than fwd / inv differs from the scene's");
-    suCheck(suFiniteWords(a.fwd, 16) && suFiniteWords(a.inv, 16), "light " + std::to_string(i) + ": a matrix word is not finite");
+    suCheck(finiteWords(a.fwd, 16) && finiteWords(a.inv, 16), "light " + std::to_string(i) + ": a matrix word is not finite");
   }
-  for (size_t m = 0; m < h.meshBox.size(); m++)
-    suCheck(suFiniteWords(h.meshBox[m].mn, 3) && suFiniteWords(h.meshBox[m].mx, 3),
-            "mesh " + std::to_string(m) + ": its vertex box is not finite (such a scene is re-created, not updated)");
+  checkMeshBoxes(suCheck, h, nullptr);
 }
 
-void suUpdate(YartScene& s, const YartSceneUpdate& u, hipStream_t stream, YartSceneUpdateStats* stats) {
-  const auto wall0 = std::chrono::high_resolution_clock::now();
-  HIP_CHECK(hipSetDevice(s.device));
+// The chain in the caller's frame (the mesh update ends in it); returns with the frame closed: the stream synchronised.
+// flags: suIdentityFlags' of u.nodes (a copy reads them: declared before the caller's frame)
+void suRun(YartScene& s, const YartSceneUpdate& u, const std::vector<uint32_t>& flags, bool allIdentity, UpdateCall& call) {
+  const hipStream_t stream = call.stream;
   HostImage& h = s.host;
   SceneUpdateTables& t = s.su;
   const uint32_t nn = u.n_nodes;
   if (!t.ready) suBuildTables(s);
-  std::vector<uint32_t> flags(nn);
-  const bool allIdentity = suIdentityFlags(u.nodes, nn, flags.data());
-  uint32_t launches = 0;
-  Timer tm;
-  HIP_CHECK(hipEventRecord(tm.a, stream));
-  auto launched = [&] { HIP_CHECK(hipGetLastError()); launches++; };
   const uint32_t nodeBlocks = (nn + kBlock - 1u) / kBlock;
   if (t.levels <= kSceneUpdateMaxLevels) {
     t.stageDesc.ensure(size_t(nn) * 34u); t.stageFlags.ensure(nn);
@@ -214,16 +195,16 @@ void suUpdate(YartScene& s, const YartSceneUpdate& u, hipStream_t stream, YartSc
     HIP_CHECK(hipMemcpyAsync(t.stageFlags.p, flags.data(), size_t(nn) * 4u, hipMemcpyHostToDevice, stream));
     SuScatterArgs sa{t.stageDesc.p, t.stageFlags.p, t.meshBox.p, s.nodes.p, nn};
     hipLaunchKernelGGL(k_su_scatter, dim3(uint32_t((uint64_t(nn) * 32u + kBlock - 1u) / kBlock)), dim3(kBlock), 0, stream, sa);
-    launched();
+    call.launched();
     for (uint32_t l = t.levels; l-- > 0u;) {
       if (t.levelBig[l] + t.levelSmall[l] == 0u) continue;
       SuFoldArgs fa{s.nodes.p, t.parents.p, t.childOff.p, t.childIdx.p, t.levelFirst[l], t.levelBig[l], t.levelSmall[l]};
       hipLaunchKernelGGL(k_su_fold, dim3(t.levelBig[l] + (t.levelSmall[l] + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, fa);
-      launched();
+      call.launched();
     }
     SuWorldArgs wa{s.nodes.p, s.nodeWorld.p, nn};
     hipLaunchKernelGGL(k_su_world, dim3(nodeBlocks), dim3(kBlock), 0, stream, wa);
-    launched();
+    call.launched();
     HIP_CHECK(hipMemcpyAsync(h.nodes.data(), s.nodes.p, size_t(nn) * sizeof(NodeDev), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipMemcpyAsync(h.nodeWorld.data(), s.nodeWorld.p, size_t(nn) * 2u * sizeof(f4), hipMemcpyDeviceToHost, stream));
   } else {
@@ -247,30 +228,26 @@ void suUpdate(YartScene& s, const YartSceneUpdate& u, hipStream_t stream, YartSc
       for (size_t l = t.tlasFirst.size() - 1u; l-- > 0u;) {
         SuTlasArgs ta{s.tlas.p, s.nodeWorld.p, t.tlasOrder.p, t.tlasFirst[l], t.tlasFirst[l + 1u] - t.tlasFirst[l]};
         hipLaunchKernelGGL(k_su_tlas_refit, dim3((ta.n + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, ta);
-        launched();
+        call.launched();
       }
       HIP_CHECK(hipMemcpyAsync(h.tlas.data(), s.tlas.p, h.tlas.size() * sizeof(TlasNode), hipMemcpyDeviceToHost, stream));
     }
   }
   if (u.n_lights) {                                            // the lights, on the host, by the code scene creation uses
     rederiveLights(h, u.lights, u.n_lights);
-    s.dev.totalPower = h.totalPower;
-    HIP_CHECK(hipMemcpyAsync(s.lights.p, h.lights.data(), h.lights.size() * sizeof(LightDev), hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(s.areaPowerCdf.p, h.areaPowerCdf.data(), h.areaPowerCdf.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    uploadLights(s, stream);
   }
-  HIP_CHECK(hipEventRecord(tm.b, stream));
-  HIP_CHECK(hipStreamSynchronize(stream));
+  call.close();
   h.allIdentity = allIdentity;                                 // (the render plan reads it: only once the device holds the new transforms)
-  if (stats) {
-    YartSceneUpdateStats st{};
-    st.struct_size = stats->struct_size;
-    st.launches = launches;
-    float ms = 0.0f;
-    HIP_CHECK(hipEventElapsedTime(&ms, tm.a, tm.b));
-    st.ms_device = ms;
-    st.ms_total = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - wall0).count();
-    std::memcpy(stats, &st, std::min<size_t>(stats->struct_size, sizeof(st)));
-  }
+}
+
+void suUpdate(YartScene& s, const YartSceneUpdate& u, hipStream_t stream, YartSceneUpdateStats* stats) {
+  const auto wall0 = WallClock::now();
+  std::vector<uint32_t> flags(u.n_nodes);
+  const bool allIdentity = suIdentityFlags(u.nodes, u.n_nodes, flags.data());
+  UpdateCall call(wall0, s.device, stream);
+  suRun(s, u, flags, allIdentity, call);
+  call.finish(stats);
 }
 
 }  // namespace
@@ -278,13 +255,7 @@ void suUpdate(YartScene& s, const YartSceneUpdate& u, hipStream_t stream, YartSc
 extern "C" {
 
 int yart_hip_scene_update(YartScene* scene, const YartSceneUpdate* update, void* stream, YartSceneUpdateStats* stats) {
-  return guarded([&] {
-    const YartSceneUpdate u = suValidateArguments(scene, update);
-    suCheck(!stats || stats->struct_size >= 8u, "stats: struct_size is smaller than its first two fields");
-    std::lock_guard<std::mutex> lock(scene->mu);
-    suValidateAgainstScene(scene, u);
-    suUpdate(*scene, u, static_cast<hipStream_t>(stream), stats);
-  });
+  return updateEntry(suCheck, "YartSceneUpdate", scene, update, stream, stats, suValidateArguments, suValidateAgainstScene, suUpdate);
 }
 
 }  // extern "C"

@@ -65,24 +65,17 @@ __global__ void __launch_bounds__(kBlock) k_tu_links(TuLinkArgs a) {
   if (i == 0u) a.mesh->hasAlpha = alpha ? 1u : 0u;
 }
 
-void tuCheck(bool ok, const std::string& what) {
-  if (!ok) throw std::invalid_argument("scene_update_textures: " + what);
-}
+constexpr UpdateCheck tuCheck{"scene_update_textures: "};
 
-// Everything that can refuse an update before the scene is looked at. Returns the update copied into a struct of this build's size.
-YartSceneTextureUpdate tuValidateArguments(const YartScene* scene, const YartSceneTextureUpdate* up) {
-  tuCheck(scene != nullptr, "scene pointer is null");
-  tuCheck(up != nullptr, "update pointer is null");
-  tuCheck(up->struct_size >= sizeof(YartSceneTextureUpdate), "struct_size is smaller than YartSceneTextureUpdate");
-  YartSceneTextureUpdate u = *up;
+// Everything that can refuse an update before the scene is looked at (behind updateHead's checks)
+void tuValidateArguments(const YartSceneTextureUpdate& u) {
   tuCheck(u.flags == 0u, "unknown flags (none are defined)");
   tuCheck(u.n_textures >= 1u, "n_textures is 0");
   tuCheck(u.textures != nullptr, "textures pointer is null");
-  return u;
 }
 // ... and what compares it with the scene
-void tuValidateAgainstScene(const YartScene* scene, const YartSceneTextureUpdate& u) {
-  const HostImage& h = scene->host;
+void tuValidateAgainstScene(const YartScene& scene, const YartSceneTextureUpdate& u) {
+  const HostImage& h = scene.host;
   std::vector<uint8_t> listed(h.textures.size(), 0);
   for (uint32_t k = 0; k < u.n_textures; k++) {
     const YartTextureUpdate& tu = u.textures[k];
@@ -103,27 +96,13 @@ void tuValidateAgainstScene(const YartScene* scene, const YartSceneTextureUpdate
   }
 }
 
-void tuStats(YartSceneUpdateStats* stats, uint32_t launches, Timer& tm, std::chrono::high_resolution_clock::time_point wall0) {
-  if (!stats) return;
-  YartSceneUpdateStats out{};
-  out.struct_size = stats->struct_size;
-  out.launches = launches;
-  float ms = 0.0f;
-  HIP_CHECK(hipEventElapsedTime(&ms, tm.a, tm.b));
-  out.ms_device = ms;
-  out.ms_total = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - wall0).count();
-  std::memcpy(stats, &out, std::min<size_t>(stats->struct_size, sizeof(out)));
-}
-
 void tuUpdate(YartScene& s, const YartSceneTextureUpdate& u, hipStream_t stream, YartSceneUpdateStats* stats) {
-  const auto wall0 = std::chrono::high_resolution_clock::now();
-  HIP_CHECK(hipSetDevice(s.device));
+  std::vector<uint32_t> result;                              // (copies write the two: before the frame)
+  uint32_t error = 0;
+  UpdateCall call(WallClock::now(), s.device, stream);
   HostImage& h = s.host;
   TextureUpdateState& tu = s.texUp;
   const std::vector<YartMaterialDesc>& desc = s.lightUp.materialDesc;     // (tex_base as the caller gave it: h.materials hold clone indices)
-  uint32_t launches = 0;
-  Timer tm;
-  HIP_CHECK(hipEventRecord(tm.a, stream));
   // result words: one per listed texture ("an alpha byte below 255"), then the chain's error word
   tu.result.ensure(size_t(u.n_textures) + 1u);
   HIP_CHECK(hipMemsetAsync(tu.result.p, 0, (size_t(u.n_textures) + 1u) * 4u, stream));
@@ -140,24 +119,21 @@ void tuUpdate(YartScene& s, const YartSceneTextureUpdate& u, hipStream_t stream,
         const TexDev& p = h.textures[place];
         TexQuadArgs qa{s.texU8.p, s.texF32.p, p, s.texQuads.p + size_t(p.quadOffset) * 16u};
         hipLaunchKernelGGL(k_tex_quads, dim3(luGrid(nTexels)), dim3(kBlock), 0, stream, qa);
-        HIP_CHECK(hipGetLastError());
-        launches++;
+        call.launched();
       }
     bool isBase = false;
     for (const YartMaterialDesc& m : desc) isBase |= m.tex_base == int32_t(e.texture);
     if (isBase && t.channels == 4u) {
       const uint32_t grid = uint32_t(std::min<size_t>((nTexels / 4u + kBlock - 1u) / kBlock + 1u, 2048u));
       hipLaunchKernelGGL(k_tu_alpha, dim3(grid), dim3(kBlock), 0, stream, reinterpret_cast<const uint32_t*>(s.texU8.p + t.offset), uint32_t(nTexels), tu.result.p + k);
-      HIP_CHECK(hipGetLastError());
-      launches++;
+      call.launched();
       reduced[k] = 1;
     }
     if (!onDevice) std::memcpy(h.texU8.data() + t.offset, e.pixels, bytes);   // (while the device works)
   }
-  std::vector<uint32_t> result(size_t(u.n_textures) + 1u, 0u);
+  result.assign(size_t(u.n_textures) + 1u, 0u);
   HIP_CHECK(hipMemcpyAsync(result.data(), tu.result.p, result.size() * 4u, hipMemcpyDeviceToHost, stream));
-  HIP_CHECK(hipEventRecord(tm.b, stream));
-  HIP_CHECK(hipStreamSynchronize(stream));
+  call.close();
 
   // ---- the materials whose flag changed, and the meshes with a face of one of them
   std::vector<uint8_t> flipped(h.nMaterials, 0);
@@ -193,26 +169,23 @@ void tuUpdate(YartScene& s, const YartSceneTextureUpdate& u, hipStream_t stream,
       MeshDev& md = h.meshes[mi];
       LeafTri* leaves = s.leafTris.p + md.leafOffset;
       hipLaunchKernelGGL(k_tu_leaves, dim3((md.nTris + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, leaves, s.materials.p, md.nTris, h.nMaterials);
-      launches++;
+      call.launched();
       if (alpha) {
         mu.prefix.ensure(size_t(md.nTris) + 1u);
         hipLaunchKernelGGL(k_mu_alpha_scan, dim3(1), dim3(kMuScanBlock), 0, stream, leaves, mu.prefix.p, md.nTris);
-        launches++;
+        call.launched();
       }
       TuLinkArgs la{s.bvhNodes.p + md.nodeOffset, leaves, alpha ? mu.prefix.p : nullptr, s.meshes.p + mi, tu.result.p + u.n_textures, md.nNodes, md.nTris};
       hipLaunchKernelGGL(k_tu_links, dim3((md.nNodes + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, la);
-      launches++;
-      HIP_CHECK(hipGetLastError());
+      call.launched();
       md.hasAlpha = alpha ? 1u : 0u;
       if (mi < mu.meshAlpha.size()) mu.meshAlpha[mi] = int8_t(-1);
     }
-    uint32_t error = 0;
     HIP_CHECK(hipMemcpyAsync(&error, tu.result.p + u.n_textures, 4, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipEventRecord(tm.b, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
+    call.close();                                            // (a second time: ms_device ends behind the chain)
     if (error) throw HipError("scene_update_textures: the node array of a mesh is not a tree of its leaf order");
   }
-  tuStats(stats, launches, tm, wall0);
+  call.finish(stats);
 }
 
 }  // namespace
@@ -220,13 +193,7 @@ void tuUpdate(YartScene& s, const YartSceneTextureUpdate& u, hipStream_t stream,
 extern "C" {
 
 int yart_hip_scene_update_textures(YartScene* scene, const YartSceneTextureUpdate* update, void* stream, YartSceneUpdateStats* stats) {
-  return guarded([&] {
-    const YartSceneTextureUpdate u = tuValidateArguments(scene, update);
-    tuCheck(!stats || stats->struct_size >= 8u, "stats: struct_size is smaller than its first two fields");
-    std::lock_guard<std::mutex> lock(scene->mu);
-    tuValidateAgainstScene(scene, u);
-    tuUpdate(*scene, u, static_cast<hipStream_t>(stream), stats);
-  });
+  return updateEntry(tuCheck, "YartSceneTextureUpdate", scene, update, stream, stats, tuValidateArguments, tuValidateAgainstScene, tuUpdate);
 }
 
 int yart_hip_probe_textures(YartScene* scene, YartTexturesProbe* p) {

@@ -24,7 +24,7 @@
 //                multi_device.inc       several GPUs behind one handle, with its pixel pack / unpack / copy kernels
 //                postprocess.inc        tonemap / encode, the a-trous denoiser (denoise_kernels.inc) and temporal accumulation
 //                                       (temporal_kernels.inc): kernels, drivers and entries
-//                scene_update_kernels.inc, mesh_update_kernels.inc, lighting_update_kernels.inc, texture_update_kernels.inc,
+//                scene_update_common.inc, scene_update_kernels.inc, mesh_update_kernels.inc, lighting_update_kernels.inc, texture_update_kernels.inc,
 //                scene_motion_kernels.inc      a scene's next frame in place: new transforms, new vertices, new materials / light
 //                                       emission / environment images, new texels of material textures, and the per-pixel motion
 //                                       between the two frames
@@ -44,6 +44,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -1644,6 +1645,7 @@ int yart_hip_bvh_build_host(const float* positions, uint32_t n_verts, const uint
 }  // extern "C"
 
 #include "postprocess.inc"
+#include "scene_update_common.inc"
 #include "scene_update_kernels.inc"
 #include "mesh_update_kernels.inc"
 #include "lighting_update_kernels.inc"
