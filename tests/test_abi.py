@@ -53,7 +53,6 @@ def test_null_arguments_are_rejected(built):
     assert L.yart_hip_probe_math_pairs(api.MATH_FNS["div"], 16, None, None, None) == api.YART_E_INVALID
     assert b"probe_math" in L.yart_hip_last_error()
     # ... and so does the shading probe: null pointers and unknown form bits never reach one
-    L.yart_hip_probe_shading.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
     words = (ctypes.c_uint32 * 32)()
     assert L.yart_hip_probe_shading(None, 1, words, 0, words) == api.YART_E_INVALID
     assert b"probe_shading: null pointer" in L.yart_hip_last_error()

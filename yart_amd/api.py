@@ -459,6 +459,120 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_exposure_apply_device", "yart_hip_exposure_apply_host", "yart_hip_exposure_get",
            "yart_hip_debug_exposure_time"]
 
+# ---------------------------------------------------------------------------
+# The signature of every export of include/yart_hip.h: name -> (argtypes, restype), applied by lib(). An export without
+# argtypes would take a Python int as a C int and cut a 64-bit pointer in half, so every name of EXPORTS has its entry.
+# ---------------------------------------------------------------------------
+def _sig(*argtypes, restype=C.c_int):
+    return argtypes, restype
+
+
+_P, _U32, _U64, _INT, _FLT = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_float
+_U32_OUT, _HANDLE_OUT = C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)
+# the heads the families share
+_RENDER = (_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), _P)                      # scene / multi, camera, parameters, frame
+_PROGRESSIVE = _RENDER + (C.POINTER(Stats), WAVE_CALLBACK)                                # ... statistics, on_wave
+_MESH_ARRAYS = (_P, _U32, _P, _U32, _U32)                                                 # positions, n_verts, faces, face_stride, n_faces
+_BVH_OUT = (_P, _P, _U32_OUT, C.POINTER(C.c_double))                                      # nodes, indices, n_nodes, milliseconds
+_IMAGE = (_P, _U32, _U32)                                                                 # pixels, width, height
+_HANDLE_IMAGE = (_P,) + _IMAGE                                                            # exposure handle, pixels, width, height
+
+
+def _update(desc):                  # yart_hip_scene_update*: scene, update, stream, statistics
+    return _sig(_P, C.POINTER(desc), _P, C.POINTER(SceneUpdateStats))
+
+
+def _denoise(n_inputs, params, *stream):      # frame (, variance), albedo, normal, depth, width, height, parameters, out (, stream)
+    return _sig(*(_P,) * n_inputs, _U32, _U32, C.POINTER(params), _P, *stream)
+
+
+def _accumulate(params, *stream):   # handle, camera, frame, variance, features, parameters, out, out variance, out length (, stream)
+    return _sig(_P, C.POINTER(CameraDesc), _P, _P, C.POINTER(AovBuffers), C.POINTER(params), _P, _P, _P, *stream)
+
+
+SIGNATURES = {
+    "yart_hip_abi_version": _sig(),
+    "yart_hip_device_count": _sig(),
+    "yart_hip_last_error": _sig(restype=C.c_char_p),
+    "yart_hip_scene_create": _sig(C.POINTER(SceneDesc), _INT, _HANDLE_OUT),
+    "yart_hip_scene_create_flags": _sig(C.POINTER(SceneDesc), _INT, _U32, _HANDLE_OUT),
+    "yart_hip_scene_load": _sig(C.c_char_p, _INT, _HANDLE_OUT),
+    "yart_hip_scene_load_gltf": _sig(C.c_char_p, C.POINTER(ImportOptions), _INT, _HANDLE_OUT),
+    "yart_hip_gltf_to_yscn": _sig(C.c_char_p, C.POINTER(ImportOptions), C.c_char_p),
+    "yart_hip_scene_destroy": _sig(_P, restype=None),
+    "yart_hip_render": _sig(*_RENDER, C.POINTER(Stats)),
+    "yart_hip_render_waves": _sig(*_PROGRESSIVE, _P),
+    "yart_hip_render_tiles": _sig(*_PROGRESSIVE, TILE_CALLBACK, _P),
+    "yart_hip_render_device": _sig(*_RENDER, _P, C.POINTER(Stats)),
+    "yart_hip_render_aovs": _sig(*_RENDER, C.POINTER(AovBuffers), C.POINTER(Stats)),
+    "yart_hip_render_aovs_device": _sig(*_RENDER, C.POINTER(AovBuffers), _P, C.POINTER(Stats)),
+    "yart_hip_render_moments": _sig(*_RENDER, C.POINTER(AovBuffers), C.POINTER(MomentBuffers), C.POINTER(Stats)),
+    "yart_hip_render_moments_device": _sig(*_RENDER, C.POINTER(AovBuffers), C.POINTER(MomentBuffers), _P, C.POINTER(Stats)),
+    "yart_hip_multi_create": _sig(C.POINTER(SceneDesc), C.POINTER(C.c_int), _U32, _HANDLE_OUT),
+    "yart_hip_multi_load": _sig(C.c_char_p, C.POINTER(ImportOptions), C.POINTER(C.c_int), _U32, _HANDLE_OUT),
+    "yart_hip_multi_destroy": _sig(_P, restype=None),
+    "yart_hip_multi_device_count": _sig(_P),
+    "yart_hip_multi_failed_devices": _sig(_P, _P, _U32),
+    "yart_hip_multi_rccl_selftest": _sig(_INT, _U32),
+    "yart_hip_multi_render": _sig(*_RENDER, C.POINTER(Stats)),
+    "yart_hip_multi_render_tiles": _sig(*_PROGRESSIVE, TILE_CALLBACK, _P),
+    "yart_hip_scene_update": _update(SceneUpdate),
+    "yart_hip_scene_update_meshes": _update(SceneMeshUpdate),
+    "yart_hip_scene_update_lighting": _update(SceneLightingUpdate),
+    "yart_hip_scene_update_textures": _update(SceneTextureUpdate),
+    "yart_hip_scene_keep_previous": _sig(_P, _P),
+    "yart_hip_scene_pixel_motion_device": _sig(_P, C.POINTER(AovBuffers), _U32, _U32, _P, _P),
+    "yart_hip_scene_pixel_motion_host": _sig(_P, C.POINTER(AovBuffers), _U32, _U32, _P),
+    "yart_hip_probe_samples": _sig(*_RENDER[:3], _U32, _P, _P, C.POINTER(C.c_uint64)),
+    "yart_hip_probe_camera_rays": _sig(*_RENDER[:3], _U32, _P, _P),
+    "yart_hip_probe_hits": _sig(_P, _U32, _P, _P),
+    "yart_hip_probe_rays": _sig(_P, C.POINTER(RenderParams), _U32, _P, _INT, _P),
+    "yart_hip_probe_shading": _sig(_P, _U32, _P, _U32, _P),
+    "yart_hip_probe_sampler": _sig(_P, _U32, _U32, _U32, _P, _U32, _P, _INT, _P),
+    "yart_hip_probe_math": _sig(_INT, _U32, _U64, _FLT, _P),
+    "yart_hip_probe_math_pairs": _sig(_INT, _U64, _P, _P, _P),
+    "yart_hip_probe_moments": _sig(_P, _U32, _U32, _P, _U32, _FLT, _P, _P, _P),
+    "yart_hip_probe_estimator": _sig(_P, _U32, _U32, _INT, _FLT, _P, _U32, _U32, _FLT, _FLT, _P, _P),
+    "yart_hip_probe_scene_graph": _sig(_P, _P, _P, _P, _U32_OUT),
+    "yart_hip_probe_mesh": _sig(_P, _U32, *(_P,) * 7, _U32_OUT),
+    "yart_hip_probe_lighting": _sig(_P, C.POINTER(LightingProbe)),
+    "yart_hip_probe_texel_sum": _sig(_P, _U64, _P),
+    "yart_hip_probe_textures": _sig(_P, C.POINTER(TexturesProbe)),
+    "yart_hip_debug_counters": _sig(_P, _P),
+    "yart_hip_debug_shade_regions": _sig(_P),
+    "yart_hip_bvh_info": _sig(_P, _U32, _U32_OUT, _U32_OUT),
+    "yart_hip_bvh_copy": _sig(_P, _U32, _P, _P),
+    "yart_hip_bvh_build_device": _sig(_INT, *_MESH_ARRAYS, *_BVH_OUT),
+    "yart_hip_bvh_build_host": _sig(*_MESH_ARRAYS, _U32, *_BVH_OUT),
+    "yart_hip_tonemap_agx": _sig(*_IMAGE, _INT, _P, _P),
+    "yart_hip_encode_rgb8": _sig(*_IMAGE, _P, _P),
+    "yart_hip_tonemap_host": _sig(*_IMAGE, _INT, _P, _P),
+    "yart_hip_denoise_atrous_device": _denoise(4, DenoiseParams, _P),
+    "yart_hip_denoise_atrous_host": _denoise(4, DenoiseParams),
+    "yart_hip_denoise_atrous_var_device": _denoise(5, DenoiseVarParams, _P),
+    "yart_hip_denoise_atrous_var_host": _denoise(5, DenoiseVarParams),
+    "yart_hip_temporal_create": _sig(_U32, _U32, _INT, _HANDLE_OUT),
+    "yart_hip_temporal_destroy": _sig(_P, restype=None),
+    "yart_hip_temporal_reset": _sig(_P),
+    "yart_hip_temporal_set_motion": _sig(_P, C.POINTER(TemporalMotion)),
+    "yart_hip_temporal_set_pixel_motion": _sig(_P, C.POINTER(TemporalPixelMotion)),
+    "yart_hip_temporal_set_clip": _sig(_P, C.POINTER(TemporalClip)),
+    "yart_hip_temporal_accumulate_device": _accumulate(TemporalParams, _P),
+    "yart_hip_temporal_accumulate_host": _accumulate(TemporalParams),
+    "yart_hip_temporal_accumulate_moments_device": _accumulate(TemporalMomentParams, _P),
+    "yart_hip_temporal_accumulate_moments_host": _accumulate(TemporalMomentParams),
+    "yart_hip_exposure_create": _sig(_INT, _HANDLE_OUT),
+    "yart_hip_exposure_destroy": _sig(_P, restype=None),
+    "yart_hip_exposure_reset": _sig(_P),
+    "yart_hip_exposure_meter_device": _sig(*_HANDLE_IMAGE, C.POINTER(ExposureParams), _FLT, _P),
+    "yart_hip_exposure_meter_host": _sig(*_HANDLE_IMAGE, C.POINTER(ExposureParams), _FLT),
+    "yart_hip_exposure_apply_device": _sig(*_HANDLE_IMAGE, _INT, _P, _P, _P),
+    "yart_hip_exposure_apply_host": _sig(*_HANDLE_IMAGE, _INT, _P, _P),
+    "yart_hip_exposure_get": _sig(_P, C.POINTER(ExposureStateRecord), _P),
+    "yart_hip_debug_exposure_time": _sig(*_HANDLE_IMAGE, C.POINTER(ExposureParams), _INT, _U32, _P, _P, C.POINTER(C.c_float)),
+}
+assert set(SIGNATURES) == set(EXPORTS)
+
 LIB_COUNT_PATH = os.path.join(_HERE, "libyart_hip_count.so")   # instrumented twin (exact test counters)
 _libs = {}
 
@@ -476,114 +590,115 @@ def lib(instrumented: bool = False):
         if L.yart_hip_abi_version() != ABI_VERSION:
             raise YartError(YART_E_INVALID, f"{path} has ABI {L.yart_hip_abi_version()}, this module binds ABI {ABI_VERSION} "
                                             "(include/yart_hip.h: YART_HIP_ABI_VERSION); rebuild the library")
-        L.yart_hip_last_error.restype = C.c_char_p
-        L.yart_hip_scene_create.argtypes = [C.POINTER(SceneDesc), C.c_int, C.POINTER(C.c_void_p)]
-        L.yart_hip_scene_load.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
-        L.yart_hip_scene_load_gltf.argtypes = [C.c_char_p, C.POINTER(ImportOptions), C.c_int, C.POINTER(C.c_void_p)]
-        L.yart_hip_gltf_to_yscn.argtypes = [C.c_char_p, C.POINTER(ImportOptions), C.c_char_p]
-        L.yart_hip_scene_destroy.argtypes = [C.c_void_p]
-        L.yart_hip_scene_destroy.restype = None
-        L.yart_hip_render.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams),
-                                      C.c_void_p, C.POINTER(Stats)]
-        L.yart_hip_render_waves.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p,
-                                            C.POINTER(Stats), WAVE_CALLBACK, C.c_void_p]
-        L.yart_hip_render_tiles.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p,
-                                            C.POINTER(Stats), WAVE_CALLBACK, TILE_CALLBACK, C.c_void_p]
-        L.yart_hip_render_device.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams),
-                                             C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        L.yart_hip_probe_samples.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams),
-                                             C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
-        L.yart_hip_probe_hits.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-        L.yart_hip_probe_rays.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
-        L.yart_hip_probe_shading.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
-        L.yart_hip_probe_sampler.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
-        L.yart_hip_tonemap_agx.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
-        L.yart_hip_encode_rgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-        L.yart_hip_tonemap_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
-        L.yart_hip_multi_create.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)]
-        L.yart_hip_multi_load.argtypes = [C.c_char_p, C.POINTER(ImportOptions), C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)]
-        L.yart_hip_multi_destroy.argtypes = [C.c_void_p]
-        L.yart_hip_multi_destroy.restype = None
-        L.yart_hip_multi_device_count.argtypes = [C.c_void_p]
-        L.yart_hip_multi_render.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p, C.POINTER(Stats)]
-        L.yart_hip_multi_render_tiles.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p,
-                                                  C.POINTER(Stats), WAVE_CALLBACK, TILE_CALLBACK, C.c_void_p]
-        L.yart_hip_render_aovs.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p,
-                                           C.POINTER(AovBuffers), C.POINTER(Stats)]
-        L.yart_hip_render_aovs_device.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p,
-                                                  C.POINTER(AovBuffers), C.c_void_p, C.POINTER(Stats)]
-        L.yart_hip_probe_camera_rays.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_uint32,
-                                                 C.c_void_p, C.c_void_p]
-        L.yart_hip_probe_math.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_float, C.c_void_p]
-        L.yart_hip_probe_math_pairs.argtypes = [C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.yart_hip_denoise_atrous_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
-                                                     C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p]
-        L.yart_hip_denoise_atrous_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
-                                                   C.POINTER(DenoiseParams), C.c_void_p]
-        L.yart_hip_render_moments.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p,
-                                              C.POINTER(AovBuffers), C.POINTER(MomentBuffers), C.POINTER(Stats)]
-        L.yart_hip_render_moments_device.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p,
-                                                     C.POINTER(AovBuffers), C.POINTER(MomentBuffers), C.c_void_p, C.POINTER(Stats)]
-        L.yart_hip_probe_moments.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float,
-                                             C.c_void_p, C.c_void_p, C.c_void_p]
-        L.yart_hip_probe_estimator.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_void_p, C.c_uint32,
-                                               C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
-        L.yart_hip_denoise_atrous_var_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
-                                                         C.c_uint32, C.POINTER(DenoiseVarParams), C.c_void_p, C.c_void_p]
-        L.yart_hip_denoise_atrous_var_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
-                                                       C.c_uint32, C.POINTER(DenoiseVarParams), C.c_void_p]
-        L.yart_hip_temporal_create.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
-        L.yart_hip_temporal_destroy.argtypes = [C.c_void_p]
-        L.yart_hip_temporal_destroy.restype = None
-        L.yart_hip_temporal_reset.argtypes = [C.c_void_p]
-        L.yart_hip_temporal_set_motion.argtypes = [C.c_void_p, C.POINTER(TemporalMotion)]
-        L.yart_hip_temporal_accumulate_device.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers),
-                                                          C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.yart_hip_temporal_accumulate_host.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.c_void_p, C.c_void_p, C.POINTER(AovBuffers),
-                                                        C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p]
-        L.yart_hip_temporal_accumulate_moments_device.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.c_void_p, C.c_void_p,
-                                                                  C.POINTER(AovBuffers), C.POINTER(TemporalMomentParams), C.c_void_p,
-                                                                  C.c_void_p, C.c_void_p, C.c_void_p]
-        L.yart_hip_temporal_accumulate_moments_host.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.c_void_p, C.c_void_p,
-                                                                C.POINTER(AovBuffers), C.POINTER(TemporalMomentParams), C.c_void_p,
-                                                                C.c_void_p, C.c_void_p]
-        L.yart_hip_scene_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdate), C.c_void_p, C.POINTER(SceneUpdateStats)]
-        L.yart_hip_probe_scene_graph.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
-        L.yart_hip_scene_update_meshes.argtypes = [C.c_void_p, C.POINTER(SceneMeshUpdate), C.c_void_p, C.POINTER(SceneUpdateStats)]
-        L.yart_hip_probe_mesh.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.POINTER(C.c_uint32)]
-        L.yart_hip_scene_update_lighting.argtypes = [C.c_void_p, C.POINTER(SceneLightingUpdate), C.c_void_p, C.POINTER(SceneUpdateStats)]
-        L.yart_hip_probe_lighting.argtypes = [C.c_void_p, C.POINTER(LightingProbe)]
-        L.yart_hip_probe_texel_sum.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
-        L.yart_hip_scene_update_textures.argtypes = [C.c_void_p, C.POINTER(SceneTextureUpdate), C.c_void_p, C.POINTER(SceneUpdateStats)]
-        L.yart_hip_probe_textures.argtypes = [C.c_void_p, C.POINTER(TexturesProbe)]
-        L.yart_hip_scene_keep_previous.argtypes = [C.c_void_p, C.c_void_p]
-        L.yart_hip_scene_pixel_motion_device.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-        L.yart_hip_scene_pixel_motion_host.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.c_uint32, C.c_uint32, C.c_void_p]
-        L.yart_hip_temporal_set_pixel_motion.argtypes = [C.c_void_p, C.POINTER(TemporalPixelMotion)]
-        L.yart_hip_temporal_set_clip.argtypes = [C.c_void_p, C.POINTER(TemporalClip)]
-        L.yart_hip_exposure_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.yart_hip_exposure_destroy.argtypes = [C.c_void_p]
-        L.yart_hip_exposure_destroy.restype = None
-        L.yart_hip_exposure_reset.argtypes = [C.c_void_p]
-        L.yart_hip_exposure_meter_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(ExposureParams), C.c_float,
-                                                     C.c_void_p]
-        L.yart_hip_exposure_meter_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(ExposureParams), C.c_float]
-        L.yart_hip_exposure_apply_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
-                                                     C.c_void_p]
-        L.yart_hip_exposure_apply_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
-        L.yart_hip_exposure_get.argtypes = [C.c_void_p, C.POINTER(ExposureStateRecord), C.c_void_p]
-        L.yart_hip_debug_exposure_time.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(ExposureParams), C.c_int,
-                                                   C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
-        L.yart_hip_bvh_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        L.yart_hip_bvh_copy.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        for name, (argtypes, restype) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes, restype
         _libs[path] = L
     return _libs[path]
 
 
-def _check(code, L=None):
+def _check(code, L):
+    """``L``: the library whose entry returned ``code`` — the last error is per library (the instrumented twin has its own)."""
     if code != YART_OK:
-        raise YartError(code, (L or lib()).yart_hip_last_error().decode())
+        raise YartError(code, L.yart_hip_last_error().decode())
+
+
+def _device_tensor(t, what, *, shape=None, numel=None, dtype=None, element_size=None, optional=False):
+    """The device pointer of the torch tensor ``t`` after the check every ``_into`` call makes of it — on the device, contiguous
+    and, where given, of that ``shape`` / ``numel`` / ``dtype`` / ``element_size`` —, ``what`` being the assertion's message.
+    ``optional``: None gives None."""
+    if t is None and optional:
+        return None
+    assert (t.is_cuda and t.is_contiguous() and (shape is None or tuple(t.shape) == tuple(shape)) and
+            (numel is None or t.numel() == numel) and (dtype is None or t.dtype == dtype) and
+            (element_size is None or t.element_size() == element_size)), what
+    return C.c_void_p(t.data_ptr())
+
+
+def _stream_of(stream, tensor=None):
+    """A call's stream argument: the integer handle ``stream``; None: torch's current stream of ``tensor``'s device — or, without
+    a tensor, the null stream, as 0 is."""
+    if stream is None and tensor is not None:
+        import torch
+        stream = torch.cuda.current_stream(tensor.device).cuda_stream
+    return C.c_void_p(stream) if stream else None
+
+
+def _buffer_struct(cls, table, h, w, names=None, *, host=None, device=None, required=True):
+    """One YartAovBuffers / YartMomentBuffers (``cls``; ``table``: AOVS / MOMENTS) of an h x w image -> (struct, {name: buffer}).
+    The buffers of ``names`` come in one of three forms: neither ``host`` nor ``device``: new NumPy outputs, (h, w, channels) or
+    (h, w) for one channel; ``host``: {name: array}, made contiguous in the table's dtype (the returned copies keep the pointers
+    alive); ``device``: {name: torch tensor}. ``names`` None: every name of that mapping. ``required`` False: a name the mapping
+    lacks, or holds None for, is left out; True: it is a KeyError."""
+    source = host if host is not None else device
+    st, bufs = cls(C.sizeof(cls)), {}
+    for name in (source if names is None else names):
+        bit, ch, dt = table[name]
+        if source is None:
+            a = np.empty((h, w, ch) if ch > 1 else (h, w), dt)
+        else:
+            a = source[name] if required else source.get(name)
+            if a is None and not required:
+                continue
+        if device is not None:
+            ptr = _device_tensor(a, name, numel=h * w * ch, element_size=np.dtype(dt).itemsize)
+        else:
+            a = np.ascontiguousarray(a, dt)
+            assert a.size == h * w * ch, name
+            ptr = a.ctypes.data_as(C.c_void_p)
+        bufs[name] = a
+        st.mask |= bit
+        setattr(st, name, ptr)
+    return st, bufs
+
+
+def _render_call(p, rank=0, world_size=1, flags=0, accumulated=None, into=None):
+    """What every render entry starts from -> (cam, head, st, frame): the CameraDesc, ``head`` = the (camera, parameters, frame)
+    arguments of the C call, a Stats to fill, and the frame: a new (H, W, 4) float32 array holding ``accumulated`` (the frame of
+    the samples before p["start_sample"]) if that is given — or ``into``, a device tensor of H*W*4 elements."""
+    cam, rp = make_camera(p), make_params(p, rank, world_size, flags)
+    if into is None:
+        frame = np.empty((cam.height, cam.width, 4), np.float32)
+        if accumulated is not None:
+            frame[...] = accumulated
+        ptr = frame.ctypes.data_as(C.c_void_p)
+    else:
+        frame, ptr = into, _device_tensor(into, "frame", numel=cam.width * cam.height * 4)
+    return cam, (C.byref(cam), C.byref(rp), ptr), Stats(), frame
+
+
+def _run_progressive(fn, L, handle, p, on_wave, on_tile=None, *, tiles=True, rays=True, **call):
+    """A progressive render through ``fn``, a bound yart_hip_*render_waves (``tiles`` False: the entry takes no tile callback) or
+    *render_tiles: ``on_wave(frame, info)`` / ``on_tile(frame, tile)`` behind trampolines (None: a null callback), ``info`` with
+    the wave's ``rays`` if ``rays``; ``call``: ``_render_call``'s. An exception of a callback stops the render and is raised
+    after the C call has returned. Returns (frame, stats, aborted)."""
+    _cam, head, st, out = _render_call(p, **call)
+    errors = []
+
+    def trampoline(callback, info):
+        def tr(_user, *args):
+            try:
+                return 1 if callback(out, info(*args)) else 0
+            except BaseException as e:          # an exception must not unwind through the C frames
+                errors.append(e)
+                return 1
+        return tr
+
+    def wave_info(stats, wave, wave_samples, taken, total):
+        info = dict(wave=wave, wave_samples=wave_samples, samples_taken=taken, total_samples=total)
+        if rays:
+            info["rays"] = int(C.cast(stats, C.POINTER(Stats)).contents.rays) if stats else 0
+        return info
+    wave_tr, tile_tr = trampoline(on_wave, wave_info), trampoline(on_tile, lambda tile: tile.contents.asdict())
+    callbacks = [WAVE_CALLBACK(wave_tr) if on_wave else WAVE_CALLBACK()]
+    if tiles:
+        callbacks.append(TILE_CALLBACK(tile_tr) if on_tile else TILE_CALLBACK())
+    rc = fn(handle, *head, C.byref(st), *callbacks, None)
+    if errors:
+        raise errors[0]
+    if rc != YART_ABORTED:
+        _check(rc, L)
+    return out, st.asdict(), rc == YART_ABORTED
 
 
 # enum YartMathFn (include/yart_hip.h): what yart_hip_probe_math[_pairs] evaluates
@@ -633,12 +748,8 @@ def bvh_build(positions, faces, device=None, threads=0):
     n, ms = C.c_uint32(0), C.c_double(0)
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
     if device is None:
-        L.yart_hip_bvh_build_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
-                                              C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
         _check(L.yart_hip_bvh_build_host(vp(pos), len(pos), vp(f), f.shape[1], len(f), threads, vp(nodes), vp(idx), C.byref(n), C.byref(ms)), L)
     else:
-        L.yart_hip_bvh_build_device.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
-                                                C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
         _check(L.yart_hip_bvh_build_device(int(device), vp(pos), len(pos), vp(f), f.shape[1], len(f), vp(nodes), vp(idx), C.byref(n), C.byref(ms)), L)
     return nodes[:n.value].copy(), idx, ms.value
 
@@ -718,7 +829,6 @@ class DeviceScene:
             desc = self._describe(scene)
             self._nodes, self._n_nodes = _motion_snapshot(scene.nodes), len(scene.nodes)
             if host_bvh:      # YART_SCENE_HOST_BVH: the meshes' BVHs from the host builder instead of the device build (same bytes)
-                self._L.yart_hip_scene_create_flags.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
                 _check(self._L.yart_hip_scene_create_flags(C.byref(desc), device, 2, C.byref(self._h)), self._L)
             else:
                 _check(self._L.yart_hip_scene_create(C.byref(desc), device, C.byref(self._h)), self._L)
@@ -901,15 +1011,7 @@ class DeviceScene:
         scene as it is now -> (H, W, 8) float32, what ``TemporalAccumulator.accumulate(pixel_motion=)`` takes.
         yart_amd.scene_motion.scene_motion_reference states the arithmetic in NumPy."""
         h, w = np.asarray(aovs["coverage"]).shape[:2]
-        ab, keep = AovBuffers(), []
-        ab.struct_size = C.sizeof(AovBuffers)
-        for name in PIXEL_MOTION_AOVS:
-            bit, ch, dt = AOVS[name]
-            a = np.ascontiguousarray(aovs[name], dt)
-            assert a.size == h * w * ch, name
-            keep.append(a)
-            ab.mask |= bit
-            setattr(ab, name, a.ctypes.data_as(C.c_void_p))
+        ab, _keep = _buffer_struct(AovBuffers, AOVS, h, w, PIXEL_MOTION_AOVS, host=aovs)
         rec = np.empty((h, w, 8), np.float32)
         _check(self._L.yart_hip_scene_pixel_motion_host(self._h, C.byref(ab), w, h, rec.ctypes.data_as(C.c_void_p)), self._L)
         return rec
@@ -920,20 +1022,9 @@ class DeviceScene:
         two dimensions; what ``TemporalAccumulator.accumulate_into(pixel_motion=)`` takes."""
         import torch
         h, w = int(records_tensor.shape[0]), int(records_tensor.shape[1])
-        assert records_tensor.is_cuda and records_tensor.is_contiguous() and records_tensor.dtype == torch.float32
-        assert records_tensor.numel() == h * w * 8
-        ab = AovBuffers()
-        ab.struct_size = C.sizeof(AovBuffers)
-        for name in PIXEL_MOTION_AOVS:
-            t = aov_tensors[name]
-            bit, ch, _ = AOVS[name]
-            assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() == h * w * ch, name
-            ab.mask |= bit
-            setattr(ab, name, C.c_void_p(t.data_ptr()))
-        if stream is None:
-            stream = torch.cuda.current_stream(records_tensor.device).cuda_stream
-        _check(self._L.yart_hip_scene_pixel_motion_device(self._h, C.byref(ab), w, h, C.c_void_p(records_tensor.data_ptr()),
-                                                          C.c_void_p(stream) if stream else None), self._L)
+        rec = _device_tensor(records_tensor, "records", numel=h * w * 8, dtype=torch.float32)
+        ab, _ = _buffer_struct(AovBuffers, AOVS, h, w, PIXEL_MOTION_AOVS, device=aov_tensors)
+        _check(self._L.yart_hip_scene_pixel_motion_device(self._h, C.byref(ab), w, h, rec, _stream_of(stream, records_tensor)), self._L)
         return records_tensor
 
     def mesh_records(self, mesh):
@@ -984,12 +1075,8 @@ class DeviceScene:
     def render(self, p: dict, rank=0, world_size=1, flags=0, accumulated=None):
         """Blocking render to a host array (H, W, 4) float32 + stats dict. `accumulated`: the frame of the
         samples before p["start_sample"] when resuming (YartRenderParams.start_sample)."""
-        cam, rp, st = make_camera(p), make_params(p, rank, world_size, flags), Stats()
-        out = np.empty((cam.height, cam.width, 4), np.float32)
-        if accumulated is not None:
-            out[...] = accumulated
-        _check(self._L.yart_hip_render(self._h, C.byref(cam), C.byref(rp), out.ctypes.data_as(C.c_void_p),
-                                     C.byref(st)))
+        _cam, head, st, out = _render_call(p, rank, world_size, flags, accumulated)
+        _check(self._L.yart_hip_render(self._h, *head, C.byref(st)), self._L)
         return out, st.asdict()
 
     def render_waves(self, p: dict, on_wave=None, rank=0, world_size=1, flags=0, accumulated=None):
@@ -997,154 +1084,69 @@ class DeviceScene:
         ``on_wave(frame, info)`` is called after every wave with the frame blended so far (a view of the output
         array) and ``info = dict(wave, wave_samples, samples_taken, total_samples)``; returning a true value stops
         the render after that wave (Renderer::abort). Returns (frame, stats, aborted)."""
-        cam, rp, st = make_camera(p), make_params(p, rank, world_size, flags), Stats()
-        out = np.empty((cam.height, cam.width, 4), np.float32)
-        if accumulated is not None:
-            out[...] = accumulated
-        errors = []
-
-        def trampoline(_user, _stats, wave, wave_samples, taken, total):
-            try:
-                stop = on_wave(out, dict(wave=wave, wave_samples=wave_samples, samples_taken=taken, total_samples=total))
-                return 1 if stop else 0
-            except BaseException as e:          # an exception must not unwind through the C frames
-                errors.append(e)
-                return 1
-        cb = WAVE_CALLBACK(trampoline) if on_wave else WAVE_CALLBACK()
-        rc = self._L.yart_hip_render_waves(self._h, C.byref(cam), C.byref(rp), out.ctypes.data_as(C.c_void_p),
-                                           C.byref(st), cb, None)
-        if errors:
-            raise errors[0]
-        if rc != YART_ABORTED:
-            _check(rc, self._L)
-        return out, st.asdict(), rc == YART_ABORTED
+        return _run_progressive(self._L.yart_hip_render_waves, self._L, self._h, p, on_wave, tiles=False, rays=False,
+                                rank=rank, world_size=world_size, flags=flags, accumulated=accumulated)
 
     def render_tiles(self, p: dict, on_tile=None, on_wave=None, rank=0, world_size=1, flags=0, accumulated=None):
         """Like :meth:`render_waves`, with tile granularity (Renderer::onRenderTileComplete): ``on_tile(frame, tile)``
         is called for every pixel block a batch of a wave has finished, ``frame`` being the output array (holding the
         blended values of that block) and ``tile`` a dict of YartTileInfo; a true return stops the render.
         ``p["max_batch_paths"]`` bounds a batch, i.e. how many blocks arrive together. Returns (frame, stats, aborted)."""
-        cam, rp, st = make_camera(p), make_params(p, rank, world_size, flags), Stats()
-        out = np.empty((cam.height, cam.width, 4), np.float32)
-        if accumulated is not None:
-            out[...] = accumulated
-        errors = []
-
-        def wave_tr(_user, _stats, wave, wave_samples, taken, total):
-            try:
-                ws = C.cast(_stats, C.POINTER(Stats)).contents if _stats else None
-                return 1 if on_wave(out, dict(wave=wave, wave_samples=wave_samples, samples_taken=taken, total_samples=total,
-                                              rays=int(ws.rays) if ws is not None else 0)) else 0
-            except BaseException as e:
-                errors.append(e)
-                return 1
-
-        def tile_tr(_user, tile):
-            try:
-                return 1 if on_tile(out, tile.contents.asdict()) else 0
-            except BaseException as e:
-                errors.append(e)
-                return 1
-        wcb = WAVE_CALLBACK(wave_tr) if on_wave else WAVE_CALLBACK()
-        tcb = TILE_CALLBACK(tile_tr) if on_tile else TILE_CALLBACK()
-        rc = self._L.yart_hip_render_tiles(self._h, C.byref(cam), C.byref(rp), out.ctypes.data_as(C.c_void_p),
-                                           C.byref(st), wcb, tcb, None)
-        if errors:
-            raise errors[0]
-        if rc != YART_ABORTED:
-            _check(rc, self._L)
-        return out, st.asdict(), rc == YART_ABORTED
+        return _run_progressive(self._L.yart_hip_render_tiles, self._L, self._h, p, on_wave, on_tile,
+                                rank=rank, world_size=world_size, flags=flags, accumulated=accumulated)
 
     def render_into(self, tensor, p: dict, rank=0, world_size=1, flags=0, stream=None):
         """Render into a CUDA/HIP torch tensor of shape (H, W, 4) float32 (device memory)."""
-        cam, rp, st = make_camera(p), make_params(p, rank, world_size, flags), Stats()
-        assert tensor.is_cuda and tensor.is_contiguous() and tensor.numel() == cam.width * cam.height * 4
-        sp = C.c_void_p(stream) if stream else None
-        _check(self._L.yart_hip_render_device(self._h, C.byref(cam), C.byref(rp),
-                                            C.c_void_p(tensor.data_ptr()), sp, C.byref(st)))
+        _cam, head, st, _ = _render_call(p, rank, world_size, flags, into=tensor)
+        _check(self._L.yart_hip_render_device(self._h, *head, _stream_of(stream), C.byref(st)), self._L)
+        return st.asdict()
+
+    def _render_buffers(self, p, aovs, moments, rank, world_size, flags):
+        """``render_moments``, and with ``moments`` None ``render_aovs``: the same call but for the entry and its moments argument"""
+        _cam, head, st, out = _render_call(p, rank, world_size, flags)
+        h, w = out.shape[:2]
+        ab, bufs = _buffer_struct(AovBuffers, AOVS, h, w, aovs)
+        mb, moms = _buffer_struct(MomentBuffers, MOMENTS, h, w, moments or ())
+        if moments is None:
+            _check(self._L.yart_hip_render_aovs(self._h, *head, C.byref(ab), C.byref(st)), self._L)
+        else:
+            _check(self._L.yart_hip_render_moments(self._h, *head, C.byref(ab), C.byref(mb), C.byref(st)), self._L)
+        return out, bufs, moms, st.asdict()
+
+    def _render_buffers_into(self, tensor, aov_tensors, moment_tensors, p, rank, world_size, flags, stream):
+        """``render_moments_into``, and with ``moment_tensors`` None ``render_aovs_into``"""
+        cam, head, st, _ = _render_call(p, rank, world_size, flags, into=tensor)
+        ab, _ = _buffer_struct(AovBuffers, AOVS, cam.height, cam.width, device=aov_tensors)
+        mb, _ = _buffer_struct(MomentBuffers, MOMENTS, cam.height, cam.width, device=moment_tensors or {})
+        if moment_tensors is None:
+            _check(self._L.yart_hip_render_aovs_device(self._h, *head, C.byref(ab), _stream_of(stream), C.byref(st)), self._L)
+        else:
+            _check(self._L.yart_hip_render_moments_device(self._h, *head, C.byref(ab), C.byref(mb), _stream_of(stream), C.byref(st)),
+                   self._L)
         return st.asdict()
 
     def render_aovs(self, p: dict, aovs: Sequence[str] = AOV_ALL, rank=0, world_size=1, flags=0):
         """``render`` + first-hit feature buffers (include/yart_hip.h: YartAovBuffers) from the same camera samples.
         Returns (frame HxWx4 float32, {name: ndarray HxWxC (HxW for one channel)}, stats dict); names from ``AOVS``."""
-        cam, rp, st = make_camera(p), make_params(p, rank, world_size, flags), Stats()
-        out = np.empty((cam.height, cam.width, 4), np.float32)
-        ab, bufs = AovBuffers(), {}
-        ab.struct_size = C.sizeof(AovBuffers)
-        for name in aovs:
-            bit, ch, dt = AOVS[name]
-            bufs[name] = np.empty((cam.height, cam.width, ch) if ch > 1 else (cam.height, cam.width), dt)
-            ab.mask |= bit
-            setattr(ab, name, bufs[name].ctypes.data_as(C.c_void_p))
-        _check(self._L.yart_hip_render_aovs(self._h, C.byref(cam), C.byref(rp), out.ctypes.data_as(C.c_void_p),
-                                            C.byref(ab), C.byref(st)), self._L)
-        return out, bufs, st.asdict()
+        out, bufs, _, st = self._render_buffers(p, aovs, None, rank, world_size, flags)
+        return out, bufs, st
 
     def render_aovs_into(self, tensor, aov_tensors: dict, p: dict, rank=0, world_size=1, flags=0, stream=None):
         """``render_into`` + feature buffers written into CUDA/HIP torch tensors: ``aov_tensors`` maps names of ``AOVS`` to
         contiguous device tensors of H*W*channels elements (float32; ids int32; rays int32 holding the uint32 counts)."""
-        cam, rp, st = make_camera(p), make_params(p, rank, world_size, flags), Stats()
-        assert tensor.is_cuda and tensor.is_contiguous() and tensor.numel() == cam.width * cam.height * 4
-        ab = AovBuffers()
-        ab.struct_size = C.sizeof(AovBuffers)
-        for name, t in aov_tensors.items():
-            bit, ch, _ = AOVS[name]
-            assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() == cam.width * cam.height * ch, name
-            ab.mask |= bit
-            setattr(ab, name, C.c_void_p(t.data_ptr()))
-        sp = C.c_void_p(stream) if stream else None
-        _check(self._L.yart_hip_render_aovs_device(self._h, C.byref(cam), C.byref(rp), C.c_void_p(tensor.data_ptr()),
-                                                   C.byref(ab), sp, C.byref(st)), self._L)
-        return st.asdict()
+        return self._render_buffers_into(tensor, aov_tensors, None, p, rank, world_size, flags, stream)
 
     def render_moments(self, p: dict, moments: Sequence[str] = MOMENT_ALL, aovs: Sequence[str] = (), rank=0, world_size=1, flags=0):
         """``render_aovs`` + per-pixel sample moments (include/yart_hip.h: YartMomentBuffers) of the frame's own samples.
         Returns (frame HxWx4 float32, {aov name: ndarray}, {moment name: ndarray HxWx3 / HxW}, stats dict); moment names
         from ``MOMENTS``. yart_amd.moments.moments_reference states the arithmetic in NumPy."""
-        cam, rp, st = make_camera(p), make_params(p, rank, world_size, flags), Stats()
-        out = np.empty((cam.height, cam.width, 4), np.float32)
-        ab, bufs = AovBuffers(), {}
-        ab.struct_size = C.sizeof(AovBuffers)
-        for name in aovs:
-            bit, ch, dt = AOVS[name]
-            bufs[name] = np.empty((cam.height, cam.width, ch) if ch > 1 else (cam.height, cam.width), dt)
-            ab.mask |= bit
-            setattr(ab, name, bufs[name].ctypes.data_as(C.c_void_p))
-        mb, moms = MomentBuffers(), {}
-        mb.struct_size = C.sizeof(MomentBuffers)
-        for name in moments:
-            bit, ch, dt = MOMENTS[name]
-            moms[name] = np.empty((cam.height, cam.width, ch) if ch > 1 else (cam.height, cam.width), dt)
-            mb.mask |= bit
-            setattr(mb, name, moms[name].ctypes.data_as(C.c_void_p))
-        _check(self._L.yart_hip_render_moments(self._h, C.byref(cam), C.byref(rp), out.ctypes.data_as(C.c_void_p),
-                                               C.byref(ab), C.byref(mb), C.byref(st)), self._L)
-        return out, bufs, moms, st.asdict()
+        return self._render_buffers(p, aovs, tuple(moments), rank, world_size, flags)
 
     def render_moments_into(self, tensor, aov_tensors: dict, moment_tensors: dict, p: dict, rank=0, world_size=1, flags=0,
                             stream=None):
         """``render_aovs_into`` + sample moments written into CUDA/HIP torch tensors: ``moment_tensors`` maps names of
         ``MOMENTS`` to contiguous device tensors of H*W*channels 4-byte elements (float32; count int32 holding the uint32)."""
-        cam, rp, st = make_camera(p), make_params(p, rank, world_size, flags), Stats()
-        assert tensor.is_cuda and tensor.is_contiguous() and tensor.numel() == cam.width * cam.height * 4
-        ab = AovBuffers()
-        ab.struct_size = C.sizeof(AovBuffers)
-        for name, t in (aov_tensors or {}).items():
-            bit, ch, _ = AOVS[name]
-            assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() == cam.width * cam.height * ch, name
-            ab.mask |= bit
-            setattr(ab, name, C.c_void_p(t.data_ptr()))
-        mb = MomentBuffers()
-        mb.struct_size = C.sizeof(MomentBuffers)
-        for name, t in (moment_tensors or {}).items():
-            bit, ch, _ = MOMENTS[name]
-            assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() == cam.width * cam.height * ch, name
-            mb.mask |= bit
-            setattr(mb, name, C.c_void_p(t.data_ptr()))
-        sp = C.c_void_p(stream) if stream else None
-        _check(self._L.yart_hip_render_moments_device(self._h, C.byref(cam), C.byref(rp), C.c_void_p(tensor.data_ptr()),
-                                                      C.byref(ab), C.byref(mb), sp, C.byref(st)), self._L)
-        return st.asdict()
+        return self._render_buffers_into(tensor, aov_tensors or {}, moment_tensors or {}, p, rank, world_size, flags, stream)
 
     def render_denoised(self, p: dict, iterations=None, sigma_color=DEFAULT_SIGMA_COLOR, sigma_normal=None, sigma_depth=None,
                         demodulate=True, rank=0, world_size=1, flags=0, device="cuda", variance_guided=False,
@@ -1247,15 +1249,14 @@ class DeviceScene:
         out = np.empty((len(a), 3), np.float32)
         rays = C.c_uint64()
         _check(self._L.yart_hip_probe_samples(self._h, C.byref(cam), C.byref(rp), len(a),
-                                            a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
-                                            C.byref(rays)))
+                                              a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
+                                              C.byref(rays)), self._L)
         return out, rays.value
 
     def probe_hits(self, rays):
         a = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         out = np.empty((len(a), 16), np.float32)
-        _check(self._L.yart_hip_probe_hits(self._h, len(a), a.ctypes.data_as(C.c_void_p),
-                                         out.ctypes.data_as(C.c_void_p)))
+        _check(self._L.yart_hip_probe_hits(self._h, len(a), a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)), self._L)
         return out
 
     def probe_rays(self, p: dict, rays, walk: int = 0):
@@ -1291,16 +1292,14 @@ class DeviceScene:
 
     def debug_counters(self):
         out = (C.c_uint64 * 32)()
-        self._L.yart_hip_debug_counters.argtypes = [C.c_void_p, C.c_void_p]
         _check(self._L.yart_hip_debug_counters(self._h, out), self._L)
         return [int(v) for v in out]
 
     def bvh(self, mesh: int):
         nn, nt = C.c_uint32(), C.c_uint32()
-        _check(self._L.yart_hip_bvh_info(self._h, mesh, C.byref(nn), C.byref(nt)))
+        _check(self._L.yart_hip_bvh_info(self._h, mesh, C.byref(nn), C.byref(nt)), self._L)
         nodes = np.empty((nn.value, 8), np.uint32); idx = np.empty(nt.value, np.uint32)
-        _check(self._L.yart_hip_bvh_copy(self._h, mesh, nodes.ctypes.data_as(C.c_void_p),
-                                       idx.ctypes.data_as(C.c_void_p)))
+        _check(self._L.yart_hip_bvh_copy(self._h, mesh, nodes.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p)), self._L)
         return nodes, idx
 
 
@@ -1327,51 +1326,20 @@ class MultiDeviceScene:
     def failed_replicas(self):
         """Replicas taken out of service by a device failure (their blocks are rendered on devices[0]); [] normally."""
         out = (C.c_int * 64)()
-        self._L.yart_hip_multi_failed_devices.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         n = int(self._L.yart_hip_multi_failed_devices(self._h, out, 64))
         return [int(out[k]) for k in range(min(n, 64))]
 
     def render(self, p: dict, rank=0, world_size=1, flags=0, accumulated=None):
-        cam, rp, st = make_camera(p), make_params(p, rank, world_size, flags), Stats()
-        out = np.empty((cam.height, cam.width, 4), np.float32)
-        if accumulated is not None:
-            out[...] = accumulated
-        _check(self._L.yart_hip_multi_render(self._h, C.byref(cam), C.byref(rp), out.ctypes.data_as(C.c_void_p), C.byref(st)), self._L)
+        _cam, head, st, out = _render_call(p, rank, world_size, flags, accumulated)
+        _check(self._L.yart_hip_multi_render(self._h, *head, C.byref(st)), self._L)
         return out, st.asdict()
 
     def render_tiles(self, p: dict, on_tile=None, on_wave=None, rank=0, world_size=1, flags=0, accumulated=None):
         """The progressive form (yart_hip_multi_render_tiles): every wave rendered by all devices, merged, reported through
         ``on_wave(frame, info)``; with ``on_tile(frame, tile)`` every block of the frame once per wave (Morton order, its own
         ray count). Returns (frame, stats, aborted)."""
-        cam, rp, st = make_camera(p), make_params(p, rank, world_size, flags), Stats()
-        out = np.empty((cam.height, cam.width, 4), np.float32)
-        if accumulated is not None:
-            out[...] = accumulated
-        errors = []
-
-        def wave_tr(_user, _stats, wave, wave_samples, taken, total):
-            try:
-                ws = C.cast(_stats, C.POINTER(Stats)).contents if _stats else None
-                return 1 if on_wave(out, dict(wave=wave, wave_samples=wave_samples, samples_taken=taken, total_samples=total,
-                                              rays=int(ws.rays) if ws is not None else 0)) else 0
-            except BaseException as e:
-                errors.append(e)
-                return 1
-
-        def tile_tr(_user, tile):
-            try:
-                return 1 if on_tile(out, tile.contents.asdict()) else 0
-            except BaseException as e:
-                errors.append(e)
-                return 1
-        wcb = WAVE_CALLBACK(wave_tr) if on_wave else WAVE_CALLBACK()
-        tcb = TILE_CALLBACK(tile_tr) if on_tile else TILE_CALLBACK()
-        rc = self._L.yart_hip_multi_render_tiles(self._h, C.byref(cam), C.byref(rp), out.ctypes.data_as(C.c_void_p), C.byref(st), wcb, tcb, None)
-        if errors:
-            raise errors[0]
-        if rc != YART_ABORTED:
-            _check(rc, self._L)
-        return out, st.asdict(), rc == YART_ABORTED
+        return _run_progressive(self._L.yart_hip_multi_render_tiles, self._L, self._h, p, on_wave, on_tile,
+                                rank=rank, world_size=world_size, flags=flags, accumulated=accumulated)
 
     def close(self):
         if self._h:
@@ -1494,8 +1462,9 @@ def tonemap(hdr: np.ndarray, look: Optional[str] = "none"):
     h, w = hdr.shape[:2]
     ldr = np.empty_like(hdr)
     rgb = np.empty((h, w, 3), np.uint8)
-    _check(lib().yart_hip_tonemap_host(hdr.ctypes.data_as(C.c_void_p), w, h, -1 if look is None else AGX_LOOKS[look],
-                                       ldr.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p)))
+    L = lib()
+    _check(L.yart_hip_tonemap_host(hdr.ctypes.data_as(C.c_void_p), w, h, -1 if look is None else AGX_LOOKS[look],
+                                   ldr.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p)), L)
     return ldr, rgb
 
 
@@ -1532,28 +1501,17 @@ def _denoise_device(var, out_tensor, frame_tensor, variance_tensor, guides, dp, 
     h, w = int(frame_tensor.shape[0]), int(frame_tensor.shape[1])
     if demodulate is None:
         demodulate = (guides or {}).get("albedo") is not None
-    ptrs = {}
-    for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1)):
-        t = (guides or {}).get(name)
-        if t is not None:
-            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == h * w * ch, name
-        ptrs[name] = None if t is None else C.c_void_p(t.data_ptr())
-    unknown = set(guides or {}) - set(ptrs)
+    guides = guides or {}
+    ptrs = [_device_tensor(guides.get(name), name, numel=h * w * ch, dtype=torch.float32, optional=True)
+            for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1))]
+    unknown = set(guides) - {"albedo", "normal", "depth"}
     assert not unknown, f"{'denoise_var_into' if var else 'denoise_into'}: unknown guides {sorted(unknown)}"
-    for t in (frame_tensor, out_tensor):
-        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4)
-    first = [C.c_void_p(frame_tensor.data_ptr())]
-    if var:
-        v = variance_tensor
-        assert v.is_cuda and v.is_contiguous() and v.dtype == torch.float32 and v.numel() == h * w, "variance"
-        first.append(C.c_void_p(v.data_ptr()))
-    if stream is None:
-        stream = torch.cuda.current_stream(frame_tensor.device).cuda_stream
+    frame, out = (_device_tensor(t, what, shape=(h, w, 4), dtype=torch.float32) for t, what in ((frame_tensor, "frame"), (out_tensor, "out")))
+    first = [frame, _device_tensor(variance_tensor, "variance", numel=h * w, dtype=torch.float32)] if var else [frame]
     L = lib()
     fn = L.yart_hip_denoise_atrous_var_device if var else L.yart_hip_denoise_atrous_device
     with torch.cuda.device(frame_tensor.device):
-        _check(fn(*first, ptrs["albedo"], ptrs["normal"], ptrs["depth"], w, h, C.byref(dp(demodulate)),
-                  C.c_void_p(out_tensor.data_ptr()), C.c_void_p(stream) if stream else None), L)
+        _check(fn(*first, *ptrs, w, h, C.byref(dp(demodulate)), out, _stream_of(stream, frame_tensor)), L)
     return out_tensor
 
 
@@ -1683,8 +1641,7 @@ class TemporalAccumulator:
             assert records.dtype == np.float32 and records.flags.c_contiguous, "pixel motion: a contiguous float32 array"
             ptr = records.ctypes.data
         else:
-            assert records.is_cuda and records.is_contiguous() and records.element_size() == 4, "pixel motion: a contiguous float32 device tensor"
-            ptr = records.data_ptr()
+            ptr = _device_tensor(records, "pixel motion: a contiguous float32 device tensor", element_size=4).value
         n = records.size if isinstance(records, np.ndarray) else records.numel()
         assert n == self.width * self.height * 8, "pixel motion: (H, W, 8) records"
         pm = TemporalPixelMotion(C.sizeof(TemporalPixelMotion), C.c_void_p(ptr))
@@ -1714,18 +1671,7 @@ class TemporalAccumulator:
         assert frame.shape == (h, w, 4) and variance.size == h * w
         if demodulate is None:
             demodulate = aovs.get("albedo") is not None
-        ab, keep = AovBuffers(), []
-        ab.struct_size = C.sizeof(AovBuffers)
-        for name in TEMPORAL_AOVS + (("albedo",) if demodulate else ()):
-            a = aovs.get(name)
-            if a is None:
-                continue
-            bit, ch, dt = AOVS[name]
-            a = np.ascontiguousarray(a, dt)
-            assert a.size == h * w * ch, name
-            keep.append(a)
-            ab.mask |= bit
-            setattr(ab, name, a.ctypes.data_as(C.c_void_p))
+        ab, _keep = _buffer_struct(AovBuffers, AOVS, h, w, TEMPORAL_AOVS + (("albedo",) if demodulate else ()), host=aovs, required=False)
         if out is None:
             out = np.empty_like(frame)
         if out_variance is None:
@@ -1759,23 +1705,10 @@ class TemporalAccumulator:
         h, w = self.height, self.width
         if demodulate is None:
             demodulate = aov_tensors.get("albedo") is not None
-        for t in (frame_tensor, out_tensor):
-            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == h * w * 4
-        for t in (variance_tensor, out_variance_tensor, out_length_tensor):
-            assert t is None or (t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() == h * w)
-        ab = AovBuffers()
-        ab.struct_size = C.sizeof(AovBuffers)
-        for name in TEMPORAL_AOVS + (("albedo",) if demodulate else ()):
-            t = aov_tensors.get(name)
-            if t is None:
-                continue
-            bit, ch, _ = AOVS[name]
-            assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() == h * w * ch, name
-            ab.mask |= bit
-            setattr(ab, name, C.c_void_p(t.data_ptr()))
-        if stream is None:
-            stream = torch.cuda.current_stream(frame_tensor.device).cuda_stream
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        frame, out = (_device_tensor(t, what, numel=h * w * 4, dtype=torch.float32) for t, what in ((frame_tensor, "frame"), (out_tensor, "out")))
+        variance, out_variance, out_length = (_device_tensor(t, what, numel=h * w, element_size=4, optional=True) for t, what in
+                                              ((variance_tensor, "variance"), (out_variance_tensor, "out variance"), (out_length_tensor, "out length")))
+        ab, _ = _buffer_struct(AovBuffers, AOVS, h, w, TEMPORAL_AOVS + (("albedo",) if demodulate else ()), device=aov_tensors, required=False)
         tp = self._params(demodulate, over)
         assert motion is None or pixel_motion is None, "one motion at a time: motion= or pixel_motion="
         if motion is not None:
@@ -1785,9 +1718,8 @@ class TemporalAccumulator:
             self.set_pixel_motion(pixel_motion)
         with torch.cuda.device(frame_tensor.device):
             fn = self._L.yart_hip_temporal_accumulate_moments_device if self.moments else self._L.yart_hip_temporal_accumulate_device
-            _check(fn(self._h, C.byref(self._camera(cam)), ptr(frame_tensor), ptr(variance_tensor), C.byref(ab), C.byref(tp),
-                      ptr(out_tensor), ptr(out_variance_tensor), ptr(out_length_tensor), C.c_void_p(stream) if stream else None),
-                   self._L)
+            _check(fn(self._h, C.byref(self._camera(cam)), frame, variance, C.byref(ab), C.byref(tp), out, out_variance, out_length,
+                      _stream_of(stream, frame_tensor)), self._L)
         return out_tensor
 
 
@@ -1855,13 +1787,10 @@ class AutoExposure:
         import torch
         t = frame_tensor
         h, w = int(t.shape[0]), int(t.shape[1])
-        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4)
-        if stream is None:
-            stream = torch.cuda.current_stream(t.device).cuda_stream
+        frame = _device_tensor(t, "frame", shape=(h, w, 4), dtype=torch.float32)
         ep = make_exposure_params(**self.params)
         with torch.cuda.device(t.device):
-            _check(self._L.yart_hip_exposure_meter_device(self._h, C.c_void_p(t.data_ptr()), w, h, C.byref(ep), float(dt),
-                                                          C.c_void_p(stream) if stream else None), self._L)
+            _check(self._L.yart_hip_exposure_meter_device(self._h, frame, w, h, C.byref(ep), float(dt), _stream_of(stream, t)), self._L)
 
     def apply_into(self, ldr_tensor, rgb8_tensor, frame_tensor, look="none", stream=None):
         """``apply`` on torch tensors (yart_hip_exposure_apply_device): ``ldr_tensor`` (H, W, 4) float32 or None (it may be
@@ -1869,19 +1798,11 @@ class AutoExposure:
         import torch
         t = frame_tensor
         h, w = int(t.shape[0]), int(t.shape[1])
-        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4)
-        if ldr_tensor is not None:
-            o = ldr_tensor
-            assert o.is_cuda and o.is_contiguous() and o.dtype == torch.float32 and tuple(o.shape) == (h, w, 4), "ldr"
-        if rgb8_tensor is not None:
-            o = rgb8_tensor
-            assert o.is_cuda and o.is_contiguous() and o.dtype == torch.uint8 and tuple(o.shape) == (h, w, 3), "rgb8"
-        if stream is None:
-            stream = torch.cuda.current_stream(t.device).cuda_stream
-        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        frame = _device_tensor(t, "frame", shape=(h, w, 4), dtype=torch.float32)
+        ldr = _device_tensor(ldr_tensor, "ldr", shape=(h, w, 4), dtype=torch.float32, optional=True)
+        rgb8 = _device_tensor(rgb8_tensor, "rgb8", shape=(h, w, 3), dtype=torch.uint8, optional=True)
         with torch.cuda.device(t.device):
-            _check(self._L.yart_hip_exposure_apply_device(self._h, C.c_void_p(t.data_ptr()), w, h, look_index(look), ptr(ldr_tensor),
-                                                          ptr(rgb8_tensor), C.c_void_p(stream) if stream else None), self._L)
+            _check(self._L.yart_hip_exposure_apply_device(self._h, frame, w, h, look_index(look), ldr, rgb8, _stream_of(stream, t)), self._L)
 
     def state(self, histogram=False):
         """The state record as a dict (``cur_ev``, ``target_ev``, ``mean_ev``, ``gain`` as np.float32; ``n_counted``,

@@ -1296,21 +1296,31 @@ int yart_hip_render_device(YartScene* scene, const YartCameraDesc* cam, const Ya
   });
 }
 
-int yart_hip_render(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params,
-                    float* out_rgba, YartStats* stats) {
+// The frame of the host-pointer render entries, opened after an entry's last argument check: the scene's lock, the call's clock,
+// the scene's device, and its frame buffer holding the caller's accumulated frame when the render resumes
+struct HostFrame {
+  YartScene& s;
+  float* const out; const size_t n;                                     // the caller's frame, its floats
+  std::lock_guard<std::mutex> lock;
+  const std::chrono::high_resolution_clock::time_point t0 = std::chrono::high_resolution_clock::now();
+  HostFrame(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, float* out_rgba)
+      : s(*scene), out(out_rgba), n(size_t(cam->width) * cam->height * 4), lock(scene->mu) {
+    HIP_CHECK(hipSetDevice(s.device));
+    s.hdr.ensure(n);
+    if (params->start_sample > 0) HIP_CHECK(hipMemcpy(s.hdr.p, out, n * sizeof(float), hipMemcpyHostToDevice));
+  }
+  void copyBack() const { HIP_CHECK(hipMemcpy(out, s.hdr.p, n * sizeof(float), hipMemcpyDeviceToHost)); }
+  double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count(); }
+};
+
+int yart_hip_render(YartScene* scene, const YartCameraDesc* cam, const YartRenderParams* params, float* out_rgba, YartStats* stats) {
   return guarded([&] {
     require(scene && out_rgba, "scene / output pointer is null");
     validate(cam, params);
-    std::lock_guard<std::mutex> lock(scene->mu);
-    auto t0 = std::chrono::high_resolution_clock::now();
-    HIP_CHECK(hipSetDevice(scene->device));
-    const size_t n = size_t(cam->width) * cam->height * 4;
-    scene->hdr.ensure(n);
-    if (params->start_sample > 0) HIP_CHECK(hipMemcpy(scene->hdr.p, out_rgba, n * sizeof(float), hipMemcpyHostToDevice));
+    HostFrame f(scene, cam, params, out_rgba);
     renderToDevice(*scene, *cam, *params, scene->hdr.p, nullptr, stats);
-    HIP_CHECK(hipMemcpy(out_rgba, scene->hdr.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    if (stats)
-      stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+    f.copyBack();
+    if (stats) stats->ms_total = f.ms();                        // the whole call's wall time, copies included
   });
 }
 
@@ -1364,12 +1374,8 @@ int yart_hip_render_moments(YartScene* scene, const YartCameraDesc* cam, const Y
     const bool any = checkAovs(aovs, cam, params, host);
     const bool anyM = checkMoments(moments, params, hostM);
     require(scene && out_rgba, "scene / output pointer is null");
-    std::lock_guard<std::mutex> lock(scene->mu);
-    auto t0 = std::chrono::high_resolution_clock::now();
-    HIP_CHECK(hipSetDevice(scene->device));
-    const size_t wh = size_t(cam->width) * cam->height, n = wh * 4;
-    scene->hdr.ensure(n);
-    if (params->start_sample > 0) HIP_CHECK(hipMemcpy(scene->hdr.p, out_rgba, n * sizeof(float), hipMemcpyHostToDevice));
+    HostFrame f(scene, cam, params, out_rgba);
+    const size_t wh = f.n / 4;
     // the requested buffers side by side in one device allocation each (render_host.hpp: kAovTable, kMomentTable)
     YartAovBuffers dev = host;
     if (any) {
@@ -1382,12 +1388,11 @@ int yart_hip_render_moments(YartScene* scene, const YartCameraDesc* cam, const Y
       layOutBuffers(kMomentTable, hostM.mask, wh, scene->momOut.p, devM);
     }
     renderToDevice(*scene, *cam, *params, scene->hdr.p, nullptr, stats, nullptr, any ? &dev : nullptr, anyM ? &devM : nullptr);
-    HIP_CHECK(hipMemcpy(out_rgba, scene->hdr.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    f.copyBack();
     const auto toHost = [](void* dst, const void* src, size_t bytes) { HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); };
     if (any) copyBuffers(kAovTable, host, dev, wh, toHost);
     if (anyM) copyBuffers(kMomentTable, hostM, devM, wh, toHost);
-    if (stats)
-      stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+    if (stats) stats->ms_total = f.ms();
   });
 }
 
@@ -1404,15 +1409,10 @@ static int renderProgressive(YartScene* scene, const YartCameraDesc* cam, const 
   const int rc = guarded([&] {
     require(scene && out_rgba, "scene / output pointer is null");
     validate(cam, params);
-    std::lock_guard<std::mutex> lock(scene->mu);
-    auto t0 = std::chrono::high_resolution_clock::now();
-    HIP_CHECK(hipSetDevice(scene->device));
-    const uint32_t W = cam->width, H = cam->height;
-    const size_t n = size_t(W) * H * 4;
-    scene->hdr.ensure(n);
+    HostFrame f(scene, cam, params, out_rgba);
+    const uint32_t W = cam->width;
     const uint32_t stop = params->stop_sample ? params->stop_sample : params->samples;
-    if (params->start_sample > 0) HIP_CHECK(hipMemcpy(scene->hdr.p, out_rgba, n * sizeof(float), hipMemcpyHostToDevice));
-    else if (on_tile) std::memset(out_rgba, 0, n * sizeof(float));       // tiles arrive one by one: the rest of the frame is defined
+    if (params->start_sample == 0 && on_tile) std::memset(out_rgba, 0, f.n * sizeof(float));   // tiles arrive one by one: the rest of the frame is defined
     YartStats total{};
     for (WaveSchedule ws(params->samples, params->first_wave_samples, params->max_wave_samples); !aborted && ws.next();) {
       const uint32_t taken = uint32_t(ws.takenBefore);
@@ -1444,18 +1444,18 @@ static int renderProgressive(YartScene* scene, const YartCameraDesc* cam, const 
         };
         const bool stopped = renderToDevice(*scene, *cam, q, scene->hdr.p, nullptr, &st, on_tile ? &hook : nullptr);
         // after a wave the whole frame (with a tile callback: every tile has been copied already unless the render stopped)
-        if (!on_tile || stopped) HIP_CHECK(hipMemcpy(out_rgba, scene->hdr.p, n * sizeof(float), hipMemcpyDeviceToHost));
+        if (!on_tile || stopped) f.copyBack();
         total.rays += st.rays; total.waves += st.waves; total.ms_device += st.ms_device; total.samples += st.samples;
         total.ms_extend += st.ms_extend; total.ms_shade += st.ms_shade; total.ms_connect += st.ms_connect; total.ms_gmon += st.ms_gmon;
         total.ms_traverse += st.ms_traverse; total.launches_traverse += st.launches_traverse;
         total.pipeline_flags = st.pipeline_flags;
-        st.ms_total = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+        st.ms_total = f.ms();
         if (stopped) aborted = true;
         else if (on_wave && on_wave(user, &st, uint32_t(wave), uint32_t(waveSamples), uint32_t(taken + waveSamples), params->samples) != 0)
           aborted = true;
       }
     }
-    total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+    total.ms_total = f.ms();
     if (stats) *stats = total;
   });
   return rc == YART_OK && aborted ? YART_ABORTED : rc;
