@@ -232,7 +232,8 @@ void yart_hip_scene_destroy(YartScene* scene);
 /* New node and light transforms for a scene that is on the device — the next frame of a rigid animation without
  * yart_hip_scene_destroy + yart_hip_scene_create. Re-derived, on the device unless noted: the nodes' transforms, identity flags and
  * children-inclusive boxes, their padded world boxes, the boxes of the top-level hierarchy (scenes of 64 nodes and more; refitted
- * in the tree the scene has, or with YART_UPDATE_REBUILD_TOP rebuilt on the host by scene creation's code), and on the host the
+ * in the tree the scene has; with YART_UPDATE_REBUILD_TOP rebuilt on the host by scene creation's code; with
+ * YART_UPDATE_REBUILD_TOP_DEVICE rebuilt on the device, see below), and on the host the
  * lights' transforms, the area lights' area and power, the power CDF and the total power. The scene then renders the bits a scene
  * freshly created from the same description renders. Nothing else is rebuilt or uploaded: BVHs, vertex / leaf / texture arrays,
  * materials and environment tables stay. A scene graph of more than 64 levels is re-derived on the host and uploaded.
@@ -241,7 +242,8 @@ void yart_hip_scene_destroy(YartScene* scene);
  * Returns after the work has completed on `stream`. Takes the scene's lock like a render: it must not be called from a wave or tile
  * callback of the same scene.
  * YART_E_INVALID, with the scene and the device exactly as they were (everything is checked before the first write): scene, update
- * or nodes NULL; struct_size too small; unknown flags; n_nodes not the scene's; a node's parent or mesh changed; n_lights neither 0
+ * or nodes NULL; struct_size too small; unknown flags; YART_UPDATE_REBUILD_TOP_DEVICE on a `scene` that is not a live handle of this
+ * library (that flag alone is checked against the handle before it is read); n_nodes not the scene's; a node's parent or mesh changed; n_lights neither 0
  * nor the scene's; a light field other than fwd / inv changed; a matrix word of a node or light not finite; a mesh of the scene
  * whose vertex box is not finite; a `stats` whose struct_size is below 8 (its first two fields).
  * stats: the caller sets stats->struct_size = sizeof(YartSceneUpdateStats) before the call; that many bytes are written.
@@ -250,10 +252,22 @@ void yart_hip_scene_destroy(YartScene* scene);
  * Stream order: the copies and kernels of the update are enqueued on `stream`; the caller orders them against renders of this
  * scene that are still running on OTHER streams (yart_hip_render*_device). A scene's first update (and the first refit after a
  * YART_UPDATE_REBUILD_TOP) also uploads its topology tables with blocking copies on the null stream.
+ * The top-level hierarchy after an update. A refit (flags 0) keeps the tree the scene has and is the cheapest; the tree filters
+ * poorly once instances have moved far from where it was built. YART_UPDATE_REBUILD_TOP synchronises the stream, rebuilds on the host
+ * from the downloaded world boxes and uploads. YART_UPDATE_REBUILD_TOP_DEVICE rebuilds on `stream` from the world boxes the update's
+ * own chain has just written (csrc/tlas_build_kernels.inc): no synchronisation and no host work between the world-box kernel and the
+ * last build kernel, the finished tree is copied to the library's host image asynchronously, and the wait at the end of the call is
+ * the only one. All three leave the bytes of a freshly created scene in the device's and the host's tree (a refit: its boxes). The
+ * two rebuild flags exclude each other (YART_E_INVALID). A scene without a hierarchy (fewer than 64 nodes) takes either and builds
+ * nothing. The device rebuild's first use uploads the tables of the scene's leaf count with blocking copies; its launches are counted
+ * in stats->launches: per level that holds a range of more than 2048 mesh nodes 2 + the bitonic merge stages above 2048 keys, one
+ * for all subtrees, one per level of the tree. Cost on an MI355X (profiles/top_rebuild.txt; refit / host rebuild / device rebuild of
+ * one run): 0.26 / 1.10 / 0.61 ms for 4 096 instances, 0.41 / 4.41 / 0.82 ms for 16 000, 1.15 / 20.4 / 1.78 ms for 65 536.
  * Out of scope — re-create the scene: a changed topology (nodes added, removed, re-parented or re-meshed) and the replicas of a
  * YartMulti. Deforming meshes: yart_hip_scene_update_meshes below; materials, light emission and environment images:
  * yart_hip_scene_update_lighting below. */
 #define YART_UPDATE_REBUILD_TOP 1u   /* rebuild the top-level hierarchy (host, create's own code) instead of refitting its boxes */
+#define YART_UPDATE_REBUILD_TOP_DEVICE 2u   /* rebuild it on the device, on the caller's stream: the same bytes */
 typedef struct YartSceneUpdate {
   uint32_t struct_size;              /* sizeof(YartSceneUpdate) */
   uint32_t n_nodes;                  /* the scene's node count */
@@ -276,7 +290,7 @@ int yart_hip_scene_update(YartScene* scene, const YartSceneUpdate* update, void*
  * when a tree's node count changed; the traversal stack bound is re-derived (it sizes the spill area of the next render, growing or
  * shrinking). On the host, from the caller's positions: the mesh's vertex box (exact in the sign of zeros) and area, power, power CDF
  * and total power of area lights on a listed mesh. Then the nodes' boxes, world boxes and the top-level hierarchy are re-derived by
- * yart_hip_scene_update's own chain with the scene's current transforms (flags: YART_UPDATE_REBUILD_TOP as there). Afterwards the
+ * yart_hip_scene_update's own chain with the scene's current transforms (flags: YART_UPDATE_REBUILD_TOP / _DEVICE as there). Afterwards the
  * scene holds, and renders, the bits of a scene freshly created from the same description; yart_hip_bvh_info / yart_hip_bvh_copy
  * return the new tree, a later yart_hip_scene_update starts from the new boxes. The two entries combine in either order for a frame
  * that moves nodes and deforms meshes. Faces, materials, uvs, face_light, the node list and the transforms are unchanged.
@@ -306,7 +320,7 @@ typedef struct YartSceneMeshUpdate {
   uint32_t struct_size;              /* sizeof(YartSceneMeshUpdate) */
   uint32_t n_meshes;                 /* meshes listed: 1 .. the scene's mesh count */
   const YartMeshUpdate* meshes;      /* each mesh at most once */
-  uint32_t flags;                    /* YART_UPDATE_REBUILD_TOP */
+  uint32_t flags;                    /* YART_UPDATE_REBUILD_TOP or YART_UPDATE_REBUILD_TOP_DEVICE */
 } YartSceneMeshUpdate;
 int yart_hip_scene_update_meshes(YartScene* scene, const YartSceneMeshUpdate* update, void* stream, YartSceneUpdateStats* stats /* may be NULL */);
 
@@ -771,6 +785,18 @@ int yart_hip_bvh_build_device(int device, const float* positions, uint32_t n_ver
 int yart_hip_bvh_build_host(const float* positions, uint32_t n_verts, const uint32_t* faces, uint32_t face_stride, uint32_t n_faces,
                             uint32_t threads, uint32_t* nodes_out, uint32_t* indices_out, uint32_t* n_nodes, double* ms_host);
 int yart_hip_bvh_copy(YartScene* scene, uint32_t mesh, uint32_t* nodes_out, uint32_t* indices_out);
+/* The top-level hierarchy of a node list, outside a scene: on the device (csrc/tlas_build_kernels.inc, what
+ * YART_UPDATE_REBUILD_TOP_DEVICE runs) and on the host (host_scene.hpp::buildTopLevel, what scene creation runs); byte for byte the
+ * same records. node_world: n_nodes x 8 floats, the nodes' padded world boxes as lo.xyz, -, hi.xyz, - (the fourth words are
+ * ignored); mesh: per node, < 0 = not a mesh node. tlas_out: room for 2 L - 1 records of 32 bytes (lo[3], a, hi[3], b), L the number
+ * of mesh nodes. n_nodes < 64 or L = 0 gives 0 records, as scene creation does. YART_E_INVALID: a NULL pointer, n_nodes >= 2^20.
+ * Outside the contract: a bound that is a NaN, and a bound that is +0 on one mesh node and -0 on another.
+ * yart_hip_tlas_build_launches: the kernel launches the device build makes for L mesh nodes. */
+int yart_hip_tlas_build_device(int device, const float* node_world, const int32_t* mesh, uint32_t n_nodes, void* tlas_out,
+                               uint32_t* n_tlas_out, uint32_t* height_out);
+int yart_hip_tlas_build_host(const float* node_world, const int32_t* mesh, uint32_t n_nodes, void* tlas_out, uint32_t* n_tlas_out,
+                             uint32_t* height_out);
+int yart_hip_tlas_build_launches(uint32_t n_leaves);
 
 /* The step after the path: AgX tonemap of the RGBA32F frame as
  * cpu/tile-renderer.hpp:234-237 applies it per tile (core/tonemapping.hpp:14-92; look 0 none, 1 golden,

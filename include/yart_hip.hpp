@@ -71,8 +71,11 @@ class DeviceScene {
   DeviceScene& operator=(const DeviceScene&) = delete;
   ~DeviceScene() { yart_hip_scene_destroy(h_); }
   YartScene* handle() const { return h_; }
+  // How an update leaves the top-level hierarchy: its boxes refitted, or the tree rebuilt on the host (YART_UPDATE_REBUILD_TOP) or on
+  // the device, on the update's stream (YART_UPDATE_REBUILD_TOP_DEVICE)
+  enum class TopLevel : uint32_t { Refit = 0u, RebuildHost = YART_UPDATE_REBUILD_TOP, RebuildDevice = YART_UPDATE_REBUILD_TOP_DEVICE };
   // yart_hip_scene_update: new transforms for the scene's nodes (parent / mesh as at create) and, if any are given, its lights
-  // (every other field as at create); rebuildTop: YART_UPDATE_REBUILD_TOP. Returns the update's statistics.
+  // (every other field as at create); rebuildTop: YART_UPDATE_REBUILD_TOP, or `top` for any of the three. Returns the update's statistics.
   YartSceneUpdateStats update(const std::vector<YartNodeDesc>& nodes, const std::vector<YartLightDesc>& lights = {}, bool rebuildTop = false,
                               void* stream = nullptr) {
     YartSceneUpdate u{};
@@ -82,13 +85,28 @@ class DeviceScene {
     u.flags = rebuildTop ? YART_UPDATE_REBUILD_TOP : 0u;
     return updateWith(yart_hip_scene_update, u, stream);
   }
+  YartSceneUpdateStats update(const std::vector<YartNodeDesc>& nodes, const std::vector<YartLightDesc>& lights, TopLevel top, void* stream = nullptr) {
+    YartSceneUpdate u{};
+    u.struct_size = uint32_t(sizeof(u));
+    u.n_nodes = uint32_t(nodes.size()); u.nodes = nodes.data();
+    u.n_lights = uint32_t(lights.size()); u.lights = lights.empty() ? nullptr : lights.data();
+    u.flags = uint32_t(top);
+    return updateWith(yart_hip_scene_update, u, stream);
+  }
   // yart_hip_scene_update_meshes: new vertices for the listed meshes (each at most once; vertex counts as at create; normals /
-  // tangents NULL: kept); rebuildTop: YART_UPDATE_REBUILD_TOP. Returns the update's statistics.
+  // tangents NULL: kept); rebuildTop: YART_UPDATE_REBUILD_TOP, or `top` as for update. Returns the update's statistics.
   YartSceneUpdateStats updateMeshes(const std::vector<YartMeshUpdate>& meshes, bool rebuildTop = false, void* stream = nullptr) {
     YartSceneMeshUpdate u{};
     u.struct_size = uint32_t(sizeof(u));
     u.n_meshes = uint32_t(meshes.size()); u.meshes = meshes.data();
     u.flags = rebuildTop ? YART_UPDATE_REBUILD_TOP : 0u;
+    return updateWith(yart_hip_scene_update_meshes, u, stream);
+  }
+  YartSceneUpdateStats updateMeshes(const std::vector<YartMeshUpdate>& meshes, TopLevel top, void* stream = nullptr) {
+    YartSceneMeshUpdate u{};
+    u.struct_size = uint32_t(sizeof(u));
+    u.n_meshes = uint32_t(meshes.size()); u.meshes = meshes.data();
+    u.flags = uint32_t(top);
     return updateWith(yart_hip_scene_update_meshes, u, stream);
   }
   // yart_hip_scene_update_lighting: new material values (empty: untouched; else every material of the scene), new light emission /

@@ -148,6 +148,8 @@ class TexturesProbe(C.Structure):
 
 
 UPDATE_REBUILD_TOP = 1
+UPDATE_REBUILD_TOP_DEVICE = 2
+TLAS_LOCAL_LEAVES = 2048            # csrc/tlas_build.hpp kTlasLocalLeaves: the leaves a subtree of the device build holds at most
 TEXELS_ON_DEVICE = 1
 # the records of DeviceScene.lighting_records(): csrc/scene_types.hpp MaterialDev (flags: 1 thin, 2 alpha-tested, 4 emissive,
 # 8 transparent), LightDev, EnvDev and TexDev (quad_offset in 16-byte units, 0xffffffff: no footprint records of its own)
@@ -431,7 +433,8 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_scene_create", "yart_hip_scene_load", "yart_hip_scene_destroy",
            "yart_hip_scene_load_gltf", "yart_hip_gltf_to_yscn",
            "yart_hip_render", "yart_hip_render_waves", "yart_hip_render_tiles", "yart_hip_render_device", "yart_hip_probe_samples",
-           "yart_hip_probe_hits", "yart_hip_probe_sampler", "yart_hip_bvh_info", "yart_hip_bvh_copy", "yart_hip_scene_create_flags", "yart_hip_bvh_build_device", "yart_hip_bvh_build_host", "yart_hip_debug_counters", "yart_hip_debug_shade_regions",
+           "yart_hip_probe_hits", "yart_hip_probe_sampler", "yart_hip_bvh_info", "yart_hip_bvh_copy", "yart_hip_scene_create_flags", "yart_hip_bvh_build_device", "yart_hip_bvh_build_host",
+           "yart_hip_tlas_build_device", "yart_hip_tlas_build_host", "yart_hip_tlas_build_launches", "yart_hip_debug_counters", "yart_hip_debug_shade_regions",
            "yart_hip_tonemap_agx", "yart_hip_encode_rgb8", "yart_hip_tonemap_host",
            "yart_hip_multi_create", "yart_hip_multi_load", "yart_hip_multi_destroy", "yart_hip_multi_device_count", "yart_hip_multi_failed_devices",
            "yart_hip_multi_render", "yart_hip_multi_render_tiles", "yart_hip_multi_rccl_selftest",
@@ -474,6 +477,7 @@ _RENDER = (_P, C.POINTER(CameraDesc), C.POINTER(RenderParams), _P)              
 _PROGRESSIVE = _RENDER + (C.POINTER(Stats), WAVE_CALLBACK)                                # ... statistics, on_wave
 _MESH_ARRAYS = (_P, _U32, _P, _U32, _U32)                                                 # positions, n_verts, faces, face_stride, n_faces
 _BVH_OUT = (_P, _P, _U32_OUT, C.POINTER(C.c_double))                                      # nodes, indices, n_nodes, milliseconds
+_TLAS_BUILD = (_P, _P, _U32, _P, _U32_OUT, _U32_OUT)                                      # node_world, mesh, n_nodes, tlas, n_tlas, height
 _IMAGE = (_P, _U32, _U32)                                                                 # pixels, width, height
 _HANDLE_IMAGE = (_P,) + _IMAGE                                                            # exposure handle, pixels, width, height
 
@@ -544,6 +548,9 @@ SIGNATURES = {
     "yart_hip_bvh_copy": _sig(_P, _U32, _P, _P),
     "yart_hip_bvh_build_device": _sig(_INT, *_MESH_ARRAYS, *_BVH_OUT),
     "yart_hip_bvh_build_host": _sig(*_MESH_ARRAYS, _U32, *_BVH_OUT),
+    "yart_hip_tlas_build_device": _sig(_INT, *_TLAS_BUILD),
+    "yart_hip_tlas_build_host": _sig(*_TLAS_BUILD),
+    "yart_hip_tlas_build_launches": _sig(_U32),
     "yart_hip_tonemap_agx": _sig(*_IMAGE, _INT, _P, _P),
     "yart_hip_encode_rgb8": _sig(*_IMAGE, _P, _P),
     "yart_hip_tonemap_host": _sig(*_IMAGE, _INT, _P, _P),
@@ -754,6 +761,35 @@ def bvh_build(positions, faces, device=None, threads=0):
     return nodes[:n.value].copy(), idx, ms.value
 
 
+def tlas_build(node_world, mesh, device=0):
+    """The top-level hierarchy of a node list, built outside a scene: on HIP device ``device`` (csrc/tlas_build_kernels.inc) or, with
+    ``device=None``, on the host (host_scene.hpp::buildTopLevel). ``node_world``: (n, 8) float32, the nodes' padded world boxes as
+    lo.xyz, -, hi.xyz, -; ``mesh``: (n,) int32, < 0 = not a mesh node. Returns (tlas as TLAS_DTYPE, height); both builds give the
+    same bytes, and fewer than 64 nodes give no records."""
+    L = lib()
+    world = np.ascontiguousarray(node_world, np.float32).reshape(-1, 8)
+    m = np.ascontiguousarray(mesh, np.int32).reshape(-1)
+    if len(m) != len(world):
+        raise YartError(YART_E_INVALID, "tlas_build: node_world and mesh differ in their node counts")
+    tlas = np.zeros(max(2 * int((m >= 0).sum()) - 1, 1), TLAS_DTYPE)
+    n, height = C.c_uint32(0), C.c_uint32(0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    if device is None:
+        _check(L.yart_hip_tlas_build_host(vp(world), vp(m), len(m), vp(tlas), C.byref(n), C.byref(height)), L)
+    else:
+        _check(L.yart_hip_tlas_build_device(int(device), vp(world), vp(m), len(m), vp(tlas), C.byref(n), C.byref(height)), L)
+    return tlas[:n.value].copy(), height.value
+
+
+def _top_flags(rebuild_top):
+    """rebuild_top of update / update_meshes -> YART_UPDATE_* flags: False refit, True or "host" the host rebuild, "device" the device's"""
+    if rebuild_top is False or rebuild_top is True:
+        return UPDATE_REBUILD_TOP if rebuild_top else 0
+    if isinstance(rebuild_top, str) and rebuild_top in ("host", "device"):
+        return UPDATE_REBUILD_TOP if rebuild_top == "host" else UPDATE_REBUILD_TOP_DEVICE
+    raise YartError(YART_E_INVALID, f"rebuild_top is {rebuild_top!r}: False, True, 'host' or 'device'")
+
+
 def _f(arr, n):
     return (C.c_float * n)(*[float(v) for v in np.asarray(arr, np.float32).reshape(-1)[:n]])
 
@@ -882,7 +918,8 @@ class DeviceScene:
     def update(self, nodes, lights=None, rebuild_top=False, motion=False, stream=None):
         """yart_hip_scene_update: new transforms for the scene in place. ``nodes`` / ``lights``: the node / light lists of a
         :class:`yscn.Scene` — parent and mesh, and every light field but fwd / inv, as at create; ``lights=None`` leaves the lights
-        untouched. ``rebuild_top``: rebuild the top-level hierarchy instead of refitting its boxes. With ``motion=True`` returns
+        untouched. ``rebuild_top``: rebuild the top-level hierarchy instead of refitting its boxes — True or "host" on the host,
+        "device" on the device on the update's stream (the same bytes; anything else raises). With ``motion=True`` returns
         ``yart_amd.temporal.node_motion(the node list the scene held before, nodes)``. The call's statistics are in
         ``self.last_update``."""
         nodes = list(nodes)
@@ -891,7 +928,7 @@ class DeviceScene:
             nd[i] = NodeDesc(n.parent, n.mesh, _f(n.fwd, 16), _f(n.inv, 16))
         lights = list(lights) if lights is not None else []
         ld = _light_descs(lights)
-        up = SceneUpdate(C.sizeof(SceneUpdate), len(nodes), nd, len(lights), ld if lights else None, UPDATE_REBUILD_TOP if rebuild_top else 0)
+        up = SceneUpdate(C.sizeof(SceneUpdate), len(nodes), nd, len(lights), ld if lights else None, _top_flags(rebuild_top))
         if motion and self._nodes is None:
             raise YartError(YART_E_INVALID, "update(motion=True): the scene was loaded from a file, its previous node list is not known")
         self._update("yart_hip_scene_update", up, stream)
@@ -905,7 +942,7 @@ class DeviceScene:
         """yart_hip_scene_update_meshes: new vertices for meshes of the scene in place. ``meshes``: {mesh index: positions} or
         {mesh index: (positions, normals, tangents)} with (n, 3) / (n, 3) / (n, 4) arrays for the mesh's n vertices; normals /
         tangents may be None or left out: kept. Faces, uvs, materials and the node list stay. ``rebuild_top``: rebuild the top-level
-        hierarchy instead of refitting its boxes. The call's statistics are in ``self.last_update``."""
+        hierarchy instead of refitting its boxes, as for :meth:`update`. The call's statistics are in ``self.last_update``."""
         keep, md = [], (MeshUpdate * max(len(meshes), 1))()
         for k, (mesh, arrays) in enumerate(meshes.items()):
             if isinstance(arrays, np.ndarray) or not isinstance(arrays, (tuple, list)):
@@ -924,7 +961,7 @@ class DeviceScene:
                 ptrs.append(a.ctypes.data_as(C.c_void_p))
             n = n or 0
             md[k] = MeshUpdate(int(mesh), n, ptrs[0], ptrs[1], ptrs[2])
-        up = SceneMeshUpdate(C.sizeof(SceneMeshUpdate), len(meshes), md, UPDATE_REBUILD_TOP if rebuild_top else 0)
+        up = SceneMeshUpdate(C.sizeof(SceneMeshUpdate), len(meshes), md, _top_flags(rebuild_top))
         self._update("yart_hip_scene_update_meshes", up, stream)
 
     def update_lighting(self, materials=None, lights=None, images=None, stream=None):

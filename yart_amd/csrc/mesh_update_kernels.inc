@@ -110,7 +110,7 @@ constexpr UpdateCheck muCheck{"scene_update_meshes: "};
 // Everything that can refuse an update before a mesh is built (behind updateHead's checks)
 void muValidateArguments(const YartSceneMeshUpdate& u) {
   muCheck(u.meshes != nullptr, "meshes pointer is null");
-  muCheck((u.flags & ~YART_UPDATE_REBUILD_TOP) == 0u, "unknown flags");
+  checkUpdateFlags(muCheck, u.flags);
   muCheck(u.n_meshes >= 1u, "n_meshes is 0");
 }
 // ... and what compares it with the scene; boxes: the new vertex box of every listed mesh
@@ -316,7 +316,8 @@ extern "C" {
 int yart_hip_scene_update_meshes(YartScene* scene, const YartSceneMeshUpdate* update, void* stream, YartSceneUpdateStats* stats) {
   std::vector<SuBox> boxes;                                  // (the listed meshes' new vertex boxes: from the checks to the run)
   return updateEntry(
-      muCheck, "YartSceneMeshUpdate", scene, update, stream, stats, muValidateArguments,
+      muCheck, "YartSceneMeshUpdate", scene, update, stream, stats,
+      [&](const YartSceneMeshUpdate& u) { muValidateArguments(u); checkDeviceRebuildHandle(muCheck, u.flags, scene); },
       [&](const YartScene& s, const YartSceneMeshUpdate& u) { muValidateAgainstScene(s, u, boxes); },
       [&](YartScene& s, const YartSceneMeshUpdate& u, hipStream_t st, YartSceneUpdateStats* out) { muUpdate(s, u, boxes, st, out); });
 }

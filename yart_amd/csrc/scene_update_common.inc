@@ -14,6 +14,21 @@ bool finiteWords(const float* m, size_t n) {
   return true;
 }
 
+// The flags of YartSceneUpdate / YartSceneMeshUpdate: how the top-level hierarchy follows, at most one of the two rebuilds
+void checkUpdateFlags(const UpdateCheck& check, uint32_t flags) {
+  check((flags & ~(YART_UPDATE_REBUILD_TOP | YART_UPDATE_REBUILD_TOP_DEVICE)) == 0u, "unknown flags");
+  check((flags & YART_UPDATE_REBUILD_TOP) == 0u || (flags & YART_UPDATE_REBUILD_TOP_DEVICE) == 0u,
+        "flags: YART_UPDATE_REBUILD_TOP and YART_UPDATE_REBUILD_TOP_DEVICE exclude each other");
+}
+
+// YART_UPDATE_REBUILD_TOP_DEVICE is checked against the handle as well, behind the entry's other argument checks and before the
+// handle is read: the flag is new, and callers that probed "unknown flags" with its value on a pointer that is no scene got an
+// error return for it; they still do (SceneRegistry: the scenes that exist). Flags 0 and 1 take the handle as they always did.
+void checkDeviceRebuildHandle(const UpdateCheck& check, uint32_t flags, const void* scene) {
+  check((flags & YART_UPDATE_REBUILD_TOP_DEVICE) == 0u || SceneRegistry::get().has(scene),
+        "flags: YART_UPDATE_REBUILD_TOP_DEVICE on a handle that is not a live scene of this library");
+}
+
 // The fields of a light that no update may change
 bool sameLightTopology(const YartLightDesc& a, const YartLightDesc& b) {
   return a.type == b.type && a.mesh == b.mesh && a.tri == b.tri && a.two_sided == b.two_sided && a.texture == b.texture;

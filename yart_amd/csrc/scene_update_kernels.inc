@@ -9,6 +9,7 @@
 //   k_su_world       the padded world boxes (nodeWorld x, y, z; the .w words belong to the topology and stay)
 //   k_su_tlas_refit  one launch per level of the top-level hierarchy, leaves first: a leaf takes its node's world box, an inner node
 //                    the min / max of its two children. The tree itself (a, b) stays
+//   (YART_UPDATE_REBUILD_TOP_DEVICE: tlas_build_kernels.inc's launches in the refit's place — a new tree on the same stream)
 //
 // The tables the launches walk depend on the topology only; they are built at the scene's first update (SceneUpdateTables).
 namespace {
@@ -159,7 +160,7 @@ constexpr UpdateCheck suCheck{"scene_update: "};
 // before its lock is taken —, then what compares the update with the scene
 void suValidateArguments(const YartSceneUpdate& u) {
   suCheck(u.nodes != nullptr, "nodes pointer is null");
-  suCheck((u.flags & ~YART_UPDATE_REBUILD_TOP) == 0u, "unknown flags");
+  checkUpdateFlags(suCheck, u.flags);
 }
 void suValidateAgainstScene(const YartScene& scene, const YartSceneUpdate& u) {
   const HostImage& h = scene.host;
@@ -188,6 +189,13 @@ void suRun(YartScene& s, const YartSceneUpdate& u, const std::vector<uint32_t>& 
   SceneUpdateTables& t = s.su;
   const uint32_t nn = u.n_nodes;
   if (!t.ready) suBuildTables(s);
+  const bool deviceTop = s.dev.nTlas && (u.flags & YART_UPDATE_REBUILD_TOP_DEVICE);
+  if (deviceTop && !t.tlasBuild.ready) {                       // (first use: the tables of the scene's leaf list, blocking uploads)
+    std::vector<int32_t> mesh(nn);
+    for (uint32_t i = 0; i < nn; i++) mesh[i] = h.nodes[i].mesh;
+    tbPrepare(t.tlasBuild, tlasLeafIds(mesh.data(), nn));
+    require(t.tlasBuild.shape.records() == s.dev.nTlas && t.tlasBuild.shape.height == h.tlasHeight, "scene_update: the top-level hierarchy's shape does not fit the scene's");
+  }
   const uint32_t nodeBlocks = (nn + kBlock - 1u) / kBlock;
   if (t.levels <= kSceneUpdateMaxLevels) {
     t.stageDesc.ensure(size_t(nn) * 34u); t.stageFlags.ensure(nn);
@@ -213,7 +221,12 @@ void suRun(YartScene& s, const YartSceneUpdate& u, const std::vector<uint32_t>& 
     HIP_CHECK(hipMemcpyAsync(s.nodes.p, h.nodes.data(), size_t(nn) * sizeof(NodeDev), hipMemcpyHostToDevice, stream));
     HIP_CHECK(hipMemcpyAsync(s.nodeWorld.p, h.nodeWorld.data(), size_t(nn) * 2u * sizeof(f4), hipMemcpyHostToDevice, stream));
   }
-  if (s.dev.nTlas) {
+  if (deviceTop) {
+    // the tree of a fresh scene, built on the stream behind k_su_world (or the upload of the host's nodeWorld): same shape, same
+    // height — both depend on the number of mesh nodes only —, so the level lists of a later refit stay as they are
+    call.launchedBy(tbBuild(t.tlasBuild, s.nodeWorld.p, s.tlas.p, stream));
+    HIP_CHECK(hipMemcpyAsync(h.tlas.data(), s.tlas.p, h.tlas.size() * sizeof(TlasNode), hipMemcpyDeviceToHost, stream));
+  } else if (s.dev.nTlas) {
     if (u.flags & YART_UPDATE_REBUILD_TOP) {
       HIP_CHECK(hipStreamSynchronize(stream));                 // (the new nodeWorld is in h.nodeWorld on both paths)
       std::vector<TlasNode> rebuilt;                           // (swapped in only once it is known to fit)
@@ -255,7 +268,9 @@ void suUpdate(YartScene& s, const YartSceneUpdate& u, hipStream_t stream, YartSc
 extern "C" {
 
 int yart_hip_scene_update(YartScene* scene, const YartSceneUpdate* update, void* stream, YartSceneUpdateStats* stats) {
-  return updateEntry(suCheck, "YartSceneUpdate", scene, update, stream, stats, suValidateArguments, suValidateAgainstScene, suUpdate);
+  return updateEntry(suCheck, "YartSceneUpdate", scene, update, stream, stats,
+                     [&](const YartSceneUpdate& u) { suValidateArguments(u); checkDeviceRebuildHandle(suCheck, u.flags, scene); },
+                     suValidateAgainstScene, suUpdate);
 }
 
 }  // extern "C"

@@ -24,7 +24,7 @@
 //                multi_device.inc       several GPUs behind one handle, with its pixel pack / unpack / copy kernels
 //                postprocess.inc        tonemap / encode, the a-trous denoiser (denoise_kernels.inc) and temporal accumulation
 //                                       (temporal_kernels.inc): kernels, drivers and entries
-//                scene_update_common.inc, scene_update_kernels.inc, mesh_update_kernels.inc, lighting_update_kernels.inc, texture_update_kernels.inc,
+//                scene_update_common.inc, tlas_build_kernels.inc, scene_update_kernels.inc, mesh_update_kernels.inc, lighting_update_kernels.inc, texture_update_kernels.inc,
 //                scene_motion_kernels.inc      a scene's next frame in place: new transforms, new vertices, new materials / light
 //                                       emission / environment images, new texels of material textures, and the per-pixel motion
 //                                       between the two frames
@@ -47,11 +47,13 @@
 #include <optional>
 #include <string>
 #include <type_traits>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/yart_hip.h"
 #include "estimator.hpp"
 #include "host_scene.hpp"
+#include "tlas_build.hpp"
 #include "mesh_update.hpp"
 #include "lighting_update.hpp"
 #include "texture_update.hpp"
@@ -287,6 +289,16 @@ struct Timer {
 
 }  // namespace
 
+// What a device build of the top-level hierarchy keeps (tlas_build_kernels.inc): the tables of a leaf list — its shape and the leaves'
+// first order, on the host and uploaded — and the working arrays: the leaves' current order, the keys, the ranges' centre extents.
+struct TlasBuildState {
+  bool ready = false;
+  TlasShape shape;
+  std::vector<uint32_t> leafIds;
+  DevBuf<uint32_t> dLeafIds, dRecA, dOrder, dRoots, ids, ext;
+  DevBuf<unsigned long long> keys;
+};
+
 // What yart_hip_scene_update keeps per scene (scene_update_kernels.inc): tables of the topology, built at the first update, and
 // the staging buffers of the uploaded transforms.
 struct SceneUpdateTables {
@@ -297,6 +309,7 @@ struct SceneUpdateTables {
   DevBuf<SuBox> meshBox;
   DevBuf<uint32_t> tlasOrder; std::vector<uint32_t> tlasFirst;   // the top-level tree's nodes by level
   DevBuf<uint32_t> stageDesc, stageFlags;
+  TlasBuildState tlasBuild;                             // YART_UPDATE_REBUILD_TOP_DEVICE: allocated at its first use
 };
 
 // What yart_hip_scene_update_meshes keeps per scene (mesh_update_kernels.inc), all grown on demand so that an animation allocates
@@ -331,7 +344,19 @@ struct TextureUpdateState {
   std::vector<std::vector<uint32_t>> meshMaterials;
 };
 
+// The scenes that exist: what YART_UPDATE_REBUILD_TOP_DEVICE is checked against before an update reads its handle
+// (scene_update_common.inc::checkDeviceRebuildHandle). (Never destroyed: scenes may outlive the library's static objects at exit.)
+struct SceneRegistry {
+  std::mutex mu;
+  std::unordered_set<const void*> live;
+  static SceneRegistry& get() { static SceneRegistry* r = new SceneRegistry; return *r; }
+  void add(const void* s) { std::lock_guard<std::mutex> l(mu); live.insert(s); }
+  void remove(const void* s) { std::lock_guard<std::mutex> l(mu); live.erase(s); }
+  bool has(const void* s) { std::lock_guard<std::mutex> l(mu); return live.count(s) != 0; }
+};
+
 struct YartScene {
+  YartScene() { SceneRegistry::get().add(this); }
   int device = 0;
   HostImage host;
   SceneDev dev{};
@@ -361,7 +386,7 @@ struct YartScene {
   DevBuf<MomentState> momState; DevBuf<uint32_t> momOut;
   DevBuf<uint32_t> poolMap;                // path pool: the path (index of L) each slot carries, kWfFreeSlot = free
   uint32_t* poolHost = nullptr;            // pinned: the queue counters of the last rounds (the host's view of "is the batch done")
-  ~YartScene() { if (poolHost) (void)hipHostFree(poolHost); }
+  ~YartScene() { SceneRegistry::get().remove(this); if (poolHost) (void)hipHostFree(poolHost); }
   DevBuf<uint32_t> qA, qB, qS, qR, wfCounters; // wavefront queues
   DevBuf<uint64_t> smpEntries, smpHash; DevBuf<uint32_t> smpSobol1;   // SamplerTables of the current render
   std::vector<uint32_t> pixelsHost;
@@ -1646,6 +1671,7 @@ int yart_hip_bvh_build_host(const float* positions, uint32_t n_verts, const uint
 
 #include "postprocess.inc"
 #include "scene_update_common.inc"
+#include "tlas_build_kernels.inc"
 #include "scene_update_kernels.inc"
 #include "mesh_update_kernels.inc"
 #include "lighting_update_kernels.inc"
