@@ -263,9 +263,9 @@ void yart_hip_scene_destroy(YartScene* scene);
  * in stats->launches: per level that holds a range of more than 2048 mesh nodes 2 + the bitonic merge stages above 2048 keys, one
  * for all subtrees, one per level of the tree. Cost on an MI355X (profiles/top_rebuild.txt; refit / host rebuild / device rebuild of
  * one run): 0.26 / 1.10 / 0.61 ms for 4 096 instances, 0.41 / 4.41 / 0.82 ms for 16 000, 1.15 / 20.4 / 1.78 ms for 65 536.
- * Out of scope — re-create the scene: a changed topology (nodes added, removed, re-parented or re-meshed) and the replicas of a
- * YartMulti. Deforming meshes: yart_hip_scene_update_meshes below; materials, light emission and environment images:
- * yart_hip_scene_update_lighting below. */
+ * Out of scope — re-create the scene: the replicas of a YartMulti. A changed topology (nodes added, removed, re-parented or
+ * re-meshed) is refused here and taken by yart_hip_scene_update_graph below. Deforming meshes: yart_hip_scene_update_meshes below;
+ * materials, light emission and environment images: yart_hip_scene_update_lighting below. */
 #define YART_UPDATE_REBUILD_TOP 1u   /* rebuild the top-level hierarchy (host, create's own code) instead of refitting its boxes */
 #define YART_UPDATE_REBUILD_TOP_DEVICE 2u   /* rebuild it on the device, on the caller's stream: the same bytes */
 typedef struct YartSceneUpdate {
@@ -279,6 +279,59 @@ typedef struct YartSceneUpdate {
 /* launches: kernels launched; ms_total: wall time of the call; ms_device: from the first copy to the last on the stream */
 typedef struct YartSceneUpdateStats { uint32_t struct_size, launches; double ms_total, ms_device; } YartSceneUpdateStats;
 int yart_hip_scene_update(YartScene* scene, const YartSceneUpdate* update, void* stream, YartSceneUpdateStats* stats /* may be NULL */);
+
+/* A new NODE LIST for a scene that is on the device — an object spawned or removed, one hidden (mesh = -1), a level of detail swapped
+ * (a node's mesh index), an instance moved to another group — without yart_hip_scene_destroy + yart_hip_scene_create: no mesh BVH is
+ * rebuilt and no texture uploaded. The contract is that of the other update entries: afterwards the scene holds, and renders in
+ * every pipeline, the bits of a scene freshly created from the same description with the new node list, and the entry combines with
+ * the other four in any order. Meshes, BVHs, vertex / leaf / texture arrays, materials and environment tables stay where they are.
+ * Lights do not depend on the nodes (a YartLightDesc carries its own mesh, triangle and transform): they are touched only when
+ * `lights` is given, exactly as in yart_hip_scene_update.
+ * nodes: the whole new list, n_nodes records in pre-order, node 0 the root; the count, every parent, every mesh index and every
+ * transform may differ from the scene's. Re-derived: on the host, in one integer pass over the list (csrc/graph_update.hpp), skip
+ * links, depths, the topology words of the world boxes, identity flags, the level tables of the update chain and the leaf list of the
+ * top-level hierarchy; on the device, on `stream`, from the staged descriptors and 16 bytes of topology per node: the node records'
+ * topology fields (one kernel), then yart_hip_scene_update's own chain — transforms, children-inclusive boxes, world boxes — and the
+ * top-level hierarchy, BUILT (there is no refit: the leaf set changed): on the device with flags 0 or YART_UPDATE_REBUILD_TOP_DEVICE,
+ * on the host by scene creation's code with YART_UPDATE_REBUILD_TOP. A list of fewer than 64 nodes, or one without a mesh node,
+ * leaves no hierarchy, and a render takes the forms a fresh scene of that size takes. A graph of more than 64 levels is re-derived on
+ * the host and uploaded, as in yart_hip_scene_update. The traversal stack bound follows (the deepest mesh or the new hierarchy's height).
+ * Memory: the node, world-box, hierarchy and staging arrays and the tables grow on demand — an array that has to hold n elements and
+ * does not is re-allocated for n + n / 2 + 64 — and never shrink: an animation that appends a node per frame allocates on a vanishing
+ * share of its frames. A grown array is a new allocation: the caller orders the update against renders still running on other streams,
+ * as for every update. The tables of a changed leaf list are uploaded with blocking copies (an unchanged one: none).
+ * The kept previous frame. A graph update discards what yart_hip_scene_keep_previous kept — the kept node array is another list's —:
+ * until the next yart_hip_scene_keep_previous, yart_hip_scene_pixel_motion_* answers as on a scene that never kept a frame,
+ * YART_E_INVALID ("yart_hip_scene_keep_previous was never called on this scene"). Per-pixel motion across a graph change is out of
+ * scope. Node indices are the temporal accumulator's key (ids(p)[0]): a caller who wants history across a change keeps the surviving
+ * nodes' indices stable — hide a node with mesh = -1 instead of removing it, and append new children of the root at the end of the
+ * list, which pre-order allows. The accumulator does not remap indices.
+ * Not kept current: the default pipeline's lobe-share heuristic stays as at create (every pipeline renders the same frame).
+ * Locking, `stream`, `stats` and failures other than YART_E_INVALID as for yart_hip_scene_update; stats->launches counts the topology
+ * kernel, the chain's launches and the device build's.
+ * YART_E_INVALID, with the scene and the device exactly as they were (everything is checked before the first write): scene, update
+ * or nodes NULL; struct_size too small; unknown flags or both rebuild flags; n_nodes 0 or 2^20 and more; node 0's parent not -1;
+ * another node's parent negative or not below the node's index; with flags 0 or YART_UPDATE_REBUILD_TOP_DEVICE a `scene` that is
+ * not a live handle of this library; a `stats` whose struct_size is below 8; n_lights neither 0 nor the scene's, or a light that
+ * yart_hip_scene_update would refuse; a mesh index that is not below the scene's mesh count (any negative index: no mesh); a matrix
+ * word of a node not finite; a mesh of the scene whose vertex box is not finite; a hierarchy higher than the 192 entries of the
+ * traversal stack (its height depends on the number of mesh nodes only, so it is known before any write; below 2^20 nodes it is at
+ * most 20).
+ * Cost on an MI355X (profiles/graph_update.txt; 1 % of the instances appended, device build / host build / destroy + create of the
+ * same run): 0.70 / 1.15 / 2.9 ms for 4 096 instances, 1.10 / 4.55 / 7.6 ms for 16 000, 2.79 / 20.4 / 27.3 ms for 65 536; the
+ * transform update with a device rebuild on the same scenes: 0.62, 0.84 and 1.78 ms.
+ * Out of scope — re-create the scene: face or vertex counts, uvs, texture assignments, lights added or removed, and the replicas of
+ * a YartMulti. */
+typedef struct YartSceneGraphUpdate {
+  uint32_t struct_size;              /* sizeof(YartSceneGraphUpdate) */
+  uint32_t n_nodes;                  /* the NEW node count: 1 .. 2^20 - 1 */
+  const YartNodeDesc* nodes;         /* the new list, pre-order, node 0 the root (parent -1) */
+  uint32_t n_lights;                 /* as YartSceneUpdate: 0 = untouched, else the scene's count */
+  const YartLightDesc* lights;
+  uint32_t flags;                    /* 0 or YART_UPDATE_REBUILD_TOP_DEVICE: the hierarchy built on the device;
+                                        YART_UPDATE_REBUILD_TOP: on the host. There is no refit: the leaf set changed. */
+} YartSceneGraphUpdate;
+int yart_hip_scene_update_graph(YartScene* scene, const YartSceneGraphUpdate* update, void* stream, YartSceneUpdateStats* stats /* may be NULL */);
 
 /* New vertices for meshes of a scene that is on the device — the next frame of a skinned character, a cloth or a morphing height
  * field without yart_hip_scene_destroy + yart_hip_scene_create: textures, footprint records, environment tables, materials and every
@@ -417,7 +470,8 @@ int yart_hip_scene_update_textures(YartScene* scene, const YartSceneTextureUpdat
 /* The scene remembers the frame it holds as its PREVIOUS frame: its node array and its vertex positions are copied into scene-owned
  * arrays — two device-to-device copies on `stream`; the call returns after they have completed. The arrays are allocated by the
  * first call: a scene that never calls it pays nothing. Called once per frame, BEFORE that frame's yart_hip_scene_update /
- * yart_hip_scene_update_meshes (which run in either order and do not change). Locking as for the update entries. The replicas of a
+ * yart_hip_scene_update_meshes (which run in either order and do not change; yart_hip_scene_update_graph discards the kept frame:
+ * keep again after it). Locking as for the update entries. The replicas of a
  * YartMulti are out of scope. YART_E_INVALID: a NULL scene; YART_E_HIP: the allocation or a copy failed. */
 int yart_hip_scene_keep_previous(YartScene* scene, void* stream);
 

@@ -93,6 +93,19 @@ class DeviceScene {
     u.flags = uint32_t(top);
     return updateWith(yart_hip_scene_update, u, stream);
   }
+  // yart_hip_scene_update_graph: a new node list for the scene (pre-order, node 0 the root; count, parents, mesh indices and
+  // transforms may all differ from the scene's) and, if any are given, its lights' transforms. The top-level hierarchy is built on
+  // the device (RebuildDevice, the default; Refit is the same: the leaf set changed, there is nothing to refit) or on the host
+  // (RebuildHost). Discards the frame keepPrevious kept. Returns the update's statistics.
+  YartSceneUpdateStats updateGraph(const std::vector<YartNodeDesc>& nodes, const std::vector<YartLightDesc>& lights = {},
+                                   TopLevel top = TopLevel::RebuildDevice, void* stream = nullptr) {
+    YartSceneGraphUpdate u{};
+    u.struct_size = uint32_t(sizeof(u));
+    u.n_nodes = uint32_t(nodes.size()); u.nodes = nodes.data();
+    u.n_lights = uint32_t(lights.size()); u.lights = lights.empty() ? nullptr : lights.data();
+    u.flags = uint32_t(top);
+    return updateWith(yart_hip_scene_update_graph, u, stream);
+  }
   // yart_hip_scene_update_meshes: new vertices for the listed meshes (each at most once; vertex counts as at create; normals /
   // tangents NULL: kept); rebuildTop: YART_UPDATE_REBUILD_TOP, or `top` as for update. Returns the update's statistics.
   YartSceneUpdateStats updateMeshes(const std::vector<YartMeshUpdate>& meshes, bool rebuildTop = false, void* stream = nullptr) {

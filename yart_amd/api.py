@@ -99,6 +99,10 @@ class SceneUpdate(C.Structure):
                 ("n_lights", C.c_uint32), ("lights", C.POINTER(LightDesc)), ("flags", C.c_uint32)]
 
 
+class SceneGraphUpdate(C.Structure):                # YartSceneGraphUpdate: the fields of YartSceneUpdate, n_nodes / nodes the NEW list
+    _fields_ = SceneUpdate._fields_
+
+
 class SceneUpdateStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_double), ("ms_device", C.c_double)]
 
@@ -448,7 +452,7 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_temporal_accumulate_device", "yart_hip_temporal_accumulate_host",
            "yart_hip_temporal_accumulate_moments_device", "yart_hip_temporal_accumulate_moments_host",
            "yart_hip_temporal_set_motion",
-           "yart_hip_scene_update", "yart_hip_probe_scene_graph",
+           "yart_hip_scene_update", "yart_hip_probe_scene_graph", "yart_hip_scene_update_graph",
            "yart_hip_scene_update_meshes", "yart_hip_probe_mesh",
            "yart_hip_scene_update_lighting", "yart_hip_probe_lighting", "yart_hip_probe_texel_sum",
            "yart_hip_scene_update_textures", "yart_hip_probe_textures",
@@ -521,6 +525,7 @@ SIGNATURES = {
     "yart_hip_multi_render": _sig(*_RENDER, C.POINTER(Stats)),
     "yart_hip_multi_render_tiles": _sig(*_PROGRESSIVE, TILE_CALLBACK, _P),
     "yart_hip_scene_update": _update(SceneUpdate),
+    "yart_hip_scene_update_graph": _update(SceneGraphUpdate),
     "yart_hip_scene_update_meshes": _update(SceneMeshUpdate),
     "yart_hip_scene_update_lighting": _update(SceneLightingUpdate),
     "yart_hip_scene_update_textures": _update(SceneTextureUpdate),
@@ -937,6 +942,24 @@ class DeviceScene:
             from . import temporal
             return temporal.node_motion(previous, self._nodes)
         return None
+
+    def update_graph(self, nodes, lights=None, rebuild_top="device", stream=None):
+        """yart_hip_scene_update_graph: a new node list for the scene in place — nodes added, removed, hidden (``mesh = -1``),
+        re-meshed or re-parented. ``nodes``: the whole new list of a :class:`yscn.Scene`, in pre-order; ``lights``: as for
+        :meth:`update` (None: untouched). ``rebuild_top``: where the top-level hierarchy is built — "device" (on the update's
+        stream) or "host"; there is no refit, the leaf set changed. Discards the frame :meth:`keep_previous` kept. The call's
+        statistics are in ``self.last_update``."""
+        if rebuild_top not in ("device", "host"):
+            raise YartError(YART_E_INVALID, f"update_graph: rebuild_top is {rebuild_top!r}: 'device' or 'host'")
+        nodes = list(nodes)
+        nd = (NodeDesc * max(len(nodes), 1))()
+        for i, n in enumerate(nodes):
+            nd[i] = NodeDesc(n.parent, n.mesh, _f(n.fwd, 16), _f(n.inv, 16))
+        lights = list(lights) if lights is not None else []
+        ld = _light_descs(lights)
+        up = SceneGraphUpdate(C.sizeof(SceneGraphUpdate), len(nodes), nd, len(lights), ld if lights else None, _top_flags(rebuild_top))
+        self._update("yart_hip_scene_update_graph", up, stream)
+        self._nodes, self._n_nodes = _motion_snapshot(nodes), len(nodes)
 
     def update_meshes(self, meshes, rebuild_top=False, stream=None):
         """yart_hip_scene_update_meshes: new vertices for meshes of the scene in place. ``meshes``: {mesh index: positions} or

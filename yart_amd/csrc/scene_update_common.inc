@@ -34,6 +34,21 @@ bool sameLightTopology(const YartLightDesc& a, const YartLightDesc& b) {
   return a.type == b.type && a.mesh == b.mesh && a.tri == b.tri && a.two_sided == b.two_sided && a.texture == b.texture;
 }
 
+// The light rules of the entries that take new light transforms (yart_hip_scene_update, yart_hip_scene_update_graph): the count,
+// then — behind the entry's checks of its nodes — every record
+void checkLightCount(const UpdateCheck& check, const HostImage& h, uint32_t nLights, const YartLightDesc* lights) {
+  check(nLights == 0u || nLights == h.nLights, "n_lights is neither 0 nor the scene's light count " + std::to_string(h.nLights));
+  check(nLights == 0u || lights != nullptr, "lights pointer is null");
+}
+void checkLightTransforms(const UpdateCheck& check, const HostImage& h, uint32_t nLights, const YartLightDesc* lights) {
+  for (uint32_t i = 0; i < nLights; i++) {
+    const YartLightDesc& a = lights[i]; const YartLightDesc& b = h.lightDesc[i];
+    check(sameLightTopology(a, b) && std::memcmp(&a.radius, &b.radius, 4) == 0 && std::memcmp(a.emission, b.emission, 12) == 0,
+          "light " + std::to_string(i) + ": a field other than fwd / inv differs from the scene's");
+    check(finiteWords(a.fwd, 16) && finiteWords(a.inv, 16), "light " + std::to_string(i) + ": a matrix word is not finite");
+  }
+}
+
 // The update chain folds the meshes' vertex boxes; listed: the meshes whose box the update replaces (nullptr: none)
 void checkMeshBoxes(const UpdateCheck& check, const HostImage& h, const uint8_t* listed) {
   for (size_t m = 0; m < h.meshBox.size(); m++)

@@ -165,19 +165,13 @@ void suValidateArguments(const YartSceneUpdate& u) {
 void suValidateAgainstScene(const YartScene& scene, const YartSceneUpdate& u) {
   const HostImage& h = scene.host;
   suCheck(u.n_nodes == h.nodes.size(), "n_nodes is " + std::to_string(u.n_nodes) + ", the scene has " + std::to_string(h.nodes.size()) + " nodes");
-  suCheck(u.n_lights == 0u || u.n_lights == h.nLights, "n_lights is neither 0 nor the scene's light count " + std::to_string(h.nLights));
-  suCheck(u.n_lights == 0u || u.lights != nullptr, "lights pointer is null");
+  checkLightCount(suCheck, h, u.n_lights, u.lights);
   for (uint32_t i = 0; i < u.n_nodes; i++) {
     suCheck(u.nodes[i].parent == h.nodes[i].parent && u.nodes[i].mesh == h.nodes[i].mesh,
             "node " + std::to_string(i) + ": parent / mesh differ from the scene's (the topology cannot change)");
     suCheck(finiteWords(u.nodes[i].fwd, 16) && finiteWords(u.nodes[i].inv, 16), "node " + std::to_string(i) + ": a matrix word is not finite");
   }
-  for (uint32_t i = 0; i < u.n_lights; i++) {
-    const YartLightDesc& a = u.lights[i]; const YartLightDesc& b = h.lightDesc[i];
-    suCheck(sameLightTopology(a, b) && std::memcmp(&a.radius, &b.radius, 4) == 0 && std::memcmp(a.emission, b.emission, 12) == 0,
-            "light " + std::to_string(i) + ": a field other than fwd / inv differs from the scene's");
-    suCheck(finiteWords(a.fwd, 16) && finiteWords(a.inv, 16), "light " + std::to_string(i) + ": a matrix word is not finite");
-  }
+  checkLightTransforms(suCheck, h, u.n_lights, u.lights);
   checkMeshBoxes(suCheck, h, nullptr);
 }
 

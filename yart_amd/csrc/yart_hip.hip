@@ -24,8 +24,8 @@
 //                multi_device.inc       several GPUs behind one handle, with its pixel pack / unpack / copy kernels
 //                postprocess.inc        tonemap / encode, the a-trous denoiser (denoise_kernels.inc) and temporal accumulation
 //                                       (temporal_kernels.inc): kernels, drivers and entries
-//                scene_update_common.inc, tlas_build_kernels.inc, scene_update_kernels.inc, mesh_update_kernels.inc, lighting_update_kernels.inc, texture_update_kernels.inc,
-//                scene_motion_kernels.inc      a scene's next frame in place: new transforms, new vertices, new materials / light
+//                scene_update_common.inc, tlas_build_kernels.inc, scene_update_kernels.inc, graph_update_kernels.inc, mesh_update_kernels.inc, lighting_update_kernels.inc, texture_update_kernels.inc,
+//                scene_motion_kernels.inc      a scene's next frame in place: new transforms, a new node list, new vertices, new materials / light
 //                                       emission / environment images, new texels of material textures, and the per-pixel motion
 //                                       between the two frames
 //                probes.inc             the diagnostic kernels k_probe_* and the yart_hip_probe_* entries
@@ -54,6 +54,7 @@
 #include "estimator.hpp"
 #include "host_scene.hpp"
 #include "tlas_build.hpp"
+#include "graph_update.hpp"
 #include "mesh_update.hpp"
 #include "lighting_update.hpp"
 #include "texture_update.hpp"
@@ -344,6 +345,13 @@ struct TextureUpdateState {
   std::vector<std::vector<uint32_t>> meshMaterials;
 };
 
+// What yart_hip_scene_update_graph keeps per scene (graph_update_kernels.inc): the last call's topology pass — the host arrays its
+// copies on the stream read — and the staged topology records.
+struct GraphUpdateState {
+  GuDerived derived;
+  DevBuf<uint32_t> stageTopo;
+};
+
 // The scenes that exist: what YART_UPDATE_REBUILD_TOP_DEVICE is checked against before an update reads its handle
 // (scene_update_common.inc::checkDeviceRebuildHandle). (Never destroyed: scenes may outlive the library's static objects at exit.)
 struct SceneRegistry {
@@ -398,6 +406,7 @@ struct YartScene {
   MeshUpdateState meshUp;
   LightingUpdateState lightUp;
   TextureUpdateState texUp;
+  GraphUpdateState graphUp;
   // yart_hip_scene_keep_previous (scene_motion_kernels.inc): the node and vertex arrays of the previous frame, allocated by the first
   // call; the nodes' composed transforms and the host entry's staging buffer of yart_hip_scene_pixel_motion_*
   DevBuf<NodeDev> nodesPrev; DevBuf<f4> vPosPrev, smChains; DevBuf<float> smStage;
@@ -1673,6 +1682,7 @@ int yart_hip_bvh_build_host(const float* positions, uint32_t n_verts, const uint
 #include "scene_update_common.inc"
 #include "tlas_build_kernels.inc"
 #include "scene_update_kernels.inc"
+#include "graph_update_kernels.inc"
 #include "mesh_update_kernels.inc"
 #include "lighting_update_kernels.inc"
 #include "texture_update_kernels.inc"
