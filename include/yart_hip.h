@@ -169,7 +169,9 @@ typedef struct YartRenderParams {
                                        takes the batch's next path) instead of one slot per path of the batch. Same frame either way */
 /* ABI history. 3: YART_FLAG_PATH_POOL (and the since-retired value 256); YartStats grew (wide_* fields at the end, now always 0); value 128 has meant NO_RESUME since the end of
  * ABI 2 (it selected a since-removed 4-wide re-layout before: an old client passing it gets the same frame, a little slower);
- * YartRenderParams grew (pool_paths); max_batch_paths = 0 now means a fixed 2^28 paths, no longer a share of the free device memory; value 1024 is retired and ignored; YartTileInfo.rays is a real count; yart_hip_multi_render_tiles was added. */
+ * YartRenderParams grew (pool_paths); max_batch_paths = 0 now means a fixed 2^28 paths, no longer a share of the free device memory; value 1024 is retired and ignored; YartTileInfo.rays is a real count; yart_hip_multi_render_tiles was added.
+ * Added to ABI 3 without a bump (new exports and structs only, no existing layout changed): yart_hip_scene_replace_meshes with
+ * YartMeshReplace / YartSceneMeshReplace, yart_hip_probe_geometry with YartGeometryProbe. */
 
 /* Renderer::RenderData counters (src/core/renderer.hpp:22-28) + per-stage device time. */
 typedef struct YartStats {
@@ -358,7 +360,8 @@ int yart_hip_scene_update_graph(YartScene* scene, const YartSceneGraphUpdate* up
  * A mesh the device build refuses, and every mesh under the environment variable YART_HOST_BVH, is built and derived on the host
  * and uploaded: the same bytes.
  * Not kept current: the default pipeline's lobe-share heuristic stays as at create (every pipeline renders the same frame).
- * Out of scope — re-create the scene: changed faces or vertex counts, uvs, a face's material index, the replicas of a YartMulti
+ * Changed faces or vertex counts, uvs, a face's material index: yart_hip_scene_replace_meshes below. Out of scope — re-create the
+ * scene: the replicas of a YartMulti
  * (the materials' values, light emission and environment images: yart_hip_scene_update_lighting below).
  * Motion for the temporal accumulator: yart_hip_scene_keep_previous before the frame's updates and yart_hip_scene_pixel_motion_device
  * after its render (below) say per pixel where a deformed — or rigidly moved — surface point was in the previous frame. */
@@ -376,6 +379,47 @@ typedef struct YartSceneMeshUpdate {
   uint32_t flags;                    /* YART_UPDATE_REBUILD_TOP or YART_UPDATE_REBUILD_TOP_DEVICE */
 } YartSceneMeshUpdate;
 int yart_hip_scene_update_meshes(YartScene* scene, const YartSceneMeshUpdate* update, void* stream, YartSceneUpdateStats* stats /* may be NULL */);
+
+/* Whole new meshes for a scene that is on the device — a fluid surface extracted every frame, a re-tessellated terrain, a level of
+ * detail streamed in — without yart_hip_scene_destroy + yart_hip_scene_create: textures, footprint records, environment tables,
+ * materials and the trees of every mesh that is not listed stay on the device. `desc` is what yart_hip_scene_create takes for a mesh:
+ * positions, normals, tangents, uvs and faces (i0, i1, i2, material), all required; n_vertices and n_faces are free to differ from
+ * the mesh's. Per listed mesh the arrays are uploaded, the BVH is built by the builder scene creation uses, and leaf records, link
+ * words, the alpha flag, the shading records (normals, tangents, uvs, material, light -1) and the vertex arrays are derived on the
+ * device into scratch. Then the pools that are indexed by triangle, by vertex and by BVH node — shadeTris, leafTris, triVerts,
+ * triLight, vPos, vNormal, vTangent, vUV, bvhNodes — are repacked on the device into second arrays as scene creation lays them
+ * out (triOffset, leafOffset and vertOffset running sums, odd nodeOffsets behind a zero pad record, two zero records behind the
+ * last mesh; the ShadeTri index in the leaf records of every mesh that moves is shifted), and the arrays are swapped. If no listed
+ * mesh changes its triangle, vertex or node count, nothing is repacked: the new records are copied into place. The stack bound, the
+ * nodes' boxes, world boxes and the top-level hierarchy follow as for yart_hip_scene_update_meshes (flags: YART_UPDATE_REBUILD_TOP /
+ * _DEVICE as there; the default is a refit — the leaf set of the top level does not change). Afterwards the scene holds, and renders
+ * in every pipeline, the bits of a scene freshly created from the same description; the entry combines in any order with the five
+ * yart_hip_scene_update* entries. Locking, `stream` and `stats` as for yart_hip_scene_update_meshes. The frame
+ * yart_hip_scene_keep_previous kept is discarded (its vertex array is indexed by scene-wide vertex).
+ * Memory: the second arrays are kept in the scene, each grown to one and a half times what a call needs when it is too small, so an
+ * animation allocates nothing per frame once both arrays of every pool have held its largest frame — and holds up to twice the geometry pools it needs (per
+ * triangle 128 + 48 + 16 + 4 bytes, per vertex 56 bytes, per BVH node 32 bytes), plus the scratch of the listed meshes.
+ * YART_E_INVALID, with the scene and the device exactly as they were (counts are checked before any array is read): scene, update or
+ * meshes NULL; struct_size too small; unknown flags or both rebuild flags; YART_UPDATE_REBUILD_TOP_DEVICE on a handle that is not a
+ * live scene; n_meshes 0 or more than the scene's mesh count; a mesh index out of range or listed twice; n_faces 0 or 2^25 and
+ * more; n_vertices 0; positions, normals, tangents, uvs or faces NULL; a vertex index >= n_vertices; a material index >= the scene's
+ * material count; a position, normal, tangent or uv word not finite; a mesh that is not listed whose vertex box is not finite; a
+ * rebuilt tree deeper than 192 levels (every listed mesh is built into scratch first, the scene is written once all have built);
+ * stats->struct_size below 8; a listed mesh that a light of the scene names (YartLightDesc::mesh) or that was created with a
+ * face_light entry other than -1; a face_light that is not NULL and has an entry other than -1.
+ * Out of scope — re-create the scene: emissive meshes (a mesh with area lights changes the light list, which no entry does), the
+ * replicas of a YartMulti. */
+typedef struct YartMeshReplace {
+  uint32_t mesh;                     /* index into the scene's meshes */
+  YartMeshDesc desc;                 /* HOST arrays, as for yart_hip_scene_create; face_light NULL or all -1 */
+} YartMeshReplace;
+typedef struct YartSceneMeshReplace {
+  uint32_t struct_size;              /* sizeof(YartSceneMeshReplace) */
+  uint32_t n_meshes;                 /* meshes listed: 1 .. the scene's mesh count */
+  const YartMeshReplace* meshes;     /* each mesh at most once */
+  uint32_t flags;                    /* YART_UPDATE_REBUILD_TOP or YART_UPDATE_REBUILD_TOP_DEVICE */
+} YartSceneMeshReplace;
+int yart_hip_scene_replace_meshes(YartScene* scene, const YartSceneMeshReplace* update, void* stream, YartSceneUpdateStats* stats /* may be NULL */);
 
 /* New materials, new light emission and new environment images for a scene that is on the device — a lamp that dims, a material
  * whose colour or roughness is keyed, a sky whose sun moves — without yart_hip_scene_destroy + yart_hip_scene_create: meshes, BVHs,
@@ -824,6 +868,21 @@ typedef struct YartTexturesProbe {
   uint8_t* tex_u8; void* textures;
 } YartTexturesProbe;
 int yart_hip_probe_textures(YartScene* scene, YartTexturesProbe* probe);
+/* diagnostic read-back of the geometry pools as the kernels see them, from the device (not from the library's host copy), for
+ * yart_hip_scene_replace_meshes. The caller sets struct_size; the call fills in stack_bound (the scene's current traversal stack
+ * bound) and every count — from the meshes' layout, not from the capacity of a buffer — and copies into every array pointer that is
+ * not NULL: a first call with all of them NULL gives the sizes. bvh_nodes: BvhNode records (32 bytes) of all meshes, the zero pad
+ * records in front of the meshes and the two behind the last included; leaf_tris: LeafTri (48 bytes); shade_tris: ShadeTri (128
+ * bytes); tri_verts: 4 words per triangle; tri_light: 1 word; vpos / vnormal / vtangent: 4 floats per vertex; vuv: 2 floats;
+ * meshes: MeshDev records (64 bytes, as in yart_hip_probe_mesh). */
+typedef struct YartGeometryProbe {
+  uint32_t struct_size;              /* sizeof(YartGeometryProbe) */
+  uint32_t stack_bound;
+  uint64_t n_bvh_nodes, n_leaf_tris, n_shade_tris, n_tri_verts, n_tri_light, n_vpos, n_vnormal, n_vtangent, n_vuv, n_meshes;
+  void* bvh_nodes; void* leaf_tris; void* shade_tris; uint32_t* tri_verts; int32_t* tri_light; float* vpos; float* vnormal;
+  float* vtangent; float* vuv; void* meshes;
+} YartGeometryProbe;
+int yart_hip_probe_geometry(YartScene* scene, YartGeometryProbe* probe);
 /* measurement builds (-DYART_SHADE_REGIONS=1, tools/shade_regions.py) only: wave cycles [0..15], visits [16..31] and
  * active lanes [32..47] per code region of the shade kernel since the last call; YART_E_INVALID in the product build */
 int yart_hip_debug_shade_regions(uint64_t* out48);

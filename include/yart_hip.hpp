@@ -122,6 +122,23 @@ class DeviceScene {
     u.flags = uint32_t(top);
     return updateWith(yart_hip_scene_update_meshes, u, stream);
   }
+  // yart_hip_scene_replace_meshes: whole new meshes (each at most once; positions, normals, tangents, uvs and faces as for create,
+  // with counts of their own; no lights on the mesh); rebuildTop: YART_UPDATE_REBUILD_TOP, or `top` as for update. Discards the
+  // frame keepPrevious kept. Returns the update's statistics.
+  YartSceneUpdateStats replaceMeshes(const std::vector<YartMeshReplace>& meshes, bool rebuildTop = false, void* stream = nullptr) {
+    YartSceneMeshReplace u{};
+    u.struct_size = uint32_t(sizeof(u));
+    u.n_meshes = uint32_t(meshes.size()); u.meshes = meshes.data();
+    u.flags = rebuildTop ? YART_UPDATE_REBUILD_TOP : 0u;
+    return updateWith(yart_hip_scene_replace_meshes, u, stream);
+  }
+  YartSceneUpdateStats replaceMeshes(const std::vector<YartMeshReplace>& meshes, TopLevel top, void* stream = nullptr) {
+    YartSceneMeshReplace u{};
+    u.struct_size = uint32_t(sizeof(u));
+    u.n_meshes = uint32_t(meshes.size()); u.meshes = meshes.data();
+    u.flags = uint32_t(top);
+    return updateWith(yart_hip_scene_replace_meshes, u, stream);
+  }
   // yart_hip_scene_update_lighting: new material values (empty: untouched; else every material of the scene), new light emission /
   // radius / transforms (empty: untouched; else every light) and new texels for the maps of image lights (each texture at most
   // once; the size as at create). Returns the update's statistics.

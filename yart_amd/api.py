@@ -116,6 +116,22 @@ class SceneMeshUpdate(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_meshes", C.c_uint32), ("meshes", C.POINTER(MeshUpdate)), ("flags", C.c_uint32)]
 
 
+class MeshReplace(C.Structure):                     # YartMeshReplace: a mesh index and what create takes for a mesh
+    _fields_ = [("mesh", C.c_uint32), ("desc", MeshDesc)]
+
+
+class SceneMeshReplace(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_meshes", C.c_uint32), ("meshes", C.POINTER(MeshReplace)), ("flags", C.c_uint32)]
+
+
+GEOMETRY_PROBE_ARRAYS = ("bvh_nodes", "leaf_tris", "shade_tris", "tri_verts", "tri_light", "vpos", "vnormal", "vtangent", "vuv", "meshes")
+
+
+class GeometryProbe(C.Structure):
+    _fields_ = ([("struct_size", C.c_uint32), ("stack_bound", C.c_uint32)] + [("n_" + n, C.c_uint64) for n in GEOMETRY_PROBE_ARRAYS] +
+                [(n, C.c_void_p) for n in GEOMETRY_PROBE_ARRAYS])
+
+
 class EnvImageUpdate(C.Structure):
     _fields_ = [("texture", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("pixels", C.c_void_p)]
 
@@ -454,6 +470,7 @@ EXPORTS = ["yart_hip_abi_version", "yart_hip_device_count", "yart_hip_last_error
            "yart_hip_temporal_set_motion",
            "yart_hip_scene_update", "yart_hip_probe_scene_graph", "yart_hip_scene_update_graph",
            "yart_hip_scene_update_meshes", "yart_hip_probe_mesh",
+           "yart_hip_scene_replace_meshes", "yart_hip_probe_geometry",
            "yart_hip_scene_update_lighting", "yart_hip_probe_lighting", "yart_hip_probe_texel_sum",
            "yart_hip_scene_update_textures", "yart_hip_probe_textures",
            "yart_hip_scene_keep_previous", "yart_hip_scene_pixel_motion_device", "yart_hip_scene_pixel_motion_host",
@@ -527,6 +544,7 @@ SIGNATURES = {
     "yart_hip_scene_update": _update(SceneUpdate),
     "yart_hip_scene_update_graph": _update(SceneGraphUpdate),
     "yart_hip_scene_update_meshes": _update(SceneMeshUpdate),
+    "yart_hip_scene_replace_meshes": _update(SceneMeshReplace),
     "yart_hip_scene_update_lighting": _update(SceneLightingUpdate),
     "yart_hip_scene_update_textures": _update(SceneTextureUpdate),
     "yart_hip_scene_keep_previous": _sig(_P, _P),
@@ -544,6 +562,7 @@ SIGNATURES = {
     "yart_hip_probe_estimator": _sig(_P, _U32, _U32, _INT, _FLT, _P, _U32, _U32, _FLT, _FLT, _P, _P),
     "yart_hip_probe_scene_graph": _sig(_P, _P, _P, _P, _U32_OUT),
     "yart_hip_probe_mesh": _sig(_P, _U32, *(_P,) * 7, _U32_OUT),
+    "yart_hip_probe_geometry": _sig(_P, C.POINTER(GeometryProbe)),
     "yart_hip_probe_lighting": _sig(_P, C.POINTER(LightingProbe)),
     "yart_hip_probe_texel_sum": _sig(_P, _U64, _P),
     "yart_hip_probe_textures": _sig(_P, C.POINTER(TexturesProbe)),
@@ -986,6 +1005,49 @@ class DeviceScene:
             md[k] = MeshUpdate(int(mesh), n, ptrs[0], ptrs[1], ptrs[2])
         up = SceneMeshUpdate(C.sizeof(SceneMeshUpdate), len(meshes), md, _top_flags(rebuild_top))
         self._update("yart_hip_scene_update_meshes", up, stream)
+
+    def replace_meshes(self, meshes, rebuild_top=False, stream=None):
+        """yart_hip_scene_replace_meshes: whole new meshes for the scene in place — faces, vertex counts, uvs and per-face materials
+        may all differ from the mesh's. ``meshes``: {mesh index: a :class:`yscn.Mesh`, or (positions, normals, tangents, uvs, faces)}
+        with (n, 3) / (n, 3) / (n, 4) / (n, 2) float arrays and an (m, 4) unsigned array of i0, i1, i2, material. A mesh with lights
+        is refused. ``rebuild_top``: as for :meth:`update_meshes`. Discards the frame :meth:`keep_previous` kept. The call's
+        statistics are in ``self.last_update``."""
+        keep, md = [], (MeshReplace * max(len(meshes), 1))()
+        for k, (mesh, m) in enumerate(meshes.items()):
+            light = None
+            if not isinstance(m, (tuple, list)):
+                light = getattr(m, "face_light", None)
+                m = (m.positions, m.normals, m.tangents, m.uvs, m.faces)
+            if len(m) != 5:
+                raise YartError(YART_E_INVALID, f"replace_meshes: mesh {mesh}: not a mesh and not (positions, normals, tangents, uvs, faces)")
+            arrays = [np.ascontiguousarray(a, np.float32).reshape(-1, w) for a, w in zip(m[:4], (3, 3, 4, 2))]
+            faces = np.ascontiguousarray(m[4], np.uint32).reshape(-1, 4)
+            if len({len(a) for a in arrays}) != 1:
+                raise YartError(YART_E_INVALID, f"replace_meshes: mesh {mesh}: the arrays differ in their vertex counts")
+            if light is not None:
+                light = np.ascontiguousarray(light, np.int32).reshape(-1)
+                if len(light) != len(faces):
+                    raise YartError(YART_E_INVALID, f"replace_meshes: mesh {mesh}: face_light and faces differ in their counts")
+            keep += arrays + [faces, light]
+            vp = lambda a: a.ctypes.data_as(C.c_void_p)
+            md[k] = MeshReplace(int(mesh), MeshDesc(len(arrays[0]), len(faces), *(vp(a) for a in arrays), vp(faces),
+                                                    vp(light) if light is not None else None))
+        up = SceneMeshReplace(C.sizeof(SceneMeshReplace), len(meshes), md, _top_flags(rebuild_top))
+        self._update("yart_hip_scene_replace_meshes", up, stream)
+
+    def geometry(self):
+        """yart_hip_probe_geometry: the pools ``replace_meshes`` repacks, read back whole from the device: dict(bvh_nodes:
+        BVH_NODE_DTYPE (the zero pad records and the two tail records included), leaf_tris: LEAF_TRI_DTYPE, shade_tris:
+        SHADE_TRI_DTYPE, tri_verts: (n, 4) uint32, tri_light: int32, vpos / vnormal / vtangent: (n, 4) float32, vuv: (n, 2)
+        float32, meshes: MESH_DTYPE, stack_bound: the scene's current traversal stack bound)."""
+        pr = GeometryProbe(C.sizeof(GeometryProbe))
+        f4, f2, u4 = np.dtype((np.float32, 4)), np.dtype((np.float32, 2)), np.dtype((np.uint32, 4))
+        out = self._probe("yart_hip_probe_geometry", pr, lambda: dict(
+            bvh_nodes=(pr.n_bvh_nodes, BVH_NODE_DTYPE), leaf_tris=(pr.n_leaf_tris, LEAF_TRI_DTYPE), shade_tris=(pr.n_shade_tris, SHADE_TRI_DTYPE),
+            tri_verts=(pr.n_tri_verts, u4), tri_light=(pr.n_tri_light, np.int32), vpos=(pr.n_vpos, f4), vnormal=(pr.n_vnormal, f4),
+            vtangent=(pr.n_vtangent, f4), vuv=(pr.n_vuv, f2), meshes=(pr.n_meshes, MESH_DTYPE)))
+        out["stack_bound"] = int(pr.stack_bound)
+        return out
 
     def update_lighting(self, materials=None, lights=None, images=None, stream=None):
         """yart_hip_scene_update_lighting: new material values, new light emission / radius / transforms and new environment images

@@ -33,9 +33,10 @@ inline uint8_t lobeClass(const MaterialDev& mt) {
                  ((mt.clearcoat > 0.0f || mt.texClearcoat >= 0) ? 2u : 0u) | (mt.cMetallic > 0.0f ? 4u : 0u));
 }
 
-// After yart_hip_scene_update_meshes the per-mesh records that only the upload reads — shadeTris, bvhNodes, leafTris, vNormal,
-// vTangent — are the device's alone (re-derived there, not mirrored here); everything the library reads after create is kept
-// current: meshes, bvhIndices, vPos, meshBox, meshStackNeed, stackBound, nodes, nodeWorld, tlas, the lights.
+// After yart_hip_scene_update_meshes and yart_hip_scene_replace_meshes the per-mesh records that only the upload reads — shadeTris,
+// bvhNodes, leafTris, vNormal, vTangent, vUV — are the device's alone (re-derived and repacked there, not mirrored here: after a
+// replacement they may even have another mesh's old size); everything the library reads after create is kept current: meshes,
+// bvhIndices, vPos, triVerts, triLight, meshBox, meshStackNeed, stackBound, nodes, nodeWorld, tlas, the lights.
 struct HostImage {
   std::vector<ShadeTri> shadeTris;
   std::vector<BvhNode> bvhNodes;

@@ -19,6 +19,9 @@
 //   k_mu_shade       (normals or tangents given) the ShadeTri normals / tangents of the mesh's faces
 //   suRun            the scene-update chain with the scene's current transforms over the new vertex boxes
 //
+// The staging (muStageCore) and what follows the meshes' own records (muRederiveScene: MeshDev records, stack bound, suRun) are
+// yart_hip_scene_replace_meshes' too (mesh_replace_kernels.inc), which brings faces and counts of its own.
+//
 // A mesh the device build refuses (more than devbvh::kMaxLevels levels) — and every mesh under the environment variable
 // YART_HOST_BVH, as at scene creation — is built and derived on the host (muDeriveHost) and uploaded into the same staging arrays.
 namespace {
@@ -137,26 +140,29 @@ void muValidateAgainstScene(const YartScene& scene, const YartSceneMeshUpdate& u
   checkMeshBoxes(muCheck, h, listed.data());
 }
 
-// One listed mesh into its staging arrays: upload, build, derive. Nothing of the scene is written.
-void muStageMesh(YartScene& s, const YartMeshUpdate& m, MeshStage& st, UpdateCall& call) {
+// What a mesh is staged from: its counts, the caller's vertex arrays (host), its faces on the host and on the device (x, y, z vertices,
+// w material), the offset its ShadeTri records will have, and whether a face has an alpha-tested material. yart_hip_scene_update_meshes
+// takes faces, counts and offset from the scene; yart_hip_scene_replace_meshes (mesh_replace_kernels.inc) from its caller.
+struct MuStageIn {
+  uint32_t mesh, nVerts, nTris, triOffset;
+  const float *positions, *normals, *tangents;
+  const u4 *facesHost, *facesDev;
+  bool alpha;
+};
+
+// One listed mesh into its staging arrays: upload, build, derive. Nothing of the scene is written. check: the entry's.
+void muStageCore(YartScene& s, const MuStageIn& m, MeshStage& st, UpdateCall& call, const UpdateCheck& check) {
   const hipStream_t stream = call.stream;
   const HostImage& h = s.host;
   MeshUpdateState& mu = s.meshUp;
-  const MeshDev& md = h.meshes[m.mesh];
-  const uint32_t nv = md.nVerts, nt = md.nTris;
+  const uint32_t nv = m.nVerts, nt = m.nTris;
   st.pos.ensure(size_t(nv) * 3u);
   HIP_CHECK(hipMemcpyAsync(st.pos.p, m.positions, size_t(nv) * 12u, hipMemcpyHostToDevice, stream));
   if (m.normals) { st.nrm.ensure(size_t(nv) * 3u); HIP_CHECK(hipMemcpyAsync(st.nrm.p, m.normals, size_t(nv) * 12u, hipMemcpyHostToDevice, stream)); }
   if (m.tangents) { st.tan.ensure(size_t(nv) * 4u); HIP_CHECK(hipMemcpyAsync(st.tan.p, m.tangents, size_t(nv) * 16u, hipMemcpyHostToDevice, stream)); }
   st.nodes.ensure(size_t(nt) * 2u); st.idx.ensure(nt); st.leaf.ensure(nt);
   mu.result.ensure(4);
-  if (mu.meshAlpha.size() != h.meshes.size()) mu.meshAlpha.assign(h.meshes.size(), int8_t(-1));
-  if (mu.meshAlpha[m.mesh] < 0) {                          // does a face of the mesh have an alpha-tested material? (the faces never change)
-    int8_t any = 0;
-    for (uint32_t f = 0; f < nt && !any; f++) any = (h.materials[h.triVerts[md.triOffset + f].w].flags & MAT_HAS_ALPHA) ? 1 : 0;
-    mu.meshAlpha[m.mesh] = any;
-  }
-  const uint32_t* faces = reinterpret_cast<const uint32_t*>(s.triVerts.p + md.triOffset);
+  const uint32_t* faces = reinterpret_cast<const uint32_t*>(m.facesDev);
   devbvh::Built built;
   uint32_t res[3] = {0u, 0u, 0u};
   st.idxHost.resize(nt);
@@ -165,10 +171,10 @@ void muStageMesh(YartScene& s, const YartMeshUpdate& m, MeshStage& st, UpdateCal
     call.launchedBy(built.launches);
     st.nNodes = built.nNodes();
     HIP_CHECK(hipMemsetAsync(mu.result.p, 0, 16, stream));
-    MuLeafArgs la{st.pos.p, s.triVerts.p + md.triOffset, s.materials.p, st.idx.p, st.leaf.p, md.triOffset, nt, nv, uint32_t(h.materials.size()), mu.result.p};
+    MuLeafArgs la{st.pos.p, m.facesDev, s.materials.p, st.idx.p, st.leaf.p, m.triOffset, nt, nv, uint32_t(h.materials.size()), mu.result.p};
     hipLaunchKernelGGL(k_mu_leaves, dim3((nt + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, la);
     call.launched();
-    const bool alpha = mu.meshAlpha[m.mesh] > 0;
+    const bool alpha = m.alpha;
     if (alpha) {
       mu.prefix.ensure(size_t(nt) + 1u);
       hipLaunchKernelGGL(k_mu_alpha_scan, dim3(1), dim3(kMuScanBlock), 0, stream, st.leaf.p, mu.prefix.p, nt);
@@ -184,8 +190,8 @@ void muStageMesh(YartScene& s, const YartMeshUpdate& m, MeshStage& st, UpdateCal
     HIP_CHECK(hipMemcpyAsync(res, mu.result.p, 12, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipMemcpyAsync(st.idxHost.data(), st.idx.p, size_t(nt) * 4u, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
-    muCheck(res[1] != 1u, "mesh " + std::to_string(m.mesh) + ": a BVH leaf of 2^24 or more triangles is not supported");
-    if (res[1]) throw HipError("scene_update_meshes: the device build of mesh " + std::to_string(m.mesh) + " is inconsistent");
+    check(res[1] != 1u, "mesh " + std::to_string(m.mesh) + ": a BVH leaf of 2^24 or more triangles is not supported");
+    if (res[1]) throw HipError(std::string(check.prefix) + "the device build of mesh " + std::to_string(m.mesh) + " is inconsistent");
     st.need = res[0]; st.hasAlpha = res[2];
   } else {
     // more levels than the level kernels take, or YART_HOST_BVH: the host builder (the same bytes) and the host statement of the derivation
@@ -193,13 +199,13 @@ void muStageMesh(YartScene& s, const YartMeshUpdate& m, MeshStage& st, UpdateCal
     SahBvhBuilder hb;
     const char* e = std::getenv("YART_BVH_THREADS");
     hb.setThreads(e ? unsigned(std::atoi(e)) : 0u);
-    hb.build(m.positions, reinterpret_cast<const uint32_t*>(h.triVerts.data() + md.triOffset), 4, nt);
+    hb.build(m.positions, reinterpret_cast<const uint32_t*>(m.facesHost), 4, nt);
     std::vector<uint32_t> flags;
     for (const MaterialDev& mt : h.materials) flags.push_back(mt.flags);
     std::vector<BvhNode> nodes(hb.nodes.size());
     std::vector<LeafTri> leaf(nt);
-    const MuDerived d = muDeriveHost(hb.nodes.data(), uint32_t(hb.nodes.size()), hb.indices.data(), nt, m.positions, h.triVerts.data() + md.triOffset,
-                                     md.triOffset, flags.data(), nodes.data(), leaf.data());
+    const MuDerived d = muDeriveHost(hb.nodes.data(), uint32_t(hb.nodes.size()), hb.indices.data(), nt, m.positions, m.facesHost,
+                                     m.triOffset, flags.data(), nodes.data(), leaf.data());
     st.nNodes = uint32_t(nodes.size()); st.need = d.stackNeed; st.hasAlpha = d.hasAlpha;
     st.idxHost = hb.indices;
     if (st.need <= kMaxStackBound) {
@@ -210,6 +216,52 @@ void muStageMesh(YartScene& s, const YartMeshUpdate& m, MeshStage& st, UpdateCal
     }
   }
   checkStackBound(st.need, m.mesh);                          // create's message: "mesh N: its BVH is D levels deep, ..."
+}
+
+// ... a mesh of yart_hip_scene_update_meshes: the scene's own faces and counts
+void muStageMesh(YartScene& s, const YartMeshUpdate& m, MeshStage& st, UpdateCall& call) {
+  const HostImage& h = s.host;
+  MeshUpdateState& mu = s.meshUp;
+  const MeshDev& md = h.meshes[m.mesh];
+  if (mu.meshAlpha.size() != h.meshes.size()) mu.meshAlpha.assign(h.meshes.size(), int8_t(-1));
+  if (mu.meshAlpha[m.mesh] < 0) {                          // does a face of the mesh have an alpha-tested material? (kept until the faces or a flag change)
+    int8_t any = 0;
+    for (uint32_t f = 0; f < md.nTris && !any; f++) any = (h.materials[h.triVerts[md.triOffset + f].w].flags & MAT_HAS_ALPHA) ? 1 : 0;
+    mu.meshAlpha[m.mesh] = any;
+  }
+  const MuStageIn in{m.mesh, md.nVerts, md.nTris, md.triOffset, m.positions, m.normals, m.tangents, h.triVerts.data() + md.triOffset,
+                     s.triVerts.p + md.triOffset, mu.meshAlpha[m.mesh] > 0};
+  muStageCore(s, in, st, call, muCheck);
+}
+
+// What follows the meshes' own records, for yart_hip_scene_update_meshes and yart_hip_scene_replace_meshes alike (the host image holds
+// the new MeshDev records, stack needs and vertex boxes of the `listed` meshes): the MeshDev array, the stack bound, and the nodes'
+// boxes, world boxes and top-level hierarchy through the scene-update chain. nodes / flags: the caller's, declared before its frame.
+void muRederiveScene(YartScene& s, const std::vector<uint32_t>& listed, uint32_t updateFlags, std::vector<YartNodeDesc>& nodes,
+                     std::vector<uint32_t>& flags, UpdateCall& call) {
+  const hipStream_t stream = call.stream;
+  HostImage& h = s.host;
+  HIP_CHECK(hipMemcpyAsync(s.meshes.p, h.meshes.data(), h.meshes.size() * sizeof(MeshDev), hipMemcpyHostToDevice, stream));
+  // the stack bound as create derives it: the deepest mesh, and the top-level hierarchy's height (a median split's: it depends on
+  // the number of mesh nodes only)
+  uint32_t bound = h.tlasHeight;
+  for (uint32_t need : h.meshStackNeed) bound = std::max(bound, need);
+  h.stackBound = bound;
+  // the nodes' boxes, world boxes and the top-level hierarchy over the new vertex boxes: the scene-update chain, current transforms
+  if (!s.su.ready) suBuildTables(s);                        // (uploads h.meshBox)
+  else for (uint32_t mesh : listed)
+    HIP_CHECK(hipMemcpyAsync(s.su.meshBox.p + mesh, &h.meshBox[mesh], sizeof(SuBox), hipMemcpyHostToDevice, stream));
+  // (the chain takes transforms as the caller of yart_hip_scene_update gives them — its scatter kernel reads YartNodeDesc records —, so
+  // the current ones go to it in that form)
+  nodes.resize(h.nodes.size());
+  for (size_t i = 0; i < nodes.size(); i++) {
+    nodes[i].parent = h.nodes[i].parent; nodes[i].mesh = h.nodes[i].mesh;
+    std::memcpy(nodes[i].fwd, h.nodes[i].xf.fwd, 64); std::memcpy(nodes[i].inv, h.nodes[i].xf.inv, 64);
+  }
+  YartSceneUpdate su{};
+  su.struct_size = sizeof(su); su.n_nodes = uint32_t(nodes.size()); su.nodes = nodes.data(); su.flags = updateFlags;
+  flags.resize(nodes.size());
+  suRun(s, su, flags, suIdentityFlags(su.nodes, su.n_nodes, flags.data()), call);
 }
 
 void muUpdate(YartScene& s, const YartSceneMeshUpdate& u, const std::vector<SuBox>& boxes, hipStream_t stream, YartSceneUpdateStats* stats) {
@@ -279,27 +331,9 @@ void muUpdate(YartScene& s, const YartSceneMeshUpdate& u, const std::vector<SuBo
     }
     for (uint32_t i = 0; i < h.nLights; i++) lightsChange |= h.lights[i].type == LIGHT_AREA && h.lights[i].mesh == int32_t(m.mesh);
   }
-  HIP_CHECK(hipMemcpyAsync(s.meshes.p, h.meshes.data(), h.meshes.size() * sizeof(MeshDev), hipMemcpyHostToDevice, stream));
-  // the stack bound as create derives it: the deepest mesh, and the top-level hierarchy's height (a median split's: it depends on
-  // the number of mesh nodes only)
-  uint32_t bound = h.tlasHeight;
-  for (uint32_t need : h.meshStackNeed) bound = std::max(bound, need);
-  h.stackBound = bound;
-  // the nodes' boxes, world boxes and the top-level hierarchy over the new vertex boxes: the scene-update chain, current transforms
-  if (!s.su.ready) suBuildTables(s);                        // (uploads h.meshBox)
-  else for (uint32_t k = 0; k < u.n_meshes; k++)
-    HIP_CHECK(hipMemcpyAsync(s.su.meshBox.p + u.meshes[k].mesh, &h.meshBox[u.meshes[k].mesh], sizeof(SuBox), hipMemcpyHostToDevice, stream));
-  // (the chain takes transforms as the caller of yart_hip_scene_update gives them — its scatter kernel reads YartNodeDesc records —, so
-  // the current ones go to it in that form)
-  nodes.resize(h.nodes.size());
-  for (size_t i = 0; i < nodes.size(); i++) {
-    nodes[i].parent = h.nodes[i].parent; nodes[i].mesh = h.nodes[i].mesh;
-    std::memcpy(nodes[i].fwd, h.nodes[i].xf.fwd, 64); std::memcpy(nodes[i].inv, h.nodes[i].xf.inv, 64);
-  }
-  YartSceneUpdate su{};
-  su.struct_size = sizeof(su); su.n_nodes = uint32_t(nodes.size()); su.nodes = nodes.data(); su.flags = u.flags;
-  flags.resize(nodes.size());
-  suRun(s, su, flags, suIdentityFlags(su.nodes, su.n_nodes, flags.data()), call);
+  std::vector<uint32_t> listed;
+  for (uint32_t k = 0; k < u.n_meshes; k++) listed.push_back(u.meshes[k].mesh);
+  muRederiveScene(s, listed, u.flags, nodes, flags, call);
   if (lightsChange) {                                        // area lights on an updated mesh: from the host's new vertices, as create derives them
     const std::vector<YartLightDesc> desc = h.lightDesc;
     rederiveLights(h, desc.data(), h.nLights);

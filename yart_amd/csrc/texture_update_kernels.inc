@@ -149,7 +149,7 @@ void tuUpdate(YartScene& s, const YartSceneTextureUpdate& u, hipStream_t stream,
   }
   if (anyFlip) {
     HIP_CHECK(hipMemcpyAsync(s.materials.p, h.materials.data(), h.materials.size() * sizeof(MaterialDev), hipMemcpyHostToDevice, stream));
-    if (tu.meshMaterials.size() != h.meshes.size()) {        // per mesh the materials of its faces (the faces never change)
+    if (tu.meshMaterials.size() != h.meshes.size()) {        // per mesh the materials of its faces (kept until yart_hip_scene_replace_meshes changes faces: it clears the table)
       tu.meshMaterials.assign(h.meshes.size(), {});
       for (size_t mi = 0; mi < h.meshes.size(); mi++) {
         std::vector<uint32_t>& mm = tu.meshMaterials[mi];

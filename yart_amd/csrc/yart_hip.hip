@@ -56,6 +56,7 @@
 #include "tlas_build.hpp"
 #include "graph_update.hpp"
 #include "mesh_update.hpp"
+#include "mesh_replace.hpp"
 #include "lighting_update.hpp"
 #include "texture_update.hpp"
 #include "integrator.hpp"
@@ -321,12 +322,26 @@ struct MeshStage {
   DevBuf<BvhNode> nodes; DevBuf<uint32_t> idx; DevBuf<LeafTri> leaf;
   std::vector<uint32_t> idxHost;
   uint32_t nNodes = 0, hasAlpha = 0, need = 0;
+  // yart_hip_scene_replace_meshes (mesh_replace_kernels.inc) only: the caller's uvs and faces, and the mesh's records of the pools
+  // that are indexed by triangle and by vertex, as create lays them out
+  DevBuf<float> uv;
+  DevBuf<u4> faces; DevBuf<int32_t> light; DevBuf<ShadeTri> shade;
+  DevBuf<f4> vPos, vNormal, vTangent; DevBuf<f2> vUV;
+};
+// The second array of every pool yart_hip_scene_replace_meshes repacks (bvhNodes: MeshUpdateState::nodesAlt, which
+// yart_hip_scene_update_meshes repacks into as well). A repack writes the second array and swaps the two, so each holds the pool of
+// the frame before; grown by half beyond what a frame needs, and kept.
+struct MeshReplacePools {
+  DevBuf<ShadeTri> shadeTris; DevBuf<LeafTri> leafTris; DevBuf<u4> triVerts; DevBuf<int32_t> triLight;
+  DevBuf<f4> vPos, vNormal, vTangent; DevBuf<f2> vUV;
+  DevBuf<MrSource> segments;                            // the segment tables of one call, pool after pool
 };
 struct MeshUpdateState {
   devbvh::Scratch scratch;
   std::vector<std::unique_ptr<MeshStage>> stages;
   DevBuf<uint32_t> prefix, result;
   DevBuf<BvhNode> nodesAlt;
+  MeshReplacePools alt;
   std::vector<int8_t> meshAlpha;                        // per mesh: a face has an alpha-tested material (-1: not looked at yet)
 };
 
@@ -1684,6 +1699,7 @@ int yart_hip_bvh_build_host(const float* positions, uint32_t n_verts, const uint
 #include "scene_update_kernels.inc"
 #include "graph_update_kernels.inc"
 #include "mesh_update_kernels.inc"
+#include "mesh_replace_kernels.inc"
 #include "lighting_update_kernels.inc"
 #include "texture_update_kernels.inc"
 #include "scene_motion_kernels.inc"
